@@ -1,6 +1,6 @@
 """Benchmark of the hot path: batched `env.run(until=T)` on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--scenarios S]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--scenarios S] [--full] [--dump-outputs DIR]
 
 Workload (BASELINE.json configs[1], the one the metric is quoted on, default): the 2-server +
 load-balancer topology of examples/yaml_input/data/two_servers_lb.yml (400 users x 20 rpm,
@@ -22,6 +22,12 @@ are timed between barrier + torch.cuda.synchronize() on both sides, MAX over ran
 ONE JSON line.  value = request-events simulated by all ranks / that time (request-event = one
 timed state transition of a request: arrival, edge delivery, CPU-step end, I/O-step end;
 SURVEY.md section 8d).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what the headline does not need, after the
+timed region: the CPU baseline legs (before HIP is initialised), the oracle parity spot check, the end-to-end sweep and
+residency-tail diagnostics, and the committed PMC binding of the roofline.  `--dump-outputs DIR` writes what the last timed step
+computed (counts, latency stats and, for a fixed seeded sample of scenarios, the analyzer's other outputs, rqs_clock and the
+sampled series) as DIR/<name>.npy.
 
 N > 1: one process per GPU.  Under torchrun (RANK / WORLD_SIZE in the environment) this process IS
 a rank; called plainly with --gpus N it re-executes itself under `python -m torch.distributed.run
@@ -460,6 +466,71 @@ def parity_spot_check(sw: "RankSweep", k: int = 16) -> dict:
             "check_s": time.perf_counter() - t0}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_ROWS = 1024          # scenarios whose per-second / histogram / series summaries are written
+DUMP_FULL_ROWS = 8        # scenarios whose whole rqs_clock and sampled series are written
+
+
+def dump_outputs(sw: "RankSweep", out_dir: Path) -> dict:
+    """What the timed path handed its caller in the last step, as out_dir/<name>.npy (float64 / float32, <= 64 MB in all):
+    the per-scenario counts and latency stats of every scenario of the rank, the per-second completions, latency histogram
+    and series mean / max of a fixed sample of DUMP_ROWS scenarios, and the whole rqs_clock and sampled series of
+    DUMP_FULL_ROWS of them.  The samples are drawn with a fixed seed from the scenarios whose clock / series are still
+    resident (the last slice of the step), so that the same arguments always write the same scenarios."""
+    from asyncflow_amd import _abi
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    torch = sw.torch
+    torch.cuda.synchronize(sw.dev)
+    counts = sw.counts.cpu().numpy().view(np.uint32)
+    rng = np.random.default_rng(0x5EED)
+    rows = np.sort(rng.choice(sw.n, size=min(DUMP_ROWS, sw.n), replace=False))
+    last_lo = ((sw.n - 1) // sw.slice) * sw.slice            # the slice whose clock / series the buffers hold
+    full = np.sort(rng.choice(np.arange(last_lo, sw.n), size=min(DUMP_FULL_ROWS, sw.n - last_lo), replace=False))
+    sel = torch.from_numpy(rows).to(sw.dev)
+    arrays: dict[str, np.ndarray] = {
+        "counts": counts[:, :5].astype(np.float64),          # generated, completed, dropped, request-events, ticks
+        "latency_stats": sw.s_stats.double().cpu().numpy(),  # per scenario: the analyzer's eight statistics
+        "sample_index": rows.astype(np.float64),
+        "rps": sw.s_rps.index_select(0, sel).cpu().numpy().astype(np.float32),
+        "latency_hist": sw.s_hist.index_select(0, sel).cpu().numpy().astype(np.float32),
+        "full_index": full.astype(np.float64),
+    }
+    if sw.samples is not None:
+        j = np.arange(sw.plan.n_series)
+        series_float = (j >= sw.plan.n_edges) & ((j - sw.plan.n_edges) % 3 == 2)    # ram_in_use columns hold float32 bits
+
+        def decode(words: np.ndarray) -> np.ndarray:
+            w = np.ascontiguousarray(words).view(np.uint32)
+            out = w.view(np.int32).astype(np.float64)
+            out[..., series_float] = w[..., series_float].view(np.float32).astype(np.float64)
+            return out
+
+        arrays["series_mean"] = sw.s_mean.index_select(0, sel).double().cpu().numpy()
+        arrays["series_max"] = decode(sw.s_max.index_select(0, sel).cpu().numpy())
+    total = sum(a.nbytes for a in arrays.values())
+    for k, i in enumerate(full):
+        whole: dict[str, np.ndarray] = {}
+        if sw.clock is not None:
+            done = min(int(counts[i, _abi.CNT_COMPLETED]), sw.clock_cap)
+            whole[f"rqs_clock_{k}"] = sw.clock[i - last_lo, :done].cpu().numpy()
+        if sw.samples is not None:
+            ticks = min(int(counts[i, _abi.CNT_TICKS]), sw.ticks)
+            whole[f"sampled_series_{k}"] = decode(sw.samples[i - last_lo, :ticks, : sw.plan.n_series].cpu().numpy())
+        size = sum(a.nbytes for a in whole.values())
+        if total + size > DUMP_LIMIT_BYTES:      # (the sample is a fixed prefix of `full`: still the same for the same arguments)
+            arrays["full_index"] = full[:k].astype(np.float64)
+            break
+        arrays.update(whole)
+        total += size
+    if total > DUMP_LIMIT_BYTES:
+        msg = f"--dump-outputs would write {total / 2**20:.1f} MiB (limit {DUMP_LIMIT_BYTES >> 20} MiB)"
+        raise RuntimeError(msg)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", np.ascontiguousarray(a))
+    return {"dir": str(out_dir), "files": len(arrays), "bytes": total}
+
+
 # --------------------------------------------------------------------------- #
 # the rank's sweep: engine + HBM-resident outputs, run as slices                 #
 # --------------------------------------------------------------------------- #
@@ -719,9 +790,9 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--scenarios", "--replicas", type=int, default=0, dest="scenarios",
                     help="scenarios per GPU (configs 1-3) or in total (configs 4, 5); 0 = the BASELINE size")
     ap.add_argument("--horizon", type=int, default=0, help="simulated seconds (0 = the BASELINE horizon)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-check", action="store_true", help="skip the post-run oracle comparison of >= 16 benched scenarios (every slice of the step)")
-    ap.add_argument("--no-diagnostics", action="store_true", help="skip the post-run end-to-end / residency-tail measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-parity-check", action="store_true", help="with --full: skip the post-run oracle comparison of >= 16 benched scenarios (every slice of the step)")
+    ap.add_argument("--no-diagnostics", action="store_true", help="with --full: skip the post-run end-to-end / residency-tail measurements")
     ap.add_argument("--no-series", action="store_true", help="do not store the sampled series")
     ap.add_argument("--lanes", type=int, default=0, help="scenario lanes per wave of the sequential kernel (0 = engine default)")
     ap.add_argument("--global-state", action="store_true", help="keep per-scenario state in HBM")
@@ -741,6 +812,11 @@ def make_parser() -> argparse.ArgumentParser:
     ap.add_argument("--flow-ring-rows", type=int, default=0, help="rows of the LDS tick ring (0 = auto, -1 = keep the differences in HBM)")
     ap.add_argument("--hbm-budget-gb", type=float, default=96.0, help="HBM for the output buffers of one slice")
     ap.add_argument("--selftest-cpu", action="store_true", help="launcher / sharding / gather path on CPU (gloo), no engine")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU baseline legs, the oracle parity spot check, the end-to-end "
+                         "sweep and residency-tail diagnostics, and the committed PMC binding of the roofline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     return ap
 
 
@@ -760,7 +836,7 @@ def main() -> int:  # noqa: C901, PLR0912, PLR0915
 
     wl = build_workload(args.config, rank, world, args.scenarios, args.horizon)
     base = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         from asyncflow_amd.workloads import BASELINE_SEED_BASE
 
         base = cpu_baseline(wl["payload"], BASELINE_SEED_BASE[args.config], wl["label"])  # before HIP is initialised (fork-safe)
@@ -886,13 +962,15 @@ def main() -> int:  # noqa: C901, PLR0912, PLR0915
     pooled_p95_ms = float((np.searchsorted(cdf, 0.95) + 1) * sw.hist_max / 256 * 1e3)
 
     # ---- diagnostics after the timed region (rank 0, single GPU): end-to-end wall of one sweep, residency tail
-    e2e = tail = parity = None
-    if rank == 0 and not args.no_parity_check:      # (first: the diagnostics below reuse the output buffers)
+    e2e = tail = parity = dumped = None
+    if rank == 0 and args.dump_outputs:             # (first: the checks below run slices again into the same buffers)
+        dumped = dump_outputs(sw, Path(args.dump_outputs))
+    if rank == 0 and args.full and not args.no_parity_check:      # (first: the diagnostics below reuse the output buffers)
         try:
             parity = parity_spot_check(sw)
         except Exception as exc:  # noqa: BLE001 - a broken checker build must not eat the measured line; it says so
             parity = {"scenarios": 0, "ok": None, "why": f"{type(exc).__name__}: {exc}"}
-    if rank == 0 and world == 1 and not args.no_diagnostics:
+    if rank == 0 and world == 1 and args.full and not args.no_diagnostics:
         e2e = end_to_end_sweep(sw, wl, dev)
         if flow_on:
             tail = residency_tail(sw, float(np.mean([a["flow_ms"] for a in accs])))
@@ -1014,7 +1092,10 @@ def main() -> int:  # noqa: C901, PLR0912, PLR0915
                 "residency_tail": tail,
             },
         }
-        attach_binding(line["roofline"], dom_ms, sw.n_slices, args, n, wl)
+        if args.full:
+            attach_binding(line["roofline"], dom_ms, sw.n_slices, args, n, wl)
+        else:
+            line["roofline"]["binding"] = {"why": "the committed PMC binding is attached by --full"}
         if isinstance(line["roofline"].get("binding"), dict) and line["roofline"]["binding"].get("resource"):
             res_name = str(line["roofline"]["binding"]["resource"])
             line["roofline"]["bound_actual"] = ("instruction issue: the VALU is busy most of the launch (`binding.frac`)" if res_name == "valu_issue"
@@ -1023,6 +1104,8 @@ def main() -> int:  # noqa: C901, PLR0912, PLR0915
             line["cpu_baseline"] = base
         if parity is not None:
             line["parity_spot_check"] = parity
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         try:      # (RCCL prints a version banner through C stdio, block-buffered on a pipe: out with it BEFORE the one JSON line)
             import ctypes
 

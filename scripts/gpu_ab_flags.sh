@@ -8,7 +8,7 @@ OUT=gpurun_out/ab_$TAG; mkdir -p $OUT
 for rep in 1 2; do
   i=0
   for flags in "$@"; do
-    ASYNCFLOW_JIT_EXTRA_FLAGS="$flags" python bench.py --steps 10 --warmup 3 --no-cpu-baseline --no-diagnostics > $OUT/v${i}_$rep.log 2>&1
+    ASYNCFLOW_JIT_EXTRA_FLAGS="$flags" python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline --no-diagnostics > $OUT/v${i}_$rep.log 2>&1
     i=$((i+1))
   done
 done

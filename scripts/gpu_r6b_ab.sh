@@ -8,7 +8,7 @@ for c in $CFGS; do
   for rep in 1 2; do
     i=0
     for flags in "$@"; do
-      ASYNCFLOW_JIT_EXTRA_FLAGS="$flags" timeout 600 python bench.py --config $c --steps 6 --warmup 2 --no-cpu-baseline --no-diagnostics --separate-summary > $OUT/c${c}_v${i}_$rep.log 2>&1
+      ASYNCFLOW_JIT_EXTRA_FLAGS="$flags" timeout 600 python bench.py --full --config $c --steps 6 --warmup 2 --no-cpu-baseline --no-diagnostics --separate-summary > $OUT/c${c}_v${i}_$rep.log 2>&1
       i=$((i+1))
     done
   done

@@ -11,7 +11,7 @@ for rep in 1 2; do
     if [ $v = tree ]; then cp /tmp/lib_tree.so $LIB; else cp build/variants/libaf_$v.so $LIB; fi
     for g in 40 48 64; do
       [ $v = p7 ] && [ $g != 40 ] && continue
-      AF_PREGEN_GROUP=$g timeout 600 python bench.py --config 2 --steps 6 --warmup 2 --no-cpu-baseline --no-diagnostics --separate-summary > $OUT/c2_${v}_g${g}_$rep.log 2>&1; line $OUT/c2_${v}_g${g}_$rep.log "producers $v group $g"
+      AF_PREGEN_GROUP=$g timeout 600 python bench.py --full --config 2 --steps 6 --warmup 2 --no-cpu-baseline --no-diagnostics --separate-summary > $OUT/c2_${v}_g${g}_$rep.log 2>&1; line $OUT/c2_${v}_g${g}_$rep.log "producers $v group $g"
     done
   done
 done

@@ -9,9 +9,9 @@ OUT=gpurun_out/prof_$TAG; mkdir -p $OUT
 KERN="af_flow|af_des|af_jit|af_pregen|af_arrival|af_summary|af_series"
 ( time timeout 1800 python -m pytest tests -m gpu -x -q ) > $OUT/gputests.log 2>&1; echo "rc=$?" >> $OUT/gputests.log
 tail -3 $OUT/gputests.log
-( time timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver_cmd.log 2>&1; echo "rc=$?" >> $OUT/bench_driver_cmd.log
-python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-diagnostics > $OUT/bench_unprofiled.log 2>&1
-timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt -o t -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-diagnostics > $OUT/bench_under_trace.log 2>&1
+( time timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver_cmd.log 2>&1; echo "rc=$?" >> $OUT/bench_driver_cmd.log
+python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-diagnostics > $OUT/bench_unprofiled.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt -o t -- python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-diagnostics > $OUT/bench_under_trace.log 2>&1
 cp $(find /tmp/pt -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_trace.csv
 f=$(find /tmp/pt -name "*kernel_trace.csv" | head -1); head -1 $f > $OUT/kernel_trace_af.csv; grep -E "$KERN" $f >> $OUT/kernel_trace_af.csv
 pass() { i=$1; shift; timeout 300 rocprofv3 --pmc "$@" --output-format csv -d /tmp/pp$i -o p -- python bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-parity-check --no-diagnostics > $OUT/bench_under_pmc$i.log 2>&1; f=$(find /tmp/pp$i -name "*counter_collection.csv" | head -1); head -1 $f > $OUT/pmc$i.csv; grep -E "$KERN" $f >> $OUT/pmc$i.csv; }
@@ -21,5 +21,5 @@ pass 3 FETCH_SIZE
 pass 4 WRITE_SIZE
 pass 5 SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_SMEM SQ_WAIT_INST_LDS SQ_WAIT_INST_ANY GRBM_GUI_ACTIVE
 python scripts/make_binding_json.py $OUT
-for c in 3 4 5; do python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_config$c.log 2>&1; done
+for c in 3 4 5; do python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline > $OUT/bench_config$c.log 2>&1; done
 ls -la $OUT

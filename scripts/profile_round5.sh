@@ -18,7 +18,7 @@ for step in "$@"; do
     tests)
       ( time timeout 2400 python -m pytest tests -m gpu -x -q ) > $OUT/gputests.log 2>&1; echo "rc=$?" >> $OUT/gputests.log; tail -4 $OUT/gputests.log ;;
     driver)
-      ( time timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver_cmd.log 2>&1; echo "rc=$?" >> $OUT/bench_driver_cmd.log
+      ( time timeout 900 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $OUT/bench_driver_cmd.log 2>&1; echo "rc=$?" >> $OUT/bench_driver_cmd.log
       grep '^{' $OUT/bench_driver_cmd.log | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['value'], d['ms_per_step'], d['flow_kernel_ms'], d['roofline']['frac'], d['parity_spot_check']['ok'], d['parity_spot_check']['scenarios'])" ;;
     cal)
       hipcc --offload-arch=gfx950 -O2 -o /tmp/valu_calibration scripts/microbench/valu_calibration.hip 2> /dev/null
@@ -27,7 +27,7 @@ for step in "$@"; do
       cp $(find /tmp/pcal -name "*counter_collection.csv" | head -1) $OUT/cal_counters.csv
       python scripts/make_valu_calibration.py $OUT | tail -14 ;;
     c2|c3|c4|c5|gensrv)
-      L=$step; C=$(cfg_of $L); B="python bench.py --config $C --no-cpu-baseline --no-diagnostics"
+      L=$step; C=$(cfg_of $L); B="python bench.py --full --config $C --no-cpu-baseline --no-diagnostics"
       $B --steps 3 --warmup 1 > $OUT/bench_unprofiled_$L.log 2>&1
       rm -rf /tmp/pt; timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/pt -o t -- $B --steps 3 --warmup 1 --no-parity-check > $OUT/bench_under_trace_$L.log 2>&1
       cp $(find /tmp/pt -name "*kernel_stats.csv" | head -1) $OUT/kernel_stats_trace_$L.csv

@@ -134,7 +134,7 @@ def test_bench_rank_rows_ride_in_the_one_gather(tmp_path):
     root = Path(__file__).resolve().parent.parent
     env = dict(os.environ, AF_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29611", RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
     out = subprocess.run([sys.executable, str(root / "bench.py"), "--scenarios", "256", "--horizon", "30", "--steps", "1", "--warmup", "0",
-                          "--no-cpu-baseline", "--no-diagnostics"], env=env, capture_output=True, text=True, timeout=600, check=False)
+                          "--full", "--no-cpu-baseline", "--no-diagnostics"], env=env, capture_output=True, text=True, timeout=600, check=False)
     assert out.returncode == 0, out.stderr[-2000:]
     assert out.stdout.strip().splitlines()[-1].startswith('{"metric"'), "the JSON line must be the LAST line of stdout"
     line = json.loads(out.stdout.strip().splitlines()[-1])
@@ -160,7 +160,7 @@ def test_the_bench_line_of_a_launched_rank_carries_what_rccl_says(tmp_path):
                AF_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
     root = Path(__file__).resolve().parent.parent
     res = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--scenarios", "512",
-                          "--horizon", "60", "--no-cpu-baseline", "--no-diagnostics"], env=env, capture_output=True, text=True,
+                          "--horizon", "60", "--full", "--no-cpu-baseline", "--no-diagnostics"], env=env, capture_output=True, text=True,
                          timeout=900, check=False)
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]
     assert res.returncode == 0 and lines, res.stderr[-2000:]

@@ -1,11 +1,14 @@
-"""Differential tests against the LIVE reference (build container only).
+"""Differential tests against the reference's own outputs, recorded (oracle/make_reference_live.py).
 
-Skipped wherever /root/reference is absent (e.g. the GPU box): there the
-committed fixtures of tests/golden/ stand in for it.
+tests/golden/reference_live/cases.npz holds what the UNMODIFIED reference computed on every case below: counts, every
+(start, finish) pair and every sampled series, the exception it raised where it refuses a payload, its validated model of
+each example YAML and what its analyzer reports.  The oracle is held to those bit for bit wherever the suite runs;
+`python oracle/make_reference_live.py --check` runs the reference again and compares it with the committed file.
 """
 
 from __future__ import annotations
 
+import json
 import random
 
 import numpy as np
@@ -13,24 +16,30 @@ import pytest
 
 from asyncflow_amd.plan import lower
 from oracle import oracle_lib as ol
-from oracle import ref_env
+from oracle.make_reference_live import case_key
 from oracle.scenarios import overload, random_payload, server_chain, tie_storm, wide_fanout
+from tests.conftest import GOLDEN_DIR
 
-pytestmark = [
-    pytest.mark.reference,
-    pytest.mark.skipif(not ref_env.reference_available(), reason="reference sources not present"),
-    pytest.mark.filterwarnings("ignore::DeprecationWarning"),
-]
+pytestmark = pytest.mark.filterwarnings("ignore::DeprecationWarning")
+
+_RECORDED = np.load(GOLDEN_DIR / "reference_live" / "cases.npz", allow_pickle=False)
+
+
+def _recorded(payload: dict, seed: int) -> str:
+    """The key of (payload, seed) in the recorded file; the payload is held to the recorded input, key by key."""
+    key = case_key(payload, seed)
+    assert f"{key}.payload_json" in _RECORDED.files, "no recorded reference output for this payload (oracle/make_reference_live.py)"
+    assert json.loads(str(_RECORDED[f"{key}.payload_json"])) == json.loads(json.dumps(payload))
+    return key
 
 
 def _same(payload: dict, seed: int) -> None:
-    from oracle.reference_runner import run_reference
-
-    ref = run_reference(payload, seed)
+    key = _recorded(payload, seed)
+    assert f"{key}.raised" not in _RECORDED.files, str(_RECORDED[f"{key}.raised"])
     res = ol.simulate(lower(payload), seed)
-    assert (ref.generated, ref.completed, ref.dropped, ref.ticks) == (res.generated, res.completed, res.dropped, res.ticks)
-    assert np.array_equal(ref.clock, res.clock)
-    assert np.array_equal(ref.samples, res.samples)
+    assert tuple(int(v) for v in _RECORDED[f"{key}.counts"]) == (res.generated, res.completed, res.dropped, res.ticks)
+    assert np.array_equal(_RECORDED[f"{key}.clock"], res.clock)
+    assert np.array_equal(_RECORDED[f"{key}.samples"], res.samples)
 
 
 @pytest.mark.parametrize("case", range(12))
@@ -65,39 +74,13 @@ def test_server_chain_matches_reference(dist, mean):
     _same(server_chain(dist, mean), 2)
 
 
-def test_reference_suite_passes_on_the_simpy_standin():
-    """The reference's own 183 tests are the stand-in kernel's conformance suite."""
-    import subprocess
-    import sys
-    from pathlib import Path
-
-    import os
-
-    root = Path(__file__).resolve().parent.parent
-    # the 4 system tests are statistical with an UNSEEDED numpy generator
-    # (SURVEY.md section 4) and flake occasionally: they are run by
-    # `python oracle/run_reference_tests.py`, not here.
-    env = dict(os.environ, ASYNCFLOW_RUN_SYSTEM_TESTS="0")
-    out = subprocess.run(
-        [sys.executable, str(root / "oracle" / "run_reference_tests.py")],
-        capture_output=True, text=True, timeout=600, check=False, env=env,
-    )
-    tail = out.stdout.strip().splitlines()[-1] if out.stdout.strip() else out.stderr[-300:]
-    assert out.returncode == 0, tail
-    assert "179 passed, 4 skipped" in tail
-
-
 def test_baseline_workloads_equal_the_reference_yaml():
-    """asyncflow_amd/workloads.py restates the reference's example YAMLs value for value: both sides
-    are validated by the reference's own Pydantic models and compared as dumped models."""
-    import yaml
-
-    ref_env.install()
-    from asyncflow.schemas.payload import SimulationPayload
-
+    """asyncflow_amd/workloads.py restates the reference's example YAMLs value for value: ours, normalized with every
+    default applied, equal the reference's own validated model of each YAML (recorded as dumped by its Pydantic models)."""
     from asyncflow_amd import workloads as w
+    from asyncflow_amd.payload import normalize_payload
 
-    data = ref_env.REFERENCE_ROOT / "examples" / "yaml_input" / "data"
+    theirs_all = json.loads(str(_RECORDED["yaml_models"]))
     cases = {
         "single_server.yml": w.single_server(horizon=500),
         "two_servers_lb.yml": w.lb_two_servers(),
@@ -105,50 +88,31 @@ def test_baseline_workloads_equal_the_reference_yaml():
         "event_inj_single_server.yml": w.single_server_with_spike(),
         "heavy_inj_single_server.yml": w.single_server_with_spike(heavy=True),
     }
+    assert set(theirs_all) == set(cases)
     for name, ours in cases.items():
-        theirs = SimulationPayload.model_validate(yaml.safe_load((data / name).read_text())).model_dump(mode="json")
-        mine = SimulationPayload.model_validate(ours).model_dump(mode="json")
-        assert mine == theirs, name
+        assert normalize_payload(ours) == normalize_payload(theirs_all[name]), name
 
 
-def test_results_feed_the_reference_plot_helpers(tmp_path):
-    """ScenarioResults.to_reference_analyzer(): the reference's own ResultsAnalyzer + plot helpers
-    (/root/reference/src/asyncflow/metrics/analyzer.py:264-589) run on the engine's arrays and report
-    the same statistics as the drop-in accessors."""
-    import json
-
-    import matplotlib
-
-    matplotlib.use("Agg")
-    import matplotlib.pyplot as plt
-
+def test_results_feed_the_reference_plot_helpers():
+    """ScenarioResults' drop-in accessors report what the reference's own ResultsAnalyzer and ram plot helper
+    (src/asyncflow/metrics/analyzer.py:264-589, run through to_reference_analyzer() on the same arrays, recorded) report."""
     from asyncflow_amd import _abi
     from asyncflow_amd.results import ScenarioResults
-    from tests.conftest import GOLDEN_DIR
 
-    ref_env.install()
     fx = np.load(GOLDEN_DIR / "lb2_rr_t30.npz", allow_pickle=False)
     plan = lower(json.loads(str(fx["payload_json"])))
     counts = np.zeros(_abi.CNT_SLOTS, dtype=np.uint32)
     counts[_abi.CNT_GENERATED], counts[_abi.CNT_COMPLETED] = int(fx["generated"]), int(fx["completed"])
     counts[_abi.CNT_TICKS] = int(fx["ticks"])
     sc = ScenarioResults(plan, counts, fx["clock"], fx["samples"])
-    an = sc.to_reference_analyzer()
-    theirs = {str(getattr(k, "value", k)): float(v) for k, v in an.get_latency_stats().items()}
-    assert theirs == sc.get_latency_stats()
-    assert an.get_throughput_series()[1] == sc.get_throughput_series()[1]
-    assert an.list_server_ids() == sc.list_server_ids()
-    fig, axes = plt.subplots(2, 2)
-    an.plot_base_dashboard(axes[0][0], axes[0][1])
-    sid = plan.server_ids[0]
-    an.plot_single_server_ready_queue(axes[1][0], sid)
-    an.plot_single_server_ram(axes[1][1], sid)
-    fig.savefig(tmp_path / "dash.png")
-    assert (tmp_path / "dash.png").stat().st_size > 10_000
-    lines = axes[1][1].get_lines()
-    assert lines and np.array_equal(np.asarray(lines[0].get_ydata(), dtype=np.float64),
-                                    np.asarray(sc.get_sampled_metrics()["ram_in_use"][sid], dtype=np.float64))
-    plt.close(fig)
+    theirs = json.loads(str(_RECORDED["analyzer_lb2_rr_t30"]))
+    assert theirs["latency_stats"] == sc.get_latency_stats()
+    assert theirs["throughput"] == list(sc.get_throughput_series()[1])
+    assert theirs["server_ids"] == sc.list_server_ids()
+    sid = theirs["ram_plot_server"]
+    assert sid == plan.server_ids[0] and theirs["ram_plot_ydata"]
+    assert np.array_equal(np.asarray(theirs["ram_plot_ydata"], dtype=np.float64),
+                          np.asarray(sc.get_sampled_metrics()["ram_in_use"][sid], dtype=np.float64))
 
 
 # ------------------------------------------------------------- documented deviations, shown on the reference itself
@@ -157,12 +121,11 @@ def test_reference_raises_negative_delay_where_the_engine_reports_a_flag():
     ("Negative delay"); the oracle (and the engine: tests/test_hostcheck.py) carry AF_FLAG_NEGATIVE_DELAY instead, and
     asyncflow_amd.SimulationRunner raises the same ValueError for such a scenario."""
     from asyncflow_amd import _abi
-    from oracle.reference_runner import run_reference
     from oracle.scenarios import negative_spike_residue
 
     payload = negative_spike_residue(horizon=10)
-    with pytest.raises(ValueError, match="Negative delay"):
-        run_reference(payload, 3)
+    key = _recorded(payload, 3)
+    assert f"{key}.raised" in _RECORDED.files and str(_RECORDED[f"{key}.raised"]).startswith("ValueError: Negative delay")
     assert int(ol.simulate(lower(payload), 3).counts[_abi.CNT_FLAGS]) & _abi.FLAG_NEGATIVE_DELAY
     early = negative_spike_residue(horizon=6, shift=2.0)          # no residue yet: reference and oracle agree bit for bit
     _same(early, 3)
@@ -210,8 +173,8 @@ def test_fractional_ram_fuzz_matches_reference(case):
 
 @pytest.mark.parametrize("kw", [dict(front=1), dict(front=2, algo="least_connection", backend=True, spike=True), dict(front=1, general=True)])
 def test_gateway_in_front_of_the_load_balancer_matches_reference(kw):
-    """client -> server chain -> LB -> servers [-> backend] -> client (`graph.py:100-159` validates it): the oracle against the live
-    reference, bit for bit -- the topology the stage-parallel kernel took in in round 5."""
+    """client -> server chain -> LB -> servers [-> backend] -> client (`graph.py:100-159` validates it): the oracle against the
+    reference's recorded outputs, bit for bit -- the topology the stage-parallel kernel took in in round 5."""
     from oracle.scenarios import gateway_lb
 
     _same(gateway_lb(horizon=12, **kw), 5)
