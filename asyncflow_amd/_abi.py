@@ -235,11 +235,27 @@ class AfSummary(C.Structure):
     ]
 
 
+POOL_SKIP = 0xFFFFFFFF   # AF_POOL_SKIP: af_pooled_t.group of a scenario left out
+
+
+class AfPooled(C.Structure):
+    """``af_pooled_t``: request of ``af_engine_summarize_pooled`` (``elapsed_ms`` is written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("group", C.c_void_p),
+        ("stats", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+    ]
+
+
 #: every symbol include/asyncflow_hip.h declares
 EXPORTED_SYMBOLS = (
     "af_engine_create",
     "af_engine_run",
     "af_engine_summarize",
+    "af_engine_summarize_pooled",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
     "af_engine_set_kernels",
@@ -272,6 +288,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_run.restype = C.c_int
     lib.af_engine_summarize.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSummary)]
     lib.af_engine_summarize.restype = C.c_int
+    lib.af_engine_summarize_pooled.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfPooled)]
+    lib.af_engine_summarize_pooled.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]
     lib.af_engine_run_summarized.restype = C.c_int
     lib.af_engine_jit_spec.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.c_char_p, C.c_size_t]

@@ -145,18 +145,19 @@ __device__ inline double xor_add(double v, int m) { return v + __shfl_xor(v, m, 
 // numpy's np.add.reduce over the n values elem(row i) of a scenario, in numpy's own order (the head of this file).  `elem`
 // is called once per completion by the lane that owns it -- and by every other lane of the wave with act = false (it may
 // hold wave-wide operations) -- and returns the value to be added.  wsum: [2][kWaves] doubles, slots: [kTailSlots] doubles.
-template <int kLoads, class Elem>
-__device__ __forceinline__ double numpy_sum(const double2* ck, uint32_t n, double* wsum, double* slots, Elem&& elem) {
+// Rows are double2 clock rows here and plain f64 latencies in the pooled analyzer (af_pooled.hpp).
+template <int kLoads, class Row, class Elem>
+__device__ __forceinline__ double numpy_sum(const Row* ck, uint32_t n, double* wsum, double* slots, Elem&& elem) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const uint32_t j = (uint32_t)tid & 7u, g = (uint32_t)tid >> 3;
     double tot = 0.0;   // the reduction starts from the identity
     const uint32_t n_full = n / kPiece;
     for (uint32_t c = 0; c < n_full; ++c) {   // a full piece: leaf g = elements [128 g, 128 g + 128), lane j its running sum r[j]
-        const double2* p = ck + (size_t)c * kPiece + g * 128u + j;
+        const Row* p = ck + (size_t)c * kPiece + g * 128u + j;
         double acc = -0.0;   // (-0.0 + x == x for every x: the first row needs no case of its own)
 #pragma unroll 1
         for (int r0 = 0; r0 < kLeafRows; r0 += kLoads) {
-            double2 cc[kLoads];
+            Row cc[kLoads];
 #pragma unroll
             for (int v = 0; v < kLoads; ++v) cc[v] = p[(r0 + v) * 8];
 #pragma unroll
@@ -173,7 +174,7 @@ __device__ __forceinline__ double numpy_sum(const double2* ck, uint32_t n, doubl
     if (m == 0u) return tot;
     // the partial piece: the recursion's leaves hold 64 .. 128 elements (or all m <= 128), so every leaf holds a multiple of
     // 64; group g walks the recursion down to the leaf of element 64 g (and 64 (g + 64)) and takes it if it is the first there
-    const double2* q = ck + (size_t)n_full * kPiece;
+    const Row* q = ck + (size_t)n_full * kPiece;
     if (tid < kTailSlots) slots[tid] = __longlong_as_double((long long)kAbsent);
     __syncthreads();
     const uint32_t n_cand = (m + 63u) / 64u;
@@ -194,9 +195,9 @@ __device__ __forceinline__ double numpy_sum(const double2* ck, uint32_t n, doubl
         double acc = -0.0;
 #pragma unroll 1
         for (int r0 = 0; r0 < kLeafRows; r0 += kLoads) {   // (<= 16 rows; the trip count is uniform, the rows are not)
-            double2 cc[kLoads];
+            Row cc[kLoads];
 #pragma unroll
-            for (int v = 0; v < kLoads; ++v) cc[v] = (uint32_t)(r0 + v) < rows ? q[o + (uint32_t)(r0 + v) * 8u + j] : double2{0.0, 0.0};
+            for (int v = 0; v < kLoads; ++v) cc[v] = (uint32_t)(r0 + v) < rows ? q[o + (uint32_t)(r0 + v) * 8u + j] : Row{};
 #pragma unroll
             for (int v = 0; v < kLoads; ++v) {
                 const bool act = (uint32_t)(r0 + v) < rows;
@@ -210,7 +211,7 @@ __device__ __forceinline__ double numpy_sum(const double2* ck, uint32_t n, doubl
         if (rows == 0u) leaf = -0.0;   // n < 8: one after the other, from -0.0
         {   // the len % 8 elements left over (the piece's last leaf only), one by one
             const bool act = j < rem;
-            const double2 cc = act ? q[o + 8u * rows + j] : double2{0.0, 0.0};
+            const Row cc = act ? q[o + 8u * rows + j] : Row{};
             const double x = elem(cc, act);
 #pragma unroll
             for (int t = 0; t < 7; ++t) {

@@ -26,6 +26,7 @@
 #include <dlfcn.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -38,6 +39,7 @@
 #include "af_plan_pack.hpp"
 #include "af_pregen.hpp"
 #include "af_summary.hpp"
+#include "af_pooled.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -933,6 +935,8 @@ struct af_engine {
     uint32_t* d_done_count = nullptr;          // ... its device address
     uint32_t* d_retry = nullptr;               // [2][n + 1]: count, then the scenarios the latency / the series kernel met unfinished
     size_t retry_cap = 0;
+    unsigned char* d_pool = nullptr;           // af_engine_summarize_pooled's scratch (af_pooled.hpp: compacted latencies, histograms, ...)
+    size_t pool_cap = 0;
     int wait_value_ok = -1;                    // hipDeviceAttributeCanUseStreamWaitValue (-1: not asked yet)
     uint64_t done_ptrs[2] = {0, 0};            // host copy of d_fb[kDoneWords ..] (a member: an asynchronous copy reads it)
     bool shared_instants_likely = false;
@@ -2530,6 +2534,122 @@ int af_engine_summarize(af_engine_t* e, const af_outputs_t* out, const af_summar
     return AF_OK;
 }
 
+// Pooled analyzer (af_pooled.hpp): the host reads counts and group ids back, checks them, and lays out the compacted array,
+// the groups' pieces and the tiles of the streaming passes; the kernels run on the engine's stream, one digit level per launch
+// pair while some group still needs one (a 4-byte read-back decides).
+int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_pooled_t* pl) {
+    if (!e || !out || !pl) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (pl->n_scenarios == 0 || pl->n_groups == 0) return fail(AF_ERR_INVALID, "empty pooled request (n_scenarios and n_groups must be > 0)");
+    if (!pl->stats) return fail(AF_ERR_INVALID, "pooled.stats is required");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "pooled summary needs outputs.clock");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    const uint32_t n = pl->n_scenarios, G = pl->n_groups, cap = out->clock_capacity;
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp(pl->group ? n : 0u);
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    if (pl->group) HIP_TRY(hipMemcpy(grp.data(), pl->group, grp.size() * 4u, hipMemcpyDeviceToHost));
+    std::vector<uint64_t> g_n(G, 0u), dst(n, 0u);
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = pl->group ? grp[s] : 0u;
+        if (g == afp::kSkip) continue;
+        if (g >= G) return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
+        g_n[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], cap);
+    }
+    std::vector<afp::PoolGroup> groups(G);
+    std::vector<afp::PoolTile> tiles;
+    std::vector<uint64_t> cursor(G);
+    uint64_t off = 0, pieces = 0;
+    for (uint32_t g = 0; g < G; ++g) {
+        if (g_n[g] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "group " + std::to_string(g) + " pools 2^32 or more latencies");
+        afp::PoolGroup& pg = groups[g];
+        pg = afp::PoolGroup{};
+        pg.off = cursor[g] = off;
+        pg.n = (uint32_t)g_n[g];
+        pg.n_pieces = (uint32_t)((g_n[g] + afp::kPiece - 1u) / afp::kPiece);
+        pg.piece0 = (uint32_t)pieces;
+        pg.tile0 = (uint32_t)tiles.size();
+        for (uint32_t p = 0; p < pg.n_pieces; p += afp::kTilePieces)
+            tiles.push_back(afp::PoolTile{g, p, std::min(afp::kTilePieces, pg.n_pieces - p), 0u});
+        pg.n_tiles = (uint32_t)tiles.size() - pg.tile0;
+        off += g_n[g];
+        pieces += pg.n_pieces;
+    }
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = pl->group ? grp[s] : 0u;
+        if (g == afp::kSkip) continue;
+        dst[s] = cursor[g];
+        cursor[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], cap);
+    }
+    const uint32_t n_tiles = (uint32_t)tiles.size();
+    // scratch layout (256-byte aligned parts)
+    size_t at = 0;
+    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+    const size_t o_lat = part(off * 8u), o_dst = part((size_t)n * 8u), o_grp = part(G * sizeof(afp::PoolGroup)),
+                 o_tile = part(std::max<size_t>(n_tiles, 1u) * sizeof(afp::PoolTile)), o_piece = part(std::max<uint64_t>(pieces, 1u) * 8u),
+                 o_tmin = part(std::max<size_t>(n_tiles, 1u) * 8u), o_tmax = part(std::max<size_t>(n_tiles, 1u) * 8u),
+                 o_h0 = part((size_t)G * afp::kExpBins * 4u), o_dh = part((size_t)G * afp::kRanks * afp::kDigBins * 4u),
+                 o_cn = part((size_t)G * afp::kRanks * 4u), o_cd = part((size_t)G * afp::kRanks * afp::kCand * 8u), o_flag = part(4u);
+    if (at > e->pool_cap) {
+        if (e->d_pool) HIP_TRY(hipFree(e->d_pool));
+        e->d_pool = nullptr;
+        e->pool_cap = 0;
+        HIP_TRY(hipMalloc((void**)&e->d_pool, at));
+        e->pool_cap = at;
+    }
+    unsigned char* b = e->d_pool;
+    afp::PoolArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = cap;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.group = pl->group;
+    a.dst = reinterpret_cast<const uint64_t*>(b + o_dst);
+    a.lat = reinterpret_cast<double*>(b + o_lat);
+    a.groups = reinterpret_cast<afp::PoolGroup*>(b + o_grp);
+    a.tiles = reinterpret_cast<const afp::PoolTile*>(b + o_tile);
+    a.piece_sum = reinterpret_cast<double*>(b + o_piece);
+    a.tile_min = reinterpret_cast<double*>(b + o_tmin);
+    a.tile_max = reinterpret_cast<double*>(b + o_tmax);
+    a.hist0 = reinterpret_cast<uint32_t*>(b + o_h0);
+    a.dhist = reinterpret_cast<uint32_t*>(b + o_dh);
+    a.cand_n = reinterpret_cast<uint32_t*>(b + o_cn);
+    a.cand = reinterpret_cast<double*>(b + o_cd);
+    a.any_more = reinterpret_cast<uint32_t*>(b + o_flag);
+    a.stats = pl->stats;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(b + o_dst, dst.data(), (size_t)n * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_grp, groups.data(), G * sizeof(afp::PoolGroup), hipMemcpyHostToDevice, st));
+    if (n_tiles) HIP_TRY(hipMemcpyAsync(b + o_tile, tiles.data(), n_tiles * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(a.hist0, 0, (size_t)G * afp::kExpBins * 4u, st));
+    hipLaunchKernelGGL(afp::af_pool_compact, dim3(n), dim3(afp::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (n_tiles) hipLaunchKernelGGL(afp::af_pool_pass1, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    for (int level = 0;; ++level) {   // (shift 52 -> 42 -> ... -> 2 -> 0: at most six digit levels)
+        HIP_TRY(hipMemsetAsync(a.any_more, 0, 4u, st));
+        hipLaunchKernelGGL(afp::af_pool_select, dim3(G), dim3(afp::kThreads), 0, st, a, level);
+        HIP_TRY(hipGetLastError());
+        uint32_t more = 0;
+        HIP_TRY(hipMemcpyAsync(&more, a.any_more, 4u, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!more) break;
+        if (level >= 6) return fail(AF_ERR_HIP, "pooled analyzer: radix select did not converge");
+        HIP_TRY(hipMemsetAsync(a.dhist, 0, (size_t)G * afp::kRanks * afp::kDigBins * 4u, st));
+        hipLaunchKernelGGL(afp::af_pool_digits, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(a.cand_n, 0, (size_t)G * afp::kRanks * 4u, st));
+    if (n_tiles) hipLaunchKernelGGL(afp::af_pool_last, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(afp::af_pool_final, dim3(G), dim3(afp::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    pl->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
 // af_engine_run + af_engine_summarize in one call, with the same results.  Where the sweep runs as ONE launch sequence of the
 // stage-parallel kernel over alike scenarios (no launch order), the kernel is launched in two parts -- the scenarios of its full
 // residency rounds, then the rest -- and the analyzer of the first part runs on a second stream beside the second: the last,
@@ -2607,6 +2727,7 @@ void af_engine_destroy(af_engine_t* e) {
     if (e->stream2) (void)hipStreamDestroy(e->stream2);
     if (e->d_done_flags) (void)hipFree(e->d_done_flags);
     if (e->d_retry) (void)hipFree(e->d_retry);
+    if (e->d_pool) (void)hipFree(e->d_pool);
     if (e->h_done_count) (void)hipHostFree(e->h_done_count);
     if (e->d_draws) (void)hipFree(e->d_draws);
     if (e->d_pre_flags) (void)hipFree(e->d_pre_flags);

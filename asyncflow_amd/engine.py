@@ -271,6 +271,16 @@ class Engine:
         _check(self._lib, self._lib.af_engine_summarize(self._h, C.byref(out), C.byref(summ)), "af_engine_summarize")
         return self.stats()
 
+    def summarize_pooled(self, n: int, n_groups: int, *, clock_ptr: int, clock_capacity: int, counts_ptr: int,
+                         stats_ptr: int, group_ptr: int = 0) -> float:
+        """Pooled analyzer on the device (``af_engine_summarize_pooled``): the eight latency statistics of every group of
+        scenarios, its latencies taken as one sample, into ``stats`` [n_groups, 8] f64.  ``group_ptr``: DEVICE uint32 [n]
+        group ids (``_abi.POOL_SKIP`` leaves a scenario out), 0 = all in group 0.  Returns the call's wall time in ms."""
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), 0, None, C.c_void_p(counts_ptr))
+        req = _abi.AfPooled(int(n), int(n_groups), C.c_void_p(group_ptr or None), C.c_void_p(stats_ptr or None), 0.0)
+        _check(self._lib, self._lib.af_engine_summarize_pooled(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_pooled")
+        return float(req.elapsed_ms)
+
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:
         """``af_engine_gather``: ONE grouped RCCL all-gather of the per-scenario summaries.

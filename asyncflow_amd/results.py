@@ -412,18 +412,7 @@ class BatchedResults:
             cols["series_mean"] = summ["series_mean"].cpu().numpy()
             cols["series_max"] = self.decode_series_max(summ["series_max"].cpu().numpy())
             cols["series_names"] = np.asarray(self.series_names())
-        path = str(path)
-        if path.endswith(".parquet"):
-            import pyarrow as pa
-            import pyarrow.parquet as pq
-
-            n = len(self)
-            table = {k: (pa.array(list(v)) if v.ndim == 2 and v.shape[0] == n else pa.array(v))
-                     for k, v in cols.items() if v.shape[:1] == (n,)}
-            meta = {k: ",".join(map(str, v.tolist())) for k, v in cols.items() if v.shape[:1] != (n,)}
-            pq.write_table(pa.table(table).replace_schema_metadata(meta), path)
-        else:
-            np.savez_compressed(path, **cols)
+        _write_columns(str(path), cols, len(self))
         return cols
 
     def decode_series_max(self, words: np.ndarray) -> np.ndarray:
@@ -443,12 +432,73 @@ class BatchedResults:
             names += [f"{sid}:ready_queue_len", f"{sid}:event_loop_io_sleep", f"{sid}:ram_in_use"]
         return names
 
-    def aggregate(self, level: float = 0.95) -> dict[str, Any]:
+    def aggregate(self, level: float = 0.95, by: Any = None) -> dict[str, Any]:
         """Monte-Carlo aggregation over the scenarios of the sweep (the reference's roadmap
         item, ROADMAP.md:23-29): mean, standard deviation and normal-approximation confidence
         half-width of every latency statistic, plus the mean RPS band (5th/95th percentile
-        across scenarios per 1-s window)."""
-        return aggregate_summary(self.summary(rps=True), level)
+        across scenarios per 1-s window).  That is one band over the WHOLE batch: right for
+        replicas of one point.  ``by`` (a :class:`~asyncflow_amd.sweep.Sweep` or group ids, see
+        :func:`resolve_groups`) aggregates per group instead: :func:`aggregate_by_group`."""
+        if by is None:
+            return aggregate_summary(self.summary(rps=True), level)
+        self._require_clock()
+        ids, n_groups = resolve_groups(by, len(self))
+        out = aggregate_by_group(self.summary(rps=True), ids, n_groups, level)
+        out["pooled"] = self.pooled_summary(ids)["stats"].cpu().numpy()
+        return out
+
+    def _require_clock(self) -> None:
+        if self._clock_t is None:
+            msg = "run(collect_clock=False) kept no rqs_clock (pass online_summary=... to keep a kernel-side summary)"
+            raise RuntimeError(msg)
+
+    def pooled_summary(self, by: Any = None) -> dict[str, Any]:
+        """The eight latency statistics of every GROUP of scenarios, all its latencies taken as ONE sample (a grid
+        point's replicas pooled: what one long reference run estimates), computed by the HIP pooled analyzer
+        (``af_engine_summarize_pooled``), bit-equal to numpy's on the concatenated latencies of the group's scenarios in
+        ascending scenario order.  ``by``: a ``Sweep`` (its ``point``), integer group ids [n] (negative = left out), or
+        None (one group).  Returns ``stats`` float64 [G, 8] on the run's device (LATENCY_KEYS order; a group without
+        completions: total 0, the rest NaN), ``keys``, ``replicas`` [G] (scenarios per group) and ``pooled_ms``."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_clock()
+        ids, n_groups = resolve_groups(by, len(self))
+        clock = self._clock_t
+        dev = clock.device
+        stats = torch.empty((n_groups, 8), dtype=torch.float64, device=dev)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms = self._summ_engine.summarize_pooled(len(self), n_groups, clock_ptr=clock.data_ptr(),
+                                                clock_capacity=int(clock.shape[1]), counts_ptr=self._counts_t.data_ptr(),
+                                                stats_ptr=stats.data_ptr(), group_ptr=grp.data_ptr())
+        replicas = np.bincount(ids[ids >= 0], minlength=n_groups)
+        return {"stats": stats, "keys": LATENCY_KEYS, "replicas": replicas, "pooled_ms": ms}
+
+    def save_point_summary(self, path: str, by: Any, *, level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump with one row per group (grid point): ``param:<axis>`` (for a Sweep), ``replicas``,
+        ``pooled:<key>`` (the pooled statistics), ``mean:<key>`` / ``ci_halfwidth:<key>`` (over the group's replicas,
+        as :meth:`aggregate`) and the RPS bands ``rps_mean`` / ``rps_p05`` / ``rps_p95`` [G, floor(T)].  ``.npz`` or
+        ``.parquet`` like :meth:`save_summary`; :func:`load_summary` reads it back.  Returns the columns."""
+        agg = self.aggregate(level, by=by)
+        n_groups = int(agg["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(agg["replicas"], dtype=np.int64)
+        for j, k in enumerate(LATENCY_KEYS):
+            cols[f"pooled:{k}"] = agg["pooled"][:, j].copy()
+            cols[f"mean:{k}"] = agg["mean"][:, j].copy()
+            cols[f"ci_halfwidth:{k}"] = agg["ci_halfwidth"][:, j].copy()
+        for k in ("rps_mean", "rps_p05", "rps_p95"):
+            if k in agg:
+                cols[k] = agg[k]
+        _write_columns(str(path), cols, n_groups)
+        return cols
 
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
@@ -522,6 +572,110 @@ def aggregate_summary(summ: dict[str, Any], level: float = 0.95) -> dict[str, An
         q = torch.quantile(r, torch.tensor([0.05, 0.95], dtype=torch.float64, device=r.device), dim=0)
         out["rps_p05"], out["rps_p95"] = q[0].cpu().numpy(), q[1].cpu().numpy()
     return out
+
+
+def resolve_groups(by: Any, n: int) -> tuple[np.ndarray, int]:
+    """Group id of every scenario and the number of groups G for ``by``: None (one group), a Sweep (its grid points,
+    G = points of the grid) or an integer array [n] (negative = left out, G = largest id + 1).  Returns int64 ids [n]."""
+    if by is None:
+        return np.zeros(n, dtype=np.int64), 1
+    if hasattr(by, "point") and hasattr(by, "shape"):
+        ids = np.asarray(by.point)
+        n_groups = int(np.prod(by.shape)) if by.shape else 1
+    else:
+        ids = np.asarray(by)
+        n_groups = None
+    if ids.ndim != 1 or ids.shape[0] != n:
+        msg = f"group ids must be a vector of one id per scenario ({n}), not of shape {ids.shape}"
+        raise ValueError(msg)
+    if not (np.issubdtype(ids.dtype, np.integer) and ids.dtype != np.bool_):
+        msg = f"group ids must be integers, not {ids.dtype}"
+        raise TypeError(msg)
+    ids = ids.astype(np.int64)
+    if n_groups is None:
+        n_groups = int(ids.max()) + 1 if n and ids.max() >= 0 else 0
+    if n_groups == 0:
+        msg = "no scenario is in a group"
+        raise ValueError(msg)
+    if ids.max(initial=-1) >= n_groups:
+        msg = f"group id {int(ids.max())} out of range for {n_groups} groups"
+        raise ValueError(msg)
+    return ids, n_groups
+
+
+def aggregate_by_group(summ: dict[str, Any], ids: np.ndarray, n_groups: int, level: float = 0.95) -> dict[str, Any]:
+    """:func:`aggregate_summary` per group (``ids`` from :func:`resolve_groups`): for every group the mean, unbiased
+    standard deviation and normal confidence half-width of each per-replica statistic over its scenarios with >= 1
+    completion (``n`` [G] of them), and per 1-s window the mean and the 5th / 95th linear quantiles of the RPS over
+    the group's scenarios.  Reduced on the device (no loop over groups); returned as numpy arrays [G, 8] / [G, T]."""
+    from statistics import NormalDist
+
+    import torch
+
+    st = summ["stats"]
+    dev = st.device
+    gid = torch.as_tensor(ids, device=dev)
+    member = gid >= 0
+    ok = member & (st[:, 0] > 0)
+    z = NormalDist().inv_cdf(0.5 + level / 2.0)
+    g_ok, body = gid[ok], st[ok]
+    k = torch.bincount(g_ok, minlength=n_groups).to(torch.float64)
+    total = torch.zeros((n_groups, 8), dtype=torch.float64, device=dev).index_add_(0, g_ok, body)
+    mean = total / k[:, None]
+    dev2 = torch.zeros((n_groups, 8), dtype=torch.float64, device=dev).index_add_(0, g_ok, (body - mean[g_ok]) ** 2)
+    sd = torch.where((k > 1)[:, None], (dev2 / (k - 1.0).clamp(min=1.0)[:, None]).sqrt(), torch.full_like(dev2, float("nan")))
+    mean = torch.where((k > 0)[:, None], mean, torch.full_like(mean, float("nan")))
+    out: dict[str, Any] = {
+        "n": k.to(torch.int64).cpu().numpy(),
+        "replicas": np.bincount(ids[ids >= 0], minlength=n_groups),
+        "keys": LATENCY_KEYS,
+        "mean": mean.cpu().numpy(),
+        "std": sd.cpu().numpy(),
+        "ci_halfwidth": (z * sd / k.clamp(min=1.0).sqrt()[:, None]).cpu().numpy(),
+        "level": level,
+    }
+    if "rps" in summ:
+        r = summ["rps"].to(torch.float64)[member]
+        g = gid[member]
+        T = int(r.shape[1])
+        c = torch.bincount(g, minlength=n_groups)
+        out["rps_mean"] = (torch.zeros((n_groups, T), dtype=torch.float64, device=dev).index_add_(0, g, r)
+                           / c.to(torch.float64)[:, None]).cpu().numpy()
+        # every window sorted by value, then (stably) by group: each group's values ascending in one segment
+        v, order = torch.sort(r, dim=0, stable=True)
+        gs = g[order]
+        gs, order2 = torch.sort(gs, dim=0, stable=True)
+        v = torch.gather(v, 0, order2)
+        start = torch.cumsum(c, 0) - c
+        for name, q in (("rps_p05", 0.05), ("rps_p95", 0.95)):
+            pos = (c - 1).clamp(min=0).to(torch.float64) * q
+            lo = pos.floor().to(torch.int64)
+            hi = torch.minimum(lo + 1, (c - 1).clamp(min=0))
+            t = (pos - lo.to(torch.float64))[:, None]
+            if v.shape[0] == 0:
+                band = torch.full((n_groups, T), float("nan"), dtype=torch.float64, device=dev)
+            else:
+                a = v[(start + lo).clamp(max=v.shape[0] - 1)]
+                b = v[(start + hi).clamp(max=v.shape[0] - 1)]
+                d = b - a
+                band = torch.where(t >= 0.5, b - d * (1.0 - t), a + d * t)   # (numpy's _lerp)
+                band = torch.where((c > 0)[:, None], band, torch.full_like(band, float("nan")))
+            out[name] = band.cpu().numpy()
+    return out
+
+
+def _write_columns(path: str, cols: dict[str, np.ndarray], n: int) -> None:
+    """``.parquet`` (pyarrow; [n, k] columns become list columns, vectors of another length schema metadata) or ``.npz``."""
+    if path.endswith(".parquet"):
+        import pyarrow as pa
+        import pyarrow.parquet as pq
+
+        table = {k: (pa.array(list(v)) if v.ndim == 2 and v.shape[0] == n else pa.array(v))
+                 for k, v in cols.items() if v.shape[:1] == (n,)}
+        meta = {k: ",".join(map(str, v.tolist())) for k, v in cols.items() if v.shape[:1] != (n,)}
+        pq.write_table(pa.table(table).replace_schema_metadata(meta), path)
+    else:
+        np.savez_compressed(path, **cols)
 
 
 class ShardedResults:
@@ -638,8 +792,19 @@ class ShardedResults:
                 out[key] = torch.cat([p[key].to(dev) for p in parts], dim=0).index_select(0, order)
         return out
 
-    def aggregate(self, level: float = 0.95) -> dict[str, Any]:
+    def aggregate(self, level: float = 0.95, by: Any = None) -> dict[str, Any]:
+        if by is not None:
+            msg = "aggregate(by=...) of a sweep run on several devices: pooling across devices is not implemented"
+            raise NotImplementedError(msg)
         return aggregate_summary(self.summary(rps=True), level)
+
+    def pooled_summary(self, by: Any = None) -> dict[str, Any]:
+        msg = "pooled_summary() of a sweep run on several devices: pooling across devices is not implemented"
+        raise NotImplementedError(msg)
+
+    def save_point_summary(self, path: str, by: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_point_summary() of a sweep run on several devices: pooling across devices is not implemented"
+        raise NotImplementedError(msg)
 
 
 def load_summary(path: str) -> dict[str, np.ndarray]:

@@ -32,6 +32,12 @@ class Sweep:
         """``SimulationRunner(simulation_input=payload, **sweep.runner_kwargs())``."""
         return {"seeds": self.seeds, "sweep": self.columns}
 
+    def point_columns(self) -> dict[str, np.ndarray]:
+        """``{axis: values [P]}`` of the grid points in row-major point order (``point`` indexes these rows)."""
+        vals = list(self.axes.values())
+        mesh = np.meshgrid(*vals, indexing="ij") if vals else []
+        return {k: m.reshape(-1).copy() for k, m in zip(self.axes, mesh)}
+
     def by_point(self, values: np.ndarray) -> np.ndarray:
         """Reshape per-scenario ``values`` [n, ...] to [*shape, replicas, ...] (sorted scenarios undone)."""
         values = np.asarray(values)

@@ -384,6 +384,24 @@ typedef struct af_summary_t {
  * series outputs).  Synchronous like af_engine_run. */
 int af_engine_summarize(af_engine_t* engine, const af_outputs_t* out, const af_summary_t* summary);
 
+/* Pooled analyzer: the same eight statistics per GROUP of scenarios, all latencies of a group taken as one sample
+ * (a grid point's replicas: what a long reference run estimates).  Group g's sample is the concatenation, in ascending
+ * scenario index, of finish - start over the stored rows of its scenarios (min(counts[AF_CNT_COMPLETED], clock_capacity)
+ * each); every statistic is bit-equal to numpy's on that array, mean and std_dev included.  A group without completions:
+ * total 0, the rest NaN.  group[s] = AF_POOL_SKIP leaves scenario s out; any other id must be < n_groups.  A group of 2^32
+ * or more latencies is refused (AF_ERR_CAPACITY).  The engine keeps a scratch buffer of 8 B per pooled completion plus
+ * ~56 KB per group (asyncflow_amd/csrc/af_pooled.hpp).  Synchronous like af_engine_summarize; the struct is written back
+ * (elapsed_ms), hence the non-const pointer. */
+#define AF_POOL_SKIP 0xFFFFFFFFu
+typedef struct af_pooled {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    const uint32_t* group;  /* DEVICE [n_scenarios] group id per scenario; NULL: all in group 0 */
+    double* stats;          /* DEVICE [n_groups][8] f64, LatencyKey order as af_summary_t.stats */
+    double elapsed_ms;      /* out: wall time of the call */
+} af_pooled_t;
+int af_engine_summarize_pooled(af_engine_t* engine, const af_outputs_t* out, af_pooled_t* pooled);
+
 /* af_engine_run followed by af_engine_summarize, in one call and with the same results (replaces SimulationRunner.run +
  * ResultsAnalyzer.process_all_metrics, simulation_runner.py:349-376 + analyzer.py:75-81, for the whole sweep).
  * summary->n_scenarios must equal sweep->n_scenarios.  Where the sweep is ONE launch of the stage-parallel kernel, the analyzer
