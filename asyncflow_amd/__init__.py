@@ -8,7 +8,7 @@ executed over thousands of independent scenarios by a hand-written HIP kernel
 
 from .payload import load_yaml, normalize_payload
 from .plan import DevicePlan, lower
-from .results import BatchedResults, ScenarioResults
+from .results import BatchedResults, ScenarioResults, latency_window_stats, window_edges
 from .runner import SimulationRunner
 from .sweep import Sweep, expand_grid
 
@@ -19,9 +19,11 @@ __all__ = [
     "SimulationRunner",
     "Sweep",
     "expand_grid",
+    "latency_window_stats",
     "load_yaml",
     "lower",
     "normalize_payload",
+    "window_edges",
 ]
 
 __version__ = "0.1.0"

@@ -80,6 +80,7 @@ struct PoolArgs {
     double* cand;            // [G][kRanks][kCand]
     uint32_t* any_more;      // [1]
     double* stats;           // [G][8]
+    const uint32_t* stat_row;   // null, or group g's statistics go to row stat_row[g] of stats (af_windowed.hpp: the large cells)
 };
 
 __device__ __forceinline__ unsigned long long key_of(double x) { return (unsigned long long)__double_as_longlong(x); }
@@ -235,7 +236,7 @@ __global__ __launch_bounds__(kThreads) void af_pool_select(PoolArgs a, int level
     const uint32_t n = g->n;
     if (level == 0) {
         if (n == 0u) {   // the reference leaves latency_stats empty (analyzer.py:105-106)
-            if (tid < 8) a.stats[(size_t)gi * 8u + tid] = tid == 0 ? 0.0 : __builtin_nan("");
+            if (tid < 8) a.stats[(size_t)(a.stat_row ? a.stat_row[gi] : gi) * 8u + tid] = tid == 0 ? 0.0 : __builtin_nan("");
             if (tid == 0) g->more = 0u;
             return;
         }
@@ -425,7 +426,7 @@ __global__ __launch_bounds__(kThreads) void af_pool_final(PoolArgs a) {
             const double d = hi - lo;
             return t >= 0.5 ? hi - d * (1.0 - t) : lo + d * t;
         };
-        double* st = a.stats + (size_t)gi * 8u;
+        double* st = a.stats + (size_t)(a.stat_row ? a.stat_row[gi] : gi) * 8u;
         st[0] = (double)n;
         st[1] = g->mean;
         st[2] = (n & 1u) ? val[1] : (val[0] + val[1]) / 2.0;

@@ -40,6 +40,7 @@
 #include "af_pregen.hpp"
 #include "af_summary.hpp"
 #include "af_pooled.hpp"
+#include "af_windowed.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -2534,6 +2535,96 @@ int af_engine_summarize(af_engine_t* e, const af_outputs_t* out, const af_summar
     return AF_OK;
 }
 
+// The pooled analyzer's engine-owned scratch: grown on demand (the contents are lost then), kept until the engine is destroyed.
+static int pool_reserve(af_engine_t* e, size_t bytes) {
+    if (bytes <= e->pool_cap) return AF_OK;
+    if (e->d_pool) HIP_TRY(hipFree(e->d_pool));
+    e->d_pool = nullptr;
+    e->pool_cap = 0;
+    HIP_TRY(hipMalloc((void**)&e->d_pool, bytes));
+    e->pool_cap = bytes;
+    return AF_OK;
+}
+
+// the parts of that scratch that the tiled passes need for G groups (256-byte aligned, from `at` on)
+struct PoolParts {
+    size_t grp, tile, piece, tmin, tmax, h0, dh, cn, cd, flag;
+};
+static PoolParts pool_parts(size_t& at, size_t G, size_t n_tiles, uint64_t pieces) {
+    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+    PoolParts p{};
+    p.grp = part(std::max<size_t>(G, 1u) * sizeof(afp::PoolGroup));
+    p.tile = part(std::max<size_t>(n_tiles, 1u) * sizeof(afp::PoolTile));
+    p.piece = part(std::max<uint64_t>(pieces, 1u) * 8u);
+    p.tmin = part(std::max<size_t>(n_tiles, 1u) * 8u);
+    p.tmax = part(std::max<size_t>(n_tiles, 1u) * 8u);
+    p.h0 = part(G * afp::kExpBins * 4u);
+    p.dh = part(G * afp::kRanks * afp::kDigBins * 4u);
+    p.cn = part(G * afp::kRanks * 4u);
+    p.cd = part(G * afp::kRanks * afp::kCand * 8u);
+    p.flag = part(4u);
+    return p;
+}
+static void pool_bind(afp::PoolArgs& a, unsigned char* b, const PoolParts& p) {
+    a.groups = reinterpret_cast<afp::PoolGroup*>(b + p.grp);
+    a.tiles = reinterpret_cast<const afp::PoolTile*>(b + p.tile);
+    a.piece_sum = reinterpret_cast<double*>(b + p.piece);
+    a.tile_min = reinterpret_cast<double*>(b + p.tmin);
+    a.tile_max = reinterpret_cast<double*>(b + p.tmax);
+    a.hist0 = reinterpret_cast<uint32_t*>(b + p.h0);
+    a.dhist = reinterpret_cast<uint32_t*>(b + p.dh);
+    a.cand_n = reinterpret_cast<uint32_t*>(b + p.cn);
+    a.cand = reinterpret_cast<double*>(b + p.cd);
+    a.any_more = reinterpret_cast<uint32_t*>(b + p.flag);
+}
+
+// one group more of `n` latencies at `off` of the compacted array: its pieces and the tiles of the streaming passes
+static void pool_add_group(std::vector<afp::PoolGroup>& groups, std::vector<afp::PoolTile>& tiles, uint64_t& pieces, uint64_t off, uint32_t n) {
+    const uint32_t g = (uint32_t)groups.size();
+    afp::PoolGroup pg{};
+    pg.off = off;
+    pg.n = n;
+    pg.n_pieces = (uint32_t)(((uint64_t)n + afp::kPiece - 1u) / afp::kPiece);
+    pg.piece0 = (uint32_t)pieces;
+    pg.tile0 = (uint32_t)tiles.size();
+    for (uint32_t p = 0; p < pg.n_pieces; p += afp::kTilePieces)
+        tiles.push_back(afp::PoolTile{g, p, std::min(afp::kTilePieces, pg.n_pieces - p), 0u});
+    pg.n_tiles = (uint32_t)tiles.size() - pg.tile0;
+    pieces += pg.n_pieces;
+    groups.push_back(pg);
+}
+
+// the passes over the compacted latencies (af_pooled.hpp) on the engine's stream, one digit level per launch pair while some
+// group still needs one (a 4-byte read-back decides); the last kernel is launched, not waited for
+static int pool_run(af_engine_t* e, const afp::PoolArgs& a, const std::vector<afp::PoolGroup>& groups, const std::vector<afp::PoolTile>& tiles) {
+    hipStream_t st = e->stream;
+    const uint32_t G = (uint32_t)groups.size(), n_tiles = (uint32_t)tiles.size();
+    HIP_TRY(hipMemcpyAsync(a.groups, groups.data(), (size_t)G * sizeof(afp::PoolGroup), hipMemcpyHostToDevice, st));
+    if (n_tiles) HIP_TRY(hipMemcpyAsync(const_cast<afp::PoolTile*>(a.tiles), tiles.data(), (size_t)n_tiles * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(a.hist0, 0, (size_t)G * afp::kExpBins * 4u, st));
+    if (n_tiles) hipLaunchKernelGGL(afp::af_pool_pass1, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    for (int level = 0;; ++level) {   // (shift 52 -> 42 -> ... -> 2 -> 0: at most six digit levels)
+        HIP_TRY(hipMemsetAsync(a.any_more, 0, 4u, st));
+        hipLaunchKernelGGL(afp::af_pool_select, dim3(G), dim3(afp::kThreads), 0, st, a, level);
+        HIP_TRY(hipGetLastError());
+        uint32_t more = 0;
+        HIP_TRY(hipMemcpyAsync(&more, a.any_more, 4u, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!more) break;
+        if (level >= 6) return fail(AF_ERR_HIP, "pooled analyzer: radix select did not converge");
+        HIP_TRY(hipMemsetAsync(a.dhist, 0, (size_t)G * afp::kRanks * afp::kDigBins * 4u, st));
+        hipLaunchKernelGGL(afp::af_pool_digits, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipMemsetAsync(a.cand_n, 0, (size_t)G * afp::kRanks * 4u, st));
+    if (n_tiles) hipLaunchKernelGGL(afp::af_pool_last, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(afp::af_pool_final, dim3(G), dim3(afp::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    return AF_OK;
+}
+
 // Pooled analyzer (af_pooled.hpp): the host reads counts and group ids back, checks them, and lays out the compacted array,
 // the groups' pieces and the tiles of the streaming passes; the kernels run on the engine's stream, one digit level per launch
 // pair while some group still needs one (a 4-byte read-back decides).
@@ -2557,24 +2648,16 @@ int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_poole
         if (g >= G) return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
         g_n[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], cap);
     }
-    std::vector<afp::PoolGroup> groups(G);
+    std::vector<afp::PoolGroup> groups;
     std::vector<afp::PoolTile> tiles;
     std::vector<uint64_t> cursor(G);
+    groups.reserve(G);
     uint64_t off = 0, pieces = 0;
     for (uint32_t g = 0; g < G; ++g) {
         if (g_n[g] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "group " + std::to_string(g) + " pools 2^32 or more latencies");
-        afp::PoolGroup& pg = groups[g];
-        pg = afp::PoolGroup{};
-        pg.off = cursor[g] = off;
-        pg.n = (uint32_t)g_n[g];
-        pg.n_pieces = (uint32_t)((g_n[g] + afp::kPiece - 1u) / afp::kPiece);
-        pg.piece0 = (uint32_t)pieces;
-        pg.tile0 = (uint32_t)tiles.size();
-        for (uint32_t p = 0; p < pg.n_pieces; p += afp::kTilePieces)
-            tiles.push_back(afp::PoolTile{g, p, std::min(afp::kTilePieces, pg.n_pieces - p), 0u});
-        pg.n_tiles = (uint32_t)tiles.size() - pg.tile0;
+        cursor[g] = off;
+        pool_add_group(groups, tiles, pieces, off, (uint32_t)g_n[g]);
         off += g_n[g];
-        pieces += pg.n_pieces;
     }
     for (uint32_t s = 0; s < n; ++s) {
         const uint32_t g = pl->group ? grp[s] : 0u;
@@ -2586,18 +2669,9 @@ int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_poole
     // scratch layout (256-byte aligned parts)
     size_t at = 0;
     auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
-    const size_t o_lat = part(off * 8u), o_dst = part((size_t)n * 8u), o_grp = part(G * sizeof(afp::PoolGroup)),
-                 o_tile = part(std::max<size_t>(n_tiles, 1u) * sizeof(afp::PoolTile)), o_piece = part(std::max<uint64_t>(pieces, 1u) * 8u),
-                 o_tmin = part(std::max<size_t>(n_tiles, 1u) * 8u), o_tmax = part(std::max<size_t>(n_tiles, 1u) * 8u),
-                 o_h0 = part((size_t)G * afp::kExpBins * 4u), o_dh = part((size_t)G * afp::kRanks * afp::kDigBins * 4u),
-                 o_cn = part((size_t)G * afp::kRanks * 4u), o_cd = part((size_t)G * afp::kRanks * afp::kCand * 8u), o_flag = part(4u);
-    if (at > e->pool_cap) {
-        if (e->d_pool) HIP_TRY(hipFree(e->d_pool));
-        e->d_pool = nullptr;
-        e->pool_cap = 0;
-        HIP_TRY(hipMalloc((void**)&e->d_pool, at));
-        e->pool_cap = at;
-    }
+    const size_t o_lat = part(off * 8u), o_dst = part((size_t)n * 8u);
+    const PoolParts pp = pool_parts(at, G, n_tiles, pieces);
+    if (int rc = pool_reserve(e, at)) return rc;
     unsigned char* b = e->d_pool;
     afp::PoolArgs a{};
     a.clock = out->clock;
@@ -2607,46 +2681,162 @@ int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_poole
     a.group = pl->group;
     a.dst = reinterpret_cast<const uint64_t*>(b + o_dst);
     a.lat = reinterpret_cast<double*>(b + o_lat);
-    a.groups = reinterpret_cast<afp::PoolGroup*>(b + o_grp);
-    a.tiles = reinterpret_cast<const afp::PoolTile*>(b + o_tile);
-    a.piece_sum = reinterpret_cast<double*>(b + o_piece);
-    a.tile_min = reinterpret_cast<double*>(b + o_tmin);
-    a.tile_max = reinterpret_cast<double*>(b + o_tmax);
-    a.hist0 = reinterpret_cast<uint32_t*>(b + o_h0);
-    a.dhist = reinterpret_cast<uint32_t*>(b + o_dh);
-    a.cand_n = reinterpret_cast<uint32_t*>(b + o_cn);
-    a.cand = reinterpret_cast<double*>(b + o_cd);
-    a.any_more = reinterpret_cast<uint32_t*>(b + o_flag);
+    pool_bind(a, b, pp);
     a.stats = pl->stats;
     hipStream_t st = e->stream;
     HIP_TRY(hipMemcpyAsync(b + o_dst, dst.data(), (size_t)n * 8u, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b + o_grp, groups.data(), G * sizeof(afp::PoolGroup), hipMemcpyHostToDevice, st));
-    if (n_tiles) HIP_TRY(hipMemcpyAsync(b + o_tile, tiles.data(), n_tiles * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(a.hist0, 0, (size_t)G * afp::kExpBins * 4u, st));
     hipLaunchKernelGGL(afp::af_pool_compact, dim3(n), dim3(afp::kThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
-    if (n_tiles) hipLaunchKernelGGL(afp::af_pool_pass1, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    for (int level = 0;; ++level) {   // (shift 52 -> 42 -> ... -> 2 -> 0: at most six digit levels)
-        HIP_TRY(hipMemsetAsync(a.any_more, 0, 4u, st));
-        hipLaunchKernelGGL(afp::af_pool_select, dim3(G), dim3(afp::kThreads), 0, st, a, level);
-        HIP_TRY(hipGetLastError());
-        uint32_t more = 0;
-        HIP_TRY(hipMemcpyAsync(&more, a.any_more, 4u, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (!more) break;
-        if (level >= 6) return fail(AF_ERR_HIP, "pooled analyzer: radix select did not converge");
-        HIP_TRY(hipMemsetAsync(a.dhist, 0, (size_t)G * afp::kRanks * afp::kDigBins * 4u, st));
-        hipLaunchKernelGGL(afp::af_pool_digits, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemsetAsync(a.cand_n, 0, (size_t)G * afp::kRanks * 4u, st));
-    if (n_tiles) hipLaunchKernelGGL(afp::af_pool_last, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(afp::af_pool_final, dim3(G), dim3(afp::kThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
+    if (int rc = pool_run(e, a, groups, tiles)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     pl->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Windowed analyzer (af_windowed.hpp).  The host reads the row bounds back and lays out the cells (group g, window w) of the
+// compacted array; cells of at most one numpy piece are reduced by one workgroup each, larger ones by the pooled analyzer's
+// tiled passes.
+int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) {
+    if (!e || !out || !win) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (win->n_scenarios == 0 || win->n_groups == 0 || win->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty windows request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!win->stats) return fail(AF_ERR_INVALID, "windows.stats is required");
+    if (!win->edges) return fail(AF_ERR_INVALID, "windows.edges is required");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "windowed summary needs outputs.clock");
+    const uint32_t n = win->n_scenarios, G = win->n_groups, W = win->n_windows, cap = out->clock_capacity;
+    for (uint32_t k = 0; k <= W; ++k) {
+        if (!std::isfinite(win->edges[k])) return fail(AF_ERR_INVALID, "window edge " + std::to_string(k) + " is not finite");
+        if (k > 0 && !(win->edges[k - 1] < win->edges[k]))
+            return fail(AF_ERR_INVALID, "window edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    }
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if ((uint64_t)n * ((uint64_t)W + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (n_windows + 1) must be below 2^32");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t C = (size_t)G * W, NE = (size_t)n * (W + 1u);
+    std::vector<uint32_t> grp(win->group ? n : 0u);
+    if (win->group) HIP_TRY(hipMemcpy(grp.data(), win->group, grp.size() * 4u, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = win->group ? grp[s] : 0u;
+        if (g != afw::kSkip && g >= G)
+            return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
+    }
+    // scratch, first part: edges, the error word, the bounds (unless the caller takes them)
+    size_t at = 0;
+    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+    const size_t o_edges = part(((size_t)W + 1u) * 8u), o_err = part(4u), o_bounds = win->row_bounds ? 0u : part(NE * 4u);
+    if (int rc = pool_reserve(e, at)) return rc;
+    hipStream_t st = e->stream;
+    afw::WinArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = cap;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.group = win->group;
+    a.n_scen = n;
+    a.n_win = W;
+    a.stats = win->stats;
+    auto bind_first = [&]() {
+        unsigned char* b = e->d_pool;
+        a.edges = reinterpret_cast<const double*>(b + o_edges);
+        a.err = reinterpret_cast<uint32_t*>(b + o_err);
+        a.bounds = win->row_bounds ? win->row_bounds : reinterpret_cast<uint32_t*>(b + o_bounds);
+    };
+    bind_first();
+    HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, win->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> hb(NE);
+    HIP_TRY(hipMemcpyAsync(hb.data(), a.bounds, NE * 4u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the cells: sizes, and per (scenario, window) the latencies of its cell that earlier members bring
+    std::vector<uint64_t> cell_off(C + 1u, 0u);   // (first the sizes, at [c + 1])
+    std::vector<uint32_t> pre((size_t)n * W);
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = win->group ? grp[s] : 0u;
+        if (g == afw::kSkip) continue;
+        const uint32_t* r = hb.data() + (size_t)s * (W + 1u);
+        uint64_t* sz = cell_off.data() + 1u + (size_t)g * W;
+        uint32_t* ps = pre.data() + (size_t)s * W;
+        for (uint32_t w = 0; w < W; ++w) {
+            if (r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
+                return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
+            if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
+            ps[w] = (uint32_t)sz[w];
+            sz[w] += r[w + 1u] - r[w];
+        }
+    }
+    std::vector<afp::PoolGroup> groups;
+    std::vector<afp::PoolTile> tiles;
+    std::vector<uint32_t> stat_row, small;
+    uint64_t pieces = 0;
+    for (size_t c = 0; c < C; ++c) {
+        const uint64_t len = cell_off[c + 1u];
+        if (len > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(c % W) + " of group " + std::to_string(c / W) + " holds 2^32 or more latencies");
+        if (len > afw::kSmallMax) {
+            pool_add_group(groups, tiles, pieces, cell_off[c], (uint32_t)len);
+            stat_row.push_back((uint32_t)c);
+        } else if (len > afw::kTinyMax) {
+            small.push_back((uint32_t)c);
+        }
+        cell_off[c + 1u] = cell_off[c] + len;
+    }
+    const uint64_t total = cell_off[C];
+    const uint32_t n_large = (uint32_t)groups.size(), n_tiles = (uint32_t)tiles.size(), n_small = (uint32_t)small.size();
+    // scratch, second part
+    const size_t o_lat = part(total * 8u), o_pre = part((size_t)n * W * 4u), o_off = part((C + 1u) * 8u), o_row = part((size_t)n_large * 4u),
+                 o_small = part((size_t)n_small * 4u);
+    const PoolParts pp = n_large ? pool_parts(at, n_large, n_tiles, pieces) : PoolParts{};
+    if (at > e->pool_cap) {   // the scratch moves: its first part again
+        if (int rc = pool_reserve(e, at)) return rc;
+        bind_first();
+        HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, win->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+        if (!win->row_bounds) HIP_TRY(hipMemcpyAsync(a.bounds, hb.data(), NE * 4u, hipMemcpyHostToDevice, st));
+    }
+    unsigned char* b = e->d_pool;
+    a.lat = reinterpret_cast<double*>(b + o_lat);
+    a.pre = reinterpret_cast<const uint32_t*>(b + o_pre);
+    a.cell_off = reinterpret_cast<const uint64_t*>(b + o_off);
+    a.small = reinterpret_cast<const uint32_t*>(b + o_small);
+    const uint32_t no_error = afw::kNoError;
+    HIP_TRY(hipMemcpyAsync(b + o_pre, pre.data(), (size_t)n * W * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_off, cell_off.data(), (C + 1u) * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(a.err, &no_error, 4u, hipMemcpyHostToDevice, st));
+    if (n_small) HIP_TRY(hipMemcpyAsync(b + o_small, small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
+    if (W <= afw::kLdsWindows)
+        hipLaunchKernelGGL(afw::af_win_compact<true>, dim3(n), dim3(afw::kThreads), (size_t)W * 8u + ((size_t)W + 1u) * 4u, st, a);
+    else
+        hipLaunchKernelGGL(afw::af_win_compact<false>, dim3(n), dim3(afw::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    uint32_t bad = afw::kNoError;
+    HIP_TRY(hipMemcpyAsync(&bad, a.err, 4u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    win->scratch_bytes = e->pool_cap;
+    if (bad != afw::kNoError)
+        return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(bad) + " is not in completion order (finish decreases): windows by finish time need it");
+    constexpr uint64_t kBlocksPerLaunch = 1u << 21;   // (at most 2^30 threads a launch)
+    for (uint64_t c0 = 0; c0 < C; c0 += kBlocksPerLaunch * afw::kTinyWaves) {   // every cell: a wave takes it if it is tiny (or empty)
+        const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (C - c0 + afw::kTinyWaves - 1u) / afw::kTinyWaves);
+        hipLaunchKernelGGL(afw::af_win_tiny, dim3((uint32_t)blocks), dim3(afw::kTinyWaves * 64), 0, st, a, c0, (uint64_t)C);
+        HIP_TRY(hipGetLastError());
+    }
+    for (uint64_t c0 = 0; c0 < n_small; c0 += kBlocksPerLaunch) {
+        hipLaunchKernelGGL(afw::af_win_small, dim3((uint32_t)std::min<uint64_t>(kBlocksPerLaunch, n_small - c0)), dim3(afw::kThreads), 0, st, a, (uint32_t)c0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_large) {
+        afp::PoolArgs pa{};
+        pa.lat = a.lat;
+        pool_bind(pa, b, pp);
+        pa.stats = win->stats;
+        pa.stat_row = reinterpret_cast<const uint32_t*>(b + o_row);
+        HIP_TRY(hipMemcpyAsync(b + o_row, stat_row.data(), (size_t)n_large * 4u, hipMemcpyHostToDevice, st));
+        if (int rc = pool_run(e, pa, groups, tiles)) return rc;
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    win->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
 

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 import os
 from pathlib import Path
-from typing import Sequence
+from typing import Any, Sequence
 
 import numpy as np
 
@@ -280,6 +280,23 @@ class Engine:
         req = _abi.AfPooled(int(n), int(n_groups), C.c_void_p(group_ptr or None), C.c_void_p(stats_ptr or None), 0.0)
         _check(self._lib, self._lib.af_engine_summarize_pooled(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_pooled")
         return float(req.elapsed_ms)
+
+    def summarize_windows(self, n: int, n_groups: int, edges: Any, *, clock_ptr: int, clock_capacity: int, counts_ptr: int,
+                          stats_ptr: int, group_ptr: int = 0, row_bounds_ptr: int = 0) -> tuple[float, int]:
+        """Windowed analyzer on the device (``af_engine_summarize_windows``): the eight latency statistics of every
+        (group, window by finish time) into ``stats`` [n_groups, W, 8] f64, W = len(edges) - 1 (``edges``: HOST float64,
+        strictly increasing).  ``group_ptr`` as in :meth:`summarize_pooled`; ``row_bounds_ptr``: optional DEVICE uint32
+        [n, W + 1] for the windows' row ranges.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+        if e.ndim != 1 or e.shape[0] < 2:
+            msg = f"window edges must be a vector of at least two values, not of shape {e.shape}"
+            raise ValueError(msg)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), 0, None, C.c_void_p(counts_ptr))
+        req = _abi.AfWindows(int(n), int(n_groups), int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
+                             e.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stats_ptr or None),
+                             C.c_void_p(row_bounds_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_windows(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_windows")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
 
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:

@@ -23,6 +23,73 @@ LATENCY_KEYS = ("total_requests", "mean", "median", "std_dev", "p95", "p99", "mi
 Series = tuple[list[float], list[float]]
 
 
+def window_edges(window_s: float, total_time: float) -> np.ndarray:
+    """Edges ``[0.0, w, w + w, ...]`` of the windows of ``window_s`` seconds up to ``total_time``, accumulated in floating
+    point exactly as :meth:`ScenarioResults.get_throughput_series` accumulates its timestamps (the reference's loop,
+    analyzer.py:107-125): ``window_edges(w, T)[1:]`` ARE those timestamps, so a window's ``total_requests / w`` is the
+    throughput series' value."""
+    w = float(window_s)
+    if not (np.isfinite(w) and w > 0.0):
+        msg = f"window_s must be a positive number of seconds, not {window_s!r}"
+        raise ValueError(msg)
+    out = [0.0]
+    current_end = w
+    while current_end <= total_time:
+        out.append(current_end)
+        current_end += w
+    return np.asarray(out, dtype=np.float64)
+
+
+def check_edges(edges: Any) -> np.ndarray:
+    """``edges`` as a float64 vector, or ValueError: at least two values, all finite, strictly increasing."""
+    e = np.array(edges, dtype=np.float64)
+    if e.ndim != 1 or e.shape[0] < 2:
+        msg = f"window edges must be a vector of at least two values, not of shape {e.shape}"
+        raise ValueError(msg)
+    if not np.isfinite(e).all():
+        msg = "window edges must be finite"
+        raise ValueError(msg)
+    if not (np.diff(e) > 0.0).all():
+        msg = "window edges must be strictly increasing"
+        raise ValueError(msg)
+    return e
+
+
+def _resolve_edges(window_s: float | None, edges: Any, total_time: float) -> np.ndarray:
+    if edges is not None:
+        if window_s is not None:
+            msg = "pass window_s or edges, not both"
+            raise ValueError(msg)
+        return check_edges(edges)
+    return check_edges(window_edges(1.0 if window_s is None else window_s, total_time))
+
+
+def latency_stats_row(arr: np.ndarray) -> np.ndarray:
+    """The eight statistics of one latency sample in LATENCY_KEYS order, by the reference's numpy calls
+    (analyzer.py:83-104); an empty sample: total 0, the rest NaN."""
+    if not arr.size:
+        return np.array([0.0] + [np.nan] * 7)
+    return np.array([float(arr.size), np.mean(arr), np.median(arr), np.std(arr), np.percentile(arr, 95),
+                     np.percentile(arr, 99), np.min(arr), np.max(arr)], dtype=np.float64)
+
+
+def latency_window_stats(clock: np.ndarray, edges: Any) -> np.ndarray:
+    """Latency statistics per time window of ONE scenario's ``rqs_clock`` [m, 2] (start, finish): float64 [W, 8] in
+    LATENCY_KEYS order.  Window w holds the rows with ``edges[w] < finish <= edges[w + 1]`` (the bucket rule of the
+    throughput series); rows are in completion order, so that is the row range between two ``np.searchsorted(finish,
+    edges, side="right")`` positions.  The definition the device analyzer (``af_engine_summarize_windows``) is
+    bit-equal to."""
+    e = check_edges(edges)
+    ck = np.asarray(clock, dtype=np.float64).reshape(-1, 2)
+    finish = ck[:, 1]
+    if finish.size > 1 and (np.diff(finish) < 0.0).any():
+        msg = "rqs_clock is not in completion order (finish decreases): windows by finish time need it"
+        raise ValueError(msg)
+    lat = finish - ck[:, 0]
+    r = np.searchsorted(finish, e, side="right")
+    return np.stack([latency_stats_row(lat[r[w]:r[w + 1]]) for w in range(e.shape[0] - 1)])
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -145,6 +212,11 @@ class ScenarioResults:
         if window_s is None or window_s == self._WINDOW_SIZE_S:
             return self.throughput_series or ([], [])
         return self._throughput(float(window_s))
+
+    def get_latency_window_stats(self, window_s: float | None = None, edges: Any = None) -> np.ndarray:
+        """Latency statistics per time window (by finish time): float64 [W, 8] in LATENCY_KEYS order, for windows of
+        ``window_s`` seconds (default 1 s, :func:`window_edges`) or explicit ``edges``: :func:`latency_window_stats`."""
+        return latency_window_stats(self.rqs_clock, _resolve_edges(window_s, edges, self._plan.total_time))
 
     def get_sampled_metrics(self) -> dict[str, dict[str, list[float]]]:
         self.process_all_metrics()
@@ -500,6 +572,90 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    def _window_groups(self, by: Any) -> tuple[np.ndarray, int]:
+        if isinstance(by, str):
+            if by != "scenario":
+                msg = f"by must be None, a Sweep, integer group ids or 'scenario', not {by!r}"
+                raise ValueError(msg)
+            return np.arange(len(self), dtype=np.int64), len(self)
+        return resolve_groups(by, len(self))
+
+    def window_summary(self, window_s: float | None = None, *, edges: Any = None, by: Any = None,
+                       row_bounds: bool = False) -> dict[str, Any]:
+        """The eight latency statistics of every (group, time window): the requests that FINISHED in the window
+        (``edges[w] < finish <= edges[w + 1]``), over all scenarios of the group taken as one sample -- p95 during an
+        outage, how fast it recovers.  Computed by the HIP windowed analyzer (``af_engine_summarize_windows``), bit-equal
+        to :func:`latency_window_stats` / numpy on the concatenated latencies.  Windows: ``window_s`` seconds
+        (:func:`window_edges`; default 1 s) or explicit ``edges``.  ``by`` as in :meth:`pooled_summary`, or
+        ``"scenario"`` (every scenario its own group).  Returns ``stats`` float64 [G, W, 8] on the run's device (an empty
+        window: total 0, the rest NaN), ``edges`` [W + 1], ``keys``, ``replicas`` [G], ``window_ms``, ``scratch_bytes``
+        and, with ``row_bounds=True``, ``row_bounds`` int32 [n, W + 1] (the windows' row ranges)."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_clock()
+        e = _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        n_win = int(e.shape[0] - 1)
+        clock = self._clock_t
+        dev = clock.device
+        stats = torch.empty((n_groups, n_win, 8), dtype=torch.float64, device=dev)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        rb = torch.empty((len(self), n_win + 1), dtype=torch.int32, device=dev) if row_bounds else None
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_windows(
+            len(self), n_groups, e, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), stats_ptr=stats.data_ptr(), group_ptr=grp.data_ptr(),
+            row_bounds_ptr=rb.data_ptr() if rb is not None else 0)
+        out: dict[str, Any] = {"stats": stats, "edges": e, "keys": LATENCY_KEYS,
+                               "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "window_ms": ms, "scratch_bytes": scratch}
+        if rb is not None:
+            out["row_bounds"] = rb
+        return out
+
+    def window_bands(self, window_s: float | None = None, *, edges: Any = None, by: Any = None, level: float = 0.95,
+                     q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of the windowed latency statistics (the reference's roadmap: "confidence intervals and
+        bands over time series").  Every scenario's own window statistics (``window_summary(by="scenario")``), then per
+        group (``by``) and window, over the group's replicas whose window is not empty (``n`` [G, W] of them): ``mean``,
+        unbiased ``std``, normal confidence half-width ``ci_halfwidth`` at ``level`` and the linear quantiles ``q_lo`` /
+        ``q_hi`` (``q``) of each of the eight statistics, numpy float64 [G, W, 8] each (NaN where no replica has a
+        completion in the window; ``std`` NaN below two).  Reduced on the device; ``pooled`` is
+        ``window_summary(by=by)["stats"]`` as numpy."""
+        e = _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        per = self.window_summary(edges=e, by="scenario")["stats"]
+        out = window_bands_by_group(per, ids, n_groups, level, q)
+        pooled = self.window_summary(edges=e, by=ids)
+        out["pooled"] = pooled["stats"].cpu().numpy()[:n_groups]
+        out["edges"] = e
+        return out
+
+    def save_window_summary(self, path: str, by: Any = None, *, window_s: float | None = None, edges: Any = None,
+                            level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the windowed statistics with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas``, and per latency key the [G, W] columns ``window_pooled:<key>`` (the group's replicas pooled),
+        ``window_mean:<key>``, ``window_q05:<key>`` and ``window_q95:<key>`` (over the replicas, :meth:`window_bands`);
+        ``window_edges`` [W + 1] is a per-file vector.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        bands = self.window_bands(window_s, edges=edges, by=by, level=level, q=(0.05, 0.95))
+        n_groups = int(bands["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        for j, k in enumerate(LATENCY_KEYS):
+            cols[f"window_pooled:{k}"] = np.ascontiguousarray(bands["pooled"][:, :, j])
+            cols[f"window_mean:{k}"] = np.ascontiguousarray(bands["mean"][:, :, j])
+            cols[f"window_q05:{k}"] = np.ascontiguousarray(bands["q_lo"][:, :, j])
+            cols[f"window_q95:{k}"] = np.ascontiguousarray(bands["q_hi"][:, :, j])
+        cols["window_edges"] = np.asarray(bands["edges"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -664,6 +820,63 @@ def aggregate_by_group(summ: dict[str, Any], ids: np.ndarray, n_groups: int, lev
     return out
 
 
+def window_bands_by_group(per: Any, ids: np.ndarray, n_groups: int, level: float = 0.95,
+                          q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+    """Bands of per-scenario window statistics ``per`` (torch float64 [n, W, 8]) over the scenarios of every group
+    (``ids`` from :func:`resolve_groups`), per window, over the scenarios whose window holds a completion: see
+    :meth:`BatchedResults.window_bands`.  Reduced on ``per``'s device without a loop over groups or windows."""
+    from statistics import NormalDist
+
+    import torch
+
+    dev = per.device
+    n, n_win = int(per.shape[0]), int(per.shape[1])
+    cells = n_groups * n_win
+    gid = torch.as_tensor(ids, device=dev)
+    key = gid[:, None] * n_win + torch.arange(n_win, device=dev)[None, :]            # cell of (scenario, window)
+    ok = (gid >= 0)[:, None] & (per[:, :, 0] > 0)
+    k_ok, body = key[ok], per[ok]                                                    # [N], [N, 8]
+    z = NormalDist().inv_cdf(0.5 + level / 2.0)
+    c = torch.bincount(k_ok, minlength=cells)
+    k = c.to(torch.float64)
+    nan = torch.full((cells, 8), float("nan"), dtype=torch.float64, device=dev)
+    total = torch.zeros((cells, 8), dtype=torch.float64, device=dev).index_add_(0, k_ok, body)
+    mean = total / k[:, None]
+    dev2 = torch.zeros((cells, 8), dtype=torch.float64, device=dev).index_add_(0, k_ok, (body - mean[k_ok]) ** 2)
+    sd = torch.where((k > 1)[:, None], (dev2 / (k - 1.0).clamp(min=1.0)[:, None]).sqrt(), nan)
+    mean = torch.where((k > 0)[:, None], mean, nan)
+    shape = (n_groups, n_win, 8)
+    out: dict[str, Any] = {
+        "n": c.reshape(n_groups, n_win).cpu().numpy(),
+        "replicas": np.bincount(ids[ids >= 0], minlength=n_groups),
+        "keys": LATENCY_KEYS,
+        "mean": mean.reshape(shape).cpu().numpy(),
+        "std": sd.reshape(shape).cpu().numpy(),
+        "ci_halfwidth": (z * sd / k.clamp(min=1.0).sqrt()[:, None]).reshape(shape).cpu().numpy(),
+        "level": level,
+        "q": (float(q[0]), float(q[1])),
+    }
+    # every statistic sorted by value, then (stably) by cell: each cell's values ascending in one segment
+    v, order = torch.sort(body, dim=0, stable=True)
+    ks, order2 = torch.sort(k_ok[order], dim=0, stable=True)
+    v = torch.gather(v, 0, order2)
+    start = torch.cumsum(c, 0) - c
+    for name, qq in (("q_lo", float(q[0])), ("q_hi", float(q[1]))):
+        if v.shape[0] == 0:
+            out[name] = nan.reshape(shape).cpu().numpy()
+            continue
+        pos = (c - 1).clamp(min=0).to(torch.float64) * qq
+        lo = pos.floor().to(torch.int64)
+        hi = torch.minimum(lo + 1, (c - 1).clamp(min=0))
+        t = (pos - lo.to(torch.float64))[:, None]
+        a = v[(start + lo).clamp(max=v.shape[0] - 1)]
+        b = v[(start + hi).clamp(max=v.shape[0] - 1)]
+        d = b - a
+        band = torch.where(t >= 0.5, b - d * (1.0 - t), a + d * t)   # (numpy's _lerp)
+        out[name] = torch.where((c > 0)[:, None], band, nan).reshape(shape).cpu().numpy()
+    return out
+
+
 def _write_columns(path: str, cols: dict[str, np.ndarray], n: int) -> None:
     """``.parquet`` (pyarrow; [n, k] columns become list columns, vectors of another length schema metadata) or ``.npz``."""
     if path.endswith(".parquet"):
@@ -804,6 +1017,18 @@ class ShardedResults:
 
     def save_point_summary(self, path: str, by: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_point_summary() of a sweep run on several devices: pooling across devices is not implemented"
+        raise NotImplementedError(msg)
+
+    def window_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "window_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def window_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "window_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_window_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_window_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
 

@@ -402,6 +402,34 @@ typedef struct af_pooled {
 } af_pooled_t;
 int af_engine_summarize_pooled(af_engine_t* engine, const af_outputs_t* out, af_pooled_t* pooled);
 
+/* Latency statistics per TIME WINDOW and group on the device (asyncflow_amd/csrc/af_windowed.hpp): what one would compute on
+ * the host by masking every scenario's rqs_clock by finish time -- p95 DURING an outage, how fast it recovers.  With
+ * edges[0] < edges[1] < ... < edges[n_windows] (finite seconds), m_s = min(counts[s][AF_CNT_COMPLETED], clock_capacity) and
+ * r_s[k] = #{ i < m_s : finish[s, i] <= edges[k] } (np.searchsorted(finish, edges, side="right")), window w of scenario s
+ * is its rows [r_s[w], r_s[w + 1]), i.e. edges[w] < finish <= edges[w + 1], the bucket rule of the throughput series
+ * (analyzer.py:107-125); rows with finish <= edges[0] or > edges[n_windows] belong to no window.  The sample of (group g,
+ * window w) is the concatenation, in ascending scenario index over the members of g, of finish - start over those rows;
+ * stats[g][w][0..7] are numpy's on that array, bit for bit, in LatencyKey order (an empty sample: total 0, the rest NaN).
+ * This rests on rqs_clock rows being in completion order (the client appends at env.now): finish is non-decreasing within
+ * a scenario.  The call CHECKS that on every stored row of every scenario it uses and returns AF_ERR_INVALID naming a
+ * scenario that breaks it, writing no statistics.  group as in af_pooled_t.  n_groups * n_windows must be < 2^32 - 1 and
+ * a (group, window) must hold < 2^32 latencies (AF_ERR_CAPACITY).  Scratch kept by the engine (shared with
+ * af_engine_summarize_pooled): 8 B per windowed latency + 8 B per (scenario, edge) + at most 12 B per (group, window) + the
+ * pooled analyzer's ~56 KB for every (group, window) of more than 8 192 latencies only.  Synchronous; the struct is written
+ * back. */
+typedef struct af_windows {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;   /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const double* edges;     /* HOST [n_windows + 1] strictly increasing, finite */
+    double* stats;           /* DEVICE [n_groups][n_windows][8] f64 */
+    uint32_t* row_bounds;    /* DEVICE [n_scenarios][n_windows + 1] out, optional: r_s[k] (also of skipped scenarios) */
+    double elapsed_ms;       /* out: wall time of the call */
+    uint64_t scratch_bytes;  /* out: size of the engine's scratch after the call */
+} af_windows_t;
+int af_engine_summarize_windows(af_engine_t* engine, const af_outputs_t* out, af_windows_t* windows);
+
 /* af_engine_run followed by af_engine_summarize, in one call and with the same results (replaces SimulationRunner.run +
  * ResultsAnalyzer.process_all_metrics, simulation_runner.py:349-376 + analyzer.py:75-81, for the whole sweep).
  * summary->n_scenarios must equal sweep->n_scenarios.  Where the sweep is ONE launch of the stage-parallel kernel, the analyzer
