@@ -266,6 +266,27 @@ class AfWindows(C.Structure):
     ]
 
 
+class AfSeriesWindows(C.Structure):
+    """``af_series_windows_t``: request of ``af_engine_summarize_series_windows`` (``elapsed_ms`` and ``scratch_bytes`` are
+    written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("thresholds", C.POINTER(C.c_double)),
+        ("count", C.c_void_p),
+        ("mean", C.c_void_p),
+        ("minv", C.c_void_p),
+        ("maxv", C.c_void_p),
+        ("above", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 #: every symbol include/asyncflow_hip.h declares
 EXPORTED_SYMBOLS = (
     "af_engine_create",
@@ -273,6 +294,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize",
     "af_engine_summarize_pooled",
     "af_engine_summarize_windows",
+    "af_engine_summarize_series_windows",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
     "af_engine_set_kernels",
@@ -309,6 +331,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_pooled.restype = C.c_int
     lib.af_engine_summarize_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfWindows)]
     lib.af_engine_summarize_windows.restype = C.c_int
+    lib.af_engine_summarize_series_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesWindows)]
+    lib.af_engine_summarize_series_windows.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]
     lib.af_engine_run_summarized.restype = C.c_int
     lib.af_engine_jit_spec.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.c_char_p, C.c_size_t]

@@ -13,6 +13,8 @@
 //                                          wave per workgroup, only the first 2^KLOG lanes of a wave carry scenarios;
 //                                          every edge draw pre-generated into HBM: draws[slot][stream][index]
 //   af_summary_kernel / af_series_kernel   af_engine_summarize: the analyzer (af_summary.hpp)
+//   af_swin_partial / af_swin_reduce       af_engine_summarize_series_windows: the sampled series per (group, window of
+//                                          ticks) (af_series_windows.hpp)
 //
 // Memory plan
 //   LDS  : flow kernel: [plan blob, patched per scenario][station lists, select scratch / server segments, rings,
@@ -40,6 +42,7 @@
 #include "af_pregen.hpp"
 #include "af_summary.hpp"
 #include "af_pooled.hpp"
+#include "af_series_windows.hpp"
 #include "af_windowed.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
@@ -2837,6 +2840,129 @@ int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_wind
     }
     HIP_TRY(hipStreamSynchronize(st));
     win->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Sampled-series analyzer per (group, window of ticks) (af_series_windows.hpp).  The host reads the group ids and the counts
+// back, checks them and builds the groups' member lists; one streaming pass over the sample rows, then -- unless every group
+// is a single scenario -- the fold of the members' records.
+int af_engine_summarize_series_windows(af_engine_t* e, const af_outputs_t* out, af_series_windows_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty series windows request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "series_windows.tick_edges is required");
+    if (!req->count || !req->mean) return fail(AF_ERR_INVALID, "series_windows.count and series_windows.mean are required");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->samples || out->tick_capacity == 0) return fail(AF_ERR_INVALID, "series windows need outputs.samples");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, cap = out->tick_capacity;
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch;
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    for (uint32_t j = 0; req->thresholds && j < S; ++j)
+        if (std::isnan(req->thresholds[j])) return fail(AF_ERR_INVALID, "threshold " + std::to_string(j) + " is NaN");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    if (S == 0 || pitch < S || pitch % 4u) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp(req->group ? n : 0u);
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    if (req->group) HIP_TRY(hipMemcpy(grp.data(), req->group, grp.size() * 4u, hipMemcpyDeviceToHost));
+    // the groups' members, ascending; may a cell reach 2^32 values?
+    std::vector<uint32_t> mem_off((size_t)G + 1u, 0u), members;
+    std::vector<uint64_t> g_ticks(G, 0u);
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = req->group ? grp[s] : 0u;
+        if (g == afsw::kSkip) continue;
+        if (g >= G) return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
+        mem_off[(size_t)g + 1u] += 1u;
+        g_ticks[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+    }
+    bool direct = true;
+    for (uint32_t g = 0; g < G; ++g) {
+        if (mem_off[(size_t)g + 1u] > 1u) direct = false;
+        mem_off[(size_t)g + 1u] += mem_off[g];
+    }
+    members.resize(std::max<size_t>(mem_off[G], 1u));
+    {
+        std::vector<uint32_t> cursor(mem_off.begin(), mem_off.end() - 1);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = req->group ? grp[s] : 0u;
+            if (g != afsw::kSkip) members[cursor[g]++] = s;
+        }
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+        if (g_ticks[g] <= 0xFFFFFFFFull) continue;   // (no window of the group can hold 2^32 rows)
+        for (uint32_t w = 0; w < W; ++w) {
+            uint64_t c = 0;
+            for (uint32_t k = mem_off[g]; k < mem_off[(size_t)g + 1u]; ++k) {
+                const uint32_t m = std::min(counts[(size_t)members[k] * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+                c += std::min(req->tick_edges[w + 1u], m) - std::min(req->tick_edges[w], m);
+            }
+            if (c > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more samples");
+        }
+    }
+    // scratch layout (256-byte aligned parts)
+    size_t at = 0;
+    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+    const size_t R = direct ? 0u : (size_t)n * W * S;
+    const size_t o_edges = part(((size_t)W + 1u) * 4u), o_thr = part((size_t)S * 8u), o_off = part(((size_t)G + 1u) * 4u),
+                 o_mem = part(members.size() * 4u), o_sum = part(R * 8u), o_min = part(R * 4u), o_max = part(R * 4u), o_above = part(R * 4u);
+    if (int rc = pool_reserve(e, at)) return rc;
+    unsigned char* b = e->d_pool;
+    hipStream_t st = e->stream;
+    std::vector<double> thr(S, 0.0);
+    if (req->thresholds) thr.assign(req->thresholds, req->thresholds + S);
+    HIP_TRY(hipMemcpyAsync(b + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_thr, thr.data(), (size_t)S * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_off, mem_off.data(), mem_off.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_mem, members.data(), members.size() * 4u, hipMemcpyHostToDevice, st));
+    afsw::SwinArgs a{};
+    a.samples = out->samples;
+    a.counts = out->counts;
+    a.tick_cap = cap;
+    a.pitch = pitch;
+    a.n_series = S;
+    a.n_edges = e->args.n_edges;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.group = req->group;
+    a.n_scen = n;
+    a.n_groups = G;
+    a.n_win = W;
+    a.direct = direct ? 1u : 0u;
+    a.edges = reinterpret_cast<const uint32_t*>(b + o_edges);
+    a.thr = reinterpret_cast<const double*>(b + o_thr);
+    a.mem_off = reinterpret_cast<const uint32_t*>(b + o_off);
+    a.members = reinterpret_cast<const uint32_t*>(b + o_mem);
+    a.rec_sum = reinterpret_cast<unsigned long long*>(b + o_sum);
+    a.rec_min = reinterpret_cast<uint32_t*>(b + o_min);
+    a.rec_max = reinterpret_cast<uint32_t*>(b + o_max);
+    a.rec_above = reinterpret_cast<uint32_t*>(b + o_above);
+    a.count = req->count;
+    a.mean = req->mean;
+    a.minv = req->minv;
+    a.maxv = req->maxv;
+    a.above = req->above;
+    // a wave per (scenario, run of windows): runs as long as leave the chip some 32 768 waves
+    const uint32_t want_runs = (32768u + n - 1u) / n;
+    a.run = std::max(1u, W / want_runs);
+    const uint64_t items = (uint64_t)n * ((W + a.run - 1u) / a.run);
+    hipLaunchKernelGGL(afsw::af_swin_partial, dim3((uint32_t)((items + afsw::kWaves - 1u) / afsw::kWaves)), dim3(afsw::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (!direct || mem_off[G] < G) {   // the members' fold; after a direct pass only the cells of groups without a member
+        const uint64_t entries = (uint64_t)G * W * S;
+        constexpr uint64_t kBlocksPerLaunch = 1u << 21;   // (at most 2^29 threads a launch)
+        for (uint64_t f = 0; f < entries; f += kBlocksPerLaunch * afsw::kReduceThreads) {
+            const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (entries - f + afsw::kReduceThreads - 1u) / afsw::kReduceThreads);
+            hipLaunchKernelGGL(afsw::af_swin_reduce, dim3((uint32_t)blocks), dim3(afsw::kReduceThreads), 0, st, a, f, entries);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
 

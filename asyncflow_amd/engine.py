@@ -298,6 +298,37 @@ class Engine:
         _check(self._lib, self._lib.af_engine_summarize_windows(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_windows")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_series_windows(self, n: int, n_groups: int, tick_edges: Any, *, samples_ptr: int, tick_capacity: int,
+                                 counts_ptr: int, count_ptr: int, mean_ptr: int, min_ptr: int = 0, max_ptr: int = 0,
+                                 above_ptr: int = 0, group_ptr: int = 0, thresholds: Any = None) -> tuple[float, int]:
+        """Sampled-series analyzer on the device (``af_engine_summarize_series_windows``): per (group, window of ticks)
+        ``count`` uint32 [n_groups, W] and, per series, ``mean`` f64 and ``min`` / ``max`` / ``above`` uint32 words
+        [n_groups, W, n_series], W = len(tick_edges) - 1.  ``tick_edges``: HOST uint32, strictly increasing TICK INDICES
+        (sample k carries the label k * sample_period, as the reference's ``get_series`` gives it); ``thresholds``: HOST
+        float64 [n_series] or None (0.0 each).  ``group_ptr`` as in :meth:`summarize_pooled`.  Returns the call's wall time
+        in ms and the engine's scratch size in bytes."""
+        from .results import check_tick_edges
+
+        b = check_tick_edges(tick_edges)
+        thr = None
+        if thresholds is not None:
+            thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+            if thr.shape != (self.plan.n_series,):
+                msg = f"thresholds must be a vector of one value per series ({self.plan.n_series}), not of shape {thr.shape}"
+                raise ValueError(msg)
+            if np.isnan(thr).any():
+                msg = "thresholds must not be NaN"
+                raise ValueError(msg)
+        out = _abi.AfOutputs(0, None, int(tick_capacity), C.c_void_p(samples_ptr or None), C.c_void_p(counts_ptr or None))
+        req = _abi.AfSeriesWindows(int(n), int(n_groups), int(b.shape[0] - 1), C.c_void_p(group_ptr or None),
+                                   b.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                   thr.ctypes.data_as(C.POINTER(C.c_double)) if thr is not None else None,
+                                   C.c_void_p(count_ptr or None), C.c_void_p(mean_ptr or None), C.c_void_p(min_ptr or None),
+                                   C.c_void_p(max_ptr or None), C.c_void_p(above_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_series_windows(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_series_windows")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:
         """``af_engine_gather``: ONE grouped RCCL all-gather of the per-scenario summaries.

@@ -90,6 +90,110 @@ def latency_window_stats(clock: np.ndarray, edges: Any) -> np.ndarray:
     return np.stack([latency_stats_row(lat[r[w]:r[w + 1]]) for w in range(e.shape[0] - 1)])
 
 
+def check_tick_edges(tick_edges: Any) -> np.ndarray:
+    """``tick_edges`` as a uint32 vector, or ValueError: at least two tick indices, whole, in [0, 2^32), strictly increasing."""
+    raw = np.asarray(tick_edges)
+    if raw.ndim != 1 or raw.shape[0] < 2:
+        msg = f"tick_edges must be a vector of at least two tick indices, not of shape {raw.shape}"
+        raise ValueError(msg)
+    if raw.dtype.kind not in "iu":
+        as_int = np.asarray(raw, dtype=np.float64)
+        if not (np.isfinite(as_int).all() and (as_int == np.floor(as_int)).all()):
+            msg = "tick_edges must be whole tick indices"
+            raise ValueError(msg)
+        raw = as_int
+    if (raw < 0).any() or (raw > 0xFFFFFFFF).any():
+        msg = "tick_edges must lie in [0, 2^32)"
+        raise ValueError(msg)
+    b = np.ascontiguousarray(raw, dtype=np.uint32)
+    if not (np.diff(b.astype(np.int64)) > 0).all():
+        msg = "tick_edges must be strictly increasing"
+        raise ValueError(msg)
+    return b
+
+
+def ticks_per_window_of(window_s: float, sample_period: float) -> int:
+    """``window_s`` seconds as a number of sampler ticks ``m = round(window_s / sample_period)``; ValueError unless
+    ``m >= 1`` and ``m * sample_period`` is ``window_s`` to 1e-9 relative."""
+    w = float(window_s)
+    if not (np.isfinite(w) and w > 0.0):
+        msg = f"window_s must be a positive number of seconds, not {window_s!r}"
+        raise ValueError(msg)
+    m = int(round(w / float(sample_period)))
+    if m < 1 or abs(m * float(sample_period) - w) > 1e-9 * w:
+        msg = f"window_s = {window_s!r} is not a multiple of the sample period ({sample_period!r} s)"
+        raise ValueError(msg)
+    return m
+
+
+def tick_window_edges(ticks_per_window: int, n_ticks: int) -> np.ndarray:
+    """Tick edges ``[0, m, 2 m, ..., W m]`` (uint32) of the ``W = ceil(n_ticks / m)`` windows of ``m = ticks_per_window``
+    sampler ticks that cover ``n_ticks`` samples; the last window may be short (a window ends where the samples do)."""
+    m = int(ticks_per_window)
+    if m != ticks_per_window or m < 1:
+        msg = f"ticks_per_window must be a positive whole number, not {ticks_per_window!r}"
+        raise ValueError(msg)
+    n_win = max(-(-int(n_ticks) // m), 1)
+    return check_tick_edges(np.arange(n_win + 1, dtype=np.int64) * m)
+
+
+def _resolve_tick_edges(window_s: float | None, ticks_per_window: int | None, tick_edges: Any, sample_period: float,
+                        n_ticks: int) -> np.ndarray:
+    if sum(x is not None for x in (window_s, ticks_per_window, tick_edges)) > 1:
+        msg = "pass one of window_s, ticks_per_window and tick_edges"
+        raise ValueError(msg)
+    if tick_edges is not None:
+        return check_tick_edges(tick_edges)
+    if ticks_per_window is None:
+        ticks_per_window = ticks_per_window_of(1.0 if window_s is None else window_s, sample_period)
+    return tick_window_edges(ticks_per_window, n_ticks)
+
+
+def ram_columns(n_series: int, n_edges: int) -> np.ndarray:
+    """Boolean [n_series]: the ``ram_in_use`` columns (float32 words) of the sampled series in device order."""
+    j = np.arange(n_series)
+    return (j >= n_edges) & ((j - n_edges) % 3 == 2)
+
+
+def series_window_stats(samples: np.ndarray, tick_edges: Any, n_edges: int, thresholds: Any = None) -> dict[str, np.ndarray]:
+    """Statistics per window of ticks of ONE scenario's sampled series ``samples`` (uint32 words [n_series, ticks], the
+    layout :class:`ScenarioResults` holds).  Sample ``k`` carries the label ``k * sample_period`` -- the reference's
+    ``get_series`` (analyzer.py:239-244), although the collector takes it at ``(k + 1) * period`` (collector.py:53) --; window
+    ``w`` holds the samples ``min(b[w], ticks) <= k < min(b[w + 1], ticks)`` of ``b = tick_edges``.  Returns ``count`` int64
+    [W], ``mean`` float64 [W, S] (integer series: the exact integer sum divided once; ``ram_in_use``: the float32 values
+    summed as float64; NaN in an empty window), ``min`` / ``max`` uint32 words [W, S] (float32 bits in the ram columns) and
+    ``above`` uint32 [W, S]: the values ``> thresholds[j]`` (None: 0.0 each, the non-zero samples); an empty window has 0 in
+    all three.  The definition the device analyzer (``af_engine_summarize_series_windows``) matches."""
+    b = check_tick_edges(tick_edges)
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    n_series, ticks = words.shape
+    thr = np.zeros(n_series) if thresholds is None else np.asarray(thresholds, dtype=np.float64)
+    if thr.shape != (n_series,) or np.isnan(thr).any():
+        msg = f"thresholds must be {n_series} values, none of them NaN"
+        raise ValueError(msg)
+    ram = ram_columns(n_series, n_edges)
+    n_win = b.shape[0] - 1
+    r = np.minimum(b.astype(np.int64), ticks)
+    count = np.diff(r)
+    mean = np.full((n_win, n_series), np.nan)
+    mn = np.zeros((n_win, n_series), dtype=np.uint32)
+    mx = np.zeros((n_win, n_series), dtype=np.uint32)
+    above = np.zeros((n_win, n_series), dtype=np.uint32)
+    for w in range(n_win):
+        if count[w] == 0:
+            continue
+        seg = words[:, r[w]:r[w + 1]]
+        values = seg.astype(np.float64)
+        values[ram] = seg[ram].view(np.float32).astype(np.float64)
+        mean[w] = np.where(ram, np.mean(values, axis=1), seg.astype(np.int64).sum(axis=1).astype(np.float64) / float(count[w]))
+        mn[w], mx[w] = seg.min(axis=1), seg.max(axis=1)
+        above[w] = (values > thr[:, None]).sum(axis=1)
+    return {"count": count, "mean": mean, "min": mn, "max": mx, "above": above}
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -217,6 +321,18 @@ class ScenarioResults:
         """Latency statistics per time window (by finish time): float64 [W, 8] in LATENCY_KEYS order, for windows of
         ``window_s`` seconds (default 1 s, :func:`window_edges`) or explicit ``edges``: :func:`latency_window_stats`."""
         return latency_window_stats(self.rqs_clock, _resolve_edges(window_s, edges, self._plan.total_time))
+
+    def get_series_window_stats(self, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                                tick_edges: Any = None, thresholds: Any = None) -> dict[str, np.ndarray]:
+        """Statistics of every sampled series per window of ticks (:func:`series_window_stats`): windows of ``window_s``
+        seconds (a multiple of the sample period; default 1 s), of ``ticks_per_window`` ticks, or explicit ``tick_edges``.
+        Sample ``k`` carries the label ``k * sample_period`` (``get_series``), so a window of ``m`` ticks labelled ``t``
+        holds the samples labelled ``t <= label < t + m * sample_period``."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        return series_window_stats(self._samples, b, self._plan.n_edges, thresholds)
 
     def get_sampled_metrics(self) -> dict[str, dict[str, list[float]]]:
         self.process_all_metrics()
@@ -656,6 +772,137 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    def _series_thresholds(self, thresholds: Any) -> np.ndarray | None:
+        if thresholds is None:
+            return None
+        names = self.series_names()
+        if isinstance(thresholds, dict):
+            thr = np.zeros(len(names))
+            for k, v in thresholds.items():
+                if k not in names:
+                    msg = f"unknown series {k!r} in thresholds (series_names(): {names})"
+                    raise ValueError(msg)
+                thr[names.index(k)] = float(v)
+        else:
+            thr = np.asarray(thresholds, dtype=np.float64)
+            if thr.shape != (len(names),):
+                msg = f"thresholds must be a vector of one value per series ({len(names)}) or a dict, not of shape {thr.shape}"
+                raise ValueError(msg)
+        if np.isnan(thr).any():
+            msg = "thresholds must not be NaN"
+            raise ValueError(msg)
+        return thr
+
+    def _series_tick_edges(self, window_s: float | None, ticks_per_window: int | None, tick_edges: Any) -> np.ndarray:
+        return _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self.plan.sample_period, self.plan.tick_count)
+
+    def series_window_summary(self, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                              tick_edges: Any = None, by: Any = None, thresholds: Any = None) -> dict[str, Any]:
+        """Statistics of every sampled series (``ready_queue_len``, ``event_loop_io_sleep``, ``ram_in_use`` per server,
+        ``edge_concurrent_connection`` per edge) of every (group, window of ticks), over all scenarios of the group: how
+        long a server's ready queue is DURING an outage, at each grid point.  Computed by the HIP series analyzer
+        (``af_engine_summarize_series_windows``), equal to :func:`series_window_stats` on the group's samples.  Windows:
+        ``window_s`` seconds (a multiple of the sample period; default 1 s), ``ticks_per_window`` ticks or explicit
+        ``tick_edges`` (tick indices); sample ``k`` carries the label ``k * sample_period`` as in ``get_series``.  ``by``
+        as in :meth:`window_summary`.  ``thresholds``: None (0.0), a vector [n_series] or ``{series name: value}`` over
+        :meth:`series_names` (missing: 0.0).  Returns torch tensors on the run's device: ``count`` int64 [G, W]; ``mean``,
+        ``min``, ``max`` and ``above_share`` (values above the threshold / count) float64 [G, W, S], NaN in empty cells;
+        the raw ``min_words`` / ``max_words`` / ``above`` int32; and ``series``, ``tick_edges``, ``times`` (the windows'
+        start labels in seconds), ``replicas`` [G], ``series_window_ms``, ``scratch_bytes``."""
+        import torch
+
+        from .engine import Engine
+
+        if self._samples_t is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        thr = self._series_thresholds(thresholds)
+        ids, n_groups = self._window_groups(by)
+        n_win, n_ser = int(b.shape[0] - 1), self.plan.n_series
+        samples = self._samples_t
+        dev = samples.device
+        count = torch.empty((n_groups, n_win), dtype=torch.int32, device=dev)
+        mean = torch.empty((n_groups, n_win, n_ser), dtype=torch.float64, device=dev)
+        mn, mx, ab = (torch.empty((n_groups, n_win, n_ser), dtype=torch.int32, device=dev) for _ in range(3))
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_series_windows(
+            len(self), n_groups, b, samples_ptr=samples.data_ptr(), tick_capacity=int(samples.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(), mean_ptr=mean.data_ptr(), min_ptr=mn.data_ptr(),
+            max_ptr=mx.data_ptr(), above_ptr=ab.data_ptr(), group_ptr=grp.data_ptr(), thresholds=thr)
+        cnt = count.to(torch.int64) & 0xFFFFFFFF
+        ram = torch.as_tensor(ram_columns(n_ser, self.plan.n_edges), device=dev)
+        empty = (cnt == 0)[:, :, None]
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+
+        def decode(words: Any) -> Any:   # (as decode_series_max: counts as they are, the ram columns from their float32 bits)
+            v = torch.where(ram, words.view(torch.float32).to(torch.float64), (words.to(torch.int64) & 0xFFFFFFFF).to(torch.float64))
+            return torch.where(empty, nan, v)
+
+        share = (ab.to(torch.int64) & 0xFFFFFFFF).to(torch.float64) / cnt.to(torch.float64)[:, :, None]
+        return {"count": cnt, "mean": mean, "min": decode(mn), "max": decode(mx), "above_share": torch.where(empty, nan, share),
+                "min_words": mn, "max_words": mx, "above": ab, "series": self.series_names(), "tick_edges": b,
+                "times": b[:-1].astype(np.float64) * self.plan.sample_period,
+                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "series_window_ms": ms, "scratch_bytes": scratch}
+
+    def series_window_bands(self, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                            tick_edges: Any = None, by: Any = None, thresholds: Any = None, of: str = "mean",
+                            level: float = 0.95, q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of a windowed series statistic ``of`` (``"mean"``, ``"max"`` or ``"above_share"``): every
+        scenario's own window values (``series_window_summary(by="scenario")``), then per group (``by``) and window, over
+        the group's replicas whose window is not empty (``n`` [G, W] of them): ``mean``, unbiased ``std``, normal
+        confidence half-width ``ci_halfwidth`` at ``level`` and the linear quantiles ``q_lo`` / ``q_hi`` (``q``), numpy
+        float64 [G, W, S] each (NaN where no replica has a sample in the window; ``std`` NaN below two).  Reduced on the
+        device (:func:`window_bands_by_group`); ``pooled`` is the grouped call's value of the same statistic."""
+        if of not in ("mean", "max", "above_share"):
+            msg = f"of must be 'mean', 'max' or 'above_share', not {of!r}"
+            raise ValueError(msg)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        return self._series_window_bands(b, by, thresholds, of, level, q)[0]
+
+    def _series_window_bands(self, b: np.ndarray, by: Any, thresholds: Any, of: str, level: float,
+                             q: tuple[float, float]) -> tuple[dict[str, Any], dict[str, Any]]:
+        """:meth:`series_window_bands` for resolved tick edges; also returns the grouped summary its ``pooled`` is taken from."""
+        ids, n_groups = self._window_groups(by)
+        per = self.series_window_summary(tick_edges=b, by="scenario", thresholds=thresholds)
+        out = window_bands_by_group(per[of], ids, n_groups, level, q, valid=per["count"] > 0)
+        pooled = self.series_window_summary(tick_edges=b, by=ids, thresholds=thresholds)
+        out["pooled"] = pooled[of].cpu().numpy()[:n_groups]
+        out.update(of=of, series=per["series"], tick_edges=b, times=per["times"])
+        return out, pooled
+
+    def save_series_window_summary(self, path: str, by: Any = None, *, window_s: float | None = None,
+                                   ticks_per_window: int | None = None, thresholds: Any = None,
+                                   level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the windowed series statistics with one row per group (grid point): ``param:<axis>`` (for a
+        Sweep), ``replicas``, and per series the [G, W] columns ``series_window_mean:<series>``,
+        ``series_window_max:<series>``, ``series_window_above:<series>`` (the share above the threshold) -- the group's
+        replicas taken together -- and ``series_window_q05:<series>`` / ``series_window_q95:<series>`` (of the replicas'
+        own means, :meth:`series_window_bands`); ``series_window_tick_edges`` [W + 1] and ``series_window_times`` [W] are
+        per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        b = self._series_tick_edges(window_s, ticks_per_window, None)
+        bands, pooled = self._series_window_bands(b, by, thresholds, "mean", level, (0.05, 0.95))
+        n_groups = int(bands["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        mean, mx, share = (pooled[k].cpu().numpy()[:n_groups] for k in ("mean", "max", "above_share"))
+        for j, name in enumerate(bands["series"]):
+            cols[f"series_window_mean:{name}"] = np.ascontiguousarray(mean[:, :, j])
+            cols[f"series_window_max:{name}"] = np.ascontiguousarray(mx[:, :, j])
+            cols[f"series_window_above:{name}"] = np.ascontiguousarray(share[:, :, j])
+            cols[f"series_window_q05:{name}"] = np.ascontiguousarray(bands["q_lo"][:, :, j])
+            cols[f"series_window_q95:{name}"] = np.ascontiguousarray(bands["q_hi"][:, :, j])
+        cols["series_window_tick_edges"] = np.asarray(bands["tick_edges"], dtype=np.float64)
+        cols["series_window_times"] = np.asarray(bands["times"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -821,41 +1068,44 @@ def aggregate_by_group(summ: dict[str, Any], ids: np.ndarray, n_groups: int, lev
 
 
 def window_bands_by_group(per: Any, ids: np.ndarray, n_groups: int, level: float = 0.95,
-                          q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
-    """Bands of per-scenario window statistics ``per`` (torch float64 [n, W, 8]) over the scenarios of every group
-    (``ids`` from :func:`resolve_groups`), per window, over the scenarios whose window holds a completion: see
-    :meth:`BatchedResults.window_bands`.  Reduced on ``per``'s device without a loop over groups or windows."""
+                          q: tuple[float, float] = (0.05, 0.95), valid: Any = None) -> dict[str, Any]:
+    """Bands of per-scenario window statistics ``per`` (torch float64 [n, W, K]) over the scenarios of every group
+    (``ids`` from :func:`resolve_groups`), per window, over the scenarios whose window is ``valid`` (torch bool [n, W];
+    None: the latency statistics' rule, ``per[:, :, 0] > 0``, the windows that hold a completion): see
+    :meth:`BatchedResults.window_bands` (K = 8) and :meth:`BatchedResults.series_window_bands` (K = the sampled series).
+    Reduced on ``per``'s device without a loop over groups or windows."""
     from statistics import NormalDist
 
     import torch
 
     dev = per.device
-    n, n_win = int(per.shape[0]), int(per.shape[1])
+    n_win, n_col = int(per.shape[1]), int(per.shape[2])
     cells = n_groups * n_win
     gid = torch.as_tensor(ids, device=dev)
     key = gid[:, None] * n_win + torch.arange(n_win, device=dev)[None, :]            # cell of (scenario, window)
-    ok = (gid >= 0)[:, None] & (per[:, :, 0] > 0)
-    k_ok, body = key[ok], per[ok]                                                    # [N], [N, 8]
+    ok = (gid >= 0)[:, None] & (per[:, :, 0] > 0 if valid is None else valid)
+    k_ok, body = key[ok], per[ok]                                                    # [N], [N, K]
     z = NormalDist().inv_cdf(0.5 + level / 2.0)
     c = torch.bincount(k_ok, minlength=cells)
     k = c.to(torch.float64)
-    nan = torch.full((cells, 8), float("nan"), dtype=torch.float64, device=dev)
-    total = torch.zeros((cells, 8), dtype=torch.float64, device=dev).index_add_(0, k_ok, body)
+    nan = torch.full((cells, n_col), float("nan"), dtype=torch.float64, device=dev)
+    total = torch.zeros((cells, n_col), dtype=torch.float64, device=dev).index_add_(0, k_ok, body)
     mean = total / k[:, None]
-    dev2 = torch.zeros((cells, 8), dtype=torch.float64, device=dev).index_add_(0, k_ok, (body - mean[k_ok]) ** 2)
+    dev2 = torch.zeros((cells, n_col), dtype=torch.float64, device=dev).index_add_(0, k_ok, (body - mean[k_ok]) ** 2)
     sd = torch.where((k > 1)[:, None], (dev2 / (k - 1.0).clamp(min=1.0)[:, None]).sqrt(), nan)
     mean = torch.where((k > 0)[:, None], mean, nan)
-    shape = (n_groups, n_win, 8)
+    shape = (n_groups, n_win, n_col)
     out: dict[str, Any] = {
         "n": c.reshape(n_groups, n_win).cpu().numpy(),
         "replicas": np.bincount(ids[ids >= 0], minlength=n_groups),
-        "keys": LATENCY_KEYS,
         "mean": mean.reshape(shape).cpu().numpy(),
         "std": sd.reshape(shape).cpu().numpy(),
         "ci_halfwidth": (z * sd / k.clamp(min=1.0).sqrt()[:, None]).reshape(shape).cpu().numpy(),
         "level": level,
         "q": (float(q[0]), float(q[1])),
     }
+    if valid is None:
+        out["keys"] = LATENCY_KEYS
     # every statistic sorted by value, then (stably) by cell: each cell's values ascending in one segment
     v, order = torch.sort(body, dim=0, stable=True)
     ks, order2 = torch.sort(k_ok[order], dim=0, stable=True)
@@ -1029,6 +1279,18 @@ class ShardedResults:
 
     def save_window_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_window_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_window_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_window_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_window_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_window_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_series_window_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_series_window_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
 

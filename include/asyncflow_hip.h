@@ -430,6 +430,49 @@ typedef struct af_windows {
 } af_windows_t;
 int af_engine_summarize_windows(af_engine_t* engine, const af_outputs_t* out, af_windows_t* windows);
 
+/* Statistics of every SAMPLED SERIES per window of ticks and group on the device (asyncflow_amd/csrc/af_series_windows.hpp):
+ * how long the ready queue of a server is DURING an outage, at each grid point.  Windows are on TICK INDICES: sample k of
+ * scenario s is row k of its outputs.samples block, k = 0 .. m_s - 1, m_s = min(counts[s][AF_CNT_TICKS], tick_capacity); the
+ * reference labels it k * sample_period (analyzer.py:239-244) although the collector takes it at (k + 1) * period
+ * (collector.py:53), and the windows follow the label.  With tick_edges b[0] < b[1] < ... < b[n_windows], window w of
+ * scenario s is its rows [min(b[w], m_s), min(b[w + 1], m_s)); rows at or past m_s and the padding words of a row are never
+ * read.  The sample of (group g, window w, series j) is column j over those rows of every member of g (group as in
+ * af_pooled_t).  Per (g, w): count, the values in the cell.  Per (g, w, j): mean -- integer series: the exact integer sum,
+ * divided once, (double)sum / (double)count, bit-equal to np.mean of the int64 values while the sum is below 2^53;
+ * ram_in_use (float32 words, column n_edges + 3 * server + 2): the f64 sum of the float values, divided once --; minv /
+ * maxv as 4-byte words like af_summary_t.series_max (float32 bits in the ram columns: they order like the values while
+ * these are non-negative; a NEGATIVE float, such as the -2.8e-14 residue the reference's own arithmetic can leave in
+ * ram_in_use, has the sign bit set and is therefore the largest word of its cell, not the smallest value); above: the values > thresholds[j], compared as f64 (NULL: 0.0 each, the non-zero samples).  An empty cell: count
+ * 0, mean NaN, minv = maxv = above = 0.
+ * Exactness: no atomics; the f64 partial sums of a float column are combined in a fixed order (within a scenario's window:
+ * a lane's rows top down, then a fixed tree over the lanes; across the members of a group: ascending scenario index), so the
+ * result is identical from run to run and does not depend on the batch a scenario sits in.  When every value of a cell is a
+ * multiple of 1/256 below 2^16 and count < 2^29, every partial sum is exact and the mean is bit-equal to numpy's; otherwise it
+ * is within (count - 1) * 2^-53 relative of the exactly rounded sum / count.
+ * Refused: tick_edges not strictly increasing or n_windows = 0, a NaN threshold, a group id >= n_groups, outputs.samples
+ * NULL (AF_ERR_INVALID); a cell of 2^32 or more values, n_groups * n_windows >= 2^32 - 1, tick_capacity >= 2^31
+ * (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).  Any number of series (af_engine_summarize stops at 1 024
+ * padded ones).  `out` needs samples, tick_capacity and counts; clock is not read.
+ * Scratch kept by the engine (shared with the pooled and windowed analyzers): 4 B per edge + 8 B per series + 4 B per group
+ * + 4 B per scenario + 2 KB of alignment, and -- unless every group holds at most one scenario -- 20 B per (scenario,
+ * window, series).  Synchronous; the struct is written back. */
+typedef struct af_series_windows {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing */
+    const double* thresholds;    /* HOST [af_series_count] or NULL (0.0 each) */
+    uint32_t* count;             /* DEVICE [n_groups][n_windows] */
+    double* mean;                /* DEVICE [n_groups][n_windows][af_series_count] f64 */
+    uint32_t* minv;              /* DEVICE, same shape, 4-byte words; NULL skips */
+    uint32_t* maxv;              /* DEVICE, same shape; NULL skips */
+    uint32_t* above;             /* DEVICE, same shape; NULL skips */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_series_windows_t;
+int af_engine_summarize_series_windows(af_engine_t* engine, const af_outputs_t* out, af_series_windows_t* series_windows);
+
 /* af_engine_run followed by af_engine_summarize, in one call and with the same results (replaces SimulationRunner.run +
  * ResultsAnalyzer.process_all_metrics, simulation_runner.py:349-376 + analyzer.py:75-81, for the whole sweep).
  * summary->n_scenarios must equal sweep->n_scenarios.  Where the sweep is ONE launch of the stage-parallel kernel, the analyzer
