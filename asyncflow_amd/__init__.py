@@ -8,7 +8,7 @@ executed over thousands of independent scenarios by a hand-written HIP kernel
 
 from .payload import load_yaml, normalize_payload
 from .plan import DevicePlan, lower
-from .results import BatchedResults, ScenarioResults, latency_window_stats, window_edges
+from .results import BatchedResults, ScenarioResults, latency_quantiles, latency_window_quantiles, latency_window_stats, window_edges
 from .runner import SimulationRunner
 from .sweep import Sweep, expand_grid
 
@@ -19,6 +19,8 @@ __all__ = [
     "SimulationRunner",
     "Sweep",
     "expand_grid",
+    "latency_quantiles",
+    "latency_window_quantiles",
     "latency_window_stats",
     "load_yaml",
     "lower",

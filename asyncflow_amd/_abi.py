@@ -287,6 +287,32 @@ class AfSeriesWindows(C.Structure):
     ]
 
 
+MAX_QUANTILE_LEVELS = 64   # AF_MAX_QUANTILE_LEVELS
+MAX_SLO_THRESHOLDS = 64    # AF_MAX_SLO_THRESHOLDS
+
+
+class AfQuantiles(C.Structure):
+    """``af_quantiles_t``: request of ``af_engine_summarize_quantiles`` (``elapsed_ms`` and ``scratch_bytes`` are written
+    back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("edges", C.POINTER(C.c_double)),
+        ("n_levels", C.c_uint32),
+        ("levels", C.POINTER(C.c_double)),
+        ("n_thresholds", C.c_uint32),
+        ("thresholds", C.POINTER(C.c_double)),
+        ("count", C.c_void_p),
+        ("quantiles", C.c_void_p),
+        ("within", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 #: every symbol include/asyncflow_hip.h declares
 EXPORTED_SYMBOLS = (
     "af_engine_create",
@@ -295,6 +321,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_pooled",
     "af_engine_summarize_windows",
     "af_engine_summarize_series_windows",
+    "af_engine_summarize_quantiles",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
     "af_engine_set_kernels",
@@ -333,6 +360,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_windows.restype = C.c_int
     lib.af_engine_summarize_series_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesWindows)]
     lib.af_engine_summarize_series_windows.restype = C.c_int
+    lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
+    lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]
     lib.af_engine_run_summarized.restype = C.c_int
     lib.af_engine_jit_spec.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.c_char_p, C.c_size_t]

@@ -44,6 +44,7 @@
 #include "af_pooled.hpp"
 #include "af_series_windows.hpp"
 #include "af_windowed.hpp"
+#include "af_quantiles.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -2840,6 +2841,271 @@ int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_wind
     }
     HIP_TRY(hipStreamSynchronize(st));
     win->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Quantile analyzer (af_quantiles.hpp).  The cells are laid out as the windowed analyzer's (n_windows > 0) or the pooled one's
+// (n_windows == 0: a cell per group) and compacted by those analyzers' own kernels; a cell then goes to the tier of its size.
+int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) {
+    if (!e || !out || !qr) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (qr->n_scenarios == 0 || qr->n_groups == 0) return fail(AF_ERR_INVALID, "empty quantiles request (n_scenarios and n_groups must be > 0)");
+    const uint32_t n = qr->n_scenarios, G = qr->n_groups, W = qr->n_windows, cap = out->clock_capacity, Q = qr->n_levels, T = qr->n_thresholds;
+    if (Q > AF_MAX_QUANTILE_LEVELS) return fail(AF_ERR_INVALID, "more than AF_MAX_QUANTILE_LEVELS (" + std::to_string(AF_MAX_QUANTILE_LEVELS) + ") levels");
+    if (T > AF_MAX_SLO_THRESHOLDS) return fail(AF_ERR_INVALID, "more than AF_MAX_SLO_THRESHOLDS (" + std::to_string(AF_MAX_SLO_THRESHOLDS) + ") thresholds");
+    if (Q == 0 && T == 0) return fail(AF_ERR_INVALID, "quantiles request without levels and without thresholds");
+    if (Q && !qr->levels) return fail(AF_ERR_INVALID, "quantiles.levels is required with n_levels > 0");
+    if (T && !qr->thresholds) return fail(AF_ERR_INVALID, "quantiles.thresholds is required with n_thresholds > 0");
+    for (uint32_t i = 0; i < Q; ++i)
+        if (!(qr->levels[i] >= 0.0 && qr->levels[i] <= 1.0)) return fail(AF_ERR_INVALID, "quantile level " + std::to_string(i) + " is not in [0, 1]");
+    for (uint32_t i = 0; i < T; ++i)
+        if (std::isnan(qr->thresholds[i])) return fail(AF_ERR_INVALID, "threshold " + std::to_string(i) + " is NaN");
+    if (W > 0 && !qr->edges) return fail(AF_ERR_INVALID, "quantiles.edges is required with n_windows > 0");
+    if (W == 0 && qr->edges) return fail(AF_ERR_INVALID, "quantiles.edges given with n_windows == 0 (whole-run mode takes none)");
+    for (uint32_t k = 0; W > 0 && k <= W; ++k) {
+        if (!std::isfinite(qr->edges[k])) return fail(AF_ERR_INVALID, "window edge " + std::to_string(k) + " is not finite");
+        if (k > 0 && !(qr->edges[k - 1] < qr->edges[k]))
+            return fail(AF_ERR_INVALID, "window edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    }
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || cap == 0) return fail(AF_ERR_INVALID, "quantile summary needs outputs.clock");
+    const uint32_t Wc = W ? W : 1u;
+    if ((uint64_t)G * Wc >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * max(n_windows, 1) must be below 2^32 - 1");
+    if (W && (uint64_t)n * ((uint64_t)W + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (n_windows + 1) must be below 2^32");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    const size_t C = (size_t)G * Wc, NE = W ? (size_t)n * (W + 1u) : 0u;
+    std::vector<uint32_t> grp(qr->group ? n : 0u);
+    if (qr->group) HIP_TRY(hipMemcpy(grp.data(), qr->group, grp.size() * 4u, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = qr->group ? grp[s] : 0u;
+        if (g != afp::kSkip && g >= G)
+            return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
+    }
+    hipStream_t st = e->stream;
+    size_t at = 0;
+    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+    // scratch, first part (windows: edges, the error word, the bounds)
+    const size_t o_edges = part(((size_t)W + 1u) * 8u), o_err = part(4u), o_bounds = part(NE * 4u);
+    std::vector<uint64_t> cell_off(C + 1u, 0u);   // (first the sizes, at [c + 1])
+    std::vector<uint32_t> pre, hb;
+    std::vector<uint64_t> dst;
+    afw::WinArgs wa{};
+    auto bind_first = [&]() {
+        unsigned char* b = e->d_pool;
+        wa.edges = reinterpret_cast<const double*>(b + o_edges);
+        wa.err = reinterpret_cast<uint32_t*>(b + o_err);
+        wa.bounds = reinterpret_cast<uint32_t*>(b + o_bounds);
+    };
+    if (W) {   // the cells as af_engine_summarize_windows lays them out
+        if (int rc = pool_reserve(e, at)) return rc;
+        wa.clock = out->clock;
+        wa.counts = out->counts;
+        wa.clock_cap = cap;
+        wa.cnt_completed_slot = AF_CNT_COMPLETED;
+        wa.group = qr->group;
+        wa.n_scen = n;
+        wa.n_win = W;
+        bind_first();
+        HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, qr->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, wa);
+        HIP_TRY(hipGetLastError());
+        hb.resize(NE);
+        HIP_TRY(hipMemcpyAsync(hb.data(), wa.bounds, NE * 4u, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        pre.resize((size_t)n * W);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = qr->group ? grp[s] : 0u;
+            if (g == afp::kSkip) continue;
+            const uint32_t* r = hb.data() + (size_t)s * (W + 1u);
+            uint64_t* sz = cell_off.data() + 1u + (size_t)g * W;
+            uint32_t* ps = pre.data() + (size_t)s * W;
+            for (uint32_t w = 0; w < W; ++w) {
+                if (r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
+                    return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
+                if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
+                ps[w] = (uint32_t)sz[w];
+                sz[w] += r[w + 1u] - r[w];
+            }
+        }
+    } else {   // one cell per group, as af_engine_summarize_pooled lays its groups out
+        std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS);
+        HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+        dst.assign(n, 0u);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = qr->group ? grp[s] : 0u;
+            if (g == afp::kSkip) continue;
+            dst[s] = cell_off[1u + g];   // (for now: the latencies earlier members bring)
+            cell_off[1u + g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], cap);
+        }
+    }
+    // the tiers
+    struct SmallCell { uint32_t pad, cell; };
+    std::vector<SmallCell> small_by;
+    std::vector<afq::QCell> lcells;
+    for (size_t c = 0; c < C; ++c) {
+        const uint64_t len = cell_off[c + 1u];
+        if (len > 0xFFFFFFFFull)
+            return fail(AF_ERR_CAPACITY, (W ? "window " + std::to_string(c % W) + " of group " + std::to_string(c / W) : "group " + std::to_string(c)) + " holds 2^32 or more latencies");
+        if (len > afq::kSmallMax) {
+            lcells.push_back(afq::QCell{cell_off[c], (uint32_t)len, (uint32_t)c});
+        } else if (len > afq::kTinyMax) {
+            uint32_t pad = afq::kSmallMinPad;
+            while (pad < len) pad <<= 1;
+            small_by.push_back(SmallCell{pad, (uint32_t)c});
+        }
+        cell_off[c + 1u] = cell_off[c] + len;
+    }
+    if (!W)
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = qr->group ? grp[s] : 0u;
+            if (g != afp::kSkip) dst[s] += cell_off[g];
+        }
+    std::stable_sort(small_by.begin(), small_by.end(), [](const SmallCell& x, const SmallCell& y) { return x.pad < y.pad; });
+    std::vector<uint32_t> small(small_by.size());
+    for (size_t i = 0; i < small_by.size(); ++i) small[i] = small_by[i].cell;
+    const uint64_t total = cell_off[C];
+    const uint32_t n_small = (uint32_t)small.size(), n_large = (uint32_t)lcells.size();
+    const bool want_q = Q > 0 && qr->quantiles, want_w = T > 0 && qr->within;
+    // large cells: their tiles, and a job per cell and kLv levels
+    std::vector<afp::PoolTile> ctiles, jtiles;
+    std::vector<afp::PoolGroup> jgroups;
+    std::vector<afq::QJob> jobs;
+    uint64_t pieces_unused = 0;
+    for (uint32_t lc = 0; lc < n_large; ++lc) {
+        const uint32_t np = (uint32_t)(((uint64_t)lcells[lc].n + afp::kPiece - 1u) / afp::kPiece);
+        for (uint32_t p = 0; p < np; p += afp::kTilePieces) ctiles.push_back(afp::PoolTile{lc, p, std::min(afp::kTilePieces, np - p), 0u});
+        for (uint32_t l0 = 0; want_q && l0 < Q; l0 += afq::kLv) {
+            pool_add_group(jgroups, jtiles, pieces_unused, lcells[lc].off, lcells[lc].n);
+            jobs.push_back(afq::QJob{lc, l0, std::min<uint32_t>(afq::kLv, Q - l0), 0u});
+        }
+    }
+    const uint32_t n_jobs = (uint32_t)jobs.size(), n_ctiles = (uint32_t)ctiles.size();
+    // scratch, second part
+    const size_t o_lat = part(total * 8u), o_pre = part((size_t)n * W * 4u), o_dst = part(W ? 0u : (size_t)n * 8u), o_off = part((C + 1u) * 8u),
+                 o_small = part((size_t)n_small * 4u), o_lev = part((size_t)Q * 8u), o_thr = part((size_t)T * 8u),
+                 o_lcell = part((size_t)n_large * sizeof(afq::QCell)), o_ctile = part((size_t)n_ctiles * sizeof(afp::PoolTile)),
+                 o_job = part((size_t)n_jobs * sizeof(afq::QJob)), o_thist = part((size_t)n_large * T * 4u);
+    const PoolParts pp = n_jobs ? pool_parts(at, n_jobs, jtiles.size(), 1u) : PoolParts{};
+    if (at > e->pool_cap) {   // the scratch moves: its first part again
+        if (int rc = pool_reserve(e, at)) return rc;
+        if (W) {
+            bind_first();
+            HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, qr->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(wa.bounds, hb.data(), NE * 4u, hipMemcpyHostToDevice, st));
+        }
+    }
+    unsigned char* b = e->d_pool;
+    qr->scratch_bytes = e->pool_cap;
+    afq::QArgs qa{};
+    qa.lat = reinterpret_cast<double*>(b + o_lat);
+    qa.cell_off = reinterpret_cast<const uint64_t*>(b + o_off);
+    qa.n_lev = Q;
+    qa.n_thr = T;
+    qa.levels = reinterpret_cast<const double*>(b + o_lev);
+    qa.thr = reinterpret_cast<const double*>(b + o_thr);
+    qa.count = qr->count;
+    qa.quant = qr->quantiles;
+    qa.within = qr->within;
+    qa.small = reinterpret_cast<const uint32_t*>(b + o_small);
+    qa.lcells = reinterpret_cast<const afq::QCell*>(b + o_lcell);
+    qa.ctiles = reinterpret_cast<const afp::PoolTile*>(b + o_ctile);
+    qa.jobs = reinterpret_cast<const afq::QJob*>(b + o_job);
+    qa.thist = reinterpret_cast<uint32_t*>(b + o_thist);
+    HIP_TRY(hipMemcpyAsync(b + o_off, cell_off.data(), (C + 1u) * 8u, hipMemcpyHostToDevice, st));
+    if (W) {
+        wa.lat = reinterpret_cast<double*>(b + o_lat);
+        wa.pre = reinterpret_cast<const uint32_t*>(b + o_pre);
+        wa.cell_off = qa.cell_off;
+        const uint32_t no_error = afw::kNoError;
+        HIP_TRY(hipMemcpyAsync(b + o_pre, pre.data(), (size_t)n * W * 4u, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(wa.err, &no_error, 4u, hipMemcpyHostToDevice, st));
+        if (W <= afw::kLdsWindows)
+            hipLaunchKernelGGL(afw::af_win_compact<true>, dim3(n), dim3(afw::kThreads), (size_t)W * 8u + ((size_t)W + 1u) * 4u, st, wa);
+        else
+            hipLaunchKernelGGL(afw::af_win_compact<false>, dim3(n), dim3(afw::kThreads), 0, st, wa);
+        HIP_TRY(hipGetLastError());
+        uint32_t bad = afw::kNoError;
+        HIP_TRY(hipMemcpyAsync(&bad, wa.err, 4u, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (bad != afw::kNoError)
+            return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(bad) + " is not in completion order (finish decreases): windows by finish time need it");
+    } else {
+        afp::PoolArgs ca{};
+        ca.clock = out->clock;
+        ca.counts = out->counts;
+        ca.clock_cap = cap;
+        ca.cnt_completed_slot = AF_CNT_COMPLETED;
+        ca.group = qr->group;
+        ca.dst = reinterpret_cast<const uint64_t*>(b + o_dst);
+        ca.lat = reinterpret_cast<double*>(b + o_lat);
+        HIP_TRY(hipMemcpyAsync(b + o_dst, dst.data(), (size_t)n * 8u, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(afp::af_pool_compact, dim3(n), dim3(afp::kThreads), 0, st, ca);
+        HIP_TRY(hipGetLastError());
+    }
+    if (Q) HIP_TRY(hipMemcpyAsync(b + o_lev, qr->levels, (size_t)Q * 8u, hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(b + o_thr, qr->thresholds, (size_t)T * 8u, hipMemcpyHostToDevice, st));
+    if (n_small) HIP_TRY(hipMemcpyAsync(b + o_small, small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
+    constexpr uint64_t kBlocksPerLaunch = 1u << 21;   // (at most 2^30 threads a launch)
+    if (qr->count || want_q || want_w) {
+        for (uint64_t c0 = 0; c0 < C; c0 += kBlocksPerLaunch * afq::kTinyWaves) {   // every cell: a wave takes it if it is tiny (or empty)
+            const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (C - c0 + afq::kTinyWaves - 1u) / afq::kTinyWaves);
+            hipLaunchKernelGGL(afq::af_q_tiny, dim3((uint32_t)blocks), dim3(afq::kTinyWaves * 64), 0, st, qa, c0, (uint64_t)C);
+            HIP_TRY(hipGetLastError());
+        }
+        for (size_t i0 = 0; i0 < small_by.size();) {   // the small cells, one padded size after the other
+            size_t i1 = i0;
+            while (i1 < small_by.size() && small_by[i1].pad == small_by[i0].pad && i1 - i0 < kBlocksPerLaunch) ++i1;
+            hipLaunchKernelGGL(afq::af_q_small, dim3((uint32_t)(i1 - i0)), dim3(afq::kThreads), (size_t)small_by[i0].pad * 8u, st, qa, (uint32_t)i0, small_by[i0].pad);
+            HIP_TRY(hipGetLastError());
+            i0 = i1;
+        }
+    }
+    if (n_large) {
+        HIP_TRY(hipMemcpyAsync(b + o_lcell, lcells.data(), (size_t)n_large * sizeof(afq::QCell), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + o_ctile, ctiles.data(), (size_t)n_ctiles * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
+        afp::PoolArgs pa{};
+        pa.lat = const_cast<double*>(qa.lat);
+        if (n_jobs) {
+            pool_bind(pa, b, pp);
+            HIP_TRY(hipMemcpyAsync(b + o_job, jobs.data(), (size_t)n_jobs * sizeof(afq::QJob), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(pa.groups, jgroups.data(), (size_t)n_jobs * sizeof(afp::PoolGroup), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(const_cast<afp::PoolTile*>(pa.tiles), jtiles.data(), jtiles.size() * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(pa.hist0, 0, (size_t)n_large * afp::kExpBins * 4u, st));   // (one per cell: the first n_large of the jobs')
+        }
+        if (want_w) HIP_TRY(hipMemsetAsync(qa.thist, 0, (size_t)n_large * T * 4u, st));
+        if (n_jobs || want_w) {
+            hipLaunchKernelGGL(afq::af_q_pass0, dim3(n_ctiles), dim3(afq::kThreads), 0, st, qa, pa.hist0);
+            HIP_TRY(hipGetLastError());
+        }
+        if (n_jobs) {
+            const uint32_t n_jtiles = (uint32_t)jtiles.size();
+            for (int level = 0;; ++level) {   // (shift 52 -> 42 -> ... -> 2 -> 0: at most six digit levels)
+                HIP_TRY(hipMemsetAsync(pa.any_more, 0, 4u, st));
+                hipLaunchKernelGGL(afq::af_q_select, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa, level);
+                HIP_TRY(hipGetLastError());
+                uint32_t more = 0;
+                HIP_TRY(hipMemcpyAsync(&more, pa.any_more, 4u, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                if (!more) break;
+                if (level >= 6) return fail(AF_ERR_HIP, "quantile analyzer: radix select did not converge");
+                HIP_TRY(hipMemsetAsync(pa.dhist, 0, (size_t)n_jobs * afp::kRanks * afp::kDigBins * 4u, st));
+                hipLaunchKernelGGL(afp::af_pool_digits, dim3(n_jtiles), dim3(afp::kThreads), 0, st, pa);
+                HIP_TRY(hipGetLastError());
+            }
+            HIP_TRY(hipMemsetAsync(pa.cand_n, 0, (size_t)n_jobs * afp::kRanks * 4u, st));
+            hipLaunchKernelGGL(afq::af_q_cand, dim3(n_jtiles), dim3(afq::kThreads), 0, st, pa);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(afq::af_q_final, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa);
+            HIP_TRY(hipGetLastError());
+        }
+        if (qr->count || want_w) {
+            hipLaunchKernelGGL(afq::af_q_large_rows, dim3(n_large), dim3(64), 0, st, qa);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    qr->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
 

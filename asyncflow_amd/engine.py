@@ -298,6 +298,37 @@ class Engine:
         _check(self._lib, self._lib.af_engine_summarize_windows(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_windows")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_quantiles(self, n: int, n_groups: int, levels: Any, *, edges: Any = None, thresholds: Any = None,
+                            clock_ptr: int, clock_capacity: int, counts_ptr: int, count_ptr: int = 0, quantiles_ptr: int = 0,
+                            within_ptr: int = 0, group_ptr: int = 0) -> tuple[float, int]:
+        """Quantile analyzer on the device (``af_engine_summarize_quantiles``): per (group, window by finish time)
+        ``count`` uint32 [n_groups, W], ``quantiles`` f64 [n_groups, W, Q] and ``within`` uint32 [n_groups, W, T] (the
+        latencies <= each threshold); a NULL pointer skips an output.  ``levels``: HOST float64 in [0, 1]; ``thresholds``:
+        HOST float64 seconds or None; ``edges``: HOST float64, strictly increasing, W = len(edges) - 1, or None: the whole
+        run, one cell per group (W = 1).  ``group_ptr`` as in :meth:`summarize_pooled`.  Returns the call's wall time in
+        ms and the engine's scratch size in bytes."""
+        from .results import check_levels, check_slo_thresholds
+
+        q, th = np.ascontiguousarray(check_levels(levels)), np.ascontiguousarray(check_slo_thresholds(thresholds))
+        if q.shape[0] == 0 and th.shape[0] == 0:
+            msg = "at least one quantile level or one threshold is needed"
+            raise ValueError(msg)
+        e = None
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.float64)
+            if e.ndim != 1 or e.shape[0] < 2:
+                msg = f"window edges must be a vector of at least two values, not of shape {e.shape}"
+                raise ValueError(msg)
+        pd = C.POINTER(C.c_double)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), 0, None, C.c_void_p(counts_ptr))
+        req = _abi.AfQuantiles(int(n), int(n_groups), 0 if e is None else int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
+                               e.ctypes.data_as(pd) if e is not None else None,
+                               int(q.shape[0]), q.ctypes.data_as(pd) if q.shape[0] else None,
+                               int(th.shape[0]), th.ctypes.data_as(pd) if th.shape[0] else None,
+                               C.c_void_p(count_ptr or None), C.c_void_p(quantiles_ptr or None), C.c_void_p(within_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_quantiles(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_quantiles")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def summarize_series_windows(self, n: int, n_groups: int, tick_edges: Any, *, samples_ptr: int, tick_capacity: int,
                                  counts_ptr: int, count_ptr: int, mean_ptr: int, min_ptr: int = 0, max_ptr: int = 0,
                                  above_ptr: int = 0, group_ptr: int = 0, thresholds: Any = None) -> tuple[float, int]:

@@ -90,6 +90,89 @@ def latency_window_stats(clock: np.ndarray, edges: Any) -> np.ndarray:
     return np.stack([latency_stats_row(lat[r[w]:r[w + 1]]) for w in range(e.shape[0] - 1)])
 
 
+def check_levels(levels: Any) -> np.ndarray:
+    """``levels`` as a float64 vector, or ValueError: one dimension, at most ``AF_MAX_QUANTILE_LEVELS``, each in [0, 1]."""
+    q = np.array(levels, dtype=np.float64)
+    if q.ndim != 1:
+        msg = f"quantile levels must be a vector, not of shape {q.shape}"
+        raise ValueError(msg)
+    if q.shape[0] > _abi.MAX_QUANTILE_LEVELS:
+        msg = f"at most {_abi.MAX_QUANTILE_LEVELS} quantile levels a call, not {q.shape[0]}"
+        raise ValueError(msg)
+    if not ((q >= 0.0) & (q <= 1.0)).all():
+        msg = "quantile levels must lie in [0, 1]"
+        raise ValueError(msg)
+    return q
+
+
+def check_slo_thresholds(thresholds: Any) -> np.ndarray:
+    """``thresholds`` (seconds; None: none) as a float64 vector, or ValueError: one dimension, at most
+    ``AF_MAX_SLO_THRESHOLDS``, no NaN (an infinite threshold is fine)."""
+    th = np.zeros(0, dtype=np.float64) if thresholds is None else np.array(thresholds, dtype=np.float64)
+    if th.ndim != 1:
+        msg = f"thresholds must be a vector, not of shape {th.shape}"
+        raise ValueError(msg)
+    if th.shape[0] > _abi.MAX_SLO_THRESHOLDS:
+        msg = f"at most {_abi.MAX_SLO_THRESHOLDS} thresholds a call, not {th.shape[0]}"
+        raise ValueError(msg)
+    if np.isnan(th).any():
+        msg = "thresholds must not be NaN"
+        raise ValueError(msg)
+    return th
+
+
+def latency_quantiles(lat: Any, levels: Any) -> np.ndarray:
+    """The quantiles ``levels`` (each in [0, 1]) of one latency sample: float64 [len(levels)], NaN each for an empty
+    sample.  For the sorted sample x[0] <= ... <= x[n-1]: ``v = (n - 1) * q``, ``lo = floor(v)``, ``hi = min(lo + 1,
+    n - 1)``, ``t = v - lo``, ``d = x[hi] - x[lo]``, and ``x[hi] - d * (1 - t)`` where ``t >= 0.5``, else ``x[lo] + d * t``:
+    ``np.quantile(lat, levels)`` bit for bit, written out.  The definition the device analyzer
+    (``af_engine_summarize_quantiles``) is bit-equal to."""
+    q = check_levels(levels)
+    x = np.sort(np.asarray(lat, dtype=np.float64).reshape(-1))
+    n = x.shape[0]
+    if n == 0:
+        return np.full(q.shape, np.nan)
+    v = np.float64(n - 1) * q
+    f = np.floor(v)
+    lo = f.astype(np.int64)
+    hi = np.minimum(lo + 1, n - 1)
+    t = v - f
+    a, b = x[lo], x[hi]
+    with np.errstate(invalid="ignore"):
+        d = b - a
+        return np.where(t >= 0.5, b - d * (1.0 - t), a + d * t)
+
+
+def latency_within(lat: Any, thresholds: Any) -> np.ndarray:
+    """How many latencies of one sample meet each objective: ``#{lat <= threshold}``, uint32 [len(thresholds)]."""
+    th = check_slo_thresholds(thresholds)
+    x = np.asarray(lat, dtype=np.float64).reshape(-1)
+    return np.array([np.count_nonzero(x <= t) for t in th], dtype=np.uint32)
+
+
+def latency_window_quantiles(clock: np.ndarray, edges: Any, levels: Any, thresholds: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Quantiles and SLO counts per time window of ONE scenario's ``rqs_clock`` [m, 2]: ``(count`` uint32 [W], ``quantiles``
+    float64 [W, Q], ``within`` uint32 [W, T]``)``; the windows are :func:`latency_window_stats`'s (``edges[w] < finish <=
+    edges[w + 1]``, rows in completion order).  ``edges=None``: the whole run as one window, in any row order."""
+    q, th = check_levels(levels), check_slo_thresholds(thresholds)
+    ck = np.asarray(clock, dtype=np.float64).reshape(-1, 2)
+    finish = ck[:, 1]
+    lat = finish - ck[:, 0]
+    if edges is None:
+        r = np.array([0, lat.shape[0]])
+    else:
+        e = check_edges(edges)
+        if finish.size > 1 and (np.diff(finish) < 0.0).any():
+            msg = "rqs_clock is not in completion order (finish decreases): windows by finish time need it"
+            raise ValueError(msg)
+        r = np.searchsorted(finish, e, side="right")
+    n_win = r.shape[0] - 1
+    count = np.diff(r).astype(np.uint32)
+    quant = np.stack([latency_quantiles(lat[r[w]:r[w + 1]], q) for w in range(n_win)]).reshape(n_win, q.shape[0])
+    within = np.stack([latency_within(lat[r[w]:r[w + 1]], th) for w in range(n_win)]).reshape(n_win, th.shape[0])
+    return count, quant, within
+
+
 def check_tick_edges(tick_edges: Any) -> np.ndarray:
     """``tick_edges`` as a uint32 vector, or ValueError: at least two tick indices, whole, in [0, 2^32), strictly increasing."""
     raw = np.asarray(tick_edges)
@@ -321,6 +404,21 @@ class ScenarioResults:
         """Latency statistics per time window (by finish time): float64 [W, 8] in LATENCY_KEYS order, for windows of
         ``window_s`` seconds (default 1 s, :func:`window_edges`) or explicit ``edges``: :func:`latency_window_stats`."""
         return latency_window_stats(self.rqs_clock, _resolve_edges(window_s, edges, self._plan.total_time))
+
+    def get_latency_quantiles(self, levels: Any, *, window_s: float | None = None, edges: Any = None,
+                              thresholds: Any = None) -> dict[str, Any]:
+        """Any latency quantiles (``levels`` in [0, 1]) and, with ``thresholds`` (seconds), how many requests met each
+        objective: :func:`latency_window_quantiles`.  Neither ``window_s`` nor ``edges``: the whole run (``count`` scalar,
+        ``quantiles`` [Q], ``within`` [T]); otherwise per window of ``window_s`` seconds or explicit ``edges`` (``count``
+        [W], ``quantiles`` [W, Q], ``within`` [W, T]).  ``share`` = within / count (NaN where empty)."""
+        whole = window_s is None and edges is None
+        e = None if whole else _resolve_edges(window_s, edges, self._plan.total_time)
+        count, quant, within = latency_window_quantiles(self.rqs_clock, e, levels, thresholds)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            share = np.where(count[:, None] > 0, within / count[:, None].astype(np.float64), np.nan)
+        if whole:
+            return {"count": int(count[0]), "quantiles": quant[0], "within": within[0], "share": share[0], "edges": None}
+        return {"count": count, "quantiles": quant, "within": within, "share": share, "edges": e}
 
     def get_series_window_stats(self, window_s: float | None = None, *, ticks_per_window: int | None = None,
                                 tick_edges: Any = None, thresholds: Any = None) -> dict[str, np.ndarray]:
@@ -769,6 +867,103 @@ class BatchedResults:
             cols[f"window_q05:{k}"] = np.ascontiguousarray(bands["q_lo"][:, :, j])
             cols[f"window_q95:{k}"] = np.ascontiguousarray(bands["q_hi"][:, :, j])
         cols["window_edges"] = np.asarray(bands["edges"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
+    def quantile_summary(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
+                         by: Any = None) -> dict[str, Any]:
+        """Any latency quantiles and SLO shares of every (group, time window): p99.9 at a grid point, p90 during an
+        outage, the share of requests that met a 200 ms objective in every 10 s window.  Computed by the HIP quantile
+        analyzer (``af_engine_summarize_quantiles``), bit-equal to :func:`latency_window_quantiles` / ``np.quantile`` on
+        the concatenated latencies of the group's scenarios.  ``levels`` in [0, 1] and ``thresholds`` in seconds (None:
+        none): any order, duplicates allowed, at most 64 each.  Neither ``window_s`` nor ``edges``: the whole run, one row
+        per group (W = 1, ``edges`` None; rows need not be in completion order); otherwise windows as in
+        :meth:`window_summary`.  ``by`` as there, ``"scenario"`` included.  Returns, on the run's device, ``quantiles``
+        float64 [G, W, Q] (NaN where empty), ``count`` int64 [G, W], ``within`` int64 [G, W, T] and ``share`` float64
+        [G, W, T] (= within / count, NaN where empty); ``levels``, ``thresholds``, ``edges``, ``replicas`` [G],
+        ``quantile_ms`` and ``scratch_bytes``."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_clock()
+        q, th = check_levels(levels), check_slo_thresholds(thresholds)
+        if q.shape[0] == 0 and th.shape[0] == 0:
+            msg = "quantile_summary needs at least one level or one threshold"
+            raise ValueError(msg)
+        whole = window_s is None and edges is None
+        e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        n_win = 1 if e is None else int(e.shape[0] - 1)
+        clock = self._clock_t
+        dev = clock.device
+        quant = torch.empty((n_groups, n_win, q.shape[0]), dtype=torch.float64, device=dev)
+        count = torch.empty((n_groups, n_win), dtype=torch.int32, device=dev)
+        within = torch.empty((n_groups, n_win, th.shape[0]), dtype=torch.int32, device=dev)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_quantiles(
+            len(self), n_groups, q, edges=e, thresholds=th, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(), quantiles_ptr=quant.data_ptr() if q.shape[0] else 0,
+            within_ptr=within.data_ptr() if th.shape[0] else 0, group_ptr=grp.data_ptr())
+        cnt = count.to(torch.int64) & 0xFFFFFFFF   # (the device's words are uint32)
+        wth = within.to(torch.int64) & 0xFFFFFFFF
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        share = torch.where((cnt > 0)[:, :, None], wth.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)[:, :, None], nan)
+        return {"quantiles": quant, "count": cnt, "within": wth, "share": share, "levels": q, "thresholds": th, "edges": e,
+                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "quantile_ms": ms, "scratch_bytes": scratch}
+
+    def quantile_bands(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
+                       by: Any = None, level: float = 0.95, q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of the quantiles and SLO shares: every scenario's own values
+        (``quantile_summary(by="scenario")``), then per group (``by``) and window, over the group's replicas whose window
+        is not empty (``n`` [G, W] of them), ``mean``, ``std``, ``ci_halfwidth`` (at ``level``) and the linear quantiles
+        ``q_lo`` / ``q_hi`` (``q``) as :func:`window_bands_by_group` gives them: numpy float64 [G, W, Q + T], the levels'
+        columns first, then the thresholds' shares.  ``pooled_quantiles`` [G, W, Q], ``pooled_share`` [G, W, T] and
+        ``pooled_count`` [G, W] are ``quantile_summary(by=by)`` as numpy."""
+        import torch
+
+        whole = window_s is None and edges is None
+        e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        per = self.quantile_summary(levels, thresholds=thresholds, edges=e, by="scenario")
+        out = window_bands_by_group(torch.cat([per["quantiles"], per["share"]], dim=2), ids, n_groups, level, q, valid=per["count"] > 0)
+        pooled = self.quantile_summary(levels, thresholds=thresholds, edges=e, by=ids)
+        out["pooled_quantiles"] = pooled["quantiles"].cpu().numpy()[:n_groups]
+        out["pooled_share"] = pooled["share"].cpu().numpy()[:n_groups]
+        out["pooled_count"] = pooled["count"].cpu().numpy()[:n_groups]
+        out["levels"], out["thresholds"], out["edges"] = per["levels"], per["thresholds"], e
+        return out
+
+    def save_quantile_summary(self, path: str, by: Any = None, *, levels: Any, thresholds: Any = None,
+                              window_s: float | None = None, edges: Any = None, level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the quantiles and SLO shares with one row per group (grid point): ``param:<axis>`` (for a
+        Sweep), ``replicas``, ``quantile_count`` [G, W], and per level i / threshold j the [G, W] columns
+        ``quantile_pooled:<i>`` / ``share_pooled:<j>`` (the group's replicas pooled) and ``quantile_mean:<i>``,
+        ``quantile_q05:<i>``, ``quantile_q95:<i>`` / ``share_mean:<j>``, ``share_q05:<j>``, ``share_q95:<j>`` (over the
+        replicas, :meth:`quantile_bands`); ``quantile_levels`` [Q], ``slo_thresholds`` [T] and ``window_edges`` [W + 1]
+        (empty for the whole run) are per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        bands = self.quantile_bands(levels, thresholds=thresholds, window_s=window_s, edges=edges, by=by, level=level, q=(0.05, 0.95))
+        n_groups = int(bands["replicas"].shape[0])
+        n_lev = int(bands["levels"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        cols["quantile_count"] = np.ascontiguousarray(bands["pooled_count"], dtype=np.int64)
+        for what, base, cnt, pooled in (("quantile", 0, n_lev, bands["pooled_quantiles"]),
+                                        ("share", n_lev, int(bands["thresholds"].shape[0]), bands["pooled_share"])):
+            for i in range(cnt):
+                cols[f"{what}_pooled:{i}"] = np.ascontiguousarray(pooled[:, :, i])
+                cols[f"{what}_mean:{i}"] = np.ascontiguousarray(bands["mean"][:, :, base + i])
+                cols[f"{what}_q05:{i}"] = np.ascontiguousarray(bands["q_lo"][:, :, base + i])
+                cols[f"{what}_q95:{i}"] = np.ascontiguousarray(bands["q_hi"][:, :, base + i])
+        cols["quantile_levels"] = np.asarray(bands["levels"], dtype=np.float64)
+        cols["slo_thresholds"] = np.asarray(bands["thresholds"], dtype=np.float64)
+        cols["window_edges"] = np.zeros(0, dtype=np.float64) if bands["edges"] is None else np.asarray(bands["edges"], dtype=np.float64)
         _write_columns(str(path), cols, n_groups)
         return cols
 
@@ -1291,6 +1486,18 @@ class ShardedResults:
 
     def save_series_window_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_window_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "quantile_summary() of a sweep run on several devices: quantiles across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def quantile_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "quantile_bands() of a sweep run on several devices: quantiles across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_quantile_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_quantile_summary() of a sweep run on several devices: quantiles across devices are not implemented"
         raise NotImplementedError(msg)
 
 

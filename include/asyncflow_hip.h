@@ -473,6 +473,50 @@ typedef struct af_series_windows {
 } af_series_windows_t;
 int af_engine_summarize_series_windows(af_engine_t* engine, const af_outputs_t* out, af_series_windows_t* series_windows);
 
+/* Arbitrary latency QUANTILES and SLO counts per group and time window on the device (asyncflow_amd/csrc/af_quantiles.hpp):
+ * p99.9 at a grid point, p90 during an outage, how many requests met a 200 ms objective in every 10 s window.  The cells and
+ * their samples are af_windows_t's: cell c = g * n_windows + w holds, in ascending scenario index over the members of g,
+ * finish - start over the rows with edges[w] < finish <= edges[w + 1]; the same completion-order check, AF_ERR_INVALID naming
+ * the scenario, nothing written.  With n_windows == 0 and edges == NULL there is ONE cell per group over all stored rows of
+ * its members (af_pooled_t's sample); completion order is then neither needed nor checked.  C = n_groups * max(n_windows, 1).
+ * For a cell of n >= 1 latencies x[0] <= ... <= x[n-1] and a level q in [0, 1]:
+ *     v = (double)(n - 1) * q;  lo = floor(v);  hi = min(lo + 1, n - 1);  t = v - lo;  d = x[hi] - x[lo];
+ *     quantile = t >= 0.5 ? x[hi] - d * (1 - t) : x[lo] + d * t
+ * which is np.quantile(a, q) (method 'linear') bit for bit.  Level 0.5 is therefore np.quantile(a, 0.5), which is NOT always
+ * the `median` column of the other analyzers bit for bit (np.median is the mean of the middle pair: about one sample in 280
+ * differs in the last digit); levels 0.95 and 0.99 DO equal their p95 / p99 columns, levels 0 and 1 their min / max.
+ * within[c][i] = #{ x <= thresholds[i] }, compared as f64: an exact integer.  An empty cell: count 0, every quantile NaN,
+ * every within 0.  Column i of an output belongs to levels[i] / thresholds[i]; any order, duplicates allowed.  A cell's
+ * result does not depend on which other cells, levels or thresholds the call holds, and is identical from run to run
+ * (selection by sorting / counting, integer atomics only).
+ * Refused: a level that is NaN or outside [0, 1], a NaN threshold (+-inf is fine), n_levels == 0 together with
+ * n_thresholds == 0, more than AF_MAX_QUANTILE_LEVELS levels or AF_MAX_SLO_THRESHOLDS thresholds, edges not strictly
+ * increasing or not finite, a group id >= n_groups, an inversion of completion order in windowed mode (AF_ERR_INVALID); a
+ * cell of 2^32 or more latencies, C >= 2^32 - 1 (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).
+ * Scratch kept by the engine (shared with the other group analyzers): 8 B per latency in a cell + 4 B per (scenario, edge)
+ * + 4 B per (scenario, window) + 12 B per cell + 8 B per scenario + 8 B per edge + 1 KB (levels, thresholds) + 4 KB of
+ * alignment, and for every cell of more than 8 192 latencies only: 4 B per threshold + ceil(n_levels / 3) * 58 KB +
+ * (1 + ceil(n_levels / 3)) * 16 B per 131 072 latencies.  Synchronous; the struct is written back. */
+#define AF_MAX_QUANTILE_LEVELS 64
+#define AF_MAX_SLO_THRESHOLDS 64
+typedef struct af_quantiles {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;        /* 0 (with edges NULL): one cell per group over the whole run */
+    const uint32_t* group;     /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const double* edges;       /* HOST [n_windows + 1] strictly increasing, finite; NULL with n_windows == 0 */
+    uint32_t n_levels;
+    const double* levels;      /* HOST [n_levels] in [0, 1] */
+    uint32_t n_thresholds;
+    const double* thresholds;  /* HOST [n_thresholds] seconds, not NaN; may be NULL with n_thresholds == 0 */
+    uint32_t* count;           /* DEVICE [C] u32; NULL skips */
+    double* quantiles;         /* DEVICE [C][n_levels] f64; NULL skips */
+    uint32_t* within;          /* DEVICE [C][n_thresholds] u32; NULL skips */
+    double elapsed_ms;         /* out: wall time of the call */
+    uint64_t scratch_bytes;    /* out: size of the engine's scratch after the call */
+} af_quantiles_t;
+int af_engine_summarize_quantiles(af_engine_t* engine, const af_outputs_t* out, af_quantiles_t* quantiles);
+
 /* af_engine_run followed by af_engine_summarize, in one call and with the same results (replaces SimulationRunner.run +
  * ResultsAnalyzer.process_all_metrics, simulation_runner.py:349-376 + analyzer.py:75-81, for the whole sweep).
  * summary->n_scenarios must equal sweep->n_scenarios.  Where the sweep is ONE launch of the stage-parallel kernel, the analyzer
