@@ -573,8 +573,12 @@ __global__ __launch_bounds__(kThreads, kWpe) void af_summary_kernel(SumArgs a) {
 // (samples [n][tick_cap][pitch] 4-byte words; only the first counts[CNT_TICKS] rows are valid).
 // Column j < n_edges and the ready / io columns of a server hold int32 counts; the ram_in_use
 // column (j = n_edges + 3 s + 2) holds float32 values (include/asyncflow_hip.h): its mean is the
-// f64 sum of the float values / ticks, its maximum the float maximum, returned as float32 bits
-// (for non-negative floats the bit patterns order like the values).
+// f64 sum of the float values / ticks, its maximum the float maximum, returned as float32 bits.
+// The words of non-negative floats order like their values, those of negative floats the other
+// way round (the reference's float arithmetic leaves residues such as -2.8e-14 MB in ram_in_use):
+// the float maximum is the largest word as a SIGNED integer if that is >= 0, else -- every value is
+// negative -- the smallest word; the loop keeps both beside the unsigned maximum of the integer
+// columns, and a thread hands on the order-preserving key of its float maximum (0: no row).
 struct SeriesArgs {
     const uint32_t* samples;
     const uint32_t* counts;
@@ -590,6 +594,15 @@ constexpr int kSeriesThreads = 256;
 
 __device__ __forceinline__ bool series_is_float(uint32_t j, uint32_t n_edges, uint32_t n_series) {
     return j >= n_edges && j < n_series && (j - n_edges) % 3u == 2u;
+}
+
+// float32 words (no NaN) -> unsigned keys that order like the values, all of them > 0; and back
+__device__ __forceinline__ uint32_t float_key(uint32_t w) { return (w & 0x80000000u) ? ~w : (w | 0x80000000u); }
+__device__ __forceinline__ uint32_t float_unkey(uint32_t k) { return (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k; }
+// a thread's maximum of a column: integer columns the unsigned maximum, float columns the key of the float maximum
+__device__ __forceinline__ uint32_t series_part_max(bool is_f, bool any, uint32_t umax, int32_t imax, uint32_t umin) {
+    if (!is_f) return umax;
+    return any ? float_key(imax >= 0 ? (uint32_t)imax : umin) : 0u;
 }
 
 __global__ __launch_bounds__(kSeriesThreads) void af_series_kernel(SeriesArgs a) {
@@ -610,6 +623,8 @@ __global__ __launch_bounds__(kSeriesThreads) void af_series_kernel(SeriesArgs a)
     unsigned long long s0 = 0, s1 = 0, s2 = 0, s3 = 0;
     double f0 = 0.0, f1 = 0.0, f2 = 0.0, f3 = 0.0;
     uint32_t m0 = 0, m1 = 0, m2 = 0, m3 = 0;
+    int32_t i0 = INT32_MIN, i1 = INT32_MIN, i2 = INT32_MIN, i3 = INT32_MIN;       // largest word, signed
+    uint32_t n0 = 0xFFFFFFFFu, n1 = 0xFFFFFFFFu, n2 = 0xFFFFFFFFu, n3 = 0xFFFFFFFFu;   // smallest word
     if ((uint32_t)tid < stride) {
         for (uint32_t i = tid; i < total; i += stride) {
             const uint4 v = rows[i];
@@ -618,13 +633,21 @@ __global__ __launch_bounds__(kSeriesThreads) void af_series_kernel(SeriesArgs a)
             f2 += (double)__uint_as_float(v.z); f3 += (double)__uint_as_float(v.w);
             m0 = v.x > m0 ? v.x : m0; m1 = v.y > m1 ? v.y : m1;
             m2 = v.z > m2 ? v.z : m2; m3 = v.w > m3 ? v.w : m3;
+            i0 = (int32_t)v.x > i0 ? (int32_t)v.x : i0; i1 = (int32_t)v.y > i1 ? (int32_t)v.y : i1;
+            i2 = (int32_t)v.z > i2 ? (int32_t)v.z : i2; i3 = (int32_t)v.w > i3 ? (int32_t)v.w : i3;
+            n0 = v.x < n0 ? v.x : n0; n1 = v.y < n1 ? v.y : n1;
+            n2 = v.z < n2 ? v.z : n2; n3 = v.w < n3 ? v.w : n3;
         }
     }
+    const bool any = (uint32_t)tid < stride && (uint32_t)tid < total;
     part_sum[tid][0] = series_is_float(col + 0u, a.n_edges, a.n_series) ? (unsigned long long)__double_as_longlong(f0) : s0;
     part_sum[tid][1] = series_is_float(col + 1u, a.n_edges, a.n_series) ? (unsigned long long)__double_as_longlong(f1) : s1;
     part_sum[tid][2] = series_is_float(col + 2u, a.n_edges, a.n_series) ? (unsigned long long)__double_as_longlong(f2) : s2;
     part_sum[tid][3] = series_is_float(col + 3u, a.n_edges, a.n_series) ? (unsigned long long)__double_as_longlong(f3) : s3;
-    part_max[tid][0] = m0; part_max[tid][1] = m1; part_max[tid][2] = m2; part_max[tid][3] = m3;
+    part_max[tid][0] = series_part_max(series_is_float(col + 0u, a.n_edges, a.n_series), any, m0, i0, n0);
+    part_max[tid][1] = series_part_max(series_is_float(col + 1u, a.n_edges, a.n_series), any, m1, i1, n1);
+    part_max[tid][2] = series_part_max(series_is_float(col + 2u, a.n_edges, a.n_series), any, m2, i2, n2);
+    part_max[tid][3] = series_part_max(series_is_float(col + 3u, a.n_edges, a.n_series), any, m3, i3, n3);
     __syncthreads();
     for (uint32_t j = tid; j < a.n_series; j += kSeriesThreads) {
         const uint32_t g = j / 4u, k = j % 4u;
@@ -638,7 +661,7 @@ __global__ __launch_bounds__(kSeriesThreads) void af_series_kernel(SeriesArgs a)
             mx = part_max[t][k] > mx ? part_max[t][k] : mx;
         }
         if (a.mean) a.mean[(size_t)sc * a.n_series + j] = ticks ? (is_f ? sf : (double)si) / (double)ticks : __builtin_nan("");
-        if (a.maxv) a.maxv[(size_t)sc * a.n_series + j] = mx;
+        if (a.maxv) a.maxv[(size_t)sc * a.n_series + j] = is_f && mx != 0u ? float_unkey(mx) : mx;   // (no tick: 0)
     }
 }
 

@@ -571,8 +571,13 @@ class BatchedResults:
         metrics/analyzer.py:83-104), ``rps`` float32 [n, floor(T)] (analyzer.py:108-126),
         ``hist`` int32 [n, hist_bins], ``series_mean`` float64 / ``series_max`` int32
         [n, n_series] (the ram_in_use columns of ``series_max`` hold float32 BITS, like the sample
-        words they are the maximum of: decode with :meth:`decode_series_max`).  Every statistic is bit-equal to numpy's (round 6:
-        mean and std_dev too -- the kernel adds in numpy's own order, af_summary.hpp).
+        words they are the maximum of: decode with :meth:`decode_series_max`; it is the FLOAT maximum, also of a
+        column that holds negative residues of the reference's float arithmetic).  The latency statistics, RPS windows,
+        histogram, ``series_max`` and the ``series_mean`` of the integer series are bit-equal to numpy's (round 6: mean and
+        std_dev too -- the kernel adds in numpy's own order, af_summary.hpp).  ``series_mean`` of a ram_in_use column is
+        bit-equal to numpy's while the values add exactly (multiples of 1/256 MB below 2^16, every integer RAM need), and
+        otherwise within ``n * 2**-52`` of ``math.fsum(x) / n`` relative to ``sum(abs(x)) / n`` (per-thread partial sums in
+        a fixed order: the same bytes from run to run and in every batch).
         A run made with ``SimulationRunner(summary=...)`` computed the summary in the engine call of the simulation itself
         (``af_engine_run_summarized``): the same arguments return those tensors.
         """

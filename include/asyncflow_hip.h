@@ -379,6 +379,14 @@ typedef struct af_summary_t {
     double* series_mean;    /* [n][af_series_count] f64 (needs outputs.samples)         */
     uint32_t* series_max;   /* [n][af_series_count] u32                                 */
 } af_summary_t;
+/* series_mean / series_max over the m = min(counts[AF_CNT_TICKS], tick_capacity) stored rows of a scenario (m = 0: NaN / 0).
+ * Integer series: (double)(exact integer sum) / (double)m and the largest word.  ram_in_use (float32 words, column
+ * n_edges + 3 * server + 2): series_max is the FLOAT maximum, returned as its float32 bits -- also where the reference's
+ * own arithmetic left negative residues such as -2.8e-14 in the column, whose words are larger than every positive
+ * value's; series_mean is the f64 sum of the float values, per-thread partial sums added in a fixed order, divided once:
+ * bit-equal to numpy's mean while the values add exactly (multiples of 1/256 below 2^16), otherwise within
+ * m * 2^-52 * sum|x| / m of the exactly rounded sum / m; identical from run to run and in every batch.
+ * rps_buckets + hist_bins <= 24 576 (words of LDS beside the kernel's own; AF_ERR_CAPACITY beyond). */
 
 /* `out` is the af_outputs_t the run filled (clock + counts are required, samples only for the
  * series outputs).  Synchronous like af_engine_run. */
@@ -440,8 +448,8 @@ int af_engine_summarize_windows(af_engine_t* engine, const af_outputs_t* out, af
  * af_pooled_t).  Per (g, w): count, the values in the cell.  Per (g, w, j): mean -- integer series: the exact integer sum,
  * divided once, (double)sum / (double)count, bit-equal to np.mean of the int64 values while the sum is below 2^53;
  * ram_in_use (float32 words, column n_edges + 3 * server + 2): the f64 sum of the float values, divided once --; minv /
- * maxv as 4-byte words like af_summary_t.series_max (float32 bits in the ram columns: they order like the values while
- * these are non-negative; a NEGATIVE float, such as the -2.8e-14 residue the reference's own arithmetic can leave in
+ * maxv as 4-byte words, compared as WORDS (float32 bits in the ram columns: they order like the values while these are
+ * non-negative, and maxv then equals af_summary_t.series_max, which is the float maximum; a NEGATIVE float, such as the -2.8e-14 residue the reference's own arithmetic can leave in
  * ram_in_use, has the sign bit set and is therefore the largest word of its cell, not the smallest value); above: the values > thresholds[j], compared as f64 (NULL: 0.0 each, the non-zero samples).  An empty cell: count
  * 0, mean NaN, minv = maxv = above = 0.
  * Exactness: no atomics; the f64 partial sums of a float column are combined in a fixed order (within a scenario's window:

@@ -8,7 +8,10 @@ kernel families:
 * the feed-forward range of the stage-parallel kernel (idle to saturated tandem servers, every latency law, spikes, outages);
 * the round-4 / 5 range (servers in front of the LB, 4 - 5 server levels, 13 - 16 servers, tiers, general servers, tie storms);
 * sweep columns over every accepted path, each point against the oracle on the payload a user of the reference would build;
-* round 6: fractional RAM needs -- simpy's waiting `Container.put` and dead-locked RAM (next-event kernels' SimPy-order path).
+* round 6: fractional RAM needs -- simpy's waiting `Container.put` and dead-locked RAM (next-event kernels' SimPy-order path);
+* the batched analyzer (`scripts/gpu_fuzz_analyzer.py`): every output of `summary()` and the kernel-side summary against the
+  analyzer oracle, on the campaign's mix of five families and on the fractional-RAM family (ram_in_use values that do not add
+  exactly, residues below zero).
 """
 
 from __future__ import annotations
@@ -88,6 +91,28 @@ def test_waiting_ram_puts_and_dead_locked_ram_on_the_device():
             assert not (w_waits > 0 and int(res.engine_stats.flow_scenarios) != 0), (case, "a waiting put on the stage-parallel kernel")
             dead += (w_counts[_abi.CNT_FLAGS] & _abi.FLAG_RAM_STARVED) != 0
     assert scen >= 160 and waits >= 60 and dead >= 10
+
+
+def _analyzer_tally(t: dict, n_payloads: int) -> None:
+    """Every payload ends in six scenarios and six checks of the kernel-side summary, or in an OverflowError (counted; at most
+    a quarter of the payloads).  The CPU oracle (oracle.bulk.simulate_many, which raises the same way) raises for none of the
+    30 + 12 payloads from k0 = 910 000 on."""
+    assert t["different"] == 0, t["failures"]
+    assert t["overflow_raised"] <= n_payloads // 4
+    assert t["scenarios"] == 6 * t["payloads"] > 0
+    assert t["online_checks"] > 0
+
+
+def test_analyzer_on_the_mix_of_five_payload_families():
+    """30 payloads from an index no recorded campaign used (profiles/r05, r06: 1 000 - 5 999, 20 000 - 20 699, 50 000 - 50 599,
+    100 000 - 101 499, 120 000 - 121 499, 160 000 - 161 499, 500 000 - 501 499, 700 000 - 702 999)."""
+    _analyzer_tally(_script("gpu_fuzz_analyzer").run(30, 910_000), 30)
+
+
+def test_analyzer_on_fractional_ram_payloads():
+    """The family whose ram_in_use values do not add exactly: series_max is the float maximum bit for bit (residues below
+    zero included), the ram_in_use means within n * 2^-52 of fsum / n, everything else bit for bit."""
+    _analyzer_tally(_script("gpu_fuzz_analyzer").run(12, 910_000, family="fractional_ram"), 12)
 
 
 def test_a_saturated_server_with_more_than_16384_waiters_matches_the_oracle():

@@ -189,7 +189,7 @@ def test_one_window_is_the_whole_run_summary(path):
     whole = series_window_stats(words, [0, ticks], plan.n_edges)
     mean, mx = series_mean_max(words, plan.n_edges)
     # (frac_ram_waiting_put_t20 holds 179 ram samples of -2.8e-14, float residue of the reference's own arithmetic: as WORDS
-    # they are the largest of their column, as af_engine_summarize's series_max has them; the oracle takes the float maximum)
+    # they are the largest of their column; the oracle, like af_engine_summarize's series_max, takes the float maximum)
     signed = (words >> 31).any(axis=1)
     assert signed.sum() == (1 if path.stem == "frac_ram_waiting_put_t20" else 0) and not signed[~ram].any()
     assert np.array_equal(whole["max"][0, ~signed], mx[~signed])
