@@ -8,7 +8,8 @@
 //             every 64 / L-th row below it -- consecutive lanes read consecutive 16 bytes, a lane stays on its four columns
 //             (plans of more than 256 padded series: 64 column groups at a time, the rows walked once per 64 groups).  EVERY
 //             STORED ROW INSIDE THE WINDOWS IS READ ONCE.  Per column in registers: the u64 sum of the words or the f64 sum of the
-//             float values (ram_in_use), min / max of the words, the values above the threshold.  The lanes of a column group
+//             float values (ram_in_use), min / max as keys -- the word itself, or afs::float_key of a ram_in_use word, which
+//             orders like the float values with -0.0 below +0.0 --, the values above the threshold.  The lanes of a column group
 //             meet by shuffles down L, 2 L, 4 L, ... lanes -- a fixed tree, the largest distance first -- and the first L lanes
 //             write one record per series: into the outputs when every group is a single scenario, else into scratch.
 //   reduce    a thread per (group, window, series) folds its members' records in ascending scenario index, divides once, and
@@ -19,7 +20,9 @@
 // No limit on the number of series (af_series_kernel stops at 1 024 padded ones).
 // Scratch (engine-owned, shared with the pooled and windowed analyzers): 4 B per edge + 8 B per series + 4 B per group +
 // 4 B per scenario (+ up to 256 B of alignment for each of the eight parts), and -- unless every group is a single scenario --
-// 20 B per (scenario, window, series): 8 B sum, 4 B each min, max, above.
+// 20 B per (scenario, window, series): 8 B sum, 4 B each min, max (as keys), above.
+// Every key of a value lies strictly between 0 and 0xFFFFFFFF (no NaN is sampled), so a lane, a record or a member without a row
+// keeps 0xFFFFFFFF / 0 and never wins; keys become words again only where a cell is written.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -61,7 +64,8 @@ __device__ __forceinline__ uint32_t stored_ticks(const SwinArgs& a, uint32_t s) 
 }
 
 // what a lane keeps of one column: ONE 64-bit sum -- the u64 sum of the words, or the bits of the f64 sum of the float values of
-// a ram_in_use column (the form the record stores) --, min / max of the words, the values above the threshold
+// a ram_in_use column (the form the record stores) --, min / max of the keys (the words; float_key of a ram_in_use word), the
+// values above the threshold
 struct Col {
     unsigned long long sum = 0ull;   // (+0.0 as a double)
     uint32_t mn = 0xFFFFFFFFu, mx = 0u, ab = 0u;
@@ -72,8 +76,9 @@ struct Col {
     __device__ __forceinline__ void add(uint32_t w, bool is_f, double thr) {
         const double x = is_f ? (double)__uint_as_float(w) : (double)w;
         sum = plus(sum, is_f ? (unsigned long long)__double_as_longlong(x) : (unsigned long long)w, is_f);
-        mn = w < mn ? w : mn;
-        mx = w > mx ? w : mx;
+        const uint32_t key = is_f ? afs::float_key(w) : w;
+        mn = key < mn ? key : mn;
+        mx = key > mx ? key : mx;
         ab += x > thr ? 1u : 0u;
     }
     // the partner hdist lanes up; `take` where this lane is the left operand of the tree
@@ -88,6 +93,8 @@ struct Col {
         }
     }
     __device__ __forceinline__ double total(bool is_f) const { return is_f ? __longlong_as_double((long long)sum) : (double)sum; }
+    // a key of a cell that holds a value -> the word that is written
+    __device__ __forceinline__ static uint32_t word(uint32_t key, bool is_f) { return is_f ? afs::float_unkey(key) : key; }
 };
 
 __global__ __launch_bounds__(kThreads) void af_swin_partial(SwinArgs a) {
@@ -158,8 +165,8 @@ __global__ __launch_bounds__(kThreads) void af_swin_partial(SwinArgs a) {
                     if (j >= S) continue;
                     const size_t o = cell * S + j;
                     a.mean[o] = cnt ? c[k].total(is_f[k]) / (double)cnt : __builtin_nan("");
-                    if (a.minv) a.minv[o] = cnt ? c[k].mn : 0u;
-                    if (a.maxv) a.maxv[o] = c[k].mx;
+                    if (a.minv) a.minv[o] = cnt ? Col::word(c[k].mn, is_f[k]) : 0u;
+                    if (a.maxv) a.maxv[o] = cnt ? Col::word(c[k].mx, is_f[k]) : 0u;
                     if (a.above) a.above[o] = c[k].ab;
                 }
             } else {
@@ -208,8 +215,8 @@ __global__ __launch_bounds__(kReduceThreads) void af_swin_reduce(SwinArgs a, uin
     }
     if (j == 0u) a.count[cell] = cnt;
     a.mean[idx] = cnt ? (is_f ? sf : (double)si) / (double)cnt : __builtin_nan("");
-    if (a.minv) a.minv[idx] = cnt ? mn : 0u;
-    if (a.maxv) a.maxv[idx] = mx;
+    if (a.minv) a.minv[idx] = cnt ? Col::word(mn, is_f) : 0u;
+    if (a.maxv) a.maxv[idx] = cnt ? Col::word(mx, is_f) : 0u;
     if (a.above) a.above[idx] = ab;
 }
 

@@ -244,9 +244,11 @@ def series_window_stats(samples: np.ndarray, tick_edges: Any, n_edges: int, thre
     ``get_series`` (analyzer.py:239-244), although the collector takes it at ``(k + 1) * period`` (collector.py:53) --; window
     ``w`` holds the samples ``min(b[w], ticks) <= k < min(b[w + 1], ticks)`` of ``b = tick_edges``.  Returns ``count`` int64
     [W], ``mean`` float64 [W, S] (integer series: the exact integer sum divided once; ``ram_in_use``: the float32 values
-    summed as float64; NaN in an empty window), ``min`` / ``max`` uint32 words [W, S] (float32 bits in the ram columns) and
-    ``above`` uint32 [W, S]: the values ``> thresholds[j]`` (None: 0.0 each, the non-zero samples); an empty window has 0 in
-    all three.  The definition the device analyzer (``af_engine_summarize_series_windows``) matches."""
+    summed as float64; NaN in an empty window), ``min`` / ``max`` uint32 words [W, S] -- integer series: the smallest /
+    largest word; ``ram_in_use``: the float minimum / maximum of the values as float32 bits, -0.0 below +0.0 (the IEEE total
+    order, the one ``series_max`` of the whole-run summary has), which on non-negative values is the order of the words --
+    and ``above`` uint32 [W, S]: the values ``> thresholds[j]`` (None: 0.0 each, the non-zero samples); an empty window has 0
+    in all three.  The definition the device analyzer (``af_engine_summarize_series_windows``) matches."""
     b = check_tick_edges(tick_edges)
     words = np.ascontiguousarray(samples).view(np.uint32)
     if words.ndim != 2:
@@ -272,7 +274,11 @@ def series_window_stats(samples: np.ndarray, tick_edges: Any, n_edges: int, thre
         values = seg.astype(np.float64)
         values[ram] = seg[ram].view(np.float32).astype(np.float64)
         mean[w] = np.where(ram, np.mean(values, axis=1), seg.astype(np.int64).sum(axis=1).astype(np.float64) / float(count[w]))
-        mn[w], mx[w] = seg.min(axis=1), seg.max(axis=1)
+        # (ram_in_use: keys that order like the float values -- a negative value's bits inverted, the others above them)
+        key = np.where(ram[:, None], np.where(seg >> 31 != 0, ~seg, seg | np.uint32(0x80000000)), seg)
+        kmn, kmx = key.min(axis=1), key.max(axis=1)
+        mn[w] = np.where(ram, np.where(kmn >> 31 != 0, kmn & np.uint32(0x7FFFFFFF), ~kmn), kmn)
+        mx[w] = np.where(ram, np.where(kmx >> 31 != 0, kmx & np.uint32(0x7FFFFFFF), ~kmx), kmx)
         above[w] = (values > thr[:, None]).sum(axis=1)
     return {"count": count, "mean": mean, "min": mn, "max": mx, "above": above}
 
@@ -425,7 +431,8 @@ class ScenarioResults:
         """Statistics of every sampled series per window of ticks (:func:`series_window_stats`): windows of ``window_s``
         seconds (a multiple of the sample period; default 1 s), of ``ticks_per_window`` ticks, or explicit ``tick_edges``.
         Sample ``k`` carries the label ``k * sample_period`` (``get_series``), so a window of ``m`` ticks labelled ``t``
-        holds the samples labelled ``t <= label < t + m * sample_period``."""
+        holds the samples labelled ``t <= label < t + m * sample_period``.  ``min`` / ``max`` of a ``ram_in_use`` series are
+        the float minimum / maximum (float32 bits, -0.0 below +0.0), those of the other series the smallest / largest count."""
         if self._samples is None:
             msg = "run(collect_samples=False) kept no sampled series"
             raise RuntimeError(msg)
@@ -1007,7 +1014,9 @@ class BatchedResults:
         as in :meth:`window_summary`.  ``thresholds``: None (0.0), a vector [n_series] or ``{series name: value}`` over
         :meth:`series_names` (missing: 0.0).  Returns torch tensors on the run's device: ``count`` int64 [G, W]; ``mean``,
         ``min``, ``max`` and ``above_share`` (values above the threshold / count) float64 [G, W, S], NaN in empty cells;
-        the raw ``min_words`` / ``max_words`` / ``above`` int32; and ``series``, ``tick_edges``, ``times`` (the windows'
+        the raw ``min_words`` / ``max_words`` / ``above`` int32 (``ram_in_use``: the float32 bits of the float minimum /
+        maximum, -0.0 below +0.0, so one window over the whole run has ``max_words`` equal to ``series_max`` of
+        :meth:`summary`; the other series: the smallest / largest count); and ``series``, ``tick_edges``, ``times`` (the windows'
         start labels in seconds), ``replicas`` [G], ``series_window_ms``, ``scratch_bytes``."""
         import torch
 

@@ -448,9 +448,12 @@ int af_engine_summarize_windows(af_engine_t* engine, const af_outputs_t* out, af
  * af_pooled_t).  Per (g, w): count, the values in the cell.  Per (g, w, j): mean -- integer series: the exact integer sum,
  * divided once, (double)sum / (double)count, bit-equal to np.mean of the int64 values while the sum is below 2^53;
  * ram_in_use (float32 words, column n_edges + 3 * server + 2): the f64 sum of the float values, divided once --; minv /
- * maxv as 4-byte words, compared as WORDS (float32 bits in the ram columns: they order like the values while these are
- * non-negative, and maxv then equals af_summary_t.series_max, which is the float maximum; a NEGATIVE float, such as the -2.8e-14 residue the reference's own arithmetic can leave in
- * ram_in_use, has the sign bit set and is therefore the largest word of its cell, not the smallest value); above: the values > thresholds[j], compared as f64 (NULL: 0.0 each, the non-zero samples).  An empty cell: count
+ * maxv as 4-byte words: of an integer series the smallest / largest word; of ram_in_use the float MINIMUM / MAXIMUM of the
+ * values, returned as float32 bits, with -0.0 below +0.0 (the IEEE total order on the non-NaN values; the -2.8e-14 residues
+ * that the reference's own arithmetic can leave in ram_in_use are the smallest values of their cells, not the largest).  One
+ * window over a scenario's whole run therefore has maxv equal to af_summary_t.series_max word for word, and on non-negative
+ * values the float order is the order of the words; above: the values > thresholds[j], compared as f64 (+0.0 is not above
+ * -0.0; NULL: 0.0 each, the non-zero samples).  An empty cell: count
  * 0, mean NaN, minv = maxv = above = 0.
  * Exactness: no atomics; the f64 partial sums of a float column are combined in a fixed order (within a scenario's window:
  * a lane's rows top down, then a fixed tree over the lanes; across the members of a group: ascending scenario index), so the

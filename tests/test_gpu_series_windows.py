@@ -2,7 +2,10 @@
 blocks handed straight to the entry -- padding words and the rows past a scenario's ticks filled with garbage -- against the
 host definition bit for bit, on plans of 6, 12 and 42 series; arbitrary float32 RAM values against math.fsum; run-to-run and
 batch independence; NULL outputs; the scratch bound; then event workloads through the Python API, bands, the on-disk summary
-in both formats (tests of their own) and 14.4 M (cell, series) entries of singleton groups."""
+in both formats (tests of their own) and 14.4 M (cell, series) entries of singleton groups.  RAM values of either sign,
+signed zeros and the -2^-45 residues (min / max of a ram_in_use column are the FLOAT minimum / maximum, -0.0 below +0.0);
+the same blocks through af_engine_summarize; rows of 21, 26, 63, 64, 65, 66 and 81 16-byte groups; runs of several windows
+per wave feeding the records; the fixture with negative residues through the Python API."""
 
 from __future__ import annotations
 
@@ -17,7 +20,7 @@ import pytest
 from asyncflow_amd import _abi
 from asyncflow_amd.plan import lower
 from asyncflow_amd.results import series_window_stats, tick_window_edges
-from oracle.scenarios import lb_two_servers, lb_with_events, single_server
+from oracle.scenarios import deep_chain, lb_two_servers, lb_with_events, single_server, wide_fanout
 
 pytestmark = pytest.mark.gpu
 
@@ -117,8 +120,11 @@ def _reduceat(fn, arr, r):
 
 def _want(plan, blk, counts, group, n_groups, tick_edges, thresholds=None, fsum: bool = False):
     """The definition on the host, independent of results.series_window_stats: per scenario exact window sums (integers; the
-    dyadic float values add exactly in float64 in any order), word minima / maxima and counts above the threshold by
-    ufunc.reduceat, then the members of a group combined.  fsum=True: the float means by math.fsum over the cell."""
+    dyadic float values add exactly in float64 in any order), minima / maxima and counts above the threshold by
+    ufunc.reduceat, then the members of a group combined.  Minima and maxima: the words of an integer column as they are;
+    a ram word as an integer that orders like its float value, straight from sign and magnitude -- a negative float
+    -(magnitude bits) - 1, so that -0.0 is -1, below +0.0 --, reduced and mapped back to the word.  fsum=True: the float means
+    by math.fsum over the cell, and "abs_mean", math.fsum of the absolute values / count."""
     n, cap, _ = blk.shape
     S = plan.n_series
     ram = ram_columns(S, plan.n_edges)
@@ -130,8 +136,8 @@ def _want(plan, blk, counts, group, n_groups, tick_edges, thresholds=None, fsum:
     isum = np.zeros((n_groups, W, S), dtype=np.int64)
     fsm = np.zeros((n_groups, W, S))
     terms = [[[] for _ in range(W)] for _ in range(n_groups)]
-    mn = np.full((n_groups, W, S), 0xFFFFFFFF, dtype=np.uint32)
-    mx = np.zeros((n_groups, W, S), dtype=np.uint32)
+    mn = np.full((n_groups, W, S), 2 ** 40, dtype=np.int64)
+    mx = np.full((n_groups, W, S), -2 ** 40, dtype=np.int64)
     above = np.zeros((n_groups, W, S), dtype=np.int64)
     for s in range(n):
         g = int(group[s])
@@ -148,8 +154,11 @@ def _want(plan, blk, counts, group, n_groups, tick_edges, thresholds=None, fsum:
         isum[g] += np.where(live, _reduceat(np.add, words.astype(np.int64), r), 0).T
         fsm[g] += np.where(live, _reduceat(np.add, values, r), 0.0).T
         above[g] += np.where(live, _reduceat(np.add, (values > thr[:, None]).astype(np.int64), r), 0).T
-        mn[g] = np.minimum(mn[g], np.where(live, _reduceat(np.minimum, words, r), 0xFFFFFFFF).astype(np.uint32).T)
-        mx[g] = np.maximum(mx[g], np.where(live, _reduceat(np.maximum, words, r), 0).astype(np.uint32).T)
+        order = words.astype(np.int64)
+        negative = ram[:, None] & (words >> 31 != 0)
+        order[negative] = -(words[negative] & np.uint32(0x7FFFFFFF)).astype(np.int64) - 1
+        mn[g] = np.minimum(mn[g], np.where(live, _reduceat(np.minimum, order, r), 2 ** 40).T)
+        mx[g] = np.maximum(mx[g], np.where(live, _reduceat(np.maximum, order, r), -2 ** 40).T)
         if fsum:
             for w in np.nonzero(live)[0]:
                 terms[g][w].append(values[:, r[w]:r[w + 1]])
@@ -157,34 +166,47 @@ def _want(plan, blk, counts, group, n_groups, tick_edges, thresholds=None, fsum:
     with np.errstate(invalid="ignore", divide="ignore"):
         mean = np.where(ram, fsm, isum.astype(np.float64)) / count[:, :, None].astype(np.float64)
     mean[empty] = np.nan
-    mn[empty] = 0
+    mn[empty] = mx[empty] = 0
+    assert (mn[~empty] < 2 ** 32).all() and (mx[~empty] >= -2 ** 31).all() and (mn[:, :, ~ram] >= 0).all()
+    mn, mx = (np.where(v < 0, (-v - 1) | 0x80000000, v).astype(np.uint32) for v in (mn, mx))
+    out = {"count": count, "mean": mean, "min": mn, "max": mx, "above": above.astype(np.uint32)}
     if fsum:
+        out["abs_mean"] = np.abs(mean)
         for g in range(n_groups):
             for w in range(W):
                 if count[g, w]:
                     cell = np.concatenate(terms[g][w], axis=1)
                     mean[g, w, ram] = [math.fsum(row.tolist()) / cell.shape[1] for row in cell[ram]]
-    return {"count": count, "mean": mean, "min": mn, "max": mx, "above": above.astype(np.uint32)}
+                    out["abs_mean"][g, w, ram] = [math.fsum(np.abs(row).tolist()) / cell.shape[1] for row in cell[ram]]
+    return out
 
 
-def _same(got, want, what, ram=None, float_tol: bool = False):
+def _same(got, want, what, ram=None, float_tol: bool = False, zero_sums: list | None = None):
+    """zero_sums (signed data): a cell whose exact sum is zero compares as a value -- the sign of a zero sum is not part of
+    the definition --; their number and that of the non-empty entries of the ram columns are added to the list."""
     assert np.array_equal(got["count"], want["count"].astype(np.uint32)), what
     for k in ("min", "max", "above"):
         if k in got:
             assert np.array_equal(got[k], want[k]), (what, k, np.argwhere(got[k] != want[k])[:5])
     if not float_tol:
-        bad = np.argwhere(got["mean"].view(np.uint64) != want["mean"].view(np.uint64))
-        bad = [t for t in bad if not (np.isnan(got["mean"][tuple(t)]) and np.isnan(want["mean"][tuple(t)]))]
+        differ = got["mean"].view(np.uint64) != want["mean"].view(np.uint64)
+        if zero_sums is not None:
+            zero = want["mean"] == 0.0
+            assert (got["mean"][zero] == 0.0).all(), what
+            differ &= ~zero
+            zero_sums.append((int(zero[:, :, ram].sum()), int((want["count"] > 0).sum()) * int(ram.sum())))
+        bad = [t for t in np.argwhere(differ) if not (np.isnan(got["mean"][tuple(t)]) and np.isnan(want["mean"][tuple(t)]))]
         assert not bad, (what, bad[:5])
         return
     exact = ~ram
     assert np.array_equal(got["mean"][:, :, exact], want["mean"][:, :, exact], equal_nan=True), what
     n = want["count"][:, :, None].astype(np.float64)
     err = np.abs(got["mean"][:, :, ram] - want["mean"][:, :, ram])
-    print(f"{what}: largest float-mean error / (n * 2^-52 * mean) = "
-          f"{np.nanmax(err / np.maximum(n * 2.0 ** -52 * np.abs(want['mean'][:, :, ram]), 1e-300)):.3g}, largest cell {int(n.max())}")
+    scale = want["abs_mean"][:, :, ram]                                # (fsum |x| / n: signed terms cancel in the mean)
+    print(f"{what}: largest float-mean error / (n * 2^-52 * fsum|x| / n) = "
+          f"{np.nanmax(err / np.maximum(n * 2.0 ** -52 * scale, 1e-300)):.3g}, largest cell {int(n.max())}")
     assert n.max() <= 4096
-    assert ((err <= n * 2.0 ** -52 * np.abs(want["mean"][:, :, ram])) | (want["count"] == 0)[:, :, None]).all(), what
+    assert ((err <= n * 2.0 ** -52 * scale) | (want["count"] == 0)[:, :, None]).all(), what
     assert np.isnan(got["mean"][want["count"] == 0]).all()
 
 
@@ -208,6 +230,25 @@ def _thresholds(plan, blk) -> np.ndarray:
     return thr
 
 
+def _groupings(n: int):
+    """One group (NULL and explicit), interleaved ids with an empty group and scenarios left out, singletons, singletons
+    among groups without a member."""
+    interleaved = np.array([(i * 7) % 6 for i in range(n)])
+    interleaved[interleaved == 3] = 4                                  # group 3 is empty
+    interleaved[[i for i in (2, 9, 20) if i < n]] = -1                 # and three scenarios (of 23) are left out
+    sparse = np.arange(n) * 2                                          # singletons, every other group without a member
+    sparse[5] = -1
+    return [(None, 1, "one group (NULL)"), (np.zeros(n, dtype=np.int64), 1, "one group"), (interleaved, 6, "interleaved"),
+            (np.arange(n), n, "singletons"), (sparse, 2 * n, "singletons and empty groups")]
+
+
+def _shapes(cap: int):
+    return [("one window", np.array([0, cap])), ("one tick each", np.arange(cap + 1)), ("20 ticks", tick_window_edges(20, cap)),
+            ("64 ticks", tick_window_edges(64, cap)), ("65 ticks", tick_window_edges(65, cap)),
+            ("200 ticks", tick_window_edges(200, cap)),
+            ("uneven", np.array([3, 4, 10, 75, 76, 300, 650, cap - 1, cap, cap + 9, cap + 10, 5 * cap]))]
+
+
 @pytest.mark.parametrize("name", ["single_server", "lb_two_servers", "fanout8"])
 def test_synthetic_blocks_equal_the_host_definition(name):
     plan = _plan(name)
@@ -216,17 +257,7 @@ def test_synthetic_blocks_equal_the_host_definition(name):
     n, cap = 23, 700
     blk, counts = _block(plan, rng, n, cap, _ticks(rng, n, cap))
     assert (blk[1, :, plan.n_series:] == GARBAGE).all()                 # (scenario 1 stored every tick: its padding words)
-    interleaved = np.array([(i * 7) % 6 for i in range(n)])
-    interleaved[interleaved == 3] = 4                                  # group 3 is empty
-    interleaved[[2, 9, 20]] = -1                                       # and three scenarios are left out
-    sparse = np.arange(n) * 2                                          # singletons, every other group without a member
-    sparse[5] = -1
-    groupings = [(None, 1, "one group (NULL)"), (np.zeros(n, dtype=np.int64), 1, "one group"), (interleaved, 6, "interleaved"),
-                 (np.arange(n), n, "singletons"), (sparse, 2 * n, "singletons and empty groups")]
-    shapes = [("one window", np.array([0, cap])), ("one tick each", np.arange(cap + 1)), ("20 ticks", tick_window_edges(20, cap)),
-              ("64 ticks", tick_window_edges(64, cap)), ("65 ticks", tick_window_edges(65, cap)),
-              ("200 ticks", tick_window_edges(200, cap)),
-              ("uneven", np.array([3, 4, 10, 75, 76, 300, 650, cap - 1, cap, cap + 9, cap + 10, 5 * cap]))]
+    groupings, shapes = _groupings(n), _shapes(cap)
     thr = _thresholds(plan, blk)
     for what, edges in shapes:
         for group, n_groups, gname in groupings:
@@ -245,6 +276,297 @@ def test_synthetic_blocks_equal_the_host_definition(name):
         m = min(int(counts[s, _abi.CNT_TICKS]), cap)
         host = series_window_stats(np.ascontiguousarray(blk[s, :m, :plan.n_series].T), edges, plan.n_edges, thr)
         _same({k: v[s:s + 1] for k, v in got.items()}, {k: v[None] for k, v in host.items()}, f"{name}, scenario {s}")
+
+
+# ------------------------------------------------------------------------------------ RAM values of either sign
+RESIDUE = np.float32(-(2.0 ** -45))        # what the reference's float arithmetic leaves in ram_in_use (-2.8e-14)
+NEG_ZERO = np.uint32(0x80000000)
+
+
+def _signed_block(plan, rng, n: int, cap: int, ticks, flip: int = 0, dyadic: bool = True):
+    """_block with ram values of either sign.  The ram columns alternate between two kinds (`flip` swaps them), both chosen so
+    that every float64 sum over a cell of fewer than 2^14 values is EXACT in any order:
+      wide     multiples of 1/256 in (-2^16, 2^16): a sum stays below 2^30 with its last bit at 2^-8;
+      residue  multiples of 2^-30 in (-2^-6, 2^-6) with one sample in 16 replaced by -2^-45: a sum stays below 2^8 with its
+               last bit at 2^-45, 53 bits.  (A residue among values of the wide kind would need 61.)
+    Both: one sample in 2 000 is +0.0 and one is -0.0.  Where the scenarios stored the rows, in every ram column:
+      rows 100-119 of every scenario, and rows 20-39 of scenario 1: negative values only;
+      rows 120-139 of every scenario, and rows 60-79 of scenario 1: negative values after one -0.0, the largest value;
+      rows 140-141 of every scenario, and rows 40-59 of scenario 1: +0.0 and -0.0 only, at least one of each.
+    Blocks of fewer than 700 rows -- where a window of one tick makes every lone zero a cell whose sum is zero, and fewer than
+    1 % of the cells should be such -- hold FOUR zeros per ram column, all in scenario 1: none is sprinkled, rows 140-141 are
+    zeros in scenario 1 alone, rows 40-59 are ordinary values, and of rows 120-139 only scenario 1 starts with -0.0 (the others
+    are negative throughout: -0.0 is still the largest value of the window in every group that holds scenario 1).
+    dyadic=False: arbitrary float32 over many binades with random signs, no special rows."""
+    blk, counts = _block(plan, rng, n, cap, ticks, dyadic=dyadic)
+    S = plan.n_series
+    ram = np.nonzero(ram_columns(S, plan.n_edges))[0]
+    shape = (n, cap)
+    for i, j in enumerate(ram):
+        if not dyadic:
+            v = (blk[:, :, j] | (rng.integers(0, 2, shape).astype(np.uint32) << 31)).view(np.float32)     # (a random sign bit)
+        else:
+            if (i + flip) % 2 == 0:
+                v = (rng.integers(-2 ** 24 + 1, 2 ** 24, shape) / 256.0).astype(np.float32)
+                filler = np.float32(-1.0 / 256.0)
+            else:
+                v = (rng.integers(-2 ** 24 + 1, 2 ** 24, shape) * 2.0 ** -30).astype(np.float32)
+                v[rng.random(shape) < 1 / 16] = RESIDUE
+                filler = RESIDUE
+            small = cap < 700
+            u = rng.random(shape)
+            if small:
+                v[v == 0] = filler
+            else:
+                v[u < 0.0005] = np.float32(0.0)
+                v[u > 0.9995] = np.float32(-0.0)
+
+            def zone(rows, scen, kind):
+                part = v[scen, rows]
+                if kind == "negative":
+                    part[...] = -np.abs(part)
+                    part[part == 0] = filler
+                elif kind == "negative and -0.0":
+                    part[...] = -np.abs(part)
+                    part[part == 0] = filler
+                    part[..., 0] = np.float32(-0.0)
+                else:
+                    part[...] = np.where(rng.random(part.shape) < 0.5, np.float32(0.0), np.float32(-0.0))
+                    part[..., 0], part[..., 1] = np.float32(0.0), np.float32(-0.0)
+                v[scen, rows] = part
+
+            assert cap >= 142
+            zone(slice(100, 120), slice(None), "negative")
+            zone(slice(120, 140), slice(None), "negative" if small else "negative and -0.0")
+            zone(slice(140, 142), 1 if small else slice(None), "zeros")
+            zone(slice(20, 40), 1, "negative")
+            zone(slice(60, 80), 1, "negative and -0.0")
+            if small:
+                v[1, 120] = np.float32(-0.0)
+            else:
+                zone(slice(40, 60), 1, "zeros")
+        live = np.arange(cap)[None, :] < np.minimum(counts[:, _abi.CNT_TICKS], cap)[:, None]
+        blk[:, :, j] = np.where(live, v.view(np.uint32), blk[:, :, j])     # (the rows past a scenario's ticks keep their garbage)
+    return blk, counts
+
+
+def _signed_thresholds(plan, blk, second: bool) -> np.ndarray:
+    """_thresholds for signed blocks: integer columns as there (0.0, a value that occurs, 0.5).  The ram columns, in turn:
+    -0.0 (+0.0 is not above it: the values compare as f64), a NEGATIVE value that occurs in the data, a value of either sign
+    that occurs; `second` starts the turn at the negative value (a plan with one ram column sees both)."""
+    S = plan.n_series
+    ram = ram_columns(S, plan.n_edges)
+    thr = np.zeros(S)
+    for j in range(1, S):
+        thr[j] = float(blk[1, 0, j])
+    thr[1] = 0.5
+    for i, j in enumerate(np.nonzero(ram)[0]):
+        col = blk[1, :, j].view(np.float32).astype(np.float64)              # (scenario 1 stored every tick)
+        turn = (i + (1 if second else 0)) % 3
+        thr[j] = -0.0 if turn == 0 else float(col[col < 0][7]) if turn == 1 else float(col[5])
+    assert not ram[0] and not ram[1]
+    assert (np.signbit(thr[ram]) & (thr[ram] == 0)).any() or second
+    assert (thr[ram] < 0).any() or not second
+    return thr
+
+
+def _zero_sum_share(zero_sums) -> float:
+    zero, entries = (sum(t[i] for t in zero_sums) for i in (0, 1))
+    return zero / entries
+
+
+@pytest.mark.parametrize(("name", "flip"), [("single_server", 0), ("single_server", 1), ("lb_two_servers", 0), ("fanout8", 0)])
+def test_signed_ram_values_equal_the_host_definition(name, flip):
+    """The shapes and groupings of test_synthetic_blocks_equal_the_host_definition on _signed_block: count, min, max and
+    above exact, the mean bit-equal (a cell whose exact sum is zero: as a value; fewer than 1 % of the entries)."""
+    plan = _plan(name)
+    ram = ram_columns(plan.n_series, plan.n_edges)
+    rng = np.random.default_rng(1000 + len(name) + flip)
+    n, cap = 23, 700
+    blk, counts = _signed_block(plan, rng, n, cap, _ticks(rng, n, cap), flip)
+    assert n * cap < 2 ** 14                                             # (_signed_block: every sum is exact)
+    first = int(np.nonzero(ram)[0][0])
+    thr_a, thr_b = _signed_thresholds(plan, blk, False), _signed_thresholds(plan, blk, True)
+    assert thr_a[first] == 0 and np.signbit(thr_a[first]) and thr_b[first] < 0
+    assert (blk[:, :, first] == 0).any() and (blk[:, :, first] == NEG_ZERO).any()
+    zero_sums: list = []
+    for what, edges in _shapes(cap):
+        for group, n_groups, gname in _groupings(n):
+            if what == "one tick each" and gname not in ("interleaved", "singletons"):
+                continue
+            for t, tname in ((None, "none"), (thr_a, "-0.0 first"), (thr_b, "negative first")):
+                if tname == "negative first" and what not in ("20 ticks", "uneven"):
+                    continue
+                got, _, intact = _run(plan, blk, counts, group, n_groups, edges, t)
+                want = _want(plan, blk, counts, group, n_groups, edges, t)
+                _same(got, want, f"{name}, {what}, {gname}, thresholds {tname}", ram, zero_sums=zero_sums)
+                assert intact
+                if what == "20 ticks" and gname in ("one group", "singletons") and t is None:
+                    # the rows _signed_block made: windows 5 / 6 of every scenario, windows 1 / 3 / 2 of scenario 1
+                    g = 0 if gname == "one group" else 1                  # (scenario 1 stored every tick)
+                    mx, mn = want["max"][:, :, ram], want["min"][:, :, ram]
+                    assert (mx[g, 5] > NEG_ZERO).all() and (mx[g, 6] == NEG_ZERO).all() and (mn[g, 6] > NEG_ZERO).all()
+                    if gname == "singletons":
+                        assert (mx[1, 1] > NEG_ZERO).all() and (mx[1, 3] == NEG_ZERO).all() and (mn[1, 3] > NEG_ZERO).all()
+                        assert (mx[1, 2] == 0).all() and (mn[1, 2] == NEG_ZERO).all() and (want["mean"][1, 2][ram] == 0).all()
+                        assert want["count"][3, 0] == 1 and want["count"][3, 1] == 0          # (scenario 3 stored one tick)
+                if t is thr_a and what == "one window" and gname == "one group":
+                    # +0.0 is not above -0.0: the count above -0.0 is the count of the positive values
+                    values = np.concatenate([blk[s, :min(int(counts[s, _abi.CNT_TICKS]), cap), first] for s in range(n)]).view(np.float32)
+                    assert (values == 0).sum() > 2 and want["above"][0, 0, first] == (values > 0).sum()
+    share = _zero_sum_share(zero_sums)
+    print(f"{name}, flip {flip}: cells whose exact sum is zero: {100 * share:.3f} % of the non-empty entries of the ram columns")
+    assert 0 < share < 0.01
+
+
+def test_signed_arbitrary_float_values_against_fsum():
+    plan = _plan("lb_two_servers")
+    ram = ram_columns(plan.n_series, plan.n_edges)
+    rng = np.random.default_rng(6)
+    n, cap = 8, 512
+    blk, counts = _signed_block(plan, rng, n, cap, _ticks(rng, n, cap), dyadic=False)
+    assert (blk[1, :, :plan.n_series][:, ram] >> 31).mean() > 0.3
+    edges = tick_window_edges(200, cap)
+    for group, n_groups in ((None, 1), (np.arange(n) % 3, 3), (np.arange(n), n)):
+        got, _, intact = _run(plan, blk, counts, group, n_groups, edges)
+        assert intact
+        _same(got, _want(plan, blk, counts, group, n_groups, edges, fsum=True), f"signed arbitrary floats, {n_groups} groups", ram, float_tol=True)
+
+
+# ------------------------------------------------------------------------------------ the two series kernels agree
+def _agrees_with_the_whole_run_kernel(plan, blk, counts, what):
+    """One window [0, cap], every scenario a group of its own: max words and mean bytes of af_engine_summarize's series_max /
+    series_mean (af_series_kernel) on the same buffers."""
+    from tests.test_gpu_analyzer_synthetic import _series
+
+    n, cap, _ = blk.shape
+    got, _, intact = _run(plan, blk, counts, np.arange(n), n, np.array([0, cap]))
+    assert intact
+    whole = _series(plan, blk, counts)
+    some = np.minimum(counts[:, _abi.CNT_TICKS], cap) > 0
+    assert some.sum() >= n - 1 and not some.all()
+    assert np.array_equal(got["max"][:, 0], whole["series_max"]), (what, np.argwhere(got["max"][:, 0] != whole["series_max"])[:5])
+    assert got["mean"][some, 0].tobytes() == whole["series_mean"][some].tobytes(), what
+    assert np.isnan(got["mean"][~some]).all() and np.isnan(whole["series_mean"][~some]).all()
+
+
+@pytest.mark.parametrize(("name", "flip"), [("single_server", 0), ("single_server", 1), ("lb_two_servers", 0), ("fanout8", 0)])
+def test_one_window_of_signed_values_is_the_whole_run_summary(name, flip):
+    plan = _plan(name)
+    rng = np.random.default_rng(1000 + len(name) + flip)
+    n, cap = 23, 700
+    blk, counts = _signed_block(plan, rng, n, cap, _ticks(rng, n, cap), flip)
+    _agrees_with_the_whole_run_kernel(plan, blk, counts, f"{name}, flip {flip}")
+
+
+# ------------------------------------------------------------------------------------ wide rows
+WIDE = {"wide_fanout16": (82, 84),     # 21 16-byte groups a row: three rows a step, lane 63 idle, a tree over 3 of 4
+        "wide_fanout20": (102, 104),   # 26 groups: two rows a step
+        "wide_fanout50": (252, 252),   # 63 groups: one row a step, lane 63 idle
+        "deep_chain62": (256, 256),    # 64 groups: every lane, one pass
+        "wide_fanout51": (257, 260),   # 65 groups: a second pass over the rows for one group that holds one series
+        "wide_fanout52": (262, 264),   # 66 groups
+        "wide_fanout64": (322, 324)}   # 81 groups
+
+
+def _wide_plan(name: str):
+    return lower(deep_chain(62) if name == "deep_chain62" else wide_fanout(int(name[len("wide_fanout"):])))
+
+
+def _wide_shapes(cap: int):
+    return [("one window", np.array([0, cap])), ("one tick each", np.arange(cap + 1)), ("7 ticks", tick_window_edges(7, cap)),
+            ("64 ticks", tick_window_edges(64, cap)), ("65 ticks", tick_window_edges(65, cap)),
+            ("uneven", np.array([3, 4, 10, 75, 76, 120, cap - 1, cap, cap + 9, cap + 10, 5 * cap]))]
+
+
+@pytest.mark.parametrize("name", list(WIDE))
+def test_wide_rows_equal_the_host_definition(name):
+    plan = _wide_plan(name)
+    assert (plan.n_series, plan.series_pitch) == WIDE[name]
+    ram = ram_columns(plan.n_series, plan.n_edges)
+    rng = np.random.default_rng(2000 + plan.n_series)
+    n, cap = 7, 150
+    blk, counts = _signed_block(plan, rng, n, cap, _ticks(rng, n, cap))
+    assert blk.nbytes <= 1_400_000 and (blk[1, :, plan.n_series:] == GARBAGE).all()
+    thr = _signed_thresholds(plan, blk, False)
+    zero_sums: list = []
+    for what, edges in _wide_shapes(cap):
+        for group, n_groups, gname in _groupings(n):
+            for t in (None, thr):
+                got, _, intact = _run(plan, blk, counts, group, n_groups, edges, t)
+                want = _want(plan, blk, counts, group, n_groups, edges, t)
+                _same(got, want, f"{name}, {what}, {gname}, thresholds {'set' if t is not None else 'none'}", ram, zero_sums=zero_sums)
+                assert intact
+    assert (blk[1, :, :plan.n_series][:, ram] << 1 == 0).sum(axis=0).tolist() == [4] * int(ram.sum())     # (rows 60, 120, 140, 141)
+    share = _zero_sum_share(zero_sums)
+    print(f"{name}: cells whose exact sum is zero: {100 * share:.3f} % of the non-empty entries of the ram columns")
+    assert 0 < share < 0.01
+    _agrees_with_the_whole_run_kernel(plan, blk, counts, name)
+
+
+# ------------------------------------------------------------------------------------ runs of windows into the records
+@pytest.mark.parametrize("flip", [0, 1])                               # (the plan's one ram column: of either kind of _signed_block)
+@pytest.mark.parametrize(("n", "cap", "run", "last"), [(64, 1501, 2, 1), (300, 700, 6, 4)])
+def test_runs_of_several_windows_feed_the_records(n, cap, run, last, flip):
+    """One tick per window.  The engine gives a wave max(1, W / ceil(32768 / n)) consecutive windows (engine.hip,
+    af_engine_summarize_series_windows: "runs as long as leave the chip some 32 768 waves"); the cases are chosen for THAT
+    rule -- runs of 2 windows with a last run of 1, runs of 6 with a last run of 4 -- and cover less if it changes."""
+    plan = _plan("single_server")
+    ram = ram_columns(plan.n_series, plan.n_edges)
+    W = cap
+    assert max(1, W // -(-32768 // n)) == run and W % run == last
+    rng = np.random.default_rng(n + flip)
+    blk, counts = _signed_block(plan, rng, n, cap, _ticks(rng, n, cap), flip)
+    assert ((blk[1, :, :plan.n_series][:, ram] == RESIDUE.view(np.uint32)).sum() > 20) == (flip == 1)
+    edges = np.arange(cap + 1)
+    interleaved = np.arange(n) * 7 % 6
+    interleaved[interleaved == 3] = 4                                  # five groups with members, group 3 is empty
+    interleaved[[2, 9, 20]] = -1                                       # three scenarios are left out
+    zero_sums: list = []
+    for group, n_groups, gname in ((interleaved, 6, "interleaved"), (None, 1, "one group (NULL)"), (np.arange(n), n, "singletons")):
+        got, scratch, intact = _run(plan, blk, counts, group, n_groups, edges)
+        assert intact
+        assert (scratch >= 20 * n * W * plan.n_series) == (gname != "singletons")     # (the records, or the direct path)
+        _same(got, _want(plan, blk, counts, group, n_groups, edges), f"n = {n}, {W} windows, {gname}", ram, zero_sums=zero_sums)
+    assert _zero_sum_share(zero_sums) < 0.01
+
+
+# ------------------------------------------------------------------------------------ the fixture through the Python API
+def test_fixture_with_negative_residues_through_the_python_api():
+    """tests/golden/frac_ram_waiting_put_t20.npz: 179 of the 399 samples of series 8 are -2.84e-14.  Windows of 40 ticks: the
+    largest value of series 8 is 200.6 or 300.9 MB in every window, the smallest the residue."""
+    from asyncflow_amd.runner import SimulationRunner
+
+    fx = np.load(ROOT / "tests" / "golden" / "frac_ram_waiting_put_t20.npz", allow_pickle=False)
+    payload, seed = json.loads(str(fx["payload_json"])), int(fx["seed"])
+    words = fx["samples"].view(np.uint32)
+    res = SimulationRunner(simulation_input=payload, seeds=[seed, seed + 1]).run()
+    assert np.array_equal(res[0]._samples, words)  # noqa: SLF001
+    ram = ram_columns(res.plan.n_series, res.plan.n_edges)
+    a = res.series_window_summary(ticks_per_window=40, by="scenario")
+    mx, mn = a["max"].cpu().numpy(), a["min"].cpu().numpy()
+    assert mx.shape == (2, 10, 12) and ram[8]
+    for s in range(2):
+        samples = res[s]._samples  # noqa: SLF001
+        values = samples.astype(np.float64)
+        values[ram] = samples[ram].view(np.float32).astype(np.float64)
+        for w in range(10):
+            seg = values[:, 40 * w:40 * (w + 1)]
+            assert np.array_equal(mx[s, w], seg.max(axis=1)) and np.array_equal(mn[s, w], seg.min(axis=1)), (s, w)
+    residue = float(np.float32(-2.842171e-14))
+    assert (mn[0, :, 8] == residue).all() and -2.9e-14 < residue < -2.8e-14
+    assert [round(float(v), 1) for v in mx[0, :, 8]] == [200.6, 300.9, 300.9, 200.6, 200.6, 200.6, 300.9, 200.6, 200.6, 200.6]
+    # one window over the whole run is the per-scenario series summary
+    whole = res.series_window_summary(tick_edges=[0, res.plan.tick_count], by="scenario")
+    summ = res.summary(rps=False, series=True)
+    assert np.array_equal(whole["max_words"][:, 0].cpu().numpy(), summ["series_max"].cpu().numpy())
+    assert whole["max"][0, 0, 8] > 300.0
+    # the band over the two seeds is the band of their float maxima
+    bands = res.series_window_bands(ticks_per_window=40, of="max")
+    assert (bands["n"] == 2).all()
+    np.testing.assert_allclose(bands["mean"][0], mx.mean(axis=0), rtol=1e-12, atol=0.0)
+    np.testing.assert_allclose(bands["std"][0], mx.std(axis=0, ddof=1), rtol=1e-12, atol=1e-300)
+    assert (bands["mean"][0, :, 8] > 200.0).all()
 
 
 def test_long_windows_and_long_runs():

@@ -104,9 +104,16 @@ def _fixture(path: Path):
     return plan, words, ScenarioResults(plan, counts, np.zeros((0, 2)), words)
 
 
+def _float_order(word: int) -> tuple[float, int]:
+    """Sorts the words of float32 values (no NaN) by value, -0.0 before +0.0."""
+    x = float(np.uint32(word).view(np.float32))
+    return (x, 0 if word >> 31 else 1)
+
+
 def _by_loops(words: np.ndarray, edges, n_edges: int, thr: np.ndarray):
     """The definition stated independently: a loop over windows and series with slices, numpy's mean on the int64 values /
-    on the float32 values as float64, min and max of the 4-byte words, a boolean count.  Also math.fsum / n for the float
+    on the float32 values as float64, min and max of the 4-byte words of an integer series, of a ram_in_use series the
+    words of its smallest and largest float value (-0.0 below +0.0), a boolean count.  Also math.fsum / n for the float
     columns."""
     n_series, ticks = words.shape
     n_win = len(edges) - 1
@@ -125,10 +132,11 @@ def _by_loops(words: np.ndarray, edges, n_edges: int, thr: np.ndarray):
                 vals = col.view(np.float32).astype(np.float64)
                 mean[w, j] = np.mean(vals)
                 fsum_mean[w, j] = math.fsum(vals.tolist()) / (hi - lo)
+                mn[w, j], mx[w, j] = min(col.tolist(), key=_float_order), max(col.tolist(), key=_float_order)
             else:
                 vals = col.astype(np.int64)
                 mean[w, j] = np.mean(vals)
-            mn[w, j], mx[w, j] = min(col.tolist()), max(col.tolist())
+                mn[w, j], mx[w, j] = min(col.tolist()), max(col.tolist())
             above[w, j] = np.count_nonzero(vals > thr[j])
     return count, mean, fsum_mean, mn, mx, above
 
@@ -189,11 +197,18 @@ def test_one_window_is_the_whole_run_summary(path):
     whole = series_window_stats(words, [0, ticks], plan.n_edges)
     mean, mx = series_mean_max(words, plan.n_edges)
     # (frac_ram_waiting_put_t20 holds 179 ram samples of -2.8e-14, float residue of the reference's own arithmetic: as WORDS
-    # they are the largest of their column; the oracle, like af_engine_summarize's series_max, takes the float maximum)
+    # they are the largest of their column, as VALUES the smallest; the oracle, af_engine_summarize's series_max and the
+    # windows all take the float maximum)
     signed = (words >> 31).any(axis=1)
     assert signed.sum() == (1 if path.stem == "frac_ram_waiting_put_t20" else 0) and not signed[~ram].any()
-    assert np.array_equal(whole["max"][0, ~signed], mx[~signed])
-    assert np.array_equal(whole["max"][0], words.max(axis=1)) and np.array_equal(whole["min"][0], words.min(axis=1))
+    assert np.array_equal(whole["max"][0], mx)
+    values = words.astype(np.float64)
+    values[ram] = words[ram].view(np.float32).astype(np.float64)
+    decode = lambda w: np.where(ram, w.view(np.float32).astype(np.float64), w.astype(np.float64))  # noqa: E731
+    assert np.array_equal(decode(whole["max"][0]), values.max(axis=1)) and np.array_equal(decode(whole["min"][0]), values.min(axis=1))
+    assert np.array_equal(whole["max"][0, ~signed], words.max(axis=1)[~signed])
+    assert np.array_equal(whole["min"][0, ~signed], words.min(axis=1)[~signed])
+    assert (whole["max"][0, signed] < words.max(axis=1)[signed]).all() and (whole["min"][0, signed] == words.max(axis=1)[signed]).all()
     exact = ~ram if path.stem in NOT_DYADIC else np.ones(n_series, dtype=bool)
     assert np.array_equal(whole["mean"][0, exact].view(np.uint64), mean[exact].view(np.uint64))
     np.testing.assert_allclose(whole["mean"][0], mean, rtol=ticks * 2.0 ** -52)
@@ -204,7 +219,43 @@ def test_one_window_is_the_whole_run_summary(path):
         parts = np.rint(st["count"][:, None].astype(np.float64) * st["mean"][:, ~ram]).astype(np.int64)
         assert np.array_equal(parts, np.add.reduceat(words[~ram].astype(np.int64), np.arange(0, ticks, m), axis=1).T)
         assert np.array_equal(parts.sum(axis=0), total)
-        assert np.array_equal(st["max"].max(axis=0), whole["max"][0]) and np.array_equal(st["above"].sum(axis=0), whole["above"][0])
+        assert np.array_equal(decode(st["max"]).max(axis=0), decode(whole["max"][0]))       # (as values: the windows' float maxima)
+        assert np.array_equal(st["max"].max(axis=0)[~signed], whole["max"][0, ~signed])
+        assert np.array_equal(st["above"].sum(axis=0), whole["above"][0])
+
+
+def test_series_window_stats_of_signed_ram_values():
+    """Hand-made columns: min / max of a ram_in_use column are the float minimum / maximum as float32 bits, -0.0 below +0.0;
+    an integer column keeps the order of its words, the sign bit included."""
+    n_edges = 1                                                          # series: one edge, then one server's queue, sleep, ram
+    f = lambda *v: np.array(v, dtype=np.float32).view(np.uint32)  # noqa: E731
+    ram = f(1.5, -2.0, 0.25,   -3.0, -0.5, -7.25,   0.0, -0.0, 0.0,   -0.0, -1.0, -0.0,   -0.0, 0.0, 2.0,   -2.0 ** -45, 300.5, 0.0)
+    edge = np.array([3, 0x80000001, 7] + [5] * 15, dtype=np.uint32)
+    words = np.stack([edge, np.arange(18, dtype=np.uint32), np.zeros(18, dtype=np.uint32), ram])
+    thr = np.array([4.0, 0.0, 0.0, -0.0])
+    st = series_window_stats(words, [0, 3, 6, 9, 12, 15, 18, 40, 41], n_edges, thr)
+    assert st["count"].tolist() == [3, 3, 3, 3, 3, 3, 0, 0]
+    bits = lambda x: int(np.float32(x).view(np.uint32))  # noqa: E731
+    #                              mixed      all negative  zeros      max is -0.0  -0.0 lowest  a residue      empty
+    assert st["max"][:, 3].tolist() == [bits(1.5), bits(-0.5), bits(0.0), bits(-0.0), bits(2.0), bits(300.5), 0, 0]
+    assert st["min"][:, 3].tolist() == [bits(-2.0), bits(-7.25), bits(-0.0), bits(-1.0), bits(-0.0), bits(-2.0 ** -45), 0, 0]
+    assert bits(-0.0) == 0x80000000 and bits(0.0) == 0
+    assert st["above"][:, 3].tolist() == [2, 0, 0, 0, 1, 1, 0, 0]         # (> -0.0 as f64: +0.0 is not above it)
+    assert st["mean"][:6, 3].tolist() == [-0.25 / 3, -10.75 / 3, 0.0, -1.0 / 3, 2.0 / 3, (300.5 - 2.0 ** -45) / 3] and np.isnan(st["mean"][6:]).all()
+    assert st["max"][:, 0].tolist() == [0x80000001, 5, 5, 5, 5, 5, 0, 0] and st["min"][:, 0].tolist() == [3, 5, 5, 5, 5, 5, 0, 0]
+    assert st["above"][:, 0].tolist() == [2, 3, 3, 3, 3, 3, 0, 0]
+    # the plain float reference over every window of every width
+    values = ram.view(np.float32).astype(np.float64)
+    for m in (1, 2, 5, 18):
+        st = series_window_stats(words, tick_window_edges(m, 18), n_edges)
+        for w in range(-(-18 // m)):
+            seg, raw = values[m * w:m * (w + 1)], ram[m * w:m * (w + 1)]
+            got_max, got_min = (st[k][w, 3:4].view(np.float32)[0] for k in ("max", "min"))
+            assert got_max == seg.max() and got_min == seg.min()
+            if seg.max() == 0:
+                assert np.signbit(got_max) == bool((raw[seg == 0] == 0x80000000).all())      # +0.0 if there is one
+            if seg.min() == 0:
+                assert np.signbit(got_min) == bool((raw[seg == 0] == 0x80000000).any())      # -0.0 if there is one
 
 
 def test_series_windows_show_the_spike_of_the_event_fixture():
