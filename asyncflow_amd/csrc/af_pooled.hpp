@@ -4,7 +4,8 @@
 //           m_s = min(counts[s][AF_CNT_COMPLETED], clock_capacity)
 // and the statistics are numpy's on lat_g, bit for bit, as af_summary.hpp computes them for one scenario: np.mean / np.std add
 // in numpy's order -- pieces of 8 192 elements of the CONCATENATED array, each summed pairwise, the piece sums added one after
-// the other --, the order statistics by MSB-first radix select, then selection among <= kCand candidates by counting.
+// the other --, the order statistics by MSB-first radix select, then selection among <= kCand candidates by counting
+// (af_select.hpp: the select's steps, here over a group's state in global memory).
 //
 // A group may be one scenario or a whole batch (10 000 replicas of LB-2 at T = 600 s: 7.6e8 latencies), so a group is spread
 // over the chip: the latencies are first COMPACTED into engine-owned scratch (8 B per completion, group after group, members in
@@ -31,14 +32,7 @@
 
 namespace afp {
 
-constexpr int kThreads = afs::kThreads;
-constexpr int kWaves = kThreads / 64;
-constexpr int kRanks = afs::kRanks;
-constexpr int kCand = afs::kCand;
-constexpr uint32_t kPiece = afs::kPiece;
-constexpr int kExpBins = afs::kExpBins;
-constexpr int kDigBits = afs::kDigBits;
-constexpr int kDigBins = afs::kDigBins;
+using afs::kThreads, afs::kWaves, afs::kRanks, afs::kCand, afs::kPiece, afs::kExpBins, afs::kDigBits, afs::kDigBins, afs::key_of;
 constexpr uint32_t kTilePieces = 16;   // numpy pieces per workgroup of the streaming passes (131 072 latencies)
 constexpr uint32_t kSkip = 0xFFFFFFFFu;   // group id of a scenario left out
 
@@ -82,8 +76,6 @@ struct PoolArgs {
     double* stats;           // [G][8]
     const uint32_t* stat_row;   // null, or group g's statistics go to row stat_row[g] of stats (af_windowed.hpp: the large cells)
 };
-
-__device__ __forceinline__ unsigned long long key_of(double x) { return (unsigned long long)__double_as_longlong(x); }
 
 __device__ __forceinline__ double readlane_f64(double v, int l) {
     const long long b = __double_as_longlong(v);
@@ -132,13 +124,20 @@ __device__ inline void tile_range(const PoolArgs& a, PoolTile& t, const PoolGrou
     g = a.groups + t.group;
 }
 
+// the latencies of a tile of a sample of n: [piece * kPiece, min((piece + n_pieces) * kPiece, n))
+__device__ __forceinline__ uint32_t tile_len(const PoolTile& t, uint32_t n) {
+    const uint64_t lo = (uint64_t)t.piece * kPiece;
+    const uint64_t hi_end = (uint64_t)(t.piece + t.n_pieces) * kPiece;
+    return (uint32_t)((hi_end < n ? hi_end : (uint64_t)n) - lo);
+}
+
 // pass 1: piece sums, min / max, exponent histogram
 __global__ __launch_bounds__(kThreads) void af_pool_pass1(PoolArgs a) {
     __shared__ uint32_t hist[kExpBins];
     __shared__ double wsum[2 * kWaves];
     __shared__ double slots[afs::kTailSlots];
     __shared__ double red[2][kWaves];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     PoolTile t;
     const PoolGroup* g;
     tile_range(a, t, g);
@@ -164,20 +163,11 @@ __global__ __launch_bounds__(kThreads) void af_pool_pass1(PoolArgs a) {
     }
     for (int i = tid; i < kExpBins; i += kThreads)
         if (hist[i]) atomicAdd(&a.hist0[(size_t)t.group * kExpBins + i], hist[i]);
-    mn = afs::wave_min(mn);
-    mx = afs::wave_max(mx);
-    if (lane == 0) {
-        red[0][wave] = mn;
-        red[1][wave] = mx;
-    }
-    __syncthreads();
+    double vmin, vmax;
+    afs::block_min_max(mn, mx, red, vmin, vmax);
     if (tid == 0) {
-        for (int w = 1; w < kWaves; ++w) {
-            mn = fmin(mn, red[0][w]);
-            mx = fmax(mx, red[1][w]);
-        }
-        a.tile_min[blockIdx.x] = mn;
-        a.tile_max[blockIdx.x] = mx;
+        a.tile_min[blockIdx.x] = vmin;
+        a.tile_max[blockIdx.x] = vmax;
     }
 }
 
@@ -193,30 +183,20 @@ __global__ __launch_bounds__(kThreads) void af_pool_digits(PoolArgs a) {
     const int shift = g->shift;
     const int bits = shift >= kDigBits ? kDigBits : shift;
     const int new_shift = shift - bits;
-    const uint32_t mask = (1u << bits) - 1u;
-    unsigned long long sp[kRanks];
-#pragma unroll
-    for (int q = 0; q < kRanks; ++q) sp[q] = (uint32_t)q < ns ? g->slot_pfx[q] : ~0ull;
+    uint64_t sp[kRanks];
+    afs::load_slot_prefixes(sp, g->slot_pfx, ns);
     for (uint32_t i = tid; i < ns * (uint32_t)kDigBins; i += kThreads) dig[i] = 0u;
     __syncthreads();
-    const uint64_t lo = (uint64_t)t.piece * kPiece;
-    const uint64_t hi_end = (uint64_t)(t.piece + t.n_pieces) * kPiece;
-    const uint32_t len = (uint32_t)((hi_end < g->n ? hi_end : (uint64_t)g->n) - lo);
-    const double* src = a.lat + g->off + lo;
+    const uint32_t len = tile_len(t, g->n);
+    const double* src = a.lat + g->off + (uint64_t)t.piece * kPiece;
     constexpr uint32_t kU = 4;
     for (uint32_t i0 = tid; i0 < len; i0 += kU * kThreads) {
         double x[kU];
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u) x[u] = i0 + u * kThreads < len ? src[i0 + u * kThreads] : 0.0;
 #pragma unroll
-        for (uint32_t u = 0; u < kU; ++u) {
-            if (i0 + u * kThreads >= len) continue;
-            const unsigned long long key = key_of(x[u]);
-            const unsigned long long hi = key >> shift;
-#pragma unroll
-            for (int q = 0; q < kRanks; ++q)
-                if (hi == sp[q]) atomicAdd(&dig[q * kDigBins + (uint32_t)((key >> new_shift) & mask)], 1u);
-        }
+        for (uint32_t u = 0; u < kU; ++u)
+            if (i0 + u * kThreads < len) afs::count_digit(key_of(x[u]), shift, new_shift, bits, sp, dig);
     }
     __syncthreads();
     uint32_t* gd = a.dhist + (size_t)t.group * kRanks * kDigBins;
@@ -224,74 +204,18 @@ __global__ __launch_bounds__(kThreads) void af_pool_digits(PoolArgs a) {
         if (dig[i]) atomicAdd(&gd[i], dig[i]);
 }
 
-// one workgroup per group: level 0 (after pass 1) or a digit level (after af_pool_digits)
-__global__ __launch_bounds__(kThreads) void af_pool_select(PoolArgs a, int level) {
-    __shared__ unsigned long long pfx[kRanks];
-    __shared__ uint32_t rank_in[kRanks], cnt[kRanks], want[kRanks], slot_of[kRanks];
-    __shared__ double red[2][kWaves];
+// One workgroup, one step of the select of the sample whose state is *g: level 0 (the wanted ranks in want[], LDS, filled by
+// the caller; hist0 the sample's exponent histogram) or a digit level (dhist: the digit histograms of g's slots)
+__device__ __forceinline__ void select_step(PoolGroup* g, const uint32_t* want, const uint32_t* hist0, const uint32_t* dhist, int level,
+                                            uint32_t* any_more) {
+    __shared__ uint64_t pfx[kRanks];
+    __shared__ uint32_t rank_in[kRanks], cnt[kRanks], slot_of[kRanks];
     __shared__ int shift_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t gi = blockIdx.x;
-    PoolGroup* g = a.groups + gi;
-    const uint32_t n = g->n;
+    const int tid = threadIdx.x;
     if (level == 0) {
-        if (n == 0u) {   // the reference leaves latency_stats empty (analyzer.py:105-106)
-            if (tid < 8) a.stats[(size_t)(a.stat_row ? a.stat_row[gi] : gi) * 8u + tid] = tid == 0 ? 0.0 : __builtin_nan("");
-            if (tid == 0) g->more = 0u;
-            return;
-        }
-        if (tid == 0) {   // numpy: median = mean of the middle pair; percentile 'linear' (af_summary.hpp)
-            want[0] = (n & 1u) ? n / 2u : n / 2u - 1u;
-            want[1] = n / 2u;
-            const double q[2] = {95.0 / 100.0, 99.0 / 100.0};
-            for (int p = 0; p < 2; ++p) {
-                const double v = (double)(n - 1u) * q[p];
-                if (v >= (double)(n - 1u)) {
-                    want[2 + 2 * p] = want[3 + 2 * p] = n - 1u;
-                    g->tfrac[p] = 0.0;
-                } else {
-                    const double f = floor(v);
-                    want[2 + 2 * p] = (uint32_t)f;
-                    want[3 + 2 * p] = (uint32_t)f + 1u;
-                    g->tfrac[p] = v - f;
-                }
-            }
-            shift_s = 52;
-        }
+        if (tid == 0) shift_s = 52;
         __syncthreads();
-        if (wave < kRanks) {
-            uint32_t bin, below, count;
-            afs::wave_select(a.hist0 + (size_t)gi * kExpBins, kExpBins, want[wave], bin, below, count);
-            if (lane == 0) {
-                pfx[wave] = bin;
-                rank_in[wave] = want[wave] - below;
-                cnt[wave] = count;
-            }
-        }
-        if (wave == 0) {
-            const double tot = sum_in_order(a.piece_sum + g->piece0, g->n_pieces);
-            if (lane == 0) g->mean = tot / (double)n;
-        }
-        double mn = __builtin_inf(), mx = -__builtin_inf();
-        for (uint32_t i = tid; i < g->n_tiles; i += kThreads) {
-            mn = fmin(mn, a.tile_min[g->tile0 + i]);
-            mx = fmax(mx, a.tile_max[g->tile0 + i]);
-        }
-        mn = afs::wave_min(mn);
-        mx = afs::wave_max(mx);
-        if (lane == 0) {
-            red[0][wave] = mn;
-            red[1][wave] = mx;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            for (int w = 1; w < kWaves; ++w) {
-                mn = fmin(mn, red[0][w]);
-                mx = fmax(mx, red[1][w]);
-            }
-            g->vmin = mn;
-            g->vmax = mx;
-        }
+        afs::select_first_level(hist0, want, pfx, rank_in, cnt);
     } else {
         if (!g->more) return;
         if (tid < kRanks) {
@@ -303,38 +227,59 @@ __global__ __launch_bounds__(kThreads) void af_pool_select(PoolArgs a, int level
         __syncthreads();
         const int shift = shift_s;
         const int bits = shift >= kDigBits ? kDigBits : shift;
-        if (wave < kRanks) {
-            uint32_t bin, below, count;
-            afs::wave_select(a.dhist + ((size_t)gi * kRanks + slot_of[wave]) * kDigBins, kDigBins, rank_in[wave], bin, below, count);
-            if (lane == 0) {
-                pfx[wave] = (pfx[wave] << bits) | bin;
-                rank_in[wave] -= below;
-                cnt[wave] = count;
-            }
-        }
+        afs::select_digit_level(dhist, bits, slot_of, pfx, rank_in, cnt);
         __syncthreads();
         if (tid == 0) shift_s = shift - bits;
     }
     __syncthreads();
-    if (tid == 0) {   // distinct prefixes; another level while a rank has too many candidates
+    if (tid == 0) {
         const int shift = shift_s;
-        uint32_t ns = 0, more = 0;
+        uint32_t ns, more;
+        afs::assign_slots(pfx, cnt, shift, g->slot_pfx, g->slot_of, &ns, &more);
         for (int r = 0; r < kRanks; ++r) {
-            uint32_t sidx = ns;
-            for (uint32_t q = 0; q < ns; ++q)
-                if (g->slot_pfx[q] == pfx[r]) sidx = q;
-            if (sidx == ns) g->slot_pfx[ns++] = pfx[r];
-            g->slot_of[r] = sidx;
             g->pfx[r] = pfx[r];
             g->rank_in[r] = rank_in[r];
             g->cnt[r] = cnt[r];
-            if (cnt[r] > (uint32_t)kCand && shift > 0) more = 1u;
         }
         g->n_slots = ns;
         g->shift = shift;
         g->more = more;
-        if (more) atomicOr(a.any_more, 1u);
+        if (more) atomicOr(any_more, 1u);
     }
+}
+
+// one workgroup per group: level 0 (after pass 1: also the mean, min and max) or a digit level (after af_pool_digits)
+__global__ __launch_bounds__(kThreads) void af_pool_select(PoolArgs a, int level) {
+    __shared__ uint32_t want[kRanks];
+    __shared__ double red[2][kWaves];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t gi = blockIdx.x;
+    PoolGroup* g = a.groups + gi;
+    const uint32_t n = g->n;
+    if (level == 0) {
+        if (n == 0u) {
+            afs::write_empty_row(a.stats + (size_t)(a.stat_row ? a.stat_row[gi] : gi) * 8u, tid);
+            if (tid == 0) g->more = 0u;
+            return;
+        }
+        if (tid == 0) afs::stat_ranks(n, want, g->tfrac);
+        if (wave == 0) {
+            const double tot = sum_in_order(a.piece_sum + g->piece0, g->n_pieces);
+            if (lane == 0) g->mean = tot / (double)n;
+        }
+        double mn = __builtin_inf(), mx = -__builtin_inf();
+        for (uint32_t i = tid; i < g->n_tiles; i += kThreads) {
+            mn = fmin(mn, a.tile_min[g->tile0 + i]);
+            mx = fmax(mx, a.tile_max[g->tile0 + i]);
+        }
+        double vmin, vmax;
+        afs::block_min_max(mn, mx, red, vmin, vmax);
+        if (tid == 0) {
+            g->vmin = vmin;
+            g->vmax = vmax;
+        }
+    }
+    select_step(g, want, a.hist0 + (size_t)gi * kExpBins, a.dhist + (size_t)gi * kRanks * kDigBins, level, a.any_more);
 }
 
 // last pass: squared deviations about the group's mean in numpy's order, the candidates on the way
@@ -349,9 +294,8 @@ __global__ __launch_bounds__(kThreads) void af_pool_last(PoolArgs a) {
     const double mean = g->mean;
     const int shift = g->shift;
     const uint32_t ns = g->n_slots;
-    unsigned long long sp[kRanks];
-#pragma unroll
-    for (int q = 0; q < kRanks; ++q) sp[q] = (uint32_t)q < ns ? g->slot_pfx[q] : ~0ull;
+    uint64_t sp[kRanks];
+    afs::load_slot_prefixes(sp, g->slot_pfx, ns);
     uint32_t* cn = a.cand_n + (size_t)t.group * kRanks;
     double* cd = a.cand + (size_t)t.group * kRanks * kCand;
     const double* src = a.lat + g->off;
@@ -361,15 +305,7 @@ __global__ __launch_bounds__(kThreads) void af_pool_last(PoolArgs a) {
         const uint32_t len = rest < kPiece ? (uint32_t)rest : kPiece;
         const double s = afs::numpy_sum<8>(src + k * kPiece, len, wsum, slots, [&](const double x, const bool act) -> double {
             const double d = x - mean;
-            if (act && shift > 0) {
-                const unsigned long long hi = key_of(x) >> shift;
-#pragma unroll
-                for (int q = 0; q < kRanks; ++q)
-                    if (hi == sp[q]) {
-                        const uint32_t pos = atomicAdd(&cn[q], 1u);
-                        if (pos < (uint32_t)kCand) cd[(size_t)q * kCand + pos] = x;
-                    }
-            }
+            if (act && shift > 0) afs::collect_candidate(x, shift, sp, cn, cd);
             return d * d;
         });
         if (tid == 0) a.piece_sum[g->piece0 + k] = s;
@@ -377,9 +313,21 @@ __global__ __launch_bounds__(kThreads) void af_pool_last(PoolArgs a) {
     }
 }
 
+// called by the whole workgroup: the candidates of group gi's slots (af_pool_last's, af_q_cand's) into LDS, cand: [kRanks][kCand]
+__device__ __forceinline__ void load_candidates(const PoolArgs& a, uint32_t gi, const PoolGroup* g, double* cand) {
+    const uint32_t tid = threadIdx.x;
+    if (g->shift > 0)
+        for (uint32_t q = 0; q < g->n_slots; ++q) {
+            const uint32_t c = a.cand_n[(size_t)gi * kRanks + q];
+            const uint32_t m = c < (uint32_t)kCand ? c : (uint32_t)kCand;
+            if (tid < m) cand[q * kCand + tid] = a.cand[((size_t)gi * kRanks + q) * kCand + tid];
+        }
+    __syncthreads();
+}
+
 // one workgroup per group: std_dev, the ranks' values, the stats row
 __global__ __launch_bounds__(kThreads) void af_pool_final(PoolArgs a) {
-    __shared__ double cand[kRanks][kCand];
+    __shared__ double cand[kRanks * kCand];
     __shared__ double val[kRanks];
     __shared__ double sq;
     const int tid = threadIdx.x, wave = tid >> 6;
@@ -387,55 +335,15 @@ __global__ __launch_bounds__(kThreads) void af_pool_final(PoolArgs a) {
     const PoolGroup* g = a.groups + gi;
     const uint32_t n = g->n;
     if (n == 0u) return;   // (written by the level-0 select)
-    const int shift = g->shift;
-    const uint32_t ns = g->n_slots;
     if (wave == 0) {
         const double tot = sum_in_order(a.piece_sum + g->piece0, g->n_pieces);
         if (tid == 0) sq = tot;
     }
-    if (shift > 0)
-        for (uint32_t q = 0; q < ns; ++q) {
-            const uint32_t c = a.cand_n[(size_t)gi * kRanks + q];
-            const uint32_t m = c < (uint32_t)kCand ? c : (uint32_t)kCand;
-            if ((uint32_t)tid < m) cand[q][tid] = a.cand[((size_t)gi * kRanks + q) * kCand + tid];
-        }
+    load_candidates(a, gi, g, cand);
+    afs::rank_values(cand, a.cand_n + (size_t)gi * kRanks, g->slot_of, g->rank_in, g->pfx, g->shift, val);
     __syncthreads();
-    for (int r = 0; r < kRanks; ++r) {
-        if (shift == 0) {   // the whole key is known: every candidate has this value
-            if (tid == 0) val[r] = __longlong_as_double((long long)g->pfx[r]);
-            continue;
-        }
-        const uint32_t q = g->slot_of[r];
-        const uint32_t c = a.cand_n[(size_t)gi * kRanks + q];
-        const uint32_t m = c < (uint32_t)kCand ? c : (uint32_t)kCand;
-        const uint32_t k = g->rank_in[r];
-        if ((uint32_t)tid < m) {
-            const double x = cand[q][tid];
-            uint32_t less = 0, leq = 0;
-            for (uint32_t j = 0; j < m; ++j) {
-                const double y = cand[q][j];
-                less += y < x ? 1u : 0u;
-                leq += y <= x ? 1u : 0u;
-            }
-            if (less <= k && k < leq) val[r] = x;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        auto lerp = [](double lo, double hi, double t) {   // numpy _lerp
-            const double d = hi - lo;
-            return t >= 0.5 ? hi - d * (1.0 - t) : lo + d * t;
-        };
-        double* st = a.stats + (size_t)(a.stat_row ? a.stat_row[gi] : gi) * 8u;
-        st[0] = (double)n;
-        st[1] = g->mean;
-        st[2] = (n & 1u) ? val[1] : (val[0] + val[1]) / 2.0;
-        st[3] = sqrt(sq / (double)n);
-        st[4] = lerp(val[2], val[3], g->tfrac[0]);
-        st[5] = lerp(val[4], val[5], g->tfrac[1]);
-        st[6] = g->vmin;
-        st[7] = g->vmax;
-    }
+    if (tid == 0)
+        afs::write_stats_row(a.stats + (size_t)(a.stat_row ? a.stat_row[gi] : gi) * 8u, n, g->mean, sq, val, g->tfrac, g->vmin, g->vmax);
 }
 
 }  // namespace afp

@@ -19,7 +19,7 @@
 //          16 KB and 66 exchange steps, not 64 KB and 91: at 64 KB two workgroups (32 waves) share a CU's 160 KB, at 16 KB the
 //          wave slots limit (4 workgroups of 512).
 //          (Steps whose pairs stay inside a wave's own elements, run without the workgroup barrier, measured no faster.)
-//   large  above: MSB-first radix select over the compacted range, as af_pooled.hpp's: the exponent histogram of the cell, then
+//   large  above: MSB-first radix select (af_select.hpp) over the compacted range, as af_pooled.hpp's: the cell's exponent histogram, then
 //          10 key bits per pass under the wanted ranks' prefixes (af_pool_digits, as it is) until every rank has <= kCand
 //          candidates, the candidates to global memory, selection among them by counting.  The per-rank histograms of ONE
 //          workgroup hold kRanks = 6 ranks = the lo / hi of kLv = 3 levels: more levels run as ceil(n_levels / 3) independent
@@ -42,16 +42,9 @@
 
 namespace afq {
 
-constexpr int kThreads = afs::kThreads;
-constexpr int kWaves = kThreads / 64;
-constexpr int kRanks = afs::kRanks;
+using afs::kThreads, afs::kRanks, afs::kCand, afs::kPiece, afs::kExpBins, afs::kDigBins, afs::key_of, afs::level_ranks, afs::lerp;
 constexpr int kLv = 3;                      // levels per job of the large tier: their lo / hi ranks are one workgroup's kRanks
 static_assert(2 * kLv == kRanks, "a job's ranks are the lo / hi of its levels");
-constexpr int kCand = afs::kCand;
-constexpr uint32_t kPiece = afs::kPiece;
-constexpr int kExpBins = afs::kExpBins;
-constexpr int kDigBits = afs::kDigBits;
-constexpr int kDigBins = afs::kDigBins;
 constexpr uint32_t kMaxLevels = 64;         // AF_MAX_QUANTILE_LEVELS
 constexpr uint32_t kMaxThresholds = 64;     // AF_MAX_SLO_THRESHOLDS: one lane of a wave per threshold
 constexpr uint32_t kTinyMax = 512;          // latencies of the largest cell one wave sorts
@@ -85,20 +78,6 @@ struct QArgs {
     uint32_t* thist;            // [large cells][n_thr] within counts
 };
 
-// the two order statistics a level interpolates between, and the weight of the upper one
-__device__ __forceinline__ void ranks_of(uint32_t n, double q, uint32_t& lo, uint32_t& hi, double& t) {
-    const double v = (double)(n - 1u) * q;
-    const double f = floor(v);
-    lo = (uint32_t)f;
-    hi = lo + 1u < n ? lo + 1u : n - 1u;
-    t = v - f;
-}
-
-__device__ __forceinline__ double lerp(double lo, double hi, double t) {   // numpy _lerp
-    const double d = hi - lo;
-    return t >= 0.5 ? hi - d * (1.0 - t) : lo + d * t;
-}
-
 // #{ i < n : s[i] <= th } of a sorted array
 __device__ __forceinline__ uint32_t count_leq(const double* s, uint32_t n, double th) {
     uint32_t lo = 0u, hi = n;
@@ -116,7 +95,7 @@ __device__ __forceinline__ void write_sorted_cell(const QArgs& a, uint64_t cell,
     if (t < a.n_lev && a.quant) {
         uint32_t lo, hi;
         double w;
-        ranks_of(n, a.levels[t], lo, hi, w);
+        level_ranks(n, a.levels[t], lo, hi, w);
         a.quant[cell * a.n_lev + t] = lerp(s[lo], s[hi], w);
     }
     if (t < a.n_thr && a.within) a.within[cell * a.n_thr + t] = count_leq(s, n, a.thr[t]);
@@ -201,10 +180,8 @@ __global__ __launch_bounds__(kThreads) void af_q_pass0(QArgs a, uint32_t* hist0)
     const uint32_t T = a.within ? a.n_thr : 0u;
     for (int i = tid; i < kExpBins; i += kThreads) hist[i] = 0u;
     __syncthreads();
-    const uint64_t lo = (uint64_t)t.piece * kPiece;
-    const uint64_t hi_end = (uint64_t)(t.piece + t.n_pieces) * kPiece;
-    const uint32_t len = (uint32_t)((hi_end < c.n ? hi_end : (uint64_t)c.n) - lo);
-    const double* src = a.lat + c.off + lo;
+    const uint32_t len = afp::tile_len(t, c.n);
+    const double* src = a.lat + c.off + (uint64_t)t.piece * kPiece;
     uint32_t acc = 0u;   // lane t: the latencies <= thr[t] this wave has met
     constexpr uint32_t kU = 4;
     for (uint32_t base = 0; base < len; base += kU * kThreads) {   // (uniform trip count: the ballots below are wave-wide)
@@ -214,7 +191,7 @@ __global__ __launch_bounds__(kThreads) void af_q_pass0(QArgs a, uint32_t* hist0)
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u) {
             const bool act = base + tid + u * kThreads < len;
-            if (want_hist) afs::wave_agg_add(hist, (uint32_t)(afp::key_of(x[u]) >> 52) & (kExpBins - 1), act);
+            if (want_hist) afs::wave_agg_add(hist, (uint32_t)(key_of(x[u]) >> 52) & (kExpBins - 1), act);
             for (uint32_t k = 0; k < T; ++k) {
                 const uint32_t c_k = (uint32_t)__popcll(__ballot(act && x[u] <= a.thr[k]));
                 if ((uint32_t)lane == k) acc += c_k;
@@ -228,79 +205,22 @@ __global__ __launch_bounds__(kThreads) void af_q_pass0(QArgs a, uint32_t* hist0)
             if (hist[i]) atomicAdd(&hist0[(size_t)t.group * kExpBins + i], hist[i]);
 }
 
-// one workgroup per job: level 0 (after af_q_pass0) or a digit level (after af_pool_digits); af_pool_select's, for the job's ranks
+// one workgroup per job: level 0 (after af_q_pass0) or a digit level (after af_pool_digits): afp::select_step for the job's ranks
 __global__ __launch_bounds__(kThreads) void af_q_select(QArgs qa, afp::PoolArgs a, int level) {
-    __shared__ unsigned long long pfx[kRanks];
-    __shared__ uint32_t rank_in[kRanks], cnt[kRanks], want[kRanks], slot_of[kRanks];
-    __shared__ int shift_s;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    __shared__ uint32_t want[kRanks];
+    const int tid = threadIdx.x;
     const uint32_t ji = blockIdx.x;
     const QJob job = qa.jobs[ji];
     afp::PoolGroup* g = a.groups + ji;
-    const uint32_t n = g->n;
-    if (level == 0) {
-        if (tid < kLv) {   // (a job of fewer than kLv levels repeats its first: the same prefixes, no slot more)
-            const uint32_t l = job.lev0 + ((uint32_t)tid < job.n_lev ? (uint32_t)tid : 0u);
-            uint32_t lo, hi;
-            double t;
-            ranks_of(n, qa.levels[l], lo, hi, t);
-            want[2 * tid] = lo;
-            want[2 * tid + 1] = hi;
-        }
-        if (tid == 0) shift_s = 52;
-        __syncthreads();
-        if (wave < kRanks) {
-            uint32_t bin, below, count;
-            afs::wave_select(a.hist0 + (size_t)job.lc * kExpBins, kExpBins, want[wave], bin, below, count);
-            if (lane == 0) {
-                pfx[wave] = bin;
-                rank_in[wave] = want[wave] - below;
-                cnt[wave] = count;
-            }
-        }
-    } else {
-        if (!g->more) return;
-        if (tid < kRanks) {
-            pfx[tid] = g->pfx[tid];
-            rank_in[tid] = g->rank_in[tid];
-            slot_of[tid] = g->slot_of[tid];
-        }
-        if (tid == 0) shift_s = g->shift;
-        __syncthreads();
-        const int shift = shift_s;
-        const int bits = shift >= kDigBits ? kDigBits : shift;
-        if (wave < kRanks) {
-            uint32_t bin, below, count;
-            afs::wave_select(a.dhist + ((size_t)ji * kRanks + slot_of[wave]) * kDigBins, kDigBins, rank_in[wave], bin, below, count);
-            if (lane == 0) {
-                pfx[wave] = (pfx[wave] << bits) | bin;
-                rank_in[wave] -= below;
-                cnt[wave] = count;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) shift_s = shift - bits;
+    if (level == 0 && tid < kLv) {   // (a job of fewer than kLv levels repeats its first: the same prefixes, no slot more)
+        const uint32_t l = job.lev0 + ((uint32_t)tid < job.n_lev ? (uint32_t)tid : 0u);
+        uint32_t lo, hi;
+        double t;
+        level_ranks(g->n, qa.levels[l], lo, hi, t);
+        want[2 * tid] = lo;
+        want[2 * tid + 1] = hi;
     }
-    __syncthreads();
-    if (tid == 0) {   // distinct prefixes; another level while a rank has too many candidates
-        const int shift = shift_s;
-        uint32_t ns = 0, more = 0;
-        for (int r = 0; r < kRanks; ++r) {
-            uint32_t sidx = ns;
-            for (uint32_t q = 0; q < ns; ++q)
-                if (g->slot_pfx[q] == pfx[r]) sidx = q;
-            if (sidx == ns) g->slot_pfx[ns++] = pfx[r];
-            g->slot_of[r] = sidx;
-            g->pfx[r] = pfx[r];
-            g->rank_in[r] = rank_in[r];
-            g->cnt[r] = cnt[r];
-            if (cnt[r] > (uint32_t)kCand && shift > 0) more = 1u;
-        }
-        g->n_slots = ns;
-        g->shift = shift;
-        g->more = more;
-        if (more) atomicOr(a.any_more, 1u);
-    }
+    afp::select_step(g, want, a.hist0 + (size_t)job.lc * kExpBins, a.dhist + (size_t)ji * kRanks * kDigBins, level, a.any_more);
 }
 
 // the <= kCand candidates of every rank of the tile's job into global memory (af_pool_last without its sums)
@@ -310,79 +230,39 @@ __global__ __launch_bounds__(kThreads) void af_q_cand(afp::PoolArgs a) {
     const afp::PoolGroup* g = a.groups + t.group;
     const int shift = g->shift;
     if (shift == 0) return;   // the whole key is known
-    const uint32_t ns = g->n_slots;
-    unsigned long long sp[kRanks];
-#pragma unroll
-    for (int q = 0; q < kRanks; ++q) sp[q] = (uint32_t)q < ns ? g->slot_pfx[q] : ~0ull;   // (a prefix no key >> shift can equal)
+    uint64_t sp[kRanks];
+    afs::load_slot_prefixes(sp, g->slot_pfx, g->n_slots);
     uint32_t* cn = a.cand_n + (size_t)t.group * kRanks;
     double* cd = a.cand + (size_t)t.group * kRanks * kCand;
-    const uint64_t lo = (uint64_t)t.piece * kPiece;
-    const uint64_t hi_end = (uint64_t)(t.piece + t.n_pieces) * kPiece;
-    const uint32_t len = (uint32_t)((hi_end < g->n ? hi_end : (uint64_t)g->n) - lo);
-    const double* src = a.lat + g->off + lo;
+    const uint32_t len = afp::tile_len(t, g->n);
+    const double* src = a.lat + g->off + (uint64_t)t.piece * kPiece;
     constexpr uint32_t kU = 4;
     for (uint32_t i0 = tid; i0 < len; i0 += kU * kThreads) {
         double x[kU];
 #pragma unroll
         for (uint32_t u = 0; u < kU; ++u) x[u] = i0 + u * kThreads < len ? src[i0 + u * kThreads] : 0.0;
 #pragma unroll
-        for (uint32_t u = 0; u < kU; ++u) {
-            if (i0 + u * kThreads >= len) continue;
-            const unsigned long long hi = afp::key_of(x[u]) >> shift;
-#pragma unroll
-            for (int q = 0; q < kRanks; ++q)
-                if (hi == sp[q]) {
-                    const uint32_t pos = atomicAdd(&cn[q], 1u);
-                    if (pos < (uint32_t)kCand) cd[(size_t)q * kCand + pos] = x[u];
-                }
-        }
+        for (uint32_t u = 0; u < kU; ++u)
+            if (i0 + u * kThreads < len) afs::collect_candidate(x[u], shift, sp, cn, cd);
     }
 }
 
 // one workgroup per job: the ranks' values among the candidates, the job's quantiles
 __global__ __launch_bounds__(kThreads) void af_q_final(QArgs qa, afp::PoolArgs a) {
-    __shared__ double cand[kRanks][kCand];
+    __shared__ double cand[kRanks * kCand];
     __shared__ double val[kRanks];
     const int tid = threadIdx.x;
     const uint32_t ji = blockIdx.x;
     const QJob job = qa.jobs[ji];
     const afp::PoolGroup* g = a.groups + ji;
-    const uint32_t n = g->n;
-    const int shift = g->shift;
-    const uint32_t ns = g->n_slots;
-    if (shift > 0)
-        for (uint32_t q = 0; q < ns; ++q) {
-            const uint32_t c = a.cand_n[(size_t)ji * kRanks + q];
-            const uint32_t m = c < (uint32_t)kCand ? c : (uint32_t)kCand;
-            if ((uint32_t)tid < m) cand[q][tid] = a.cand[((size_t)ji * kRanks + q) * kCand + tid];
-        }
-    __syncthreads();
-    for (int r = 0; r < kRanks; ++r) {
-        if (shift == 0) {   // the whole key is known: every candidate has this value
-            if (tid == 0) val[r] = __longlong_as_double((long long)g->pfx[r]);
-            continue;
-        }
-        const uint32_t q = g->slot_of[r];
-        const uint32_t c = a.cand_n[(size_t)ji * kRanks + q];
-        const uint32_t m = c < (uint32_t)kCand ? c : (uint32_t)kCand;
-        const uint32_t k = g->rank_in[r];
-        if ((uint32_t)tid < m) {
-            const double x = cand[q][tid];
-            uint32_t less = 0, leq = 0;
-            for (uint32_t j = 0; j < m; ++j) {
-                const double y = cand[q][j];
-                less += y < x ? 1u : 0u;
-                leq += y <= x ? 1u : 0u;
-            }
-            if (less <= k && k < leq) val[r] = x;
-        }
-    }
+    afp::load_candidates(a, ji, g, cand);
+    afs::rank_values(cand, a.cand_n + (size_t)ji * kRanks, g->slot_of, g->rank_in, g->pfx, g->shift, val);
     __syncthreads();
     if ((uint32_t)tid < job.n_lev) {
         const uint32_t l = job.lev0 + (uint32_t)tid;
         uint32_t lo, hi;
         double t;
-        ranks_of(n, qa.levels[l], lo, hi, t);
+        level_ranks(g->n, qa.levels[l], lo, hi, t);
         qa.quant[(size_t)qa.lcells[job.lc].row * qa.n_lev + l] = lerp(val[2 * tid], val[2 * tid + 1], t);
     }
 }

@@ -25,7 +25,7 @@
 //           bits: when the guess covers every wanted rank (latencies of one scenario span 2-3 binades)
 //           the first radix level costs no pass of its own
 //   pass 2+ (only while a wanted rank still has > kCand candidates) 10 more key bits per pass,
-//           MSB-first radix select, all wanted ranks at once
+//           MSB-first radix select, all wanted ranks at once (af_select.hpp describes the select and holds its steps)
 //   last    the squared deviations about the mean (which only exists after pass 1: numpy's two-pass variance cannot be had
 //           in one), and on the way the <= kCand candidates of every wanted rank into LDS; then select by counting
 // (Round 3 - 5 had a scratch array of 16-bit codes instead of the second read, and a one-pass shifted variance that agreed
@@ -37,19 +37,14 @@
 
 #include <cstdint>
 
+#include "af_select.hpp"
+
 namespace afs {
 
-constexpr int kThreads = 512;   // (1 024 threads, two scenarios per CU, in the hope of Infinity Cache hits in the second pass: 6.4 -> 6.7 ms)
-constexpr int kWaves = kThreads / 64;
-constexpr int kRanks = 6;       // median lo/hi, p95 lo/hi, p99 lo/hi
-constexpr int kCand = 512;      // candidates per rank resolved in LDS
 constexpr uint32_t kPiece = 8192;   // numpy's reduction buffer: elements per call of the pairwise sum = per step of a workgroup
 constexpr int kLeafRows = 16;       // a full piece's leaf: 128 elements = 16 rows of 8
 constexpr int kTailSlots = 128;     // leaves of the partial piece (64 .. 128 elements each, < 8 192 together)
 constexpr unsigned long long kAbsent = 0xFFF8DEADBEEF0000ull;   // an LDS slot no leaf was written to (a NaN no sum can be)
-constexpr int kExpBins = 2048;  // level 0: bits 62..52 (latencies are >= +0.0, the sign bit is clear)
-constexpr int kDigBits = 10;    // deeper levels: 10 key bits each
-constexpr int kDigBins = 1 << kDigBits;
 
 struct SumArgs {
     const double* clock;     // [n][clock_cap][2]  (start, finish)
@@ -88,14 +83,6 @@ __device__ inline bool claim_scenario(const uint32_t* done_flags, uint32_t* retr
 
 __device__ inline double wave_sum(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-__device__ inline double wave_min(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off, 64));
-    return v;
-}
-__device__ inline double wave_max(double v) {
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));
     return v;
 }
 
@@ -234,39 +221,59 @@ __device__ __forceinline__ double numpy_sum(const Row* ck, uint32_t n, double* w
     return tot;
 }
 
-// One wave finds the bin holding rank k of a histogram: bin, #elements below it, its count.
-__device__ inline void wave_select(const uint32_t* hist, int nbins, uint32_t k, uint32_t& bin, uint32_t& below,
-                                   uint32_t& count) {
-    const int lane = threadIdx.x & 63;
-    const int per = nbins / 64;
-    uint32_t mine = 0;
-    for (int j = 0; j < per; ++j) mine += hist[lane * per + j];
-    uint32_t incl = mine;
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t up = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += up;
+// The select's state of a workgroup that owns its whole sample (af_summary_kernel, af_win_small): in LDS
+struct SelectLds {
+    uint64_t pfx[kRanks];        // key >> shift of the bin holding rank r
+    uint64_t slot_pfx[kRanks];   // distinct prefixes
+    uint32_t want[kRanks];
+    uint32_t rank_in[kRanks];    // rank r relative to its bin
+    uint32_t cnt[kRanks];        // elements in that bin
+    uint32_t slot_of[kRanks];
+    uint32_t cand_n[kRanks];
+    uint32_t n_slots, more;
+    double val[kRanks], tfrac[2];
+};
+
+// What such a workgroup does once level 0 has put every wanted rank into a bin of `shift` unknown key bits, over the n >= 1
+// latencies lat_of(rows[i]): digit levels while some rank still has too many candidates; the last pass -- the squared
+// deviations in numpy's order (x - mean, squared, summed like the latencies), the candidates on the way --; the ranks' values;
+// the stats row.  dig_hist: [kRanks][kDigBins] in LDS, the candidates take its place (dead by the last pass: 35 instead of
+// 59 KB, 4 scenarios per CU); wsum, tail_slots: numpy_sum's.
+template <int kLoads, class Row, class Lat>
+__device__ __forceinline__ void select_and_finish(const Row* rows, uint32_t n, Lat&& lat_of, int shift, double mean, double vmin, double vmax,
+                                                  SelectLds& s, uint32_t* dig_hist, double* wsum, double* tail_slots, double* st) {
+    static_assert(sizeof(double) * kCand == sizeof(uint32_t) * kDigBins, "the candidates take the digit histograms' place");
+    double* cand = reinterpret_cast<double*>(dig_hist);
+    const int tid = threadIdx.x;
+    uint64_t sp[kRanks];
+    for (;;) {
+        __syncthreads();
+        if (tid == 0) assign_slots(s.pfx, s.cnt, shift, s.slot_pfx, s.slot_of, &s.n_slots, &s.more);
+        __syncthreads();
+        const uint32_t ns = s.n_slots;
+        load_slot_prefixes(sp, s.slot_pfx, ns);
+        if (!s.more) break;
+        const int bits = shift >= kDigBits ? kDigBits : shift;
+        const int new_shift = shift - bits;
+        for (uint32_t i = tid; i < ns * (uint32_t)kDigBins; i += kThreads) dig_hist[i] = 0u;
+        __syncthreads();
+        for (uint32_t i = tid; i < n; i += kThreads) count_digit(key_of(lat_of(rows[i])), shift, new_shift, bits, sp, dig_hist);
+        __syncthreads();
+        select_digit_level(dig_hist, bits, s.slot_of, s.pfx, s.rank_in, s.cnt);
+        shift = new_shift;
     }
-    const uint32_t excl = incl - mine;
-    const bool owner = excl <= k && k < incl;
-    uint32_t b = 0, bl = 0, c = 0;
-    if (owner) {
-        uint32_t run = excl;
-        for (int j = 0; j < per; ++j) {
-            const uint32_t h = hist[lane * per + j];
-            if (k < run + h) {
-                b = (uint32_t)(lane * per + j);
-                bl = run;
-                c = h;
-                break;
-            }
-            run += h;
-        }
-    }
-    const unsigned long long m = __ballot(owner);
-    const int src = m ? __ffsll((long long)m) - 1 : 0;
-    bin = __shfl(b, src, 64);
-    below = __shfl(bl, src, 64);
-    count = __shfl(c, src, 64);
+    if (tid < kRanks) s.cand_n[tid] = 0u;
+    __syncthreads();
+    const double sq_total = numpy_sum<kLoads>(rows, n, wsum, tail_slots, [&](const Row c, const bool act) -> double {
+        const double lat = lat_of(c);
+        const double d = lat - mean;
+        if (act && shift > 0) collect_candidate(lat, shift, sp, s.cand_n, cand);
+        return d * d;
+    });
+    __syncthreads();
+    rank_values(cand, s.cand_n, s.slot_of, s.rank_in, s.pfx, shift, s.val);
+    __syncthreads();
+    if (tid == 0) write_stats_row(st, n, mean, sq_total, s.val, s.tfrac, vmin, vmax);
 }
 
 // kWpe: waves per SIMD the register allocation aims at -- 4: 115 registers, two scenarios (workgroups) per CU; 8: 64 registers,
@@ -279,17 +286,8 @@ __global__ __launch_bounds__(kThreads, kWpe) void af_summary_kernel(SumArgs a) {
     extern __shared__ uint32_t dyn[];  // [rps_buckets] then [hist_bins]
     __shared__ uint32_t exp_hist[kExpBins];
     __shared__ __attribute__((aligned(16))) uint32_t dig_hist[kRanks][kDigBins];
-    static_assert(sizeof(double) * kCand == sizeof(uint32_t) * kDigBins, "the candidates take the digit histograms' place");
-    double (*cand)[kCand] = reinterpret_cast<double (*)[kCand]>(&dig_hist[0][0]);   // (dead by the last pass: 35 instead of 59 KB, 4 scenarios per CU)
-    __shared__ uint32_t cand_n[kRanks];
     __shared__ double scratch[kWaves];
-    __shared__ unsigned long long pfx[kRanks];       // key >> shift of the bin holding rank r
-    __shared__ unsigned long long slot_pfx[kRanks];  // distinct prefixes
-    __shared__ uint32_t rank_in[kRanks];             // rank r relative to its bin
-    __shared__ uint32_t cnt[kRanks];                 // elements in that bin
-    __shared__ uint32_t slot_of[kRanks];
-    __shared__ uint32_t n_slots, more;
-    __shared__ double val[kRanks];
+    __shared__ SelectLds sel;
     __shared__ uint32_t g_pfx[3];   // exponent bins guessed from the first 512 latencies
     __shared__ uint32_t g_n, g_hit;
     __shared__ double wsum[2 * kWaves];
@@ -315,7 +313,7 @@ __global__ __launch_bounds__(kThreads, kWpe) void af_summary_kernel(SumArgs a) {
         const uint32_t m = n < (uint32_t)kThreads ? n : (uint32_t)kThreads;
         if ((uint32_t)tid < m) {
             const double2 c = ck[tid];
-            atomicAdd(&exp_hist[((unsigned long long)__double_as_longlong(c.y - c.x) >> 52) & (kExpBins - 1)], 1u);
+            atomicAdd(&exp_hist[(key_of(c.y - c.x) >> 52) & (kExpBins - 1)], 1u);
         }
         __syncthreads();
         if (wave < 3 && m > 0u) {
@@ -344,7 +342,7 @@ __global__ __launch_bounds__(kThreads, kWpe) void af_summary_kernel(SumArgs a) {
     double mn = __builtin_inf(), mx = -__builtin_inf();
     const double total = numpy_sum<kLoads>(ck, n, wsum, tail_slots, [&](const double2 c, const bool act) -> double {
         const double lat = c.y - c.x;
-        const unsigned long long key = (unsigned long long)__double_as_longlong(lat);
+        const unsigned long long key = key_of(lat);
         const uint32_t ebin = (uint32_t)(key >> 52) & (kExpBins - 1);
         if (act) {
             mn = fmin(mn, lat);
@@ -396,43 +394,17 @@ __global__ __launch_bounds__(kThreads, kWpe) void af_summary_kernel(SumArgs a) {
 
     double* st = a.stats + (size_t)sc * 8u;
     if (n == 0u) {  // the reference leaves latency_stats empty (analyzer.py:105-106)
-        if (tid < 8) st[tid] = tid == 0 ? 0.0 : __builtin_nan("");
+        write_empty_row(st, tid);
         return;
     }
     const double mean = total / (double)n;
 
     // ---- wanted ranks (numpy: median = mean of the middle pair; percentile 'linear') ---------
-    __shared__ uint32_t want[kRanks];
-    __shared__ double tfrac[2];
-    if (tid == 0) {
-        want[0] = (n & 1u) ? n / 2u : n / 2u - 1u;
-        want[1] = n / 2u;
-        const double q[2] = {95.0 / 100.0, 99.0 / 100.0};
-        for (int p = 0; p < 2; ++p) {
-            const double v = (double)(n - 1u) * q[p];
-            if (v >= (double)(n - 1u)) {
-                want[2 + 2 * p] = want[3 + 2 * p] = n - 1u;
-                tfrac[p] = 0.0;
-            } else {
-                const double f = floor(v);
-                want[2 + 2 * p] = (uint32_t)f;
-                want[3 + 2 * p] = (uint32_t)f + 1u;
-                tfrac[p] = v - f;
-            }
-        }
-    }
+    if (tid == 0) stat_ranks(n, sel.want, sel.tfrac);
     __syncthreads();
 
     // ---- level 0: exponent bin of every wanted rank ---------------------------------------------
-    if (wave < kRanks) {
-        uint32_t bin, below, count;
-        wave_select(exp_hist, kExpBins, want[wave], bin, below, count);
-        if (lane == 0) {
-            pfx[wave] = bin;
-            rank_in[wave] = want[wave] - below;
-            cnt[wave] = count;
-        }
-    }
+    select_first_level(exp_hist, sel.want, sel.pfx, sel.rank_in, sel.cnt);
     int shift = 52;
     // ---- the guessed bins already carry their next 10 key bits: if they cover every wanted rank that still has
     // too many candidates ... (a rank that is already narrow enough keeps its exponent bin: prefixes of different
@@ -442,24 +414,24 @@ __global__ __launch_bounds__(kThreads, kWpe) void af_summary_kernel(SumArgs a) {
         uint32_t hit = 1u;
         for (int r = 0; r < kRanks; ++r) {
             bool ok = false;
-            for (uint32_t q = 0; q < g_n; ++q) ok = ok || pfx[r] == (unsigned long long)g_pfx[q];
+            for (uint32_t q = 0; q < g_n; ++q) ok = ok || sel.pfx[r] == (uint64_t)g_pfx[q];
             if (!ok) hit = 0u;
         }
         g_hit = hit;
     }
     __syncthreads();
     if (g_hit) {
-        if (wave < kRanks) {
+        if (wave < kRanks) {   // (select_digit_level with the guess's bins for slots)
             uint32_t q = 0;
             for (uint32_t j = 0; j < g_n; ++j)
-                if (pfx[wave] == (unsigned long long)g_pfx[j]) q = j;
+                if (sel.pfx[wave] == (uint64_t)g_pfx[j]) q = j;
             uint32_t bin, below, count;
-            wave_select(dig_hist[q], kDigBins, rank_in[wave], bin, below, count);
+            wave_select(dig_hist[q], kDigBins, sel.rank_in[wave], bin, below, count);
             __syncthreads();
             if (lane == 0) {
-                pfx[wave] = (pfx[wave] << kDigBits) | bin;
-                rank_in[wave] -= below;
-                cnt[wave] = count;
+                sel.pfx[wave] = (sel.pfx[wave] << kDigBits) | bin;
+                sel.rank_in[wave] -= below;
+                sel.cnt[wave] = count;
             }
         } else {
             __syncthreads();
@@ -467,106 +439,8 @@ __global__ __launch_bounds__(kThreads, kWpe) void af_summary_kernel(SumArgs a) {
         shift = 52 - kDigBits;
     }
 
-    // ---- deeper levels while some rank still has too many candidates ------------------------------
-    for (;;) {
-        __syncthreads();
-        if (tid == 0) {
-            uint32_t ns = 0, m = 0;
-            for (int r = 0; r < kRanks; ++r) {
-                uint32_t sidx = ns;
-                for (uint32_t q = 0; q < ns; ++q)
-                    if (slot_pfx[q] == pfx[r]) sidx = q;
-                if (sidx == ns) slot_pfx[ns++] = pfx[r];
-                slot_of[r] = sidx;
-                if (cnt[r] > (uint32_t)kCand && shift > 0) m = 1u;
-            }
-            n_slots = ns;
-            more = m;
-        }
-        __syncthreads();
-        if (!more) break;
-        const int bits = shift >= kDigBits ? kDigBits : shift;
-        const int new_shift = shift - bits;
-        const uint32_t ns = n_slots;
-        for (uint32_t i = tid; i < ns * (uint32_t)kDigBins; i += kThreads) (&dig_hist[0][0])[i] = 0u;
-        __syncthreads();
-        for (uint32_t i = tid; i < n; i += kThreads) {
-            const double2 c = ck[i];
-            const unsigned long long key = (unsigned long long)__double_as_longlong(c.y - c.x);
-            const unsigned long long hi = key >> shift;
-            for (uint32_t q = 0; q < ns; ++q)
-                if (hi == slot_pfx[q]) atomicAdd(&dig_hist[q][(key >> new_shift) & ((1u << bits) - 1u)], 1u);
-        }
-        __syncthreads();
-        if (wave < kRanks) {
-            uint32_t bin, below, count;
-            wave_select(dig_hist[slot_of[wave]], kDigBins, rank_in[wave], bin, below, count);
-            if (lane == 0) {
-                pfx[wave] = (pfx[wave] << bits) | bin;
-                rank_in[wave] -= below;
-                cnt[wave] = count;
-            }
-        }
-        shift = new_shift;
-    }
-
-    // ---- last pass: the squared deviations in numpy's order (x - mean, squared, summed like the latencies), candidates on the way
-    if (tid < kRanks) cand_n[tid] = 0u;
-    __syncthreads();
-    const uint32_t ns = n_slots;
-    unsigned long long sp[kRanks];
-#pragma unroll
-    for (int q = 0; q < kRanks; ++q) sp[q] = (uint32_t)q < ns ? slot_pfx[q] : ~0ull;   // (a prefix no key >> shift can equal: latencies are >= +0.0)
-    const double sq_total = numpy_sum<kLoads>(ck, n, wsum, tail_slots, [&](const double2 c, const bool act) -> double {
-        const double lat = c.y - c.x;
-        const double d = lat - mean;
-        if (act && shift > 0) {
-            const unsigned long long hi = (unsigned long long)__double_as_longlong(lat) >> shift;
-#pragma unroll
-            for (int q = 0; q < kRanks; ++q)
-                if (hi == sp[q]) {
-                    const uint32_t pos = atomicAdd(&cand_n[q], 1u);
-                    if (pos < (uint32_t)kCand) cand[q][pos] = lat;
-                }
-        }
-        return d * d;
-    });
-    __syncthreads();
-    for (int r = 0; r < kRanks; ++r) {
-        const uint32_t q = slot_of[r];
-        if (shift == 0) {  // the whole key is known: every candidate has this value
-            if (tid == 0) val[r] = __longlong_as_double((long long)pfx[r]);
-            continue;
-        }
-        const uint32_t m = cand_n[q] < (uint32_t)kCand ? cand_n[q] : (uint32_t)kCand;
-        const uint32_t k = rank_in[r];
-        if ((uint32_t)tid < m) {
-            const double x = cand[q][tid];
-            uint32_t less = 0, leq = 0;
-            for (uint32_t j = 0; j < m; ++j) {
-                const double y = cand[q][j];
-                less += y < x ? 1u : 0u;
-                leq += y <= x ? 1u : 0u;
-            }
-            if (less <= k && k < leq) val[r] = x;
-        }
-    }
-    __syncthreads();
-
-    if (tid == 0) {
-        auto lerp = [](double lo, double hi, double t) {  // numpy _lerp
-            const double d = hi - lo;
-            return t >= 0.5 ? hi - d * (1.0 - t) : lo + d * t;
-        };
-        st[0] = (double)n;
-        st[1] = mean;
-        st[2] = (n & 1u) ? val[1] : (val[0] + val[1]) / 2.0;
-        st[3] = sqrt(sq_total / (double)n);
-        st[4] = lerp(val[2], val[3], tfrac[0]);
-        st[5] = lerp(val[4], val[5], tfrac[1]);
-        st[6] = vmin;
-        st[7] = vmax;
-    }
+    // ---- deeper levels while some rank still has too many candidates, the last pass, the row
+    select_and_finish<kLoads>(ck, n, [](const double2 c) { return c.y - c.x; }, shift, mean, vmin, vmax, sel, &dig_hist[0][0], wsum, tail_slots, st);
 }
 
 // Per-series mean and maximum of the sampled metrics of every scenario

@@ -14,8 +14,9 @@
 //             numpy's pairwise sum with the wave's eight 8-lane groups as the recursion's (at most eight) leaves, the wanted
 //             ranks by counting over the whole cell.  No histograms, no barrier but the one after staging.
 //   small     a cell of <= kPiece latencies (one numpy piece) is reduced by ONE workgroup, everything in LDS, as
-//             af_summary_kernel does for a scenario: numpy's pairwise sum, min / max, exponent histogram; MSB-first radix
-//             select; squared deviations and candidates.  No global scratch per cell beyond its offset and list entry.
+//             af_summary_kernel does for a scenario: numpy's pairwise sum, min / max, exponent histogram; then that kernel's
+//             own afs::select_and_finish: MSB-first radix select (af_select.hpp), squared deviations and candidates.  No
+//             global scratch per cell beyond its offset and list entry.
 //   large     cells above one piece take the pooled analyzer's tiled passes (af_pooled.hpp) over their compacted range, with
 //             that analyzer's per-group scratch -- for them only.
 // Scratch (engine-owned, shared with the pooled analyzer): 8 B per windowed latency + 4 B per (scenario, edge) (the bounds,
@@ -32,16 +33,9 @@
 
 namespace afw {
 
-constexpr int kThreads = afs::kThreads;
-constexpr int kWaves = kThreads / 64;
-constexpr int kRanks = afs::kRanks;
-constexpr int kCand = afs::kCand;
-constexpr uint32_t kPiece = afs::kPiece;
-constexpr int kExpBins = afs::kExpBins;
-constexpr int kDigBits = afs::kDigBits;
-constexpr int kDigBins = afs::kDigBins;
-constexpr uint32_t kSkip = afp::kSkip;
-constexpr uint32_t kSmallMax = kPiece;        // latencies of the largest cell one workgroup reduces
+using afs::kThreads, afs::kWaves, afs::kRanks, afs::kExpBins, afs::kDigBins;
+using afp::kSkip;
+constexpr uint32_t kSmallMax = afs::kPiece;   // latencies of the largest cell one workgroup reduces
 constexpr uint32_t kTinyMax = 512;            // latencies of the largest cell one wave reduces
 constexpr int kTinyWaves = 4;                 // cells per workgroup of the wave kernel
 constexpr int kBoundsThreads = 256;
@@ -225,8 +219,8 @@ __global__ __launch_bounds__(kTinyWaves * 64) void af_win_tiny(WinArgs a, uint64
     __syncthreads();
     if (!mine) return;
     double* st = a.stats + cell * 8u;
-    if (n == 0u) {   // the reference leaves latency_stats empty (analyzer.py:105-106)
-        if (lane < 8) st[lane] = lane == 0 ? 0.0 : __builtin_nan("");
+    if (n == 0u) {
+        afs::write_empty_row(st, lane);
         return;
     }
     mn = afs::wave_min(mn);
@@ -236,27 +230,9 @@ __global__ __launch_bounds__(kTinyWaves * 64) void af_win_tiny(WinArgs a, uint64
         const double d = x - mean;
         return d * d;
     });
-    // numpy: median = mean of the middle pair; percentile 'linear' (af_summary.hpp)
     uint32_t want[kRanks];
     double tfrac[2];
-    want[0] = (n & 1u) ? n / 2u : n / 2u - 1u;
-    want[1] = n / 2u;
-    {
-        const double q[2] = {95.0 / 100.0, 99.0 / 100.0};
-#pragma unroll
-        for (int p = 0; p < 2; ++p) {
-            const double v = (double)(n - 1u) * q[p];
-            if (v >= (double)(n - 1u)) {
-                want[2 + 2 * p] = want[3 + 2 * p] = n - 1u;
-                tfrac[p] = 0.0;
-            } else {
-                const double f = floor(v);
-                want[2 + 2 * p] = (uint32_t)f;
-                want[3 + 2 * p] = (uint32_t)f + 1u;
-                tfrac[p] = v - f;
-            }
-        }
-    }
+    afs::stat_ranks(n, want, tfrac);
     double val[kRanks] = {};
     for (uint32_t i0 = 0; i0 < n; i0 += 64u) {   // the ranks by counting: every latency against the whole cell
         const bool valid = i0 + (uint32_t)lane < n;
@@ -273,42 +249,22 @@ __global__ __launch_bounds__(kTinyWaves * 64) void af_win_tiny(WinArgs a, uint64
             if (hit) val[r] = __shfl(x, __ffsll((long long)hit) - 1, 64);
         }
     }
-    if (lane == 0) {
-        auto lerp = [](double lo, double hi, double t) {   // numpy _lerp
-            const double d = hi - lo;
-            return t >= 0.5 ? hi - d * (1.0 - t) : lo + d * t;
-        };
-        st[0] = (double)n;
-        st[1] = mean;
-        st[2] = (n & 1u) ? val[1] : (val[0] + val[1]) / 2.0;
-        st[3] = sqrt(sq / (double)n);
-        st[4] = lerp(val[2], val[3], tfrac[0]);
-        st[5] = lerp(val[4], val[5], tfrac[1]);
-        st[6] = mn;
-        st[7] = mx;
-    }
+    if (lane == 0) afs::write_stats_row(st, n, mean, sq, val, tfrac, mn, mx);
 }
 
-// one workgroup per listed cell (kTinyMax < latencies <= kSmallMax): the body of af_summary_kernel over a compacted f64 range
+// one workgroup per listed cell (kTinyMax < latencies <= kSmallMax): af_summary_kernel over a compacted f64 range
 __global__ __launch_bounds__(kThreads) void af_win_small(WinArgs a, uint32_t first) {
     __shared__ uint32_t exp_hist[kExpBins];
     __shared__ __attribute__((aligned(16))) uint32_t dig_hist[kRanks][kDigBins];
-    static_assert(sizeof(double) * kCand == sizeof(uint32_t) * kDigBins, "the candidates take the digit histograms' place");
-    double (*cand)[kCand] = reinterpret_cast<double (*)[kCand]>(&dig_hist[0][0]);
-    __shared__ uint32_t cand_n[kRanks];
     __shared__ double red[2][kWaves];
-    __shared__ unsigned long long pfx[kRanks], slot_pfx[kRanks];
-    __shared__ uint32_t rank_in[kRanks], cnt[kRanks], slot_of[kRanks], want[kRanks];
-    __shared__ uint32_t n_slots, more;
-    __shared__ double val[kRanks], tfrac[2];
+    __shared__ afs::SelectLds sel;
     __shared__ double wsum[2 * kWaves];
     __shared__ double tail_slots[afs::kTailSlots];
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const uint64_t cell = a.small[first + blockIdx.x];
     const uint64_t off = a.cell_off[cell];
     const uint32_t n = (uint32_t)(a.cell_off[cell + 1u] - off);
-    double* st = a.stats + cell * 8u;
     const double* src = a.lat + off;
     for (int i = tid; i < kExpBins; i += kThreads) exp_hist[i] = 0u;
     __syncthreads();
@@ -320,149 +276,16 @@ __global__ __launch_bounds__(kThreads) void af_win_small(WinArgs a, uint32_t fir
             mn = fmin(mn, x);
             mx = fmax(mx, x);
         }
-        afs::wave_agg_add(exp_hist, (uint32_t)(afp::key_of(x) >> 52) & (kExpBins - 1), act);
+        afs::wave_agg_add(exp_hist, (uint32_t)(afs::key_of(x) >> 52) & (kExpBins - 1), act);
         return x;
     });
-    mn = afs::wave_min(mn);
-    mx = afs::wave_max(mx);
-    if (lane == 0) {
-        red[0][wave] = mn;
-        red[1][wave] = mx;
-    }
-    if (tid == 0) {   // numpy: median = mean of the middle pair; percentile 'linear' (af_summary.hpp)
-        want[0] = (n & 1u) ? n / 2u : n / 2u - 1u;
-        want[1] = n / 2u;
-        const double q[2] = {95.0 / 100.0, 99.0 / 100.0};
-        for (int p = 0; p < 2; ++p) {
-            const double v = (double)(n - 1u) * q[p];
-            if (v >= (double)(n - 1u)) {
-                want[2 + 2 * p] = want[3 + 2 * p] = n - 1u;
-                tfrac[p] = 0.0;
-            } else {
-                const double f = floor(v);
-                want[2 + 2 * p] = (uint32_t)f;
-                want[3 + 2 * p] = (uint32_t)f + 1u;
-                tfrac[p] = v - f;
-            }
-        }
-    }
-    __syncthreads();
-    double vmin = red[0][0], vmax = red[1][0];
-    for (int w = 1; w < kWaves; ++w) {
-        vmin = fmin(vmin, red[0][w]);
-        vmax = fmax(vmax, red[1][w]);
-    }
-    const double mean = total / (double)n;
-
-    int shift = 52;
-    {
-        // ---- level 0: exponent bin of every wanted rank; deeper levels while a rank has too many candidates
-        if (wave < kRanks) {
-            uint32_t bin, below, count;
-            afs::wave_select(exp_hist, kExpBins, want[wave], bin, below, count);
-            if (lane == 0) {
-                pfx[wave] = bin;
-                rank_in[wave] = want[wave] - below;
-                cnt[wave] = count;
-            }
-        }
-        for (;;) {
-            __syncthreads();
-            if (tid == 0) {
-                uint32_t ns = 0, m = 0;
-                for (int r = 0; r < kRanks; ++r) {
-                    uint32_t sidx = ns;
-                    for (uint32_t q = 0; q < ns; ++q)
-                        if (slot_pfx[q] == pfx[r]) sidx = q;
-                    if (sidx == ns) slot_pfx[ns++] = pfx[r];
-                    slot_of[r] = sidx;
-                    if (cnt[r] > (uint32_t)kCand && shift > 0) m = 1u;
-                }
-                n_slots = ns;
-                more = m;
-            }
-            __syncthreads();
-            if (!more) break;
-            const int bits = shift >= kDigBits ? kDigBits : shift;
-            const int new_shift = shift - bits;
-            const uint32_t ns = n_slots;
-            for (uint32_t i = tid; i < ns * (uint32_t)kDigBins; i += kThreads) (&dig_hist[0][0])[i] = 0u;
-            __syncthreads();
-            for (uint32_t i = tid; i < n; i += kThreads) {
-                const unsigned long long key = afp::key_of(src[i]);
-                const unsigned long long hi = key >> shift;
-                for (uint32_t q = 0; q < ns; ++q)
-                    if (hi == slot_pfx[q]) atomicAdd(&dig_hist[q][(key >> new_shift) & ((1u << bits) - 1u)], 1u);
-            }
-            __syncthreads();
-            if (wave < kRanks) {
-                uint32_t bin, below, count;
-                afs::wave_select(dig_hist[slot_of[wave]], kDigBins, rank_in[wave], bin, below, count);
-                if (lane == 0) {
-                    pfx[wave] = (pfx[wave] << bits) | bin;
-                    rank_in[wave] -= below;
-                    cnt[wave] = count;
-                }
-            }
-            shift = new_shift;
-        }
-        if (tid < kRanks) cand_n[tid] = 0u;
-    }
-    __syncthreads();
-
-    // ---- last pass: the squared deviations in numpy's order, the candidates on the way
-    const uint32_t ns = n_slots;
-    unsigned long long sp[kRanks];
-#pragma unroll
-    for (int q = 0; q < kRanks; ++q) sp[q] = (uint32_t)q < ns ? slot_pfx[q] : ~0ull;   // (a prefix no key >> shift can equal)
-    const double sq_total = afs::numpy_sum<8>(src, n, wsum, tail_slots, [&](const double x, const bool act) -> double {
-        const double d = x - mean;
-        if (act && shift > 0) {
-            const unsigned long long hi = afp::key_of(x) >> shift;
-#pragma unroll
-            for (int q = 0; q < kRanks; ++q)
-                if (hi == sp[q]) {
-                    const uint32_t pos = atomicAdd(&cand_n[q], 1u);
-                    if (pos < (uint32_t)kCand) cand[q][pos] = x;
-                }
-        }
-        return d * d;
-    });
-    __syncthreads();
-    for (int r = 0; r < kRanks; ++r) {
-        const uint32_t q = slot_of[r];
-        if (shift == 0) {   // the whole key is known: every candidate has this value
-            if (tid == 0) val[r] = __longlong_as_double((long long)pfx[r]);
-            continue;
-        }
-        const uint32_t m = cand_n[q] < (uint32_t)kCand ? cand_n[q] : (uint32_t)kCand;
-        const uint32_t k = rank_in[r];
-        if ((uint32_t)tid < m) {
-            const double x = cand[q][tid];
-            uint32_t less = 0, leq = 0;
-            for (uint32_t j = 0; j < m; ++j) {
-                const double y = cand[q][j];
-                less += y < x ? 1u : 0u;
-                leq += y <= x ? 1u : 0u;
-            }
-            if (less <= k && k < leq) val[r] = x;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        auto lerp = [](double lo, double hi, double t) {   // numpy _lerp
-            const double d = hi - lo;
-            return t >= 0.5 ? hi - d * (1.0 - t) : lo + d * t;
-        };
-        st[0] = (double)n;
-        st[1] = mean;
-        st[2] = (n & 1u) ? val[1] : (val[0] + val[1]) / 2.0;
-        st[3] = sqrt(sq_total / (double)n);
-        st[4] = lerp(val[2], val[3], tfrac[0]);
-        st[5] = lerp(val[4], val[5], tfrac[1]);
-        st[6] = vmin;
-        st[7] = vmax;
-    }
+    if (tid == 0) afs::stat_ranks(n, sel.want, sel.tfrac);
+    double vmin, vmax;
+    afs::block_min_max(mn, mx, red, vmin, vmax);
+    // ---- level 0: exponent bin of every wanted rank; then as the scenarios' kernel goes on
+    afs::select_first_level(exp_hist, sel.want, sel.pfx, sel.rank_in, sel.cnt);
+    afs::select_and_finish<8>(src, n, [](const double x) { return x; }, 52, total / (double)n, vmin, vmax, sel, &dig_hist[0][0], wsum, tail_slots,
+                              a.stats + cell * 8u);
 }
 
 }  // namespace afw

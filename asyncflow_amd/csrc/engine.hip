@@ -32,6 +32,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -2550,23 +2551,34 @@ static int pool_reserve(af_engine_t* e, size_t bytes) {
     return AF_OK;
 }
 
-// the parts of that scratch that the tiled passes need for G groups (256-byte aligned, from `at` on)
+// the layout of a request's scratch: 256-byte aligned parts, one after the other
+struct ScratchLayout {
+    size_t at = 0;
+    size_t part(size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 255u) & ~(size_t)255u;
+        return o;
+    }
+};
+
+constexpr uint64_t kBlocksPerLaunch = 1u << 21;   // workgroups of one launch of a kernel over any number of cells (at most 2^30 threads)
+
+// the parts of that scratch that the tiled passes need for G groups
 struct PoolParts {
     size_t grp, tile, piece, tmin, tmax, h0, dh, cn, cd, flag;
 };
-static PoolParts pool_parts(size_t& at, size_t G, size_t n_tiles, uint64_t pieces) {
-    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+static PoolParts pool_parts(ScratchLayout& lay, size_t G, size_t n_tiles, uint64_t pieces) {
     PoolParts p{};
-    p.grp = part(std::max<size_t>(G, 1u) * sizeof(afp::PoolGroup));
-    p.tile = part(std::max<size_t>(n_tiles, 1u) * sizeof(afp::PoolTile));
-    p.piece = part(std::max<uint64_t>(pieces, 1u) * 8u);
-    p.tmin = part(std::max<size_t>(n_tiles, 1u) * 8u);
-    p.tmax = part(std::max<size_t>(n_tiles, 1u) * 8u);
-    p.h0 = part(G * afp::kExpBins * 4u);
-    p.dh = part(G * afp::kRanks * afp::kDigBins * 4u);
-    p.cn = part(G * afp::kRanks * 4u);
-    p.cd = part(G * afp::kRanks * afp::kCand * 8u);
-    p.flag = part(4u);
+    p.grp = lay.part(std::max<size_t>(G, 1u) * sizeof(afp::PoolGroup));
+    p.tile = lay.part(std::max<size_t>(n_tiles, 1u) * sizeof(afp::PoolTile));
+    p.piece = lay.part(std::max<uint64_t>(pieces, 1u) * 8u);
+    p.tmin = lay.part(std::max<size_t>(n_tiles, 1u) * 8u);
+    p.tmax = lay.part(std::max<size_t>(n_tiles, 1u) * 8u);
+    p.h0 = lay.part(G * afp::kExpBins * 4u);
+    p.dh = lay.part(G * afp::kRanks * afp::kDigBins * 4u);
+    p.cn = lay.part(G * afp::kRanks * 4u);
+    p.cd = lay.part(G * afp::kRanks * afp::kCand * 8u);
+    p.flag = lay.part(4u);
     return p;
 }
 static void pool_bind(afp::PoolArgs& a, unsigned char* b, const PoolParts& p) {
@@ -2598,8 +2610,26 @@ static void pool_add_group(std::vector<afp::PoolGroup>& groups, std::vector<afp:
     groups.push_back(pg);
 }
 
-// the passes over the compacted latencies (af_pooled.hpp) on the engine's stream, one digit level per launch pair while some
-// group still needs one (a 4-byte read-back decides); the last kernel is launched, not waited for
+// The radix levels of G samples whose state is a.groups (af_select.hpp): launch_select(level) launches the analyzer's select
+// kernel, af_pool_digits counts the next key bits, one level per launch pair while some sample still needs one (a 4-byte
+// read-back decides).
+static int radix_levels(hipStream_t st, const afp::PoolArgs& a, uint32_t G, uint32_t n_tiles, const char* analyzer, const std::function<void(int)>& launch_select) {
+    for (int level = 0;; ++level) {   // (shift 52 -> 42 -> ... -> 2 -> 0: at most six digit levels)
+        HIP_TRY(hipMemsetAsync(a.any_more, 0, 4u, st));
+        launch_select(level);
+        HIP_TRY(hipGetLastError());
+        uint32_t more = 0;
+        HIP_TRY(hipMemcpyAsync(&more, a.any_more, 4u, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        if (!more) return AF_OK;
+        if (level >= 6) return fail(AF_ERR_HIP, std::string(analyzer) + " analyzer: radix select did not converge");
+        HIP_TRY(hipMemsetAsync(a.dhist, 0, (size_t)G * afp::kRanks * afp::kDigBins * 4u, st));
+        hipLaunchKernelGGL(afp::af_pool_digits, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+    }
+}
+
+// the passes over the compacted latencies (af_pooled.hpp) on the engine's stream; the last kernel is launched, not waited for
 static int pool_run(af_engine_t* e, const afp::PoolArgs& a, const std::vector<afp::PoolGroup>& groups, const std::vector<afp::PoolTile>& tiles) {
     hipStream_t st = e->stream;
     const uint32_t G = (uint32_t)groups.size(), n_tiles = (uint32_t)tiles.size();
@@ -2608,19 +2638,8 @@ static int pool_run(af_engine_t* e, const afp::PoolArgs& a, const std::vector<af
     HIP_TRY(hipMemsetAsync(a.hist0, 0, (size_t)G * afp::kExpBins * 4u, st));
     if (n_tiles) hipLaunchKernelGGL(afp::af_pool_pass1, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
-    for (int level = 0;; ++level) {   // (shift 52 -> 42 -> ... -> 2 -> 0: at most six digit levels)
-        HIP_TRY(hipMemsetAsync(a.any_more, 0, 4u, st));
-        hipLaunchKernelGGL(afp::af_pool_select, dim3(G), dim3(afp::kThreads), 0, st, a, level);
-        HIP_TRY(hipGetLastError());
-        uint32_t more = 0;
-        HIP_TRY(hipMemcpyAsync(&more, a.any_more, 4u, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (!more) break;
-        if (level >= 6) return fail(AF_ERR_HIP, "pooled analyzer: radix select did not converge");
-        HIP_TRY(hipMemsetAsync(a.dhist, 0, (size_t)G * afp::kRanks * afp::kDigBins * 4u, st));
-        hipLaunchKernelGGL(afp::af_pool_digits, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
-        HIP_TRY(hipGetLastError());
-    }
+    if (int rc = radix_levels(st, a, G, n_tiles, "pooled", [&](int level) { hipLaunchKernelGGL(afp::af_pool_select, dim3(G), dim3(afp::kThreads), 0, st, a, level); }))
+        return rc;
     HIP_TRY(hipMemsetAsync(a.cand_n, 0, (size_t)G * afp::kRanks * 4u, st));
     if (n_tiles) hipLaunchKernelGGL(afp::af_pool_last, dim3(n_tiles), dim3(afp::kThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
@@ -2629,9 +2648,69 @@ static int pool_run(af_engine_t* e, const afp::PoolArgs& a, const std::vector<af
     return AF_OK;
 }
 
+static int check_window_edges(const double* edges, uint32_t W) {
+    for (uint32_t k = 0; k <= W; ++k) {
+        if (!std::isfinite(edges[k])) return fail(AF_ERR_INVALID, "window edge " + std::to_string(k) + " is not finite");
+        if (k > 0 && !(edges[k - 1] < edges[k]))
+            return fail(AF_ERR_INVALID, "window edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    }
+    return AF_OK;
+}
+
+// the group ids of n scenarios to the host (none: all in group 0, grp stays empty), every one below G or AF_POOL_SKIP
+static int read_groups(const uint32_t* group, uint32_t n, uint32_t G, std::vector<uint32_t>& grp) {
+    grp.resize(group ? n : 0u);
+    if (group) HIP_TRY(hipMemcpy(grp.data(), group, grp.size() * 4u, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < grp.size(); ++s)
+        if (grp[s] != afp::kSkip && grp[s] >= G)
+            return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(grp[s]) + ", n_groups " + std::to_string(G) + ")");
+    return AF_OK;
+}
+
+// The cells of a request over whole runs: one per group, its sample the latencies of the group's members in ascending scenario
+// index.  cell_off[g] is the cell's first latency in the compacted array, dst[s] the first of scenario s.
+struct PooledCells {
+    std::vector<uint64_t> cell_off, dst;   // [G + 1], [n]
+};
+static int layout_pooled_cells(const af_outputs_t* out, const std::vector<uint32_t>& grp, uint32_t n, uint32_t G, const char* holds, PooledCells& pc) {
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS);
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    pc.cell_off.assign((size_t)G + 1u, 0u);   // (first the sizes, at [g + 1])
+    pc.dst.assign(n, 0u);
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = grp.empty() ? 0u : grp[s];
+        if (g == afp::kSkip) continue;
+        pc.dst[s] = pc.cell_off[1u + g];   // (for now: the latencies earlier members bring)
+        pc.cell_off[1u + g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], out->clock_capacity);
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+        if (pc.cell_off[1u + g] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "group " + std::to_string(g) + " " + holds + " 2^32 or more latencies");
+        pc.cell_off[1u + g] += pc.cell_off[g];
+    }
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = grp.empty() ? 0u : grp[s];
+        if (g != afp::kSkip) pc.dst[s] += pc.cell_off[g];
+    }
+    return AF_OK;
+}
+// ... and their latencies to lat (o_dst, o_lat: parts of the scratch of n * 8 and cell_off[G] * 8 bytes)
+static int compact_pooled_cells(af_engine_t* e, const af_outputs_t* out, const uint32_t* group, uint32_t n, const PooledCells& pc, size_t o_dst, size_t o_lat) {
+    afp::PoolArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = out->clock_capacity;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.group = group;
+    a.dst = reinterpret_cast<const uint64_t*>(e->d_pool + o_dst);
+    a.lat = reinterpret_cast<double*>(e->d_pool + o_lat);
+    HIP_TRY(hipMemcpyAsync(e->d_pool + o_dst, pc.dst.data(), (size_t)n * 8u, hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(afp::af_pool_compact, dim3(n), dim3(afp::kThreads), 0, e->stream, a);
+    HIP_TRY(hipGetLastError());
+    return AF_OK;
+}
+
 // Pooled analyzer (af_pooled.hpp): the host reads counts and group ids back, checks them, and lays out the compacted array,
-// the groups' pieces and the tiles of the streaming passes; the kernels run on the engine's stream, one digit level per launch
-// pair while some group still needs one (a 4-byte read-back decides).
+// the groups' pieces and the tiles of the streaming passes; the kernels run on the engine's stream.
 int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_pooled_t* pl) {
     if (!e || !out || !pl) return fail(AF_ERR_INVALID, "NULL argument");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
@@ -2641,59 +2720,137 @@ int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_poole
     if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "pooled summary needs outputs.clock");
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(e->device));
-    const uint32_t n = pl->n_scenarios, G = pl->n_groups, cap = out->clock_capacity;
-    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp(pl->group ? n : 0u);
-    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
-    if (pl->group) HIP_TRY(hipMemcpy(grp.data(), pl->group, grp.size() * 4u, hipMemcpyDeviceToHost));
-    std::vector<uint64_t> g_n(G, 0u), dst(n, 0u);
-    for (uint32_t s = 0; s < n; ++s) {
-        const uint32_t g = pl->group ? grp[s] : 0u;
-        if (g == afp::kSkip) continue;
-        if (g >= G) return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
-        g_n[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], cap);
-    }
+    const uint32_t n = pl->n_scenarios, G = pl->n_groups;
+    std::vector<uint32_t> grp;
+    if (int rc = read_groups(pl->group, n, G, grp)) return rc;
+    PooledCells pc;
+    if (int rc = layout_pooled_cells(out, grp, n, G, "pools", pc)) return rc;
     std::vector<afp::PoolGroup> groups;
     std::vector<afp::PoolTile> tiles;
-    std::vector<uint64_t> cursor(G);
     groups.reserve(G);
-    uint64_t off = 0, pieces = 0;
-    for (uint32_t g = 0; g < G; ++g) {
-        if (g_n[g] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "group " + std::to_string(g) + " pools 2^32 or more latencies");
-        cursor[g] = off;
-        pool_add_group(groups, tiles, pieces, off, (uint32_t)g_n[g]);
-        off += g_n[g];
-    }
-    for (uint32_t s = 0; s < n; ++s) {
-        const uint32_t g = pl->group ? grp[s] : 0u;
-        if (g == afp::kSkip) continue;
-        dst[s] = cursor[g];
-        cursor[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], cap);
-    }
-    const uint32_t n_tiles = (uint32_t)tiles.size();
-    // scratch layout (256-byte aligned parts)
-    size_t at = 0;
-    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
-    const size_t o_lat = part(off * 8u), o_dst = part((size_t)n * 8u);
-    const PoolParts pp = pool_parts(at, G, n_tiles, pieces);
-    if (int rc = pool_reserve(e, at)) return rc;
-    unsigned char* b = e->d_pool;
+    uint64_t pieces = 0;
+    for (uint32_t g = 0; g < G; ++g) pool_add_group(groups, tiles, pieces, pc.cell_off[g], (uint32_t)(pc.cell_off[g + 1u] - pc.cell_off[g]));
+    ScratchLayout lay;
+    const size_t o_lat = lay.part(pc.cell_off[G] * 8u), o_dst = lay.part((size_t)n * 8u);
+    const PoolParts pp = pool_parts(lay, G, tiles.size(), pieces);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    if (int rc = compact_pooled_cells(e, out, pl->group, n, pc, o_dst, o_lat)) return rc;
     afp::PoolArgs a{};
-    a.clock = out->clock;
-    a.counts = out->counts;
-    a.clock_cap = cap;
-    a.cnt_completed_slot = AF_CNT_COMPLETED;
-    a.group = pl->group;
-    a.dst = reinterpret_cast<const uint64_t*>(b + o_dst);
-    a.lat = reinterpret_cast<double*>(b + o_lat);
-    pool_bind(a, b, pp);
+    a.lat = reinterpret_cast<double*>(e->d_pool + o_lat);
+    pool_bind(a, e->d_pool, pp);
     a.stats = pl->stats;
-    hipStream_t st = e->stream;
-    HIP_TRY(hipMemcpyAsync(b + o_dst, dst.data(), (size_t)n * 8u, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(afp::af_pool_compact, dim3(n), dim3(afp::kThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
     if (int rc = pool_run(e, a, groups, tiles)) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     pl->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// The cells (group g, window w) of a request with windows by finish time (af_windowed.hpp): layout_window_cells finds the row
+// bounds on the device and from them the cells' places; the caller sorts the cells into its tiers and adds its own parts to the
+// scratch layout; compact_window_cells brings the latencies to their cells.
+struct WindowCells {
+    afw::WinArgs a;                   // what af_win_bounds / af_win_compact take (the analyzer's kernels too, where they take a WinArgs)
+    const double* edges;              // the caller's, [W + 1]
+    uint32_t* row_bounds;             // the caller's, or null: the bounds lie in the scratch
+    size_t o_edges, o_err, o_bounds, o_lat, o_pre, o_off;
+    std::vector<uint32_t> hb, pre;    // the bounds [n][W + 1]; per (scenario, window) the latencies of its cell that earlier members bring
+    std::vector<uint64_t> cell_off;   // [G * W + 1]
+};
+static void bind_window_bounds(const af_engine_t* e, WindowCells& wc) {
+    wc.a.edges = reinterpret_cast<const double*>(e->d_pool + wc.o_edges);
+    wc.a.err = reinterpret_cast<uint32_t*>(e->d_pool + wc.o_err);
+    wc.a.bounds = wc.row_bounds ? wc.row_bounds : reinterpret_cast<uint32_t*>(e->d_pool + wc.o_bounds);
+}
+static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const uint32_t* group, const std::vector<uint32_t>& grp, uint32_t n, uint32_t G,
+                               uint32_t W, const double* edges, uint32_t* row_bounds, ScratchLayout& lay, WindowCells& wc) {
+    const size_t C = (size_t)G * W, NE = (size_t)n * (W + 1u);
+    hipStream_t st = e->stream;
+    wc.edges = edges;
+    wc.row_bounds = row_bounds;
+    // scratch, first part: edges, the error word, the bounds (unless the caller takes them)
+    wc.o_edges = lay.part(((size_t)W + 1u) * 8u);
+    wc.o_err = lay.part(4u);
+    wc.o_bounds = row_bounds ? 0u : lay.part(NE * 4u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    wc.a = afw::WinArgs{};
+    wc.a.clock = out->clock;
+    wc.a.counts = out->counts;
+    wc.a.clock_cap = out->clock_capacity;
+    wc.a.cnt_completed_slot = AF_CNT_COMPLETED;
+    wc.a.group = group;
+    wc.a.n_scen = n;
+    wc.a.n_win = W;
+    bind_window_bounds(e, wc);
+    HIP_TRY(hipMemcpyAsync(e->d_pool + wc.o_edges, edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, wc.a);
+    HIP_TRY(hipGetLastError());
+    wc.hb.resize(NE);
+    HIP_TRY(hipMemcpyAsync(wc.hb.data(), wc.a.bounds, NE * 4u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    // the cells: sizes, and per (scenario, window) the latencies of its cell that earlier members bring
+    wc.cell_off.assign(C + 1u, 0u);   // (first the sizes, at [c + 1])
+    wc.pre.resize((size_t)n * W);
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = grp.empty() ? 0u : grp[s];
+        if (g == afw::kSkip) continue;
+        const uint32_t* r = wc.hb.data() + (size_t)s * (W + 1u);
+        uint64_t* sz = wc.cell_off.data() + 1u + (size_t)g * W;
+        uint32_t* ps = wc.pre.data() + (size_t)s * W;
+        for (uint32_t w = 0; w < W; ++w) {
+            if (r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
+                return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
+            if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
+            ps[w] = (uint32_t)sz[w];
+            sz[w] += r[w + 1u] - r[w];
+        }
+    }
+    for (size_t c = 0; c < C; ++c) {
+        if (wc.cell_off[c + 1u] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(c % W) + " of group " + std::to_string(c / W) + " holds 2^32 or more latencies");
+        wc.cell_off[c + 1u] += wc.cell_off[c];
+    }
+    // scratch, second part: the compacted latencies, pre, the cells' offsets; the caller's parts follow
+    wc.o_lat = lay.part(wc.cell_off[C] * 8u);
+    wc.o_pre = lay.part((size_t)n * W * 4u);
+    wc.o_off = lay.part((C + 1u) * 8u);
+    return AF_OK;
+}
+static int compact_window_cells(af_engine_t* e, const ScratchLayout& lay, WindowCells& wc) {
+    hipStream_t st = e->stream;
+    const uint32_t n = wc.a.n_scen, W = wc.a.n_win;
+    const size_t NE = (size_t)n * (W + 1u);
+    if (lay.at > e->pool_cap) {   // the scratch moves: its first part again
+        if (int rc = pool_reserve(e, lay.at)) return rc;
+        bind_window_bounds(e, wc);
+        HIP_TRY(hipMemcpyAsync(e->d_pool + wc.o_edges, wc.edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+        if (!wc.row_bounds) HIP_TRY(hipMemcpyAsync(wc.a.bounds, wc.hb.data(), NE * 4u, hipMemcpyHostToDevice, st));
+    }
+    unsigned char* b = e->d_pool;
+    wc.a.lat = reinterpret_cast<double*>(b + wc.o_lat);
+    wc.a.pre = reinterpret_cast<const uint32_t*>(b + wc.o_pre);
+    wc.a.cell_off = reinterpret_cast<const uint64_t*>(b + wc.o_off);
+    const uint32_t no_error = afw::kNoError;
+    HIP_TRY(hipMemcpyAsync(b + wc.o_pre, wc.pre.data(), wc.pre.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + wc.o_off, wc.cell_off.data(), wc.cell_off.size() * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(wc.a.err, &no_error, 4u, hipMemcpyHostToDevice, st));
+    if (W <= afw::kLdsWindows)
+        hipLaunchKernelGGL(afw::af_win_compact<true>, dim3(n), dim3(afw::kThreads), (size_t)W * 8u + ((size_t)W + 1u) * 4u, st, wc.a);
+    else
+        hipLaunchKernelGGL(afw::af_win_compact<false>, dim3(n), dim3(afw::kThreads), 0, st, wc.a);
+    HIP_TRY(hipGetLastError());
+    uint32_t bad = afw::kNoError;
+    HIP_TRY(hipMemcpyAsync(&bad, wc.a.err, 4u, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad != afw::kNoError)
+        return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(bad) + " is not in completion order (finish decreases): windows by finish time need it");
+    return AF_OK;
+}
+
+// every cell of C to the wave kernel of a tiny tier, kTinyWaves cells per workgroup: launch(blocks, first cell)
+static int launch_tiny_tier(uint64_t C, uint32_t tiny_waves, const std::function<void(uint32_t, uint64_t)>& launch) {
+    for (uint64_t c0 = 0; c0 < C; c0 += kBlocksPerLaunch * tiny_waves) {   // every cell: a wave takes it if it is tiny (or empty)
+        launch((uint32_t)std::min<uint64_t>(kBlocksPerLaunch, (C - c0 + tiny_waves - 1u) / tiny_waves), c0);
+        HIP_TRY(hipGetLastError());
+    }
     return AF_OK;
 }
 
@@ -2709,123 +2866,47 @@ int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_wind
     if (!win->edges) return fail(AF_ERR_INVALID, "windows.edges is required");
     if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
     if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "windowed summary needs outputs.clock");
-    const uint32_t n = win->n_scenarios, G = win->n_groups, W = win->n_windows, cap = out->clock_capacity;
-    for (uint32_t k = 0; k <= W; ++k) {
-        if (!std::isfinite(win->edges[k])) return fail(AF_ERR_INVALID, "window edge " + std::to_string(k) + " is not finite");
-        if (k > 0 && !(win->edges[k - 1] < win->edges[k]))
-            return fail(AF_ERR_INVALID, "window edges must be strictly increasing (edge " + std::to_string(k) + ")");
-    }
+    const uint32_t n = win->n_scenarios, G = win->n_groups, W = win->n_windows;
+    if (int rc = check_window_edges(win->edges, W)) return rc;
     if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
     if ((uint64_t)n * ((uint64_t)W + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (n_windows + 1) must be below 2^32");
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(e->device));
-    const size_t C = (size_t)G * W, NE = (size_t)n * (W + 1u);
-    std::vector<uint32_t> grp(win->group ? n : 0u);
-    if (win->group) HIP_TRY(hipMemcpy(grp.data(), win->group, grp.size() * 4u, hipMemcpyDeviceToHost));
-    for (uint32_t s = 0; s < n; ++s) {
-        const uint32_t g = win->group ? grp[s] : 0u;
-        if (g != afw::kSkip && g >= G)
-            return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
-    }
-    // scratch, first part: edges, the error word, the bounds (unless the caller takes them)
-    size_t at = 0;
-    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
-    const size_t o_edges = part(((size_t)W + 1u) * 8u), o_err = part(4u), o_bounds = win->row_bounds ? 0u : part(NE * 4u);
-    if (int rc = pool_reserve(e, at)) return rc;
-    hipStream_t st = e->stream;
-    afw::WinArgs a{};
-    a.clock = out->clock;
-    a.counts = out->counts;
-    a.clock_cap = cap;
-    a.cnt_completed_slot = AF_CNT_COMPLETED;
-    a.group = win->group;
-    a.n_scen = n;
-    a.n_win = W;
-    a.stats = win->stats;
-    auto bind_first = [&]() {
-        unsigned char* b = e->d_pool;
-        a.edges = reinterpret_cast<const double*>(b + o_edges);
-        a.err = reinterpret_cast<uint32_t*>(b + o_err);
-        a.bounds = win->row_bounds ? win->row_bounds : reinterpret_cast<uint32_t*>(b + o_bounds);
-    };
-    bind_first();
-    HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, win->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> hb(NE);
-    HIP_TRY(hipMemcpyAsync(hb.data(), a.bounds, NE * 4u, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    // the cells: sizes, and per (scenario, window) the latencies of its cell that earlier members bring
-    std::vector<uint64_t> cell_off(C + 1u, 0u);   // (first the sizes, at [c + 1])
-    std::vector<uint32_t> pre((size_t)n * W);
-    for (uint32_t s = 0; s < n; ++s) {
-        const uint32_t g = win->group ? grp[s] : 0u;
-        if (g == afw::kSkip) continue;
-        const uint32_t* r = hb.data() + (size_t)s * (W + 1u);
-        uint64_t* sz = cell_off.data() + 1u + (size_t)g * W;
-        uint32_t* ps = pre.data() + (size_t)s * W;
-        for (uint32_t w = 0; w < W; ++w) {
-            if (r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
-                return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
-            if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
-            ps[w] = (uint32_t)sz[w];
-            sz[w] += r[w + 1u] - r[w];
-        }
-    }
+    const size_t C = (size_t)G * W;
+    std::vector<uint32_t> grp;
+    if (int rc = read_groups(win->group, n, G, grp)) return rc;
+    ScratchLayout lay;
+    WindowCells wc;
+    if (int rc = layout_window_cells(e, out, win->group, grp, n, G, W, win->edges, win->row_bounds, lay, wc)) return rc;
     std::vector<afp::PoolGroup> groups;
     std::vector<afp::PoolTile> tiles;
     std::vector<uint32_t> stat_row, small;
     uint64_t pieces = 0;
     for (size_t c = 0; c < C; ++c) {
-        const uint64_t len = cell_off[c + 1u];
-        if (len > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(c % W) + " of group " + std::to_string(c / W) + " holds 2^32 or more latencies");
+        const uint64_t len = wc.cell_off[c + 1u] - wc.cell_off[c];
         if (len > afw::kSmallMax) {
-            pool_add_group(groups, tiles, pieces, cell_off[c], (uint32_t)len);
+            pool_add_group(groups, tiles, pieces, wc.cell_off[c], (uint32_t)len);
             stat_row.push_back((uint32_t)c);
         } else if (len > afw::kTinyMax) {
             small.push_back((uint32_t)c);
         }
-        cell_off[c + 1u] = cell_off[c] + len;
     }
-    const uint64_t total = cell_off[C];
-    const uint32_t n_large = (uint32_t)groups.size(), n_tiles = (uint32_t)tiles.size(), n_small = (uint32_t)small.size();
-    // scratch, second part
-    const size_t o_lat = part(total * 8u), o_pre = part((size_t)n * W * 4u), o_off = part((C + 1u) * 8u), o_row = part((size_t)n_large * 4u),
-                 o_small = part((size_t)n_small * 4u);
-    const PoolParts pp = n_large ? pool_parts(at, n_large, n_tiles, pieces) : PoolParts{};
-    if (at > e->pool_cap) {   // the scratch moves: its first part again
-        if (int rc = pool_reserve(e, at)) return rc;
-        bind_first();
-        HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, win->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
-        if (!win->row_bounds) HIP_TRY(hipMemcpyAsync(a.bounds, hb.data(), NE * 4u, hipMemcpyHostToDevice, st));
-    }
-    unsigned char* b = e->d_pool;
-    a.lat = reinterpret_cast<double*>(b + o_lat);
-    a.pre = reinterpret_cast<const uint32_t*>(b + o_pre);
-    a.cell_off = reinterpret_cast<const uint64_t*>(b + o_off);
-    a.small = reinterpret_cast<const uint32_t*>(b + o_small);
-    const uint32_t no_error = afw::kNoError;
-    HIP_TRY(hipMemcpyAsync(b + o_pre, pre.data(), (size_t)n * W * 4u, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(b + o_off, cell_off.data(), (C + 1u) * 8u, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemcpyAsync(a.err, &no_error, 4u, hipMemcpyHostToDevice, st));
-    if (n_small) HIP_TRY(hipMemcpyAsync(b + o_small, small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
-    if (W <= afw::kLdsWindows)
-        hipLaunchKernelGGL(afw::af_win_compact<true>, dim3(n), dim3(afw::kThreads), (size_t)W * 8u + ((size_t)W + 1u) * 4u, st, a);
-    else
-        hipLaunchKernelGGL(afw::af_win_compact<false>, dim3(n), dim3(afw::kThreads), 0, st, a);
-    HIP_TRY(hipGetLastError());
-    uint32_t bad = afw::kNoError;
-    HIP_TRY(hipMemcpyAsync(&bad, a.err, 4u, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
+    const uint32_t n_large = (uint32_t)groups.size(), n_small = (uint32_t)small.size();
+    const size_t o_row = lay.part((size_t)n_large * 4u), o_small = lay.part((size_t)n_small * 4u);
+    const PoolParts pp = n_large ? pool_parts(lay, n_large, tiles.size(), pieces) : PoolParts{};
+    const int rc_compact = compact_window_cells(e, lay, wc);
     win->scratch_bytes = e->pool_cap;
-    if (bad != afw::kNoError)
-        return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(bad) + " is not in completion order (finish decreases): windows by finish time need it");
-    constexpr uint64_t kBlocksPerLaunch = 1u << 21;   // (at most 2^30 threads a launch)
-    for (uint64_t c0 = 0; c0 < C; c0 += kBlocksPerLaunch * afw::kTinyWaves) {   // every cell: a wave takes it if it is tiny (or empty)
-        const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (C - c0 + afw::kTinyWaves - 1u) / afw::kTinyWaves);
-        hipLaunchKernelGGL(afw::af_win_tiny, dim3((uint32_t)blocks), dim3(afw::kTinyWaves * 64), 0, st, a, c0, (uint64_t)C);
-        HIP_TRY(hipGetLastError());
-    }
+    if (rc_compact) return rc_compact;
+    hipStream_t st = e->stream;
+    unsigned char* b = e->d_pool;
+    afw::WinArgs& a = wc.a;
+    a.small = reinterpret_cast<const uint32_t*>(b + o_small);
+    a.stats = win->stats;
+    if (n_small) HIP_TRY(hipMemcpyAsync(b + o_small, small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
+    if (int rc = launch_tiny_tier(C, afw::kTinyWaves, [&](uint32_t blocks, uint64_t c0) {
+            hipLaunchKernelGGL(afw::af_win_tiny, dim3(blocks), dim3(afw::kTinyWaves * 64), 0, st, a, c0, (uint64_t)C);
+        }))
+        return rc;
     for (uint64_t c0 = 0; c0 < n_small; c0 += kBlocksPerLaunch) {
         hipLaunchKernelGGL(afw::af_win_small, dim3((uint32_t)std::min<uint64_t>(kBlocksPerLaunch, n_small - c0)), dim3(afw::kThreads), 0, st, a, (uint32_t)c0);
         HIP_TRY(hipGetLastError());
@@ -2844,8 +2925,8 @@ int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_wind
     return AF_OK;
 }
 
-// Quantile analyzer (af_quantiles.hpp).  The cells are laid out as the windowed analyzer's (n_windows > 0) or the pooled one's
-// (n_windows == 0: a cell per group) and compacted by those analyzers' own kernels; a cell then goes to the tier of its size.
+// Quantile analyzer (af_quantiles.hpp).  The cells are laid out and compacted as the windowed analyzer's (n_windows > 0) or the
+// pooled one's (n_windows == 0: a cell per group); a cell then goes to the tier of its size.
 int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) {
     if (!e || !out || !qr) return fail(AF_ERR_INVALID, "NULL argument");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
@@ -2862,11 +2943,8 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
         if (std::isnan(qr->thresholds[i])) return fail(AF_ERR_INVALID, "threshold " + std::to_string(i) + " is NaN");
     if (W > 0 && !qr->edges) return fail(AF_ERR_INVALID, "quantiles.edges is required with n_windows > 0");
     if (W == 0 && qr->edges) return fail(AF_ERR_INVALID, "quantiles.edges given with n_windows == 0 (whole-run mode takes none)");
-    for (uint32_t k = 0; W > 0 && k <= W; ++k) {
-        if (!std::isfinite(qr->edges[k])) return fail(AF_ERR_INVALID, "window edge " + std::to_string(k) + " is not finite");
-        if (k > 0 && !(qr->edges[k - 1] < qr->edges[k]))
-            return fail(AF_ERR_INVALID, "window edges must be strictly increasing (edge " + std::to_string(k) + ")");
-    }
+    if (W > 0)
+        if (int rc = check_window_edges(qr->edges, W)) return rc;
     if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
     if (!out->clock || cap == 0) return fail(AF_ERR_INVALID, "quantile summary needs outputs.clock");
     const uint32_t Wc = W ? W : 1u;
@@ -2874,79 +2952,27 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
     if (W && (uint64_t)n * ((uint64_t)W + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (n_windows + 1) must be below 2^32");
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(e->device));
-    const size_t C = (size_t)G * Wc, NE = W ? (size_t)n * (W + 1u) : 0u;
-    std::vector<uint32_t> grp(qr->group ? n : 0u);
-    if (qr->group) HIP_TRY(hipMemcpy(grp.data(), qr->group, grp.size() * 4u, hipMemcpyDeviceToHost));
-    for (uint32_t s = 0; s < n; ++s) {
-        const uint32_t g = qr->group ? grp[s] : 0u;
-        if (g != afp::kSkip && g >= G)
-            return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
-    }
+    const size_t C = (size_t)G * Wc;
+    std::vector<uint32_t> grp;
+    if (int rc = read_groups(qr->group, n, G, grp)) return rc;
     hipStream_t st = e->stream;
-    size_t at = 0;
-    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
-    // scratch, first part (windows: edges, the error word, the bounds)
-    const size_t o_edges = part(((size_t)W + 1u) * 8u), o_err = part(4u), o_bounds = part(NE * 4u);
-    std::vector<uint64_t> cell_off(C + 1u, 0u);   // (first the sizes, at [c + 1])
-    std::vector<uint32_t> pre, hb;
-    std::vector<uint64_t> dst;
-    afw::WinArgs wa{};
-    auto bind_first = [&]() {
-        unsigned char* b = e->d_pool;
-        wa.edges = reinterpret_cast<const double*>(b + o_edges);
-        wa.err = reinterpret_cast<uint32_t*>(b + o_err);
-        wa.bounds = reinterpret_cast<uint32_t*>(b + o_bounds);
-    };
-    if (W) {   // the cells as af_engine_summarize_windows lays them out
-        if (int rc = pool_reserve(e, at)) return rc;
-        wa.clock = out->clock;
-        wa.counts = out->counts;
-        wa.clock_cap = cap;
-        wa.cnt_completed_slot = AF_CNT_COMPLETED;
-        wa.group = qr->group;
-        wa.n_scen = n;
-        wa.n_win = W;
-        bind_first();
-        HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, qr->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, wa);
-        HIP_TRY(hipGetLastError());
-        hb.resize(NE);
-        HIP_TRY(hipMemcpyAsync(hb.data(), wa.bounds, NE * 4u, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        pre.resize((size_t)n * W);
-        for (uint32_t s = 0; s < n; ++s) {
-            const uint32_t g = qr->group ? grp[s] : 0u;
-            if (g == afp::kSkip) continue;
-            const uint32_t* r = hb.data() + (size_t)s * (W + 1u);
-            uint64_t* sz = cell_off.data() + 1u + (size_t)g * W;
-            uint32_t* ps = pre.data() + (size_t)s * W;
-            for (uint32_t w = 0; w < W; ++w) {
-                if (r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
-                    return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
-                if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
-                ps[w] = (uint32_t)sz[w];
-                sz[w] += r[w + 1u] - r[w];
-            }
-        }
-    } else {   // one cell per group, as af_engine_summarize_pooled lays its groups out
-        std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS);
-        HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
-        dst.assign(n, 0u);
-        for (uint32_t s = 0; s < n; ++s) {
-            const uint32_t g = qr->group ? grp[s] : 0u;
-            if (g == afp::kSkip) continue;
-            dst[s] = cell_off[1u + g];   // (for now: the latencies earlier members bring)
-            cell_off[1u + g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], cap);
-        }
+    ScratchLayout lay;
+    WindowCells wc;     // the cells with windows
+    PooledCells pc;     // ... and without
+    if (W) {
+        if (int rc = layout_window_cells(e, out, qr->group, grp, n, G, W, qr->edges, nullptr, lay, wc)) return rc;
+    } else {
+        if (int rc = layout_pooled_cells(out, grp, n, G, "holds", pc)) return rc;
+        lay.part(8u), lay.part(4u);   // (an edge and the error word, as with windows: the scratch of a request is as large as it was)
     }
+    const std::vector<uint64_t>& cell_off = W ? wc.cell_off : pc.cell_off;
+    const size_t o_lat = W ? wc.o_lat : lay.part(cell_off[C] * 8u), o_dst = W ? 0u : lay.part((size_t)n * 8u), o_off = W ? wc.o_off : lay.part((C + 1u) * 8u);
     // the tiers
     struct SmallCell { uint32_t pad, cell; };
     std::vector<SmallCell> small_by;
     std::vector<afq::QCell> lcells;
     for (size_t c = 0; c < C; ++c) {
-        const uint64_t len = cell_off[c + 1u];
-        if (len > 0xFFFFFFFFull)
-            return fail(AF_ERR_CAPACITY, (W ? "window " + std::to_string(c % W) + " of group " + std::to_string(c / W) : "group " + std::to_string(c)) + " holds 2^32 or more latencies");
+        const uint64_t len = cell_off[c + 1u] - cell_off[c];
         if (len > afq::kSmallMax) {
             lcells.push_back(afq::QCell{cell_off[c], (uint32_t)len, (uint32_t)c});
         } else if (len > afq::kTinyMax) {
@@ -2954,17 +2980,10 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
             while (pad < len) pad <<= 1;
             small_by.push_back(SmallCell{pad, (uint32_t)c});
         }
-        cell_off[c + 1u] = cell_off[c] + len;
     }
-    if (!W)
-        for (uint32_t s = 0; s < n; ++s) {
-            const uint32_t g = qr->group ? grp[s] : 0u;
-            if (g != afp::kSkip) dst[s] += cell_off[g];
-        }
     std::stable_sort(small_by.begin(), small_by.end(), [](const SmallCell& x, const SmallCell& y) { return x.pad < y.pad; });
     std::vector<uint32_t> small(small_by.size());
     for (size_t i = 0; i < small_by.size(); ++i) small[i] = small_by[i].cell;
-    const uint64_t total = cell_off[C];
     const uint32_t n_small = (uint32_t)small.size(), n_large = (uint32_t)lcells.size();
     const bool want_q = Q > 0 && qr->quantiles, want_w = T > 0 && qr->within;
     // large cells: their tiles, and a job per cell and kLv levels
@@ -2981,22 +3000,21 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
         }
     }
     const uint32_t n_jobs = (uint32_t)jobs.size(), n_ctiles = (uint32_t)ctiles.size();
-    // scratch, second part
-    const size_t o_lat = part(total * 8u), o_pre = part((size_t)n * W * 4u), o_dst = part(W ? 0u : (size_t)n * 8u), o_off = part((C + 1u) * 8u),
-                 o_small = part((size_t)n_small * 4u), o_lev = part((size_t)Q * 8u), o_thr = part((size_t)T * 8u),
-                 o_lcell = part((size_t)n_large * sizeof(afq::QCell)), o_ctile = part((size_t)n_ctiles * sizeof(afp::PoolTile)),
-                 o_job = part((size_t)n_jobs * sizeof(afq::QJob)), o_thist = part((size_t)n_large * T * 4u);
-    const PoolParts pp = n_jobs ? pool_parts(at, n_jobs, jtiles.size(), 1u) : PoolParts{};
-    if (at > e->pool_cap) {   // the scratch moves: its first part again
-        if (int rc = pool_reserve(e, at)) return rc;
-        if (W) {
-            bind_first();
-            HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, qr->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(wa.bounds, hb.data(), NE * 4u, hipMemcpyHostToDevice, st));
-        }
+    const size_t o_small = lay.part((size_t)n_small * 4u), o_lev = lay.part((size_t)Q * 8u), o_thr = lay.part((size_t)T * 8u),
+                 o_lcell = lay.part((size_t)n_large * sizeof(afq::QCell)), o_ctile = lay.part((size_t)n_ctiles * sizeof(afp::PoolTile)),
+                 o_job = lay.part((size_t)n_jobs * sizeof(afq::QJob)), o_thist = lay.part((size_t)n_large * T * 4u);
+    const PoolParts pp = n_jobs ? pool_parts(lay, n_jobs, jtiles.size(), 1u) : PoolParts{};
+    if (W) {
+        const int rc = compact_window_cells(e, lay, wc);
+        qr->scratch_bytes = e->pool_cap;
+        if (rc) return rc;
+    } else {
+        if (int rc = pool_reserve(e, lay.at)) return rc;
+        qr->scratch_bytes = e->pool_cap;
+        HIP_TRY(hipMemcpyAsync(e->d_pool + o_off, cell_off.data(), (C + 1u) * 8u, hipMemcpyHostToDevice, st));
+        if (int rc = compact_pooled_cells(e, out, qr->group, n, pc, o_dst, o_lat)) return rc;
     }
     unsigned char* b = e->d_pool;
-    qr->scratch_bytes = e->pool_cap;
     afq::QArgs qa{};
     qa.lat = reinterpret_cast<double*>(b + o_lat);
     qa.cell_off = reinterpret_cast<const uint64_t*>(b + o_off);
@@ -3012,47 +3030,14 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
     qa.ctiles = reinterpret_cast<const afp::PoolTile*>(b + o_ctile);
     qa.jobs = reinterpret_cast<const afq::QJob*>(b + o_job);
     qa.thist = reinterpret_cast<uint32_t*>(b + o_thist);
-    HIP_TRY(hipMemcpyAsync(b + o_off, cell_off.data(), (C + 1u) * 8u, hipMemcpyHostToDevice, st));
-    if (W) {
-        wa.lat = reinterpret_cast<double*>(b + o_lat);
-        wa.pre = reinterpret_cast<const uint32_t*>(b + o_pre);
-        wa.cell_off = qa.cell_off;
-        const uint32_t no_error = afw::kNoError;
-        HIP_TRY(hipMemcpyAsync(b + o_pre, pre.data(), (size_t)n * W * 4u, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(wa.err, &no_error, 4u, hipMemcpyHostToDevice, st));
-        if (W <= afw::kLdsWindows)
-            hipLaunchKernelGGL(afw::af_win_compact<true>, dim3(n), dim3(afw::kThreads), (size_t)W * 8u + ((size_t)W + 1u) * 4u, st, wa);
-        else
-            hipLaunchKernelGGL(afw::af_win_compact<false>, dim3(n), dim3(afw::kThreads), 0, st, wa);
-        HIP_TRY(hipGetLastError());
-        uint32_t bad = afw::kNoError;
-        HIP_TRY(hipMemcpyAsync(&bad, wa.err, 4u, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        if (bad != afw::kNoError)
-            return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(bad) + " is not in completion order (finish decreases): windows by finish time need it");
-    } else {
-        afp::PoolArgs ca{};
-        ca.clock = out->clock;
-        ca.counts = out->counts;
-        ca.clock_cap = cap;
-        ca.cnt_completed_slot = AF_CNT_COMPLETED;
-        ca.group = qr->group;
-        ca.dst = reinterpret_cast<const uint64_t*>(b + o_dst);
-        ca.lat = reinterpret_cast<double*>(b + o_lat);
-        HIP_TRY(hipMemcpyAsync(b + o_dst, dst.data(), (size_t)n * 8u, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(afp::af_pool_compact, dim3(n), dim3(afp::kThreads), 0, st, ca);
-        HIP_TRY(hipGetLastError());
-    }
     if (Q) HIP_TRY(hipMemcpyAsync(b + o_lev, qr->levels, (size_t)Q * 8u, hipMemcpyHostToDevice, st));
     if (T) HIP_TRY(hipMemcpyAsync(b + o_thr, qr->thresholds, (size_t)T * 8u, hipMemcpyHostToDevice, st));
     if (n_small) HIP_TRY(hipMemcpyAsync(b + o_small, small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
-    constexpr uint64_t kBlocksPerLaunch = 1u << 21;   // (at most 2^30 threads a launch)
     if (qr->count || want_q || want_w) {
-        for (uint64_t c0 = 0; c0 < C; c0 += kBlocksPerLaunch * afq::kTinyWaves) {   // every cell: a wave takes it if it is tiny (or empty)
-            const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (C - c0 + afq::kTinyWaves - 1u) / afq::kTinyWaves);
-            hipLaunchKernelGGL(afq::af_q_tiny, dim3((uint32_t)blocks), dim3(afq::kTinyWaves * 64), 0, st, qa, c0, (uint64_t)C);
-            HIP_TRY(hipGetLastError());
-        }
+        if (int rc = launch_tiny_tier(C, afq::kTinyWaves, [&](uint32_t blocks, uint64_t c0) {
+                hipLaunchKernelGGL(afq::af_q_tiny, dim3(blocks), dim3(afq::kTinyWaves * 64), 0, st, qa, c0, (uint64_t)C);
+            }))
+            return rc;
         for (size_t i0 = 0; i0 < small_by.size();) {   // the small cells, one padded size after the other
             size_t i1 = i0;
             while (i1 < small_by.size() && small_by[i1].pad == small_by[i0].pad && i1 - i0 < kBlocksPerLaunch) ++i1;
@@ -3080,19 +3065,8 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
         }
         if (n_jobs) {
             const uint32_t n_jtiles = (uint32_t)jtiles.size();
-            for (int level = 0;; ++level) {   // (shift 52 -> 42 -> ... -> 2 -> 0: at most six digit levels)
-                HIP_TRY(hipMemsetAsync(pa.any_more, 0, 4u, st));
-                hipLaunchKernelGGL(afq::af_q_select, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa, level);
-                HIP_TRY(hipGetLastError());
-                uint32_t more = 0;
-                HIP_TRY(hipMemcpyAsync(&more, pa.any_more, 4u, hipMemcpyDeviceToHost, st));
-                HIP_TRY(hipStreamSynchronize(st));
-                if (!more) break;
-                if (level >= 6) return fail(AF_ERR_HIP, "quantile analyzer: radix select did not converge");
-                HIP_TRY(hipMemsetAsync(pa.dhist, 0, (size_t)n_jobs * afp::kRanks * afp::kDigBins * 4u, st));
-                hipLaunchKernelGGL(afp::af_pool_digits, dim3(n_jtiles), dim3(afp::kThreads), 0, st, pa);
-                HIP_TRY(hipGetLastError());
-            }
+            if (int rc = radix_levels(st, pa, n_jobs, n_jtiles, "quantile", [&](int level) { hipLaunchKernelGGL(afq::af_q_select, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa, level); }))
+                return rc;
             HIP_TRY(hipMemsetAsync(pa.cand_n, 0, (size_t)n_jobs * afp::kRanks * 4u, st));
             hipLaunchKernelGGL(afq::af_q_cand, dim3(n_jtiles), dim3(afq::kThreads), 0, st, pa);
             HIP_TRY(hipGetLastError());
@@ -3171,12 +3145,11 @@ int af_engine_summarize_series_windows(af_engine_t* e, const af_outputs_t* out, 
         }
     }
     // scratch layout (256-byte aligned parts)
-    size_t at = 0;
-    auto part = [&](size_t bytes) { const size_t o = at; at += (bytes + 255u) & ~(size_t)255u; return o; };
+    ScratchLayout lay;
     const size_t R = direct ? 0u : (size_t)n * W * S;
-    const size_t o_edges = part(((size_t)W + 1u) * 4u), o_thr = part((size_t)S * 8u), o_off = part(((size_t)G + 1u) * 4u),
-                 o_mem = part(members.size() * 4u), o_sum = part(R * 8u), o_min = part(R * 4u), o_max = part(R * 4u), o_above = part(R * 4u);
-    if (int rc = pool_reserve(e, at)) return rc;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u), o_thr = lay.part((size_t)S * 8u), o_off = lay.part(((size_t)G + 1u) * 4u),
+                 o_mem = lay.part(members.size() * 4u), o_sum = lay.part(R * 8u), o_min = lay.part(R * 4u), o_max = lay.part(R * 4u), o_above = lay.part(R * 4u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
     unsigned char* b = e->d_pool;
     hipStream_t st = e->stream;
     std::vector<double> thr(S, 0.0);
@@ -3219,7 +3192,6 @@ int af_engine_summarize_series_windows(af_engine_t* e, const af_outputs_t* out, 
     HIP_TRY(hipGetLastError());
     if (!direct || mem_off[G] < G) {   // the members' fold; after a direct pass only the cells of groups without a member
         const uint64_t entries = (uint64_t)G * W * S;
-        constexpr uint64_t kBlocksPerLaunch = 1u << 21;   // (at most 2^29 threads a launch)
         for (uint64_t f = 0; f < entries; f += kBlocksPerLaunch * afsw::kReduceThreads) {
             const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (entries - f + afsw::kReduceThreads - 1u) / afsw::kReduceThreads);
             hipLaunchKernelGGL(afsw::af_swin_reduce, dim3((uint32_t)blocks), dim3(afsw::kReduceThreads), 0, st, a, f, entries);

@@ -114,6 +114,17 @@ def test_one_group_of_twenty_thousand_tiny_members_and_odd_values():
     assert np.isnan(stats[:, 1:]).all() and (stats[:, 0] == 0).all()
 
 
+def test_candidates_that_part_in_the_last_key_bits_and_a_constant_group():
+    """0.05 + k ulp, k < 4096: every key shares its upper 52 bits, so the select takes five digit levels and stops at
+    shift 2 with a handful of distinct candidates per rank -- no tie runs it down to shift 0, as the constant group does."""
+    rng = np.random.default_rng(31)
+    n = 9000
+    for name, lat in (("last bits", 0.05 + rng.integers(0, 4096, n) * np.spacing(0.05)), ("constant", np.full(n, 0.0625))):
+        stored, stats = _pooled_synthetic([lat], [0], 1)
+        assert stored[0].size == n and (name == "constant" or np.unique(stored[0]).size > 3000)
+        _check(stats[0], _np_stats(stored[0]), name)
+
+
 def test_counts_above_the_clock_capacity_clamp():
     rng = np.random.default_rng(9)
     lats = [rng.exponential(0.03, 1000), rng.exponential(0.03, 700), rng.exponential(0.03, 50)]

@@ -174,6 +174,25 @@ def test_cell_sizes_around_the_block_boundaries_and_odd_values():
             _check(stats[g, w], want[g, w], f"odd values, group {g}, window {w}")
 
 
+def test_candidates_that_part_in_the_last_key_bits_and_a_constant_cell():
+    """0.05 + k ulp, k < 4096: every key shares its upper 52 bits, so the select takes five digit levels and stops at
+    shift 2 with a handful of distinct candidates per rank -- no tie runs it down to shift 0, as the constant cell beside it
+    does.  600 latencies: one workgroup's cell (af_win_small); 9 000: the tiled passes."""
+    rng = np.random.default_rng(31)
+    edges = np.array([0.0, 1.0])
+    sizes = (600, 9000)
+    for name, make in (("last bits", lambda n: 0.05 + rng.integers(0, 4096, n) * np.spacing(0.05)), ("constant", lambda n: np.full(n, 0.0625))):
+        clocks = []
+        for n in sizes:
+            lat = np.sort(make(n))                     # finish = latency, start = 0: exact, and in completion order
+            clocks.append(np.stack([np.zeros(n), lat], axis=1))
+        stored, stats, _, _ = _windows_synthetic(clocks, np.arange(len(sizes)), len(sizes), edges, bounds=False)
+        for s, n in enumerate(sizes):
+            lat = stored[s][:, 1] - stored[s][:, 0]
+            assert lat.size == n and (name == "constant" or np.unique(lat).size > 400)
+            _check(stats[s, 0], _np_stats(lat), f"{name}, {n} latencies")
+
+
 def test_counts_above_the_clock_capacity_and_more_windows_than_fit_the_lds():
     rng = np.random.default_rng(9)
     edges = np.array([0.0, 10.0, 20.0, 30.0])

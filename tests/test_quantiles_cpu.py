@@ -82,8 +82,9 @@ def test_af_quantiles_layout_matches_the_header(tmp_path):
 def test_the_new_header_is_a_source_of_both_builds():
     from asyncflow_amd import jit
 
-    assert "af_quantiles.hpp" in af_build.SOURCES and "af_quantiles.hpp" in jit._SOURCES  # noqa: SLF001
-    assert (ROOT / "asyncflow_amd" / "csrc" / "af_quantiles.hpp").exists()
+    for header in ("af_quantiles.hpp", "af_select.hpp"):
+        assert header in af_build.SOURCES and header in jit._SOURCES  # noqa: SLF001
+        assert (ROOT / "asyncflow_amd" / "csrc" / header).exists()
 
 
 def test_quantiles_entry_refuses_bad_requests_without_a_device(lib):
