@@ -313,6 +313,30 @@ class AfQuantiles(C.Structure):
     ]
 
 
+MAX_SERIES_QUANTILE_LEVELS = 16   # AF_MAX_SERIES_QUANTILE_LEVELS
+
+
+class AfSeriesQuantiles(C.Structure):
+    """``af_series_quantiles_t``: request of ``af_engine_summarize_series_quantiles`` (``elapsed_ms`` and ``scratch_bytes``
+    are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("n_levels", C.c_uint32),
+        ("levels", C.POINTER(C.c_double)),
+        ("n_columns", C.c_uint32),
+        ("columns", C.POINTER(C.c_uint32)),
+        ("count", C.c_void_p),
+        ("quantiles", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 #: every symbol include/asyncflow_hip.h declares
 EXPORTED_SYMBOLS = (
     "af_engine_create",
@@ -321,6 +345,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_pooled",
     "af_engine_summarize_windows",
     "af_engine_summarize_series_windows",
+    "af_engine_summarize_series_quantiles",
     "af_engine_summarize_quantiles",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
@@ -360,6 +385,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_windows.restype = C.c_int
     lib.af_engine_summarize_series_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesWindows)]
     lib.af_engine_summarize_series_windows.restype = C.c_int
+    lib.af_engine_summarize_series_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesQuantiles)]
+    lib.af_engine_summarize_series_quantiles.restype = C.c_int
     lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]

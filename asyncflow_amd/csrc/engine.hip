@@ -15,6 +15,9 @@
 //   af_summary_kernel / af_series_kernel   af_engine_summarize: the analyzer (af_summary.hpp)
 //   af_swin_partial / af_swin_reduce       af_engine_summarize_series_windows: the sampled series per (group, window of
 //                                          ticks) (af_series_windows.hpp)
+//   af_sq_small / af_sq_rows / af_sq_select / af_sq_final
+//                                          af_engine_summarize_series_quantiles: exact quantiles of the sampled series per
+//                                          (group, window of ticks, series) (af_series_quantiles.hpp)
 //
 // Memory plan
 //   LDS  : flow kernel: [plan blob, patched per scenario][station lists, select scratch / server segments, rings,
@@ -44,6 +47,7 @@
 #include "af_summary.hpp"
 #include "af_pooled.hpp"
 #include "af_series_windows.hpp"
+#include "af_series_quantiles.hpp"
 #include "af_windowed.hpp"
 #include "af_quantiles.hpp"
 
@@ -3200,6 +3204,221 @@ int af_engine_summarize_series_windows(af_engine_t* e, const af_outputs_t* out, 
     }
     HIP_TRY(hipStreamSynchronize(st));
     req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Quantiles of the sampled series per (group, window of ticks, series) (af_series_quantiles.hpp).  The host reads the group ids
+// and the counts back, checks them, sizes every cell and sends it to its tier: the small cells in one launch sequence, the
+// large ones a chunk at a time -- as many cells as the histogram budget holds, at least one.
+constexpr size_t kSeriesQuantileHistBudget = (size_t)128u << 20;
+static_assert(afsq::kMaxRanks == 2u * AF_MAX_SERIES_QUANTILE_LEVELS, "two ranks per level");
+
+int af_engine_summarize_series_quantiles(af_engine_t* e, const af_outputs_t* out, af_series_quantiles_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty series quantiles request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "series_quantiles.tick_edges is required");
+    if (!req->quantiles) return fail(AF_ERR_INVALID, "series_quantiles.quantiles is required");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, cap = out->tick_capacity, Q = req->n_levels;
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch;
+    if (Q == 0 || Q > AF_MAX_SERIES_QUANTILE_LEVELS)
+        return fail(AF_ERR_INVALID, "series_quantiles.n_levels must be 1 .. AF_MAX_SERIES_QUANTILE_LEVELS (" + std::to_string(AF_MAX_SERIES_QUANTILE_LEVELS) + ")");
+    if (!req->levels) return fail(AF_ERR_INVALID, "series_quantiles.levels is required");
+    for (uint32_t i = 0; i < Q; ++i)
+        if (!(req->levels[i] >= 0.0 && req->levels[i] <= 1.0)) return fail(AF_ERR_INVALID, "quantile level " + std::to_string(i) + " is not in [0, 1]");
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    if ((req->n_columns == 0) != (req->columns == nullptr)) return fail(AF_ERR_INVALID, "series_quantiles.columns and n_columns must be given together");
+    for (uint32_t c = 0; c < req->n_columns; ++c)
+        if (req->columns[c] >= S) return fail(AF_ERR_INVALID, "column " + std::to_string(c) + " names series " + std::to_string(req->columns[c]) + " of " + std::to_string(S));
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->samples || cap == 0) return fail(AF_ERR_INVALID, "series quantiles need outputs.samples");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    if (S == 0 || pitch < S || pitch % 4u) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp(req->group ? n : 0u);
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    if (req->group) HIP_TRY(hipMemcpy(grp.data(), req->group, grp.size() * 4u, hipMemcpyDeviceToHost));
+    // the groups' members, ascending
+    std::vector<uint32_t> mem_off((size_t)G + 1u, 0u), members;
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = req->group ? grp[s] : 0u;
+        if (g == afsq::kNone) continue;
+        if (g >= G) return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(g) + ", n_groups " + std::to_string(G) + ")");
+        mem_off[(size_t)g + 1u] += 1u;
+    }
+    for (uint32_t g = 0; g < G; ++g) mem_off[(size_t)g + 1u] += mem_off[g];
+    members.resize(std::max<size_t>(mem_off[G], 1u));
+    {
+        std::vector<uint32_t> cursor(mem_off.begin(), mem_off.end() - 1);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = req->group ? grp[s] : 0u;
+            if (g != afsq::kNone) members[cursor[g]++] = s;
+        }
+    }
+    // every cell's size, its tier
+    const size_t C = (size_t)G * W;
+    std::vector<uint32_t> small_cells, lcell, lcell_n, cell_lidx;   // (small_cells: cell, size)
+    uint32_t small_max = 0;
+    {
+        std::vector<uint64_t> row(W);
+        for (uint32_t g = 0; g < G; ++g) {
+            std::fill(row.begin(), row.end(), 0u);
+            for (uint32_t k = mem_off[g]; k < mem_off[(size_t)g + 1u]; ++k) {
+                const uint32_t m = std::min(counts[(size_t)members[k] * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+                for (uint32_t w = 0; w < W && req->tick_edges[w] < m; ++w) row[w] += std::min(req->tick_edges[w + 1u], m) - req->tick_edges[w];
+            }
+            for (uint32_t w = 0; w < W; ++w) {
+                if (row[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more samples");
+                const uint32_t cell = (uint32_t)((size_t)g * W + w);
+                if (row[w] <= afsq::kSmallMax) {
+                    small_cells.push_back(cell);
+                    small_cells.push_back((uint32_t)row[w]);
+                    small_max = std::max(small_max, (uint32_t)row[w]);
+                } else {
+                    if (cell_lidx.empty()) cell_lidx.assign(C, afsq::kNone);
+                    cell_lidx[cell] = (uint32_t)lcell.size();
+                    lcell.push_back(cell);
+                    lcell_n.push_back((uint32_t)row[w]);
+                }
+            }
+        }
+    }
+    // the selected series: distinct ones ascending, and per series the chain of its output columns
+    const uint32_t Co = req->n_columns ? req->n_columns : S;
+    std::vector<uint32_t> u_of(pitch, afsq::kNone), u_series, head, next(Co, afsq::kNone), sel_groups;
+    for (uint32_t c = 0; c < Co; ++c) u_of[req->columns ? req->columns[c] : c] = 0u;
+    for (uint32_t j = 0; j < S; ++j)
+        if (u_of[j] != afsq::kNone) {
+            u_of[j] = (uint32_t)u_series.size();
+            u_series.push_back(j);
+            if (sel_groups.empty() || sel_groups.back() != j / 4u) sel_groups.push_back(j / 4u);
+        }
+    const uint32_t U = (uint32_t)u_series.size(), R = 2u * Q;
+    head.assign(U, afsq::kNone);
+    for (uint32_t c = Co; c-- > 0u;) {   // (back to front: a chain runs in ascending column order)
+        const uint32_t u = u_of[req->columns ? req->columns[c] : c];
+        next[c] = head[u];
+        head[u] = c;
+    }
+    uint32_t lds_slots = 0;
+    for (uint32_t cg : sel_groups) {
+        uint32_t k = 0;
+        for (uint32_t j = cg * 4u; j < cg * 4u + 4u && j < S; ++j) k += u_of[j] != afsq::kNone ? 1u : 0u;
+        lds_slots = std::max(lds_slots, k);
+    }
+    const uint32_t n_small = (uint32_t)(small_cells.size() / 2u), n_large = (uint32_t)lcell.size(), n_sg = (uint32_t)sel_groups.size();
+    const size_t pair_bytes = (size_t)R * (afsq::kBins * 4u + 16u) + 12u;
+    const uint32_t chunk = n_large ? (uint32_t)std::min<size_t>(n_large, std::max<size_t>(1u, kSeriesQuantileHistBudget / (pair_bytes * U))) : 0u;
+    const size_t P = (size_t)chunk * U;   // the (cell, column) pairs of a chunk
+    if (P > 0xFFFFFFFFull / R) return fail(AF_ERR_CAPACITY, "too many selected series for one large cell");
+    // scratch layout (256-byte aligned parts)
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u), o_lev = lay.part((size_t)Q * 8u), o_off = lay.part(((size_t)G + 1u) * 4u),
+                 o_mem = lay.part(members.size() * 4u), o_uof = lay.part((size_t)pitch * 4u), o_user = lay.part((size_t)U * 4u),
+                 o_head = lay.part((size_t)U * 4u), o_next = lay.part((size_t)Co * 4u), o_sg = lay.part((size_t)n_sg * 4u),
+                 o_small = lay.part((size_t)n_small * 8u), o_lidx = lay.part(n_large ? C * 4u : 0u), o_lcell = lay.part((size_t)n_large * 4u),
+                 o_ln = lay.part((size_t)n_large * 4u), o_bmin = lay.part(P * 4u), o_bmax = lay.part(P * 4u), o_ns = lay.part(P * 4u),
+                 o_pfx = lay.part(P * R * 4u), o_rank = lay.part(P * R * 4u), o_slot = lay.part(P * R * 4u), o_spfx = lay.part(P * R * 4u),
+                 o_hist = lay.part(P * R * afsq::kBins * 4u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    req->scratch_bytes = e->pool_cap;
+    unsigned char* b = e->d_pool;
+    hipStream_t st = e->stream;
+    const auto up = [&](size_t o, const void* src, size_t bytes) { return bytes ? hipMemcpyAsync(b + o, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess; };
+    HIP_TRY(up(o_edges, req->tick_edges, ((size_t)W + 1u) * 4u));
+    HIP_TRY(up(o_lev, req->levels, (size_t)Q * 8u));
+    HIP_TRY(up(o_off, mem_off.data(), mem_off.size() * 4u));
+    HIP_TRY(up(o_mem, members.data(), members.size() * 4u));
+    HIP_TRY(up(o_uof, u_of.data(), (size_t)pitch * 4u));
+    HIP_TRY(up(o_user, u_series.data(), (size_t)U * 4u));
+    HIP_TRY(up(o_head, head.data(), (size_t)U * 4u));
+    HIP_TRY(up(o_next, next.data(), (size_t)Co * 4u));
+    HIP_TRY(up(o_sg, sel_groups.data(), (size_t)n_sg * 4u));
+    HIP_TRY(up(o_small, small_cells.data(), (size_t)n_small * 8u));
+    HIP_TRY(up(o_lidx, cell_lidx.data(), cell_lidx.size() * 4u));
+    HIP_TRY(up(o_lcell, lcell.data(), (size_t)n_large * 4u));
+    HIP_TRY(up(o_ln, lcell_n.data(), (size_t)n_large * 4u));
+    const auto u32p = [&](size_t o) { return reinterpret_cast<uint32_t*>(b + o); };
+    afsq::SqArgs a{};
+    a.samples = out->samples;
+    a.counts = out->counts;
+    a.tick_cap = cap;
+    a.pitch = pitch;
+    a.n_series = S;
+    a.n_edges = e->args.n_edges;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.group = req->group;
+    a.n_scen = n;
+    a.n_groups = G;
+    a.n_win = W;
+    a.edges = u32p(o_edges);
+    a.mem_off = u32p(o_off);
+    a.members = u32p(o_mem);
+    a.n_lev = Q;
+    a.n_out = Co;
+    a.n_uniq = U;
+    a.n_ranks = R;
+    a.levels = reinterpret_cast<const double*>(b + o_lev);
+    a.u_of = u32p(o_uof);
+    a.u_series = u32p(o_user);
+    a.head = u32p(o_head);
+    a.next = u32p(o_next);
+    a.small_cells = u32p(o_small);
+    a.sel_groups = u32p(o_sg);
+    a.n_sg = n_sg;
+    a.lds_stride = pow2_at_least(std::max(small_max, 1u));
+    a.cell_lidx = u32p(o_lidx);
+    a.lcell = u32p(o_lcell);
+    a.lcell_n = u32p(o_ln);
+    a.bmin = u32p(o_bmin);
+    a.bmax = u32p(o_bmax);
+    a.n_slots = u32p(o_ns);
+    a.pfx = u32p(o_pfx);
+    a.rank_in = u32p(o_rank);
+    a.slot_of = u32p(o_slot);
+    a.slot_pfx = u32p(o_spfx);
+    a.hist = u32p(o_hist);
+    a.count = req->count;
+    a.quant = req->quantiles;
+    // a wave per (scenario, run of windows): runs as long as leave the chip some 32 768 waves
+    const uint32_t want_runs = (32768u + n - 1u) / n;
+    a.run = std::max(1u, W / want_runs);
+    const uint64_t items = (uint64_t)n * ((W + a.run - 1u) / a.run);
+    const dim3 row_grid((uint32_t)((items + afsq::kWaves - 1u) / afsq::kWaves));
+    const uint64_t small_items = (uint64_t)n_small * n_sg;
+    const size_t small_lds = (size_t)lds_slots * a.lds_stride * 4u;
+    for (uint64_t i0 = 0; i0 < small_items; i0 += kBlocksPerLaunch) {
+        hipLaunchKernelGGL(afsq::af_sq_small, dim3((uint32_t)std::min<uint64_t>(kBlocksPerLaunch, small_items - i0)), dim3(afsq::kThreads), small_lds, st, a, i0);
+        HIP_TRY(hipGetLastError());
+    }
+    for (uint32_t l0 = 0; l0 < n_large; l0 += chunk) {
+        a.l0 = l0;
+        a.l1 = std::min(n_large, l0 + chunk);
+        const size_t pairs = (size_t)(a.l1 - a.l0) * U;
+        HIP_TRY(hipMemsetAsync(a.bmin, 0xFF, pairs * 4u, st));
+        HIP_TRY(hipMemsetAsync(a.bmax, 0, pairs * 4u, st));
+        hipLaunchKernelGGL(afsq::af_sq_rows<0>, row_grid, dim3(afsq::kThreads), 0, st, a, 0);
+        HIP_TRY(hipGetLastError());
+        // level 0 counts into slot 0 of every pair: only those are cleared here; af_sq_select clears the slots of the next level
+        HIP_TRY(hipMemset2DAsync(a.hist, (size_t)R * afsq::kBins * 4u, 0, afsq::kBins * 4u, pairs, st));
+        for (int level = 0; level * afsq::kBits < 32; ++level) {   // (a column whose key is complete takes no part)
+            if (level == 0) hipLaunchKernelGGL(afsq::af_sq_rows<1>, row_grid, dim3(afsq::kThreads), 0, st, a, level);
+            else hipLaunchKernelGGL(afsq::af_sq_rows<2>, row_grid, dim3(afsq::kThreads), 0, st, a, level);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(afsq::af_sq_select, dim3((uint32_t)pairs), dim3(afsq::kThreads), 0, st, a, level);
+            HIP_TRY(hipGetLastError());
+        }
+        const uint64_t entries = (uint64_t)pairs * Q;
+        hipLaunchKernelGGL(afsq::af_sq_final, dim3((uint32_t)((entries + afsq::kThreads - 1u) / afsq::kThreads)), dim3(afsq::kThreads), 0, st, a, entries);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }

@@ -360,6 +360,29 @@ class Engine:
                "af_engine_summarize_series_windows")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_series_quantiles(self, n: int, n_groups: int, tick_edges: Any, levels: Any, *, samples_ptr: int,
+                                   tick_capacity: int, counts_ptr: int, quantiles_ptr: int, count_ptr: int = 0,
+                                   group_ptr: int = 0, columns: Any = None) -> tuple[float, int]:
+        """Series-quantile analyzer on the device (``af_engine_summarize_series_quantiles``): per (group, window of ticks)
+        ``count`` uint32 [n_groups, W] (0 skips it) and ``quantiles`` f64 [n_groups, W, C, Q], W = len(tick_edges) - 1.
+        ``tick_edges``: HOST uint32 tick indices, strictly increasing; ``levels``: HOST float64 in [0, 1], 1 to 16 of them;
+        ``columns``: series indices (any order, duplicates allowed) or None: every series, C = n_series.  ``group_ptr`` as
+        in :meth:`summarize_pooled`.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import _check_series_columns, check_series_levels, check_tick_edges
+
+        b = check_tick_edges(tick_edges)
+        q = np.ascontiguousarray(check_series_levels(levels))
+        col = None if columns is None else np.ascontiguousarray(_check_series_columns(columns, self.plan.n_series), dtype=np.uint32)
+        out = _abi.AfOutputs(0, None, int(tick_capacity), C.c_void_p(samples_ptr or None), C.c_void_p(counts_ptr or None))
+        req = _abi.AfSeriesQuantiles(int(n), int(n_groups), int(b.shape[0] - 1), C.c_void_p(group_ptr or None),
+                                     b.ctypes.data_as(C.POINTER(C.c_uint32)), int(q.shape[0]), q.ctypes.data_as(C.POINTER(C.c_double)),
+                                     0 if col is None else int(col.shape[0]),
+                                     col.ctypes.data_as(C.POINTER(C.c_uint32)) if col is not None else None,
+                                     C.c_void_p(count_ptr or None), C.c_void_p(quantiles_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_series_quantiles(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_series_quantiles")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:
         """``af_engine_gather``: ONE grouped RCCL all-gather of the per-scenario summaries.

@@ -283,6 +283,82 @@ def series_window_stats(samples: np.ndarray, tick_edges: Any, n_edges: int, thre
     return {"count": count, "mean": mean, "min": mn, "max": mx, "above": above}
 
 
+def check_series_levels(levels: Any) -> np.ndarray:
+    """``levels`` of a series-quantile call as a float64 vector, or ValueError: one dimension, 1 to
+    ``AF_MAX_SERIES_QUANTILE_LEVELS`` (16) of them, each in [0, 1]."""
+    q = np.array(levels, dtype=np.float64)
+    if q.ndim != 1 or q.shape[0] == 0:
+        msg = f"series quantile levels must be a vector of at least one level, not of shape {q.shape}"
+        raise ValueError(msg)
+    if q.shape[0] > _abi.MAX_SERIES_QUANTILE_LEVELS:
+        msg = f"at most {_abi.MAX_SERIES_QUANTILE_LEVELS} series quantile levels a call, not {q.shape[0]}"
+        raise ValueError(msg)
+    if not ((q >= 0.0) & (q <= 1.0)).all():
+        msg = "quantile levels must lie in [0, 1]"
+        raise ValueError(msg)
+    return q
+
+
+def _check_series_columns(columns: Any, n_series: int) -> np.ndarray:
+    """``columns`` (None: every series) as series indices, or ValueError: one dimension, at least one, each < n_series."""
+    if columns is None:
+        return np.arange(n_series, dtype=np.int64)
+    raw = np.asarray(columns)
+    if raw.ndim != 1 or raw.shape[0] == 0 or raw.dtype.kind not in "iu":
+        msg = f"series columns must be a non-empty vector of series indices, not {columns!r}"
+        raise ValueError(msg)
+    col = raw.astype(np.int64)
+    if (col < 0).any() or (col >= n_series).any():
+        msg = f"series columns must lie in [0, {n_series})"
+        raise ValueError(msg)
+    return col
+
+
+def series_window_quantiles(samples: np.ndarray, tick_edges: Any, n_edges: int, levels: Any,
+                            columns: Any = None) -> tuple[np.ndarray, np.ndarray]:
+    """Exact quantiles per window of ticks of ONE scenario's sampled series ``samples`` (uint32 words [n_series, ticks]):
+    ``(count`` int64 [W], ``quantiles`` float64 [W, C, Q]``)``, the windows :func:`series_window_stats`'s.  Every word has
+    a 32-bit key: of an integer series the word itself; of a ``ram_in_use`` column the float32 bits ``w`` mapped to ``~w``
+    where the sign bit is set, else ``w | 0x80000000`` -- the IEEE total order on non-NaN floats, -0.0 below +0.0.  A
+    window's column is sorted BY KEY; ``x[0 .. n-1]`` are the values in that order as float64 (the word, or the float32
+    value).  For a level ``q``: ``v = (n - 1) * q``, ``lo = floor(v)``, ``hi = min(lo + 1, n - 1)``, ``t = v - lo``,
+    ``d = x[hi] - x[lo]``, and ``x[hi] - d * (1 - t)`` where ``t >= 0.5``, else ``x[lo] + d * t``: ``np.quantile(values,
+    levels)`` bit for bit where the window holds no zero, equal under ``==`` everywhere.  An empty window: count 0, NaN.
+    Output column ``c`` belongs to ``columns[c]`` (series indices in any order, duplicates allowed; None: every series).
+    The definition the device analyzer (``af_engine_summarize_series_quantiles``) is bit-equal to."""
+    b = check_tick_edges(tick_edges)
+    q = check_series_levels(levels)
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    n_series, ticks = words.shape
+    col = _check_series_columns(columns, n_series)
+    ram = ram_columns(n_series, n_edges)[col]
+    n_win = b.shape[0] - 1
+    r = np.minimum(b.astype(np.int64), ticks)
+    count = np.diff(r)
+    quant = np.full((n_win, col.shape[0], q.shape[0]), np.nan)
+    for w in range(n_win):
+        n = int(count[w])
+        if n == 0:
+            continue
+        seg = words[col, r[w]:r[w + 1]]
+        key = np.sort(np.where(ram[:, None], np.where(seg >> 31 != 0, ~seg, seg | np.uint32(0x80000000)), seg), axis=1)
+        back = np.where(key >> 31 != 0, key & np.uint32(0x7FFFFFFF), ~key)
+        with np.errstate(invalid="ignore"):   # (an integer word read as float32 may be a NaN: not taken)
+            x = np.where(ram[:, None], back.view(np.float32).astype(np.float64), key.astype(np.float64))
+        v = np.float64(n - 1) * q
+        f = np.floor(v)
+        lo = f.astype(np.int64)
+        hi = np.minimum(lo + 1, n - 1)
+        t = v - f
+        lo_v, hi_v = x[:, lo], x[:, hi]
+        d = hi_v - lo_v
+        quant[w] = np.where(t >= 0.5, hi_v - d * (1.0 - t), lo_v + d * t)
+    return count, quant
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -438,6 +514,20 @@ class ScenarioResults:
             raise RuntimeError(msg)
         b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
         return series_window_stats(self._samples, b, self._plan.n_edges, thresholds)
+
+    def get_series_window_quantiles(self, levels: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                                    tick_edges: Any = None, series: Any = None) -> dict[str, Any]:
+        """Exact quantiles ``levels`` (in [0, 1], at most 16) of the sampled series per window of ticks
+        (:func:`series_window_quantiles`): ``count`` [W], ``quantiles`` float64 [W, C, Q] (NaN in an empty window),
+        ``levels``, ``series`` (the indices of the C selected series) and ``tick_edges``.  Windows as in
+        :meth:`get_series_window_stats`; ``series``: None (every series) or series indices, any order."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        col = _check_series_columns(series, int(np.asarray(self._samples).shape[0]))
+        count, quant = series_window_quantiles(self._samples, b, self._plan.n_edges, levels, col)
+        return {"count": count, "quantiles": quant, "levels": check_series_levels(levels), "series": col, "tick_edges": b}
 
     def get_sampled_metrics(self) -> dict[str, dict[str, list[float]]]:
         self.process_all_metrics()
@@ -1112,6 +1202,116 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    def _require_samples(self) -> None:
+        if self._samples_t is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+
+    def _series_columns(self, series: Any) -> np.ndarray:
+        """``series`` (None, names of :meth:`series_names` or indices) as series indices."""
+        names = self.series_names()
+        if series is None:
+            return np.arange(len(names), dtype=np.int64)
+        if isinstance(series, (str, bytes)):
+            series = [series]
+        items = list(series)
+        if any(isinstance(x, str) for x in items):
+            for x in items:
+                if x not in names:
+                    msg = f"unknown series {x!r} (series_names(): {names})"
+                    raise ValueError(msg)
+            items = [names.index(x) for x in items]
+        return _check_series_columns(np.asarray(items), len(names))
+
+    def series_quantile_summary(self, levels: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                                tick_edges: Any = None, by: Any = None, series: Any = None) -> dict[str, Any]:
+        """Exact quantiles of the sampled series of every (group, window of ticks, series), over all scenarios of the
+        group: how much RAM covers 99 % of the ticks during an outage, the median ready-queue length of every 10 s window,
+        the p95 of edge concurrency.  Computed by the HIP analyzer ``af_engine_summarize_series_quantiles``, bit-equal to
+        :func:`series_window_quantiles` on the group's samples side by side.  ``levels`` in [0, 1], at most 16, any order;
+        windows and ``by`` as in :meth:`series_window_summary`; ``series``: None (all), names from :meth:`series_names`
+        or indices, any order, duplicates allowed.  Returns torch tensors on the run's device: ``quantiles`` float64
+        [G, W, C, Q] (NaN in empty cells) and ``count`` int64 [G, W]; and ``levels``, ``series`` (the selected names),
+        ``tick_edges``, ``times``, ``replicas`` [G], ``series_quantile_ms``, ``scratch_bytes``."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_samples()
+        q = check_series_levels(levels)
+        col = self._series_columns(series)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        n_win = int(b.shape[0] - 1)
+        samples = self._samples_t
+        dev = samples.device
+        count = torch.empty((n_groups, n_win), dtype=torch.int32, device=dev)
+        quant = torch.empty((n_groups, n_win, col.shape[0], q.shape[0]), dtype=torch.float64, device=dev)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_series_quantiles(
+            len(self), n_groups, b, q, samples_ptr=samples.data_ptr(), tick_capacity=int(samples.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(), quantiles_ptr=quant.data_ptr(),
+            group_ptr=grp.data_ptr(), columns=None if series is None else col)
+        names = self.series_names()
+        return {"quantiles": quant, "count": count.to(torch.int64) & 0xFFFFFFFF, "levels": q, "series": [names[j] for j in col],
+                "tick_edges": b, "times": b[:-1].astype(np.float64) * self.plan.sample_period,
+                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "series_quantile_ms": ms, "scratch_bytes": scratch}
+
+    def series_quantile_bands(self, levels: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                              tick_edges: Any = None, by: Any = None, series: Any = None, level: float = 0.95,
+                              q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of the series quantiles: every scenario's own values
+        (``series_quantile_summary(by="scenario")``), then per group (``by``) and window, over the group's replicas whose
+        window is not empty (``n`` [G, W] of them), ``mean``, ``std``, ``ci_halfwidth`` (at ``level``) and the linear
+        quantiles ``q_lo`` / ``q_hi`` (``q``) as :func:`window_bands_by_group` gives them: numpy float64 [G, W, C, Q].
+        ``pooled`` [G, W, C, Q] and ``pooled_count`` [G, W] are ``series_quantile_summary(by=by)`` as numpy.
+        The bands are reduced on the HOST from the device's per-scenario quantiles: there the sums over the replicas run
+        in scenario order, so the bands, like the quantiles, are the same bits in every run (a device ``index_add_`` adds
+        floats atomically, in no fixed order)."""
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        per = self.series_quantile_summary(levels, tick_edges=b, by="scenario", series=series)
+        shape = tuple(per["quantiles"].shape[2:])
+        out = window_bands_by_group(per["quantiles"].flatten(2).cpu(), ids, n_groups, level, q, valid=(per["count"] > 0).cpu())
+        for k in ("mean", "std", "ci_halfwidth", "q_lo", "q_hi"):
+            out[k] = out[k].reshape(out[k].shape[:2] + shape)
+        pooled = self.series_quantile_summary(levels, tick_edges=b, by=ids, series=series)
+        out["pooled"] = pooled["quantiles"].cpu().numpy()[:n_groups]
+        out["pooled_count"] = pooled["count"].cpu().numpy()[:n_groups]
+        out.update(levels=per["levels"], series=per["series"], tick_edges=b, times=per["times"])
+        return out
+
+    def save_series_quantile_summary(self, path: str, by: Any = None, *, levels: Any, series: Any = None,
+                                     window_s: float | None = None, ticks_per_window: int | None = None) -> dict[str, np.ndarray]:
+        """Columnar dump of the series quantiles with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas``, ``series_quantile_count`` [G, W] and per selected series and level the [G, W] column
+        ``series_quantile:<series>:<level>`` (the group's replicas taken together; ``<level>`` as ``repr(float)``);
+        ``series_quantile_tick_edges`` [W + 1], ``series_quantile_times`` [W] and ``series_quantile_levels`` [Q] are
+        per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, None)
+        ids, n_groups = self._window_groups(by)
+        pooled = self.series_quantile_summary(levels, tick_edges=b, by=ids, series=series)
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(pooled["replicas"], dtype=np.int64)
+        cols["series_quantile_count"] = np.ascontiguousarray(pooled["count"].cpu().numpy()[:n_groups], dtype=np.int64)
+        quant = pooled["quantiles"].cpu().numpy()[:n_groups]
+        for c, name in enumerate(pooled["series"]):
+            for i, lv in enumerate(pooled["levels"]):
+                cols[f"series_quantile:{name}:{float(lv)!r}"] = np.ascontiguousarray(quant[:, :, c, i])
+        cols["series_quantile_tick_edges"] = np.asarray(b, dtype=np.float64)
+        cols["series_quantile_times"] = np.asarray(pooled["times"], dtype=np.float64)
+        cols["series_quantile_levels"] = np.asarray(pooled["levels"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -1500,6 +1700,18 @@ class ShardedResults:
 
     def save_series_window_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_window_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_quantile_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_quantile_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_quantile_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_series_quantile_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_series_quantile_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:

@@ -484,6 +484,55 @@ typedef struct af_series_windows {
 } af_series_windows_t;
 int af_engine_summarize_series_windows(af_engine_t* engine, const af_outputs_t* out, af_series_windows_t* series_windows);
 
+/* Exact QUANTILES OF THE SAMPLED SERIES per window of ticks, group and series on the device
+ * (asyncflow_amd/csrc/af_series_quantiles.hpp): how much RAM covers 99 % of the ticks during an outage at a grid point, the
+ * median ready-queue length of every 10 s window, the p95 of edge concurrency a connection pool must be sized for.
+ * Cells: those of af_series_windows_t.  Window w of scenario s is its sample rows [min(b[w], m_s), min(b[w + 1], m_s)), with
+ * m_s = min(counts[s][AF_CNT_TICKS], tick_capacity); rows at or past m_s and the padding words of a row are never read.  The
+ * sample of (g, w, j) is column j over those rows of every member of g (group as in af_pooled_t).
+ * Key: every word has a 32-bit key -- of an integer series the word itself, unsigned; of a ram_in_use column (index n_edges +
+ * 3 * server + 2) the float32 word w mapped to (w & 0x80000000) ? ~w : (w | 0x80000000), the IEEE total order on non-NaN
+ * floats with -0.0 below +0.0 (no NaN is sampled).  Sort the sample by key; x[0 .. n-1] are the values in that order as f64:
+ * (double)word of an integer series, (double)(float) of ram_in_use.  For a level q in [0, 1]:
+ *     v = (double)(n - 1) * q;  lo = floor(v);  hi = min(lo + 1, n - 1);  t = v - lo;  d = x[hi] - x[lo];
+ *     quantile = t >= 0.5 ? x[hi] - d * (1 - t) : x[lo] + d * t
+ * which is np.quantile(values, q) (method 'linear'): bit for bit where the cell holds no zero, equal under == everywhere (numpy's
+ * sort leaves -0.0 and +0.0 in input order).  Levels 0 and 1 are af_series_windows_t's minv / maxv as values.  An empty cell:
+ * count 0, every quantile NaN.  Output column c belongs to columns[c]: any order, duplicates allowed.
+ * Independence: a cell's result does not depend on which other cells, levels or columns the call holds, on the batch a scenario
+ * sits in, or on the run: selection by sorting and counting, integer atomics only; no floating-point number is ever added
+ * across elements.
+ * Refused, no output buffer touched: n_levels == 0 or more than AF_MAX_SERIES_QUANTILE_LEVELS, a level that is NaN or outside
+ * [0, 1], tick_edges not strictly increasing or n_windows == 0, a column index >= af_series_count, n_columns == 0 with columns
+ * != NULL or the reverse, a group id >= n_groups, outputs.samples NULL (AF_ERR_INVALID); a cell of 2^32 or more values,
+ * n_groups * n_windows >= 2^32 - 1, tick_capacity >= 2^31 (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).
+ * `out` needs samples, tick_capacity and counts; clock is not read.
+ * Scratch kept by the engine (shared with the other group analyzers), with C the output columns, U the distinct series among
+ * them, P the plan's padded series (af_series_pitch) and L the cells of more than 2 048 values per column:
+ *     4 B per edge + 8 B per level + 4 B per group + 4 B per scenario + 5 B per padded series + 8 U + 4 C + 8 B per cell of at
+ *     most 2 048 values + 5 376 B of alignment, and only where L > 0:
+ *     4 B per cell + 8 L + min(L, max(1, floor(128 MiB / (U * K)))) * U * K,   K = 2 * n_levels * 8 208 + 12 bytes
+ * (one 2 048-bin histogram per wanted rank, column and cell of a chunk of large cells; the chunks run one after the other).
+ * Synchronous; the struct is written back. */
+#define AF_MAX_SERIES_QUANTILE_LEVELS 16
+typedef struct af_series_quantiles {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing */
+    uint32_t n_levels;
+    const double* levels;        /* HOST [n_levels], each in [0, 1] */
+    uint32_t n_columns;
+    const uint32_t* columns;     /* HOST [n_columns] series indices < af_series_count, any order, duplicates allowed;
+                                    NULL with n_columns == 0: every series, in device order */
+    uint32_t* count;             /* DEVICE [n_groups][n_windows]; NULL skips */
+    double* quantiles;           /* DEVICE [n_groups][n_windows][C][n_levels] f64, C = n_columns or af_series_count */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_series_quantiles_t;
+int af_engine_summarize_series_quantiles(af_engine_t* engine, const af_outputs_t* out, af_series_quantiles_t* series_quantiles);
+
 /* Arbitrary latency QUANTILES and SLO counts per group and time window on the device (asyncflow_amd/csrc/af_quantiles.hpp):
  * p99.9 at a grid point, p90 during an outage, how many requests met a 200 ms objective in every 10 s window.  The cells and
  * their samples are af_windows_t's: cell c = g * n_windows + w holds, in ascending scenario index over the members of g,
