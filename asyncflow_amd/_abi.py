@@ -337,6 +337,31 @@ class AfSeriesQuantiles(C.Structure):
     ]
 
 
+TICK_NONE = 0xFFFFFFFF   # AF_TICK_NONE
+
+
+class AfSeriesExcursions(C.Structure):
+    """``af_series_excursions_t``: request of ``af_engine_summarize_series_excursions`` (``elapsed_ms`` and
+    ``scratch_bytes`` are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("thresholds", C.POINTER(C.c_double)),
+        ("count", C.c_void_p),
+        ("above", C.c_void_p),
+        ("runs", C.c_void_p),
+        ("longest", C.c_void_p),
+        ("longest_start", C.c_void_p),
+        ("first", C.c_void_p),
+        ("last", C.c_void_p),
+        ("peak_tick", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 #: every symbol include/asyncflow_hip.h declares
 EXPORTED_SYMBOLS = (
     "af_engine_create",
@@ -346,6 +371,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_windows",
     "af_engine_summarize_series_windows",
     "af_engine_summarize_series_quantiles",
+    "af_engine_summarize_series_excursions",
     "af_engine_summarize_quantiles",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
@@ -387,6 +413,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_series_windows.restype = C.c_int
     lib.af_engine_summarize_series_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesQuantiles)]
     lib.af_engine_summarize_series_quantiles.restype = C.c_int
+    lib.af_engine_summarize_series_excursions.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesExcursions)]
+    lib.af_engine_summarize_series_excursions.restype = C.c_int
     lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]

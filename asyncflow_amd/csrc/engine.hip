@@ -18,6 +18,8 @@
 //   af_sq_small / af_sq_rows / af_sq_select / af_sq_final
 //                                          af_engine_summarize_series_quantiles: exact quantiles of the sampled series per
 //                                          (group, window of ticks, series) (af_series_quantiles.hpp)
+//   af_sexc_kernel                         af_engine_summarize_series_excursions: runs of the sampled series above a threshold
+//                                          per (scenario, window of ticks, series) (af_series_excursions.hpp)
 //
 // Memory plan
 //   LDS  : flow kernel: [plan blob, patched per scenario][station lists, select scratch / server segments, rings,
@@ -48,6 +50,7 @@
 #include "af_pooled.hpp"
 #include "af_series_windows.hpp"
 #include "af_series_quantiles.hpp"
+#include "af_series_excursions.hpp"
 #include "af_windowed.hpp"
 #include "af_quantiles.hpp"
 
@@ -3203,6 +3206,70 @@ int af_engine_summarize_series_windows(af_engine_t* e, const af_outputs_t* out, 
         }
     }
     HIP_TRY(hipStreamSynchronize(st));
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Excursions of the sampled series above a threshold per (scenario, window of ticks, series) (af_series_excursions.hpp): the
+// host checks the request and uploads the edges and the thresholds; one streaming pass over the sample rows writes the cells.
+int af_engine_summarize_series_excursions(af_engine_t* e, const af_outputs_t* out, af_series_excursions_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty series excursions request (n_scenarios and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "series_excursions.tick_edges is required");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->samples) return fail(AF_ERR_INVALID, "series excursions need outputs.samples");
+    if (out->tick_capacity == 0) return fail(AF_ERR_INVALID, "series excursions need a tick_capacity above 0");
+    const uint32_t n = req->n_scenarios, W = req->n_windows, cap = out->tick_capacity;
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch;
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    for (uint32_t j = 0; req->thresholds && j < S; ++j)
+        if (std::isnan(req->thresholds[j])) return fail(AF_ERR_INVALID, "threshold " + std::to_string(j) + " is NaN");
+    if ((uint64_t)n * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    if (S == 0 || pitch < S || pitch % 4u) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u), o_thr = lay.part((size_t)S * 8u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    unsigned char* b = e->d_pool;
+    hipStream_t st = e->stream;
+    std::vector<double> thr(S, 0.0);
+    if (req->thresholds) thr.assign(req->thresholds, req->thresholds + S);
+    HIP_TRY(hipMemcpyAsync(b + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_thr, thr.data(), (size_t)S * 8u, hipMemcpyHostToDevice, st));
+    afsx::SexArgs a{};
+    a.samples = out->samples;
+    a.counts = out->counts;
+    a.tick_cap = cap;
+    a.pitch = pitch;
+    a.n_series = S;
+    a.n_edges = e->args.n_edges;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.n_scen = n;
+    a.n_win = W;
+    a.edges = reinterpret_cast<const uint32_t*>(b + o_edges);
+    a.thr = reinterpret_cast<const double*>(b + o_thr);
+    a.count = req->count;
+    a.above = req->above;
+    a.runs = req->runs;
+    a.longest = req->longest;
+    a.longest_start = req->longest_start;
+    a.first = req->first;
+    a.last = req->last;
+    a.peak_tick = req->peak_tick;
+    // a wave per (scenario, run of windows): runs as long as leave the chip some 32 768 waves (af_engine_summarize_series_windows' rule)
+    const uint32_t want_runs = (32768u + n - 1u) / n;
+    a.run = std::max(1u, W / want_runs);
+    const uint64_t items = (uint64_t)n * ((W + a.run - 1u) / a.run);
+    hipLaunchKernelGGL(afsx::af_sexc_kernel, dim3((uint32_t)((items + afsx::kWaves - 1u) / afsx::kWaves)), dim3(afsx::kThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the host thresholds are read by the copy until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;

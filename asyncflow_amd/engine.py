@@ -360,6 +360,40 @@ class Engine:
                "af_engine_summarize_series_windows")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    #: the outputs of :meth:`summarize_series_excursions`, in the order of ``af_series_excursions_t``
+    EXCURSION_OUTPUTS = ("count", "above", "runs", "longest", "longest_start", "first", "last", "peak_tick")
+
+    def summarize_series_excursions(self, n: int, tick_edges: Any, *, samples_ptr: int, tick_capacity: int, counts_ptr: int,
+                                    count_ptr: int = 0, above_ptr: int = 0, runs_ptr: int = 0, longest_ptr: int = 0,
+                                    longest_start_ptr: int = 0, first_ptr: int = 0, last_ptr: int = 0, peak_tick_ptr: int = 0,
+                                    thresholds: Any = None) -> tuple[float, int]:
+        """Excursion analyzer on the device (``af_engine_summarize_series_excursions``): per (scenario, window of ticks)
+        ``count`` uint32 [n, W] and, per series, uint32 [n, W, n_series] each: ``above`` (the ticks above the threshold),
+        ``runs`` (the maximal stretches of such ticks, clipped at the window's edges), ``longest`` (ticks) and
+        ``longest_start``, ``first``, ``last`` and ``peak_tick`` (absolute tick indices, ``_abi.TICK_NONE`` for none); a
+        pointer of 0 skips an output.  ``tick_edges`` and ``thresholds`` as in :meth:`summarize_series_windows`.  Returns
+        the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_tick_edges
+
+        b = check_tick_edges(tick_edges)
+        thr = None
+        if thresholds is not None:
+            thr = np.ascontiguousarray(thresholds, dtype=np.float64)
+            if thr.shape != (self.plan.n_series,):
+                msg = f"thresholds must be a vector of one value per series ({self.plan.n_series}), not of shape {thr.shape}"
+                raise ValueError(msg)
+            if np.isnan(thr).any():
+                msg = "thresholds must not be NaN"
+                raise ValueError(msg)
+        out = _abi.AfOutputs(0, None, int(tick_capacity), C.c_void_p(samples_ptr or None), C.c_void_p(counts_ptr or None))
+        ptrs = (count_ptr, above_ptr, runs_ptr, longest_ptr, longest_start_ptr, first_ptr, last_ptr, peak_tick_ptr)
+        req = _abi.AfSeriesExcursions(int(n), int(b.shape[0] - 1), b.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      thr.ctypes.data_as(C.POINTER(C.c_double)) if thr is not None else None,
+                                      *(C.c_void_p(p or None) for p in ptrs), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_series_excursions(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_series_excursions")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def summarize_series_quantiles(self, n: int, n_groups: int, tick_edges: Any, levels: Any, *, samples_ptr: int,
                                    tick_capacity: int, counts_ptr: int, quantiles_ptr: int, count_ptr: int = 0,
                                    group_ptr: int = 0, columns: Any = None) -> tuple[float, int]:

@@ -283,6 +283,62 @@ def series_window_stats(samples: np.ndarray, tick_edges: Any, n_edges: int, thre
     return {"count": count, "mean": mean, "min": mn, "max": mx, "above": above}
 
 
+def series_window_excursions(samples: np.ndarray, tick_edges: Any, n_edges: int, thresholds: Any = None) -> dict[str, np.ndarray]:
+    """Excursions above a threshold per window of ticks of ONE scenario's sampled series ``samples`` (uint32 words
+    [n_series, ticks], the layout :class:`ScenarioResults` holds and :func:`series_window_stats` takes).  Window ``w`` holds
+    the ticks ``lo <= k < hi``, ``lo = min(b[w], ticks)``, ``hi = min(b[w + 1], ticks)``.  Tick ``k`` of series ``j`` is
+    ABOVE when its value as float64 -- the word of an integer series, the float32 value of a ``ram_in_use`` column, as
+    ``above`` of :func:`series_window_stats` takes it -- is ``> thresholds[j]`` (None: 0.0 each); a RUN is a maximal stretch
+    of consecutive above ticks inside the window: runs are clipped at the window's edges, and one that crosses an edge counts
+    in both windows.  Returns int64 arrays, -1 for "no such tick": ``count`` [W] (``hi - lo``) and, [W, S] each, ``above``
+    (the above ticks), ``runs``, ``longest`` (ticks of the longest run, 0 if none), ``longest_start`` (first tick of the
+    EARLIEST run of that length), ``first`` / ``last`` (smallest / largest above tick; ``last == hi - 1``: still above at
+    the window's end, otherwise ``last + 1`` is the tick at which the series had come back for good) and ``peak_tick`` (the
+    smallest tick whose key is the window's largest; the key is the word, or of ``ram_in_use`` the float32 bits ``w`` as
+    ``~w`` where the sign bit is set, else ``w | 0x80000000``: -0.0 below +0.0).  Ticks are absolute row indices.  The
+    definition the device analyzer (``af_engine_summarize_series_excursions``) equals word for word."""
+    b = check_tick_edges(tick_edges)
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    n_series, ticks = words.shape
+    thr = np.zeros(n_series) if thresholds is None else np.asarray(thresholds, dtype=np.float64)
+    if thr.shape != (n_series,) or np.isnan(thr).any():
+        msg = f"thresholds must be {n_series} values, none of them NaN"
+        raise ValueError(msg)
+    ram = ram_columns(n_series, n_edges)
+    n_win = b.shape[0] - 1
+    r = np.minimum(b.astype(np.int64), ticks)
+    out = {k: np.full((n_win, n_series), -1, dtype=np.int64) for k in ("longest_start", "first", "last", "peak_tick")}
+    out.update({k: np.zeros((n_win, n_series), dtype=np.int64) for k in ("above", "runs", "longest")})
+    out["count"] = np.diff(r)
+    rows = np.arange(n_series)
+    for w in range(n_win):
+        lo, c = int(r[w]), int(r[w + 1] - r[w])
+        if c == 0:
+            continue
+        seg = words[:, lo:lo + c]
+        with np.errstate(invalid="ignore"):   # (an integer word read as float32 may be a NaN: not taken)
+            values = np.where(ram[:, None], seg.view(np.float32).astype(np.float64), seg.astype(np.float64))
+        a = values > thr[:, None]
+        rise = a & ~np.concatenate([np.zeros((n_series, 1), dtype=bool), a[:, :-1]], axis=1)
+        idx = np.arange(c, dtype=np.int64)
+        start = np.maximum.accumulate(np.where(rise, idx, -1), axis=1)    # of the run a tick lies in (where it is above)
+        length = np.where(a, idx - start + 1, 0)
+        at = length.argmax(axis=1)                                       # (the first maximum: the end of the earliest longest run)
+        some = a.any(axis=1)
+        out["above"][w] = a.sum(axis=1)
+        out["runs"][w] = rise.sum(axis=1)
+        out["longest"][w] = length[rows, at]
+        out["longest_start"][w] = np.where(some, lo + start[rows, at], -1)
+        out["first"][w] = np.where(some, lo + a.argmax(axis=1), -1)
+        out["last"][w] = np.where(some, lo + c - 1 - a[:, ::-1].argmax(axis=1), -1)
+        key = np.where(ram[:, None], np.where(seg >> 31 != 0, ~seg, seg | np.uint32(0x80000000)), seg)
+        out["peak_tick"][w] = lo + key.argmax(axis=1)
+    return out
+
+
 def check_series_levels(levels: Any) -> np.ndarray:
     """``levels`` of a series-quantile call as a float64 vector, or ValueError: one dimension, 1 to
     ``AF_MAX_SERIES_QUANTILE_LEVELS`` (16) of them, each in [0, 1]."""
@@ -528,6 +584,22 @@ class ScenarioResults:
         col = _check_series_columns(series, int(np.asarray(self._samples).shape[0]))
         count, quant = series_window_quantiles(self._samples, b, self._plan.n_edges, levels, col)
         return {"count": count, "quantiles": quant, "levels": check_series_levels(levels), "series": col, "tick_edges": b}
+
+    def get_series_excursions(self, thresholds: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                              tick_edges: Any = None) -> dict[str, np.ndarray]:
+        """Excursions of every sampled series above ``thresholds`` (a vector [n_series]; None: 0.0 each) per window of
+        ticks (:func:`series_window_excursions`): how many ticks above, how many runs, the longest run and its start, the
+        first and the last tick above and the tick of the peak, as int64 (-1: no such tick), and ``tick_edges``.  Windows as
+        in :meth:`get_series_window_stats`, but with none of the three given ONE window over the whole run."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        if window_s is None and ticks_per_window is None and tick_edges is None:
+            tick_edges = [0, max(self._plan.tick_count, 1)]
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        out = series_window_excursions(self._samples, b, self._plan.n_edges, thresholds)
+        out["tick_edges"] = b
+        return out
 
     def get_sampled_metrics(self) -> dict[str, dict[str, list[float]]]:
         self.process_all_metrics()
@@ -1312,6 +1384,163 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    #: what :meth:`series_excursion_bands` gives bands of
+    EXCURSION_BANDS = ("longest_s", "above_s", "runs", "first_s", "recovered_s", "peak_s")
+
+    def _series_excursion_edges(self, window_s: float | None, ticks_per_window: int | None, tick_edges: Any) -> np.ndarray:
+        if window_s is None and ticks_per_window is None and tick_edges is None:
+            tick_edges = [0, max(self.plan.tick_count, 1)]
+        return self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+
+    def series_excursion_summary(self, thresholds: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                                 tick_edges: Any = None) -> dict[str, Any]:
+        """Excursions of every sampled series above a threshold, per SCENARIO and window of ticks: how long a server's
+        ready queue stayed above 50 after another went down, when it had come back (and whether it had by the end of the
+        window), how many separate backlogs formed, when the peak was.  Computed by the HIP analyzer
+        ``af_engine_summarize_series_excursions`` in one pass over the sample rows, equal word for word to
+        :func:`series_window_excursions` of every scenario.  A tick is above when its value ``> threshold``; a run is a
+        maximal stretch of consecutive above ticks inside a window (clipped at its edges).  ``thresholds``: None (0.0), a
+        vector [n_series] or ``{series name: value}`` over :meth:`series_names` (missing: 0.0).  Windows: ``window_s``
+        seconds, ``ticks_per_window`` ticks or explicit ``tick_edges`` as in :meth:`series_window_summary` -- but WITH NONE
+        OF THE THREE GIVEN, ONE WINDOW OVER THE WHOLE RUN, ``[0, plan.tick_count]`` (the sibling methods default to windows
+        of 1 s).  Returns torch tensors on the run's device: ``count`` int64 [n, W]; ``above``, ``runs``, ``longest`` (ticks),
+        ``longest_start``, ``first``, ``last``, ``peak_tick`` (tick indices, -1: none) int64 [n, W, S]; float64 [n, W, S] in
+        seconds with the label of ``get_series``, tick ``k`` at ``k * sample_period``: ``above_s``, ``longest_s`` (ticks x
+        period), ``first_s``, ``peak_s`` (NaN: none) and ``recovered_s`` = ``(last + 1) * period``, NaN where the series
+        never exceeded the threshold AND where the window ends above it; bool [n, W, S]: ``exceeded`` and ``open`` (still
+        above at the window's last tick).  And ``series``, ``thresholds``, ``tick_edges``, ``times`` (the windows' start labels
+        in seconds), ``series_excursion_ms``, ``scratch_bytes``."""
+        import torch
+
+        from .engine import Engine
+
+        thr = self._series_thresholds(thresholds)
+        self._require_samples()
+        b = self._series_excursion_edges(window_s, ticks_per_window, tick_edges)
+        n, n_win, n_ser = len(self), int(b.shape[0] - 1), self.plan.n_series
+        samples = self._samples_t
+        dev = samples.device
+        raw = {k: torch.empty((n, n_win) if k == "count" else (n, n_win, n_ser), dtype=torch.int32, device=dev)
+               for k in Engine.EXCURSION_OUTPUTS}
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_series_excursions(
+            n, b, samples_ptr=samples.data_ptr(), tick_capacity=int(samples.shape[1]), counts_ptr=self._counts_t.data_ptr(),
+            thresholds=thr, **{f"{k}_ptr": v.data_ptr() for k, v in raw.items()})
+        out: dict[str, Any] = {k: raw[k].to(torch.int64) & 0xFFFFFFFF for k in ("count", "above", "runs", "longest")}
+        for k in ("longest_start", "first", "last", "peak_tick"):
+            out[k] = raw[k].to(torch.int64)              # (0xFFFFFFFF is -1; a tick is below 2^31)
+        period = float(self.plan.sample_period)
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        m = (self._counts_t[:, _abi.CNT_TICKS].to(torch.int64) & 0xFFFFFFFF).clamp(max=int(samples.shape[1]))
+        hi = torch.minimum(torch.as_tensor(b[1:].astype(np.int64), device=dev)[None, :], m[:, None])      # [n, W]
+        exceeded = out["first"] >= 0
+        still = exceeded & (out["last"] == (hi - 1)[:, :, None])
+        out["above_s"] = out["above"].to(torch.float64) * period
+        out["longest_s"] = out["longest"].to(torch.float64) * period
+        out["first_s"] = torch.where(exceeded, out["first"].to(torch.float64) * period, nan)
+        out["peak_s"] = torch.where(out["peak_tick"] >= 0, out["peak_tick"].to(torch.float64) * period, nan)
+        out["recovered_s"] = torch.where(exceeded & ~still, (out["last"] + 1).to(torch.float64) * period, nan)
+        out["open"], out["exceeded"] = still, exceeded
+        out.update(series=self.series_names(), thresholds=np.zeros(n_ser) if thr is None else thr, tick_edges=b,
+                   times=b[:-1].astype(np.float64) * period, series_excursion_ms=ms, scratch_bytes=scratch)
+        return out
+
+    def series_excursion_bands(self, thresholds: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                               tick_edges: Any = None, by: Any = None, of: str = "longest_s", level: float = 0.95,
+                               q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of an excursion statistic ``of`` -- ``"longest_s"``, ``"above_s"``, ``"runs"``,
+        ``"first_s"``, ``"recovered_s"`` or ``"peak_s"`` of :meth:`series_excursion_summary` --: per group (``by`` as in
+        :meth:`window_summary`), window and series, over the group's replicas that are VALID there, ``mean``, unbiased
+        ``std``, ``ci_halfwidth`` at ``level`` and the linear quantiles ``q_lo`` / ``q_hi`` (``q``) as
+        :func:`window_bands_by_group` gives them, numpy float64 [G, W, S], and ``n`` [G, W, S], the valid replicas.  Valid:
+        a non-empty window (``count > 0``) for ``longest_s``, ``above_s``, ``runs`` and ``peak_s``; ``exceeded`` for
+        ``first_s``; ``exceeded & ~open`` -- the replicas that came back inside the window -- for ``recovered_s``.  Also
+        ``exceed_share`` and ``open_share`` [G, W, S]: the members that exceeded the threshold / are still above it at the
+        window's end, divided by the members with a non-empty window (NaN where there is none).  Windows and their
+        default (one window over the whole run) as in :meth:`series_excursion_summary`."""
+        if of not in self.EXCURSION_BANDS:
+            msg = f"of must be one of {', '.join(repr(k) for k in self.EXCURSION_BANDS)}, not {of!r}"
+            raise ValueError(msg)
+        per = self.series_excursion_summary(thresholds, window_s, ticks_per_window=ticks_per_window, tick_edges=tick_edges)
+        ids, n_groups = self._window_groups(by)
+        return self._series_excursion_bands(per, ids, n_groups, of, level, q)
+
+    def _series_excursion_bands(self, per: dict[str, Any], ids: np.ndarray, n_groups: int, of: str, level: float,
+                                q: tuple[float, float], shares: bool = True) -> dict[str, Any]:
+        """:meth:`series_excursion_bands` of a computed per-scenario summary ``per`` (``shares=False``: without the two
+        shares, which do not depend on ``of``)."""
+        import torch
+
+        live = per["count"] > 0                                           # [n, W]
+        valid = {"first_s": per["exceeded"], "recovered_s": per["exceeded"] & ~per["open"]}.get(of)
+        values = per[of].to(torch.float64)
+        n, n_win, n_ser = (int(x) for x in values.shape)
+        shape = (n_groups, n_win, n_ser)
+        if valid is None:
+            out = window_bands_by_group(values, ids, n_groups, level, q, valid=live)
+            out["n"] = np.repeat(out["n"][:, :, None], n_ser, axis=2)
+        else:   # valid per series: every (window, series) pair a window of its own with one column -- one call, one sort
+            out = window_bands_by_group(values.reshape(n, n_win * n_ser, 1), ids, n_groups, level, q, valid=valid.reshape(n, n_win * n_ser))
+            for k in ("n", "mean", "std", "ci_halfwidth", "q_lo", "q_hi"):
+                out[k] = out[k].reshape(shape)
+        if shares:
+            out.update(self._series_excursion_shares(per, ids, n_groups))
+        out.update(of=of, series=per["series"], thresholds=per["thresholds"], tick_edges=per["tick_edges"], times=per["times"])
+        return out
+
+    @staticmethod
+    def _series_excursion_shares(per: dict[str, Any], ids: np.ndarray, n_groups: int) -> dict[str, np.ndarray]:
+        """``exceed_share`` / ``open_share`` [G, W, S]: integer member counts (exact in any order), divided once."""
+        import torch
+
+        live = per["count"] > 0
+        dev = live.device
+        n_win, n_ser = int(live.shape[1]), int(per["exceeded"].shape[2])
+        gid = torch.as_tensor(ids, device=dev)
+        ok = (gid >= 0)[:, None] & live                                   # (an open or exceeded window is not empty)
+        cell = (gid[:, None] * n_win + torch.arange(n_win, device=dev)[None, :])[ok]
+        base = torch.bincount(cell, minlength=n_groups * n_win).to(torch.float64)[:, None]
+        out = {}
+        for name, mask in (("exceed_share", per["exceeded"]), ("open_share", per["open"])):
+            members = torch.zeros((n_groups * n_win, n_ser), dtype=torch.int64, device=dev).index_add_(0, cell, mask[ok].to(torch.int64))
+            out[name] = (members.to(torch.float64) / base).reshape(n_groups, n_win, n_ser).cpu().numpy()   # (0 / 0: NaN)
+        return out
+
+    def save_series_excursion_summary(self, path: str, by: Any = None, *, thresholds: Any, window_s: float | None = None,
+                                      ticks_per_window: int | None = None, tick_edges: Any = None,
+                                      level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the excursions with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas``, and per series the [G, W] columns ``series_excursion_longest_s:<series>`` (the mean over the replicas
+        of their longest run in seconds), ``series_excursion_q05:<series>`` / ``series_excursion_q95:<series>`` (its
+        quantiles over the replicas), ``series_excursion_recovered_s:<series>`` (the mean recovery label over the replicas
+        that came back inside the window), ``series_excursion_exceed_share:<series>`` and
+        ``series_excursion_open_share:<series>`` (:meth:`series_excursion_bands`); ``series_excursion_tick_edges`` [W + 1],
+        ``series_excursion_times`` [W] and ``series_excursion_thresholds`` [S] are per-file vectors.  Windows as in
+        :meth:`series_excursion_summary`.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        per = self.series_excursion_summary(thresholds, window_s, ticks_per_window=ticks_per_window, tick_edges=tick_edges)
+        ids, n_groups = self._window_groups(by)
+        longest = self._series_excursion_bands(per, ids, n_groups, "longest_s", level, (0.05, 0.95))
+        back = self._series_excursion_bands(per, ids, n_groups, "recovered_s", level, (0.05, 0.95), shares=False)
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(longest["replicas"], dtype=np.int64)
+        for j, name in enumerate(per["series"]):
+            cols[f"series_excursion_longest_s:{name}"] = np.ascontiguousarray(longest["mean"][:, :, j])
+            cols[f"series_excursion_q05:{name}"] = np.ascontiguousarray(longest["q_lo"][:, :, j])
+            cols[f"series_excursion_q95:{name}"] = np.ascontiguousarray(longest["q_hi"][:, :, j])
+            cols[f"series_excursion_recovered_s:{name}"] = np.ascontiguousarray(back["mean"][:, :, j])
+            cols[f"series_excursion_exceed_share:{name}"] = np.ascontiguousarray(longest["exceed_share"][:, :, j])
+            cols[f"series_excursion_open_share:{name}"] = np.ascontiguousarray(longest["open_share"][:, :, j])
+        cols["series_excursion_tick_edges"] = np.asarray(per["tick_edges"], dtype=np.float64)
+        cols["series_excursion_times"] = np.asarray(per["times"], dtype=np.float64)
+        cols["series_excursion_thresholds"] = np.asarray(per["thresholds"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -1712,6 +1941,18 @@ class ShardedResults:
 
     def save_series_quantile_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_quantile_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_excursion_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_excursion_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_excursion_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_excursion_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_series_excursion_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_series_excursion_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:

@@ -533,6 +533,59 @@ typedef struct af_series_quantiles {
 } af_series_quantiles_t;
 int af_engine_summarize_series_quantiles(af_engine_t* engine, const af_outputs_t* out, af_series_quantiles_t* series_quantiles);
 
+/* EXCURSIONS OF THE SAMPLED SERIES ABOVE A THRESHOLD per scenario, window of ticks and series on the device
+ * (asyncflow_amd/csrc/af_series_excursions.hpp): how long the ready queue of a server stayed above 50 after another went down,
+ * when it had come back below (and whether it had by the horizon), how many separate backlogs formed, when the peak was.
+ * Cells: those of af_series_windows_t, always PER SCENARIO -- a duration is a property of one replica's path, so there is no
+ * group.  With tick_edges b[0] < ... < b[W] and m_s = min(counts[s][AF_CNT_TICKS], tick_capacity), cell (s, w, j) is column j
+ * over the rows k in [lo, hi), lo = min(b[w], m_s), hi = min(b[w + 1], m_s); rows at or past m_s and the padding words of a row
+ * are never read.  x[k] is the value as f64 exactly as af_series_windows_t.above takes it -- (double)word of an integer
+ * series, (double)(float) of a ram_in_use column -- and tick k is ABOVE when x[k] > thresholds[j], compared as f64 (+0.0 is
+ * not above -0.0, a -2^-45 residue is not above 0.0; NULL: 0.0 each).  A RUN is a maximal stretch of consecutive above ticks
+ * inside [lo, hi): runs are clipped at the window's edges, and a run that crosses an edge counts in both windows with its
+ * clipped lengths.  Outputs, u32, AF_TICK_NONE for "no such tick":
+ *     count          [n][W]      hi - lo
+ *     above          [n][W][S]   the above ticks; word for word af_series_windows_t.above of singleton groups
+ *     runs           same        the runs
+ *     longest        same        the length in ticks of the longest run; 0: none
+ *     longest_start  same        the first tick (absolute row index) of the earliest run of that length; NONE: none
+ *     first          same        the smallest above k; NONE: none
+ *     last           same        the largest above k; NONE: none.  last == hi - 1: still above at the end of the window (not
+ *                                recovered, censored by the window); otherwise last + 1 is the tick at which it had come back
+ *                                for good
+ *     peak_tick      same        the smallest k whose key is the cell's largest; NONE in an empty cell.  The key is the series
+ *                                analyzers': the word of an integer series, of a ram_in_use word w the value
+ *                                (w & 0x80000000) ? ~w : (w | 0x80000000), so -0.0 < +0.0; the peak value itself is
+ *                                af_series_windows_t.maxv
+ * A NULL output pointer skips that output.  An empty cell: count 0, the counts 0, the ticks NONE.
+ * Exactness: one streaming pass that reads every stored row inside the windows once; every combining operation is an integer
+ * +, min or max: no atomics, no floating-point addition; the result does not depend on the launch, on the batch a scenario
+ * sits in, or on the run.
+ * Refused, no output touched: n_scenarios == 0 or n_windows == 0, tick_edges NULL or not strictly increasing, a NaN threshold,
+ * outputs.samples or outputs.counts NULL, tick_capacity == 0 (AF_ERR_INVALID); n_scenarios * n_windows >= 2^32 - 1, tick_capacity >= 2^31
+ * (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).  `out` needs samples, tick_capacity and counts; clock is not
+ * read.  Any number of series.
+ * Scratch kept by the engine (shared with the other analyzers): 4 B per edge + 8 B per series + 512 B of alignment -- the
+ * edges and the thresholds only, no per-cell records.  Synchronous; the struct is written back. */
+#define AF_TICK_NONE 0xFFFFFFFFu
+typedef struct af_series_excursions {
+    uint32_t n_scenarios;
+    uint32_t n_windows;
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing */
+    const double* thresholds;    /* HOST [af_series_count] or NULL (0.0 each) */
+    uint32_t* count;             /* DEVICE [n_scenarios][n_windows]; NULL skips */
+    uint32_t* above;             /* DEVICE [n_scenarios][n_windows][af_series_count]; NULL skips (as every output below) */
+    uint32_t* runs;
+    uint32_t* longest;
+    uint32_t* longest_start;
+    uint32_t* first;
+    uint32_t* last;
+    uint32_t* peak_tick;
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_series_excursions_t;
+int af_engine_summarize_series_excursions(af_engine_t* engine, const af_outputs_t* out, af_series_excursions_t* series_excursions);
+
 /* Arbitrary latency QUANTILES and SLO counts per group and time window on the device (asyncflow_amd/csrc/af_quantiles.hpp):
  * p99.9 at a grid point, p90 during an outage, how many requests met a 200 ms objective in every 10 s window.  The cells and
  * their samples are af_windows_t's: cell c = g * n_windows + w holds, in ascending scenario index over the members of g,
