@@ -8,7 +8,7 @@ executed over thousands of independent scenarios by a hand-written HIP kernel
 
 from .payload import load_yaml, normalize_payload
 from .plan import DevicePlan, lower
-from .results import BatchedResults, ScenarioResults, latency_quantiles, latency_window_quantiles, latency_window_stats, series_window_excursions, series_window_quantiles, window_edges
+from .results import BatchedResults, ScenarioResults, latency_quantiles, latency_window_quantiles, latency_window_stats, series_histogram_quantiles, series_window_excursions, series_window_histogram, series_window_quantiles, window_edges
 from .runner import SimulationRunner
 from .sweep import Sweep, expand_grid
 
@@ -25,7 +25,9 @@ __all__ = [
     "load_yaml",
     "lower",
     "normalize_payload",
+    "series_histogram_quantiles",
     "series_window_excursions",
+    "series_window_histogram",
     "series_window_quantiles",
     "window_edges",
 ]

@@ -362,6 +362,33 @@ class AfSeriesExcursions(C.Structure):
     ]
 
 
+MAX_SERIES_HISTOGRAM_BINS = 1024   # AF_MAX_SERIES_HISTOGRAM_BINS
+
+
+class AfSeriesHistogram(C.Structure):
+    """``af_series_histogram_t``: request of ``af_engine_summarize_series_histogram`` (``elapsed_ms`` and
+    ``scratch_bytes`` are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("n_columns", C.c_uint32),
+        ("columns", C.POINTER(C.c_uint32)),
+        ("n_bins", C.c_uint32),
+        ("lo", C.POINTER(C.c_double)),
+        ("width", C.POINTER(C.c_double)),
+        ("count", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("under", C.c_void_p),
+        ("over", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 #: every symbol include/asyncflow_hip.h declares
 EXPORTED_SYMBOLS = (
     "af_engine_create",
@@ -372,6 +399,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_series_windows",
     "af_engine_summarize_series_quantiles",
     "af_engine_summarize_series_excursions",
+    "af_engine_summarize_series_histogram",
     "af_engine_summarize_quantiles",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
@@ -415,6 +443,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_series_quantiles.restype = C.c_int
     lib.af_engine_summarize_series_excursions.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesExcursions)]
     lib.af_engine_summarize_series_excursions.restype = C.c_int
+    lib.af_engine_summarize_series_histogram.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesHistogram)]
+    lib.af_engine_summarize_series_histogram.restype = C.c_int
     lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]

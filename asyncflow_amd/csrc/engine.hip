@@ -20,6 +20,8 @@
 //                                          (group, window of ticks, series) (af_series_quantiles.hpp)
 //   af_sexc_kernel                         af_engine_summarize_series_excursions: runs of the sampled series above a threshold
 //                                          per (scenario, window of ticks, series) (af_series_excursions.hpp)
+//   af_shist_kernel                        af_engine_summarize_series_histogram: occupancy histograms of the sampled series
+//                                          per (group, window of ticks, output column) (af_series_histogram.hpp)
 //
 // Memory plan
 //   LDS  : flow kernel: [plan blob, patched per scenario][station lists, select scratch / server segments, rings,
@@ -51,6 +53,7 @@
 #include "af_series_windows.hpp"
 #include "af_series_quantiles.hpp"
 #include "af_series_excursions.hpp"
+#include "af_series_histogram.hpp"
 #include "af_windowed.hpp"
 #include "af_quantiles.hpp"
 
@@ -3270,6 +3273,148 @@ int af_engine_summarize_series_excursions(af_engine_t* e, const af_outputs_t* ou
     hipLaunchKernelGGL(afsx::af_sexc_kernel, dim3((uint32_t)((items + afsx::kWaves - 1u) / afsx::kWaves)), dim3(afsx::kThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));   // (the host thresholds are read by the copy until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Histograms of the sampled series per (group, window of ticks, output column) (af_series_histogram.hpp).  The host reads the
+// group ids and the counts back and checks them, sorts the output columns by series, zeroes the outputs; one streaming pass.
+static_assert(afsh::kMaxBins == AF_MAX_SERIES_HISTOGRAM_BINS, "the kernel's bins are the header's");
+
+int af_engine_summarize_series_histogram(af_engine_t* e, const af_outputs_t* out, af_series_histogram_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty series histogram request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "series_histogram.tick_edges is required");
+    if (!req->hist) return fail(AF_ERR_INVALID, "series_histogram.hist is required");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, cap = out->tick_capacity, B = req->n_bins;
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch;
+    if (B == 0 || B > AF_MAX_SERIES_HISTOGRAM_BINS)
+        return fail(AF_ERR_INVALID, "series_histogram.n_bins must be 1 .. AF_MAX_SERIES_HISTOGRAM_BINS (" + std::to_string(AF_MAX_SERIES_HISTOGRAM_BINS) + ")");
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    if ((req->n_columns == 0) != (req->columns == nullptr)) return fail(AF_ERR_INVALID, "series_histogram.columns and n_columns must be given together");
+    for (uint32_t c = 0; c < req->n_columns; ++c)
+        if (req->columns[c] >= S) return fail(AF_ERR_INVALID, "column " + std::to_string(c) + " names series " + std::to_string(req->columns[c]) + " of " + std::to_string(S));
+    if ((req->lo == nullptr) != (req->width == nullptr)) return fail(AF_ERR_INVALID, "series_histogram.lo and width must be given together");
+    const uint32_t Co = req->n_columns ? req->n_columns : S;
+    for (uint32_t c = 0; req->lo && c < Co; ++c) {
+        if (!std::isfinite(req->lo[c])) return fail(AF_ERR_INVALID, "lo of column " + std::to_string(c) + " is not finite");
+        if (!(std::isfinite(req->width[c]) && req->width[c] > 0.0)) return fail(AF_ERR_INVALID, "width of column " + std::to_string(c) + " is not a finite number above 0");
+    }
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->samples || cap == 0) return fail(AF_ERR_INVALID, "series histograms need outputs.samples");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    if (S == 0 || pitch < S || pitch % 4u) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp;
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    // may a cell reach 2^32 values?
+    {
+        std::vector<uint64_t> g_ticks(G, 0u);
+        bool big = false;
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = grp.empty() ? 0u : grp[s];
+            if (g == afsh::kSkip) continue;
+            g_ticks[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+            big = big || g_ticks[g] > 0xFFFFFFFFull;
+        }
+        if (big) {   // (else no window of a group can hold 2^32 rows)
+            std::vector<uint64_t> cells((size_t)G * W, 0u);
+            for (uint32_t s = 0; s < n; ++s) {
+                const uint32_t g = grp.empty() ? 0u : grp[s];
+                if (g == afsh::kSkip || g_ticks[g] <= 0xFFFFFFFFull) continue;
+                const uint32_t m = std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+                for (uint32_t w = 0; w < W && req->tick_edges[w] < m; ++w) {
+                    uint64_t& c = cells[(size_t)g * W + w];
+                    c += std::min(req->tick_edges[w + 1u], m) - req->tick_edges[w];
+                    if (c > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more samples");
+                }
+            }
+        }
+    }
+    // the slots: the output columns sorted by series (a counting sort, stable)
+    std::vector<uint32_t> first((size_t)S + 1u, 0u), scol(Co);
+    std::vector<double> slo(Co), swidth(Co);
+    for (uint32_t c = 0; c < Co; ++c) first[(size_t)(req->columns ? req->columns[c] : c) + 1u] += 1u;
+    for (uint32_t j = 0; j < S; ++j) first[(size_t)j + 1u] += first[j];
+    {
+        std::vector<uint32_t> cursor(first.begin(), first.end() - 1);
+        for (uint32_t c = 0; c < Co; ++c) {
+            const uint32_t q = cursor[req->columns ? req->columns[c] : c]++;
+            scol[q] = c;
+            slo[q] = req->lo ? req->lo[c] : 0.0;
+            swidth[q] = req->width ? req->width[c] : 1.0;
+        }
+    }
+    // the chunks: as many slots as the LDS of a wave holds, no series twice
+    const uint32_t chunk_cap = std::max(1u, afsh::kWaveLdsWords / (B + 2u));
+    std::vector<uint32_t> cstart{0u}, series_of(Co);
+    for (uint32_t j = 0; j < S; ++j)
+        for (uint32_t q = first[j]; q < first[(size_t)j + 1u]; ++q) series_of[q] = j;
+    uint32_t lds_slots = 1u;
+    for (uint32_t q = 1; q <= Co; ++q)
+        if (q == Co || q - cstart.back() == chunk_cap || series_of[q] == series_of[q - 1u]) {
+            lds_slots = std::max(lds_slots, q - cstart.back());
+            cstart.push_back(q);
+        }
+    const uint32_t n_chunks = (uint32_t)cstart.size() - 1u;
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u), o_first = lay.part(((size_t)S + 1u) * 4u), o_scol = lay.part((size_t)Co * 4u),
+                 o_lo = lay.part((size_t)Co * 8u), o_width = lay.part((size_t)Co * 8u), o_chunk = lay.part(cstart.size() * 4u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    unsigned char* b = e->d_pool;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(b + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_first, first.data(), first.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_scol, scol.data(), (size_t)Co * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_lo, slo.data(), (size_t)Co * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_width, swidth.data(), (size_t)Co * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_chunk, cstart.data(), cstart.size() * 4u, hipMemcpyHostToDevice, st));
+    const size_t cells = (size_t)G * W;
+    HIP_TRY(hipMemsetAsync(req->hist, 0, cells * Co * B * 4u, st));
+    if (req->count) HIP_TRY(hipMemsetAsync(req->count, 0, cells * 4u, st));
+    if (req->under) HIP_TRY(hipMemsetAsync(req->under, 0, cells * Co * 4u, st));
+    if (req->over) HIP_TRY(hipMemsetAsync(req->over, 0, cells * Co * 4u, st));
+    afsh::ShArgs a{};
+    a.samples = out->samples;
+    a.counts = out->counts;
+    a.tick_cap = cap;
+    a.pitch = pitch;
+    a.n_series = S;
+    a.n_edges = e->args.n_edges;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.group = req->group;
+    a.n_scen = n;
+    a.n_win = W;
+    a.edges = reinterpret_cast<const uint32_t*>(b + o_edges);
+    a.n_out = Co;
+    a.n_bins = B;
+    a.n_chunks = n_chunks;
+    a.lds_slots = lds_slots;
+    a.cstart = reinterpret_cast<const uint32_t*>(b + o_chunk);
+    a.first = reinterpret_cast<const uint32_t*>(b + o_first);
+    a.scol = reinterpret_cast<const uint32_t*>(b + o_scol);
+    a.slo = reinterpret_cast<const double*>(b + o_lo);
+    a.swidth = reinterpret_cast<const double*>(b + o_width);
+    a.count = req->count;
+    a.hist = req->hist;
+    a.under = req->under;
+    a.over = req->over;
+    // a wave per (scenario, run of windows): runs as long as leave the chip some 32 768 waves (af_engine_summarize_series_windows' rule)
+    const uint32_t want_runs = (32768u + n - 1u) / n;
+    a.run = std::max(1u, W / want_runs);
+    const uint64_t items = (uint64_t)n * ((W + a.run - 1u) / a.run);
+    const size_t lds = (size_t)afsh::kWaves * lds_slots * (B + 2u) * 4u;
+    hipLaunchKernelGGL(afsh::af_shist_kernel, dim3((uint32_t)((items + afsh::kWaves - 1u) / afsh::kWaves)), dim3(afsh::kThreads), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the host vectors are read by the copies until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;

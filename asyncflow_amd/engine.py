@@ -417,6 +417,36 @@ class Engine:
                "af_engine_summarize_series_quantiles")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_series_histogram(self, n: int, n_groups: int, tick_edges: Any, bins: int, *, samples_ptr: int,
+                                   tick_capacity: int, counts_ptr: int, hist_ptr: int, count_ptr: int = 0, under_ptr: int = 0,
+                                   over_ptr: int = 0, group_ptr: int = 0, columns: Any = None, lo: Any = None,
+                                   width: Any = None) -> tuple[float, int]:
+        """Series-histogram analyzer on the device (``af_engine_summarize_series_histogram``): per (group, window of ticks)
+        ``count`` uint32 [n_groups, W] and, per output column, ``hist`` uint32 [n_groups, W, C, bins] and ``under`` / ``over``
+        uint32 [n_groups, W, C], W = len(tick_edges) - 1; a pointer of 0 skips ``count``, ``under`` or ``over``.
+        ``tick_edges``: HOST uint32 tick indices, strictly increasing; ``columns``: series indices (any order, duplicates
+        allowed) or None: every series, C = n_series; ``lo`` / ``width``: HOST float64 [C] each, one binning per output
+        column, or both None (0.0 and 1.0: the bin of a count is the count).  ``group_ptr`` as in :meth:`summarize_pooled`.
+        Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import _check_series_columns, check_series_bins, check_tick_edges
+
+        b = check_tick_edges(tick_edges)
+        col = None if columns is None else np.ascontiguousarray(_check_series_columns(columns, self.plan.n_series), dtype=np.uint32)
+        n_col = self.plan.n_series if col is None else int(col.shape[0])
+        n_bins, lo_v, width_v = check_series_bins(bins, n_col, lo, width)
+        plain = lo is None and width is None
+        pd = C.POINTER(C.c_double)
+        out = _abi.AfOutputs(0, None, int(tick_capacity), C.c_void_p(samples_ptr or None), C.c_void_p(counts_ptr or None))
+        req = _abi.AfSeriesHistogram(int(n), int(n_groups), int(b.shape[0] - 1), C.c_void_p(group_ptr or None),
+                                     b.ctypes.data_as(C.POINTER(C.c_uint32)), 0 if col is None else int(col.shape[0]),
+                                     col.ctypes.data_as(C.POINTER(C.c_uint32)) if col is not None else None, n_bins,
+                                     None if plain else lo_v.ctypes.data_as(pd), None if plain else width_v.ctypes.data_as(pd),
+                                     C.c_void_p(count_ptr or None), C.c_void_p(hist_ptr or None), C.c_void_p(under_ptr or None),
+                                     C.c_void_p(over_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_series_histogram(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_series_histogram")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:
         """``af_engine_gather``: ONE grouped RCCL all-gather of the per-scenario summaries.

@@ -415,6 +415,123 @@ def series_window_quantiles(samples: np.ndarray, tick_edges: Any, n_edges: int, 
     return count, quant
 
 
+def check_series_bins(bins: Any, n_columns: int, lo: Any = None, width: Any = None) -> tuple[int, np.ndarray, np.ndarray]:
+    """The binning of a series-histogram call as ``(n_bins, lo, width)``, ``lo`` and ``width`` float64 [n_columns], or
+    ValueError: ``bins`` a whole number from 1 to ``AF_MAX_SERIES_HISTOGRAM_BINS`` (1 024); ``lo`` / ``width`` None (0.0 /
+    1.0 each), a scalar or one value per output column; every ``lo`` finite, every ``width`` finite and above 0."""
+    if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)):
+        msg = f"bins must be a whole number, not {bins!r}"
+        raise ValueError(msg)
+    n_bins = int(bins)
+    if not 1 <= n_bins <= _abi.MAX_SERIES_HISTOGRAM_BINS:
+        msg = f"bins must be 1 .. {_abi.MAX_SERIES_HISTOGRAM_BINS}, not {n_bins}"
+        raise ValueError(msg)
+    out = []
+    for name, value, default in (("lo", lo, 0.0), ("width", width, 1.0)):
+        v = np.full(n_columns, default) if value is None else np.array(value, dtype=np.float64)
+        if v.ndim == 0:
+            v = np.full(n_columns, float(v))
+        if v.shape != (n_columns,):
+            msg = f"{name} must be a scalar or one value per output column ({n_columns}), not of shape {v.shape}"
+            raise ValueError(msg)
+        if not np.isfinite(v).all():
+            msg = f"{name} must be finite"
+            raise ValueError(msg)
+        out.append(np.ascontiguousarray(v))
+    if not (out[1] > 0.0).all():
+        msg = "width must be above 0"
+        raise ValueError(msg)
+    return n_bins, out[0], out[1]
+
+
+def series_window_histogram(samples: np.ndarray, tick_edges: Any, n_edges: int, bins: int, columns: Any = None,
+                            lo: Any = None, width: Any = None) -> dict[str, np.ndarray]:
+    """Occupancy histograms per window of ticks of ONE scenario's sampled series ``samples`` (uint32 words [n_series,
+    ticks]), the windows :func:`series_window_stats`'s.  Output column ``c`` reads series ``columns[c]`` (any order,
+    duplicates allowed; None: every series) with its own binning ``lo[c]``, ``width[c]`` (:func:`check_series_bins`).  A
+    value ``x`` -- the word of an integer series, the float32 value of a ``ram_in_use`` column, as float64 -- goes to
+    ``under`` where ``x < lo`` (-0.0 is not below 0.0); otherwise ``t = (x - lo) / width`` in float64, to ``over`` where
+    ``t >= bins``, else to bin ``floor(t)``.  Returns int64 arrays: ``count`` [W] (the ticks of the window), ``hist``
+    [W, C, bins], ``under`` and ``over`` [W, C], with ``under + hist.sum(-1) + over == count``; and ``bin_edges`` float64
+    [C, bins + 1] (``lo + k * width``) and ``ram`` bool [C] (the ``ram_in_use`` columns).  The definition the device analyzer
+    (``af_engine_summarize_series_histogram``) equals word for word."""
+    b = check_tick_edges(tick_edges)
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    n_series, ticks = words.shape
+    col = _check_series_columns(columns, n_series)
+    n_col = int(col.shape[0])
+    n_bins, lo_v, width_v = check_series_bins(bins, n_col, lo, width)
+    ram = ram_columns(n_series, n_edges)[col]
+    n_win = b.shape[0] - 1
+    r = np.minimum(b.astype(np.int64), ticks)
+    live = words[col, r[0]:r[-1]]                         # the rows inside the windows
+    with np.errstate(invalid="ignore"):                   # (an integer word read as float32 may be a NaN: not taken)
+        x = np.where(ram[:, None], live.view(np.float32).astype(np.float64), live.astype(np.float64))
+        below = x < lo_v[:, None]
+        t = (x - lo_v[:, None]) / width_v[:, None]
+        above = ~below & (t >= float(n_bins))
+        # the entry of a value among the bins + 2 words of its column: its bin, then under, then over
+        entry = np.where(below, n_bins, np.where(above, n_bins + 1, np.where(below | above | np.isnan(t), 0.0, t).astype(np.int64)))
+    win = np.searchsorted(r, np.arange(r[0], r[-1]), side="right") - 1     # (the last window that starts at or before the row)
+    flat = (win[None, :] * n_col + np.arange(n_col)[:, None]) * (n_bins + 2) + entry
+    table = np.bincount(flat.ravel(), minlength=n_win * n_col * (n_bins + 2)).reshape(n_win, n_col, n_bins + 2)
+    hist, under, over = (np.ascontiguousarray(v) for v in (table[:, :, :n_bins], table[:, :, n_bins], table[:, :, n_bins + 1]))
+    return {"count": np.diff(r), "hist": hist, "under": under, "over": over,
+            "bin_edges": lo_v[:, None] + np.arange(n_bins + 1, dtype=np.float64)[None, :] * width_v[:, None], "ram": ram}
+
+
+def series_histogram_quantiles(summary: dict[str, Any], levels: Any) -> np.ndarray:
+    """Quantiles ``levels`` (any number of them, each in [0, 1]) read off a series histogram ``summary`` -- what
+    :func:`series_window_histogram`, :meth:`ScenarioResults.get_series_histogram` or
+    :meth:`BatchedResults.series_histogram_summary` returned --: float64 [..., C, Q] on the host.  For integer series binned
+    with a whole ``lo`` and ``width == 1`` bin ``k`` holds the value ``lo + k`` alone, so the sorted sample is known from the
+    cumulative counts wherever it lies inside the bins, and the quantile is ``np.quantile``'s 'linear' value by the formula
+    of :func:`series_window_quantiles` (``v = (n - 1) * q``, ``t = v - floor(v)``, ``x[hi] - d * (1 - t)`` where ``t >=
+    0.5``, else ``x[lo] + d * t``): bit-equal to it.  NaN where a rank the level needs (``floor(v)``, and the next one
+    where ``t > 0``) lies in ``under`` / ``over``, and in an empty cell.  ValueError for any other binning and for a
+    ``ram_in_use`` column."""
+    q = np.array(levels, dtype=np.float64)
+    if q.ndim != 1 or q.shape[0] == 0 or not ((q >= 0.0) & (q <= 1.0)).all():
+        msg = "quantile levels must be a vector of at least one level in [0, 1]"
+        raise ValueError(msg)
+
+    def host(x: Any) -> np.ndarray:
+        return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+    hist, under, count = host(summary["hist"]).astype(np.int64), host(summary["under"]).astype(np.int64), host(summary["count"]).astype(np.int64)
+    edges = np.asarray(summary["bin_edges"], dtype=np.float64)
+    if np.asarray(summary["ram"]).any():
+        msg = "quantiles from a histogram need integer series: a ram_in_use column is selected"
+        raise ValueError(msg)
+    lo_v = edges[:, 0]
+    if not ((lo_v == np.floor(lo_v)).all() and (np.diff(edges, axis=1) == 1.0).all()):
+        msg = "quantiles from a histogram need a whole lo and width == 1 for every column"
+        raise ValueError(msg)
+    cum = np.cumsum(hist, axis=-1)                       # [..., C, B]
+    n = np.broadcast_to(count[..., None], under.shape)   # [..., C]
+    out = np.full(under.shape + (q.shape[0],), np.nan)
+
+    def value(rank: np.ndarray) -> np.ndarray:           # the rank-th smallest value, NaN outside the bins
+        k = rank - under
+        ok = (n > 0) & (k >= 0) & (k < cum[..., -1])
+        idx = (cum <= k[..., None]).sum(axis=-1)
+        return np.where(ok, lo_v + idx.astype(np.float64), np.nan)
+
+    for i, level in enumerate(q):
+        v = (n - 1).astype(np.float64) * level
+        f = np.floor(v)
+        t = v - f
+        lo_r = f.astype(np.int64)
+        hi_r = np.where(t > 0.0, np.minimum(lo_r + 1, n - 1), lo_r)
+        lo_x, hi_x = value(lo_r), value(hi_r)
+        d = hi_x - lo_x
+        out[..., i] = np.where(t >= 0.5, hi_x - d * (1.0 - t), lo_x + d * t)
+    return out
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -599,6 +716,22 @@ class ScenarioResults:
         b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
         out = series_window_excursions(self._samples, b, self._plan.n_edges, thresholds)
         out["tick_edges"] = b
+        return out
+
+    def get_series_histogram(self, bins: int = 64, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                             tick_edges: Any = None, series: Any = None, lo: Any = None, width: Any = None) -> dict[str, Any]:
+        """Occupancy histograms of the sampled series per window of ticks (:func:`series_window_histogram`): ``count`` [W],
+        ``hist`` int64 [W, C, bins], ``under`` / ``over`` [W, C], ``bin_edges`` [C, bins + 1], ``ram``, ``series`` (the
+        indices of the C selected series) and ``tick_edges``.  Windows as in :meth:`get_series_window_stats`; ``series``:
+        None (every series) or series indices, any order, duplicates allowed; ``lo`` / ``width``: None (0.0 / 1.0), a scalar
+        or one value per selected series."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        col = _check_series_columns(series, int(np.asarray(self._samples).shape[0]))
+        out: dict[str, Any] = series_window_histogram(self._samples, b, self._plan.n_edges, bins, col, lo, width)
+        out.update(series=col, tick_edges=b)
         return out
 
     def get_sampled_metrics(self) -> dict[str, dict[str, list[float]]]:
@@ -1541,6 +1674,129 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    def _series_binning(self, name: str, value: Any, col: np.ndarray, default: float) -> Any:
+        """``lo`` / ``width`` of a histogram call -- None, a scalar, one value per selected series or ``{series name:
+        value}`` (missing: the default) -- as None, a scalar or a vector per selected series."""
+        if not isinstance(value, dict):
+            return value
+        names = self.series_names()
+        for k in value:
+            if k not in names:
+                msg = f"unknown series {k!r} in {name} (series_names(): {names})"
+                raise ValueError(msg)
+        return np.array([float(value.get(names[j], default)) for j in col], dtype=np.float64)
+
+    def series_histogram_summary(self, bins: int = 64, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                                 tick_edges: Any = None, by: Any = None, series: Any = None, lo: Any = None,
+                                 width: Any = None) -> dict[str, Any]:
+        """Occupancy histograms of the sampled series of every (group, window of ticks, selected series), over all scenarios
+        of the group: P(ready queue length = k) per window and grid point.  Computed by the HIP analyzer
+        ``af_engine_summarize_series_histogram`` in one pass over the sample rows, equal word for word to
+        :func:`series_window_histogram` of the group's scenarios added up.  Windows and ``by`` as in
+        :meth:`series_window_summary`; ``series`` as in :meth:`series_quantile_summary` (the same series may appear twice
+        with two binnings); ``lo`` / ``width``: None (0.0 / 1.0: the bin of a count is the count), a scalar, one value per
+        selected series or ``{series name: value}``.  Returns torch tensors on the run's device: ``hist`` int64 [G, W, C,
+        bins], ``under``, ``over`` [G, W, C] (the values below ``lo`` / at or past ``lo + bins * width``) and ``count`` [G,
+        W], ``under + hist.sum(-1) + over == count``; and ``bin_edges`` float64 [C, bins + 1], ``ram`` bool [C], ``series``
+        (the selected names), ``tick_edges``, ``times``, ``replicas`` [G], ``series_histogram_ms``, ``scratch_bytes``.
+        :func:`series_histogram_quantiles` reads quantiles off the result."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_samples()
+        col = self._series_columns(series)
+        n_col = int(col.shape[0])
+        n_bins, lo_v, width_v = check_series_bins(bins, n_col, self._series_binning("lo", lo, col, 0.0),
+                                                  self._series_binning("width", width, col, 1.0))
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        n_win = int(b.shape[0] - 1)
+        samples = self._samples_t
+        dev = samples.device
+        count = torch.empty((n_groups, n_win), dtype=torch.int32, device=dev)
+        hist = torch.empty((n_groups, n_win, n_col, n_bins), dtype=torch.int32, device=dev)
+        under, over = (torch.empty((n_groups, n_win, n_col), dtype=torch.int32, device=dev) for _ in range(2))
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        plain = lo is None and width is None
+        ms, scratch = self._summ_engine.summarize_series_histogram(
+            len(self), n_groups, b, n_bins, samples_ptr=samples.data_ptr(), tick_capacity=int(samples.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(), hist_ptr=hist.data_ptr(),
+            under_ptr=under.data_ptr(), over_ptr=over.data_ptr(), group_ptr=grp.data_ptr(),
+            columns=None if series is None else col, lo=None if plain else lo_v, width=None if plain else width_v)
+        names = self.series_names()
+        return {"hist": hist.to(torch.int64) & 0xFFFFFFFF, "under": under.to(torch.int64) & 0xFFFFFFFF,
+                "over": over.to(torch.int64) & 0xFFFFFFFF, "count": count.to(torch.int64) & 0xFFFFFFFF,
+                "bin_edges": lo_v[:, None] + np.arange(n_bins + 1, dtype=np.float64)[None, :] * width_v[:, None],
+                "ram": ram_columns(self.plan.n_series, self.plan.n_edges)[col], "series": [names[j] for j in col],
+                "tick_edges": b, "times": b[:-1].astype(np.float64) * self.plan.sample_period,
+                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "series_histogram_ms": ms, "scratch_bytes": scratch}
+
+    def series_histogram_bands(self, bins: int = 64, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                               tick_edges: Any = None, by: Any = None, series: Any = None, lo: Any = None, width: Any = None,
+                               level: float = 0.95, q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of the histogram SHARES: every scenario's own ``hist / count``
+        (``series_histogram_summary(by="scenario")``), then per group (``by``) and window, over the group's replicas whose
+        window is not empty (``n`` [G, W] of them), ``mean``, ``std``, ``ci_halfwidth`` (at ``level``) and the linear
+        quantiles ``q_lo`` / ``q_hi`` (``q``) as :func:`window_bands_by_group` gives them: numpy float64 [G, W, C, bins].
+        ``pooled`` [G, W, C, bins], ``pooled_under`` / ``pooled_over`` [G, W, C] and ``pooled_count`` [G, W] are the
+        histogram of the group's replicas taken together (``series_histogram_summary(by=by)``) as numpy int64.  Reduced on
+        the host, in scenario order, as :meth:`series_quantile_bands` is."""
+        import torch
+
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        per = self.series_histogram_summary(bins, tick_edges=b, by="scenario", series=series, lo=lo, width=width)
+        shape = tuple(per["hist"].shape[2:])
+        cnt = per["count"].cpu()
+        share = per["hist"].cpu().to(torch.float64) / cnt.to(torch.float64)[:, :, None, None]   # (0 / 0: NaN, not valid)
+        out = window_bands_by_group(share.flatten(2), ids, n_groups, level, q, valid=cnt > 0)
+        for k in ("mean", "std", "ci_halfwidth", "q_lo", "q_hi"):
+            out[k] = out[k].reshape(out[k].shape[:2] + shape)
+        pooled = self.series_histogram_summary(bins, tick_edges=b, by=ids, series=series, lo=lo, width=width)
+        out["pooled"] = pooled["hist"].cpu().numpy()[:n_groups]
+        for k in ("under", "over", "count"):
+            out[f"pooled_{k}"] = pooled[k].cpu().numpy()[:n_groups]
+        out.update(bin_edges=per["bin_edges"], ram=per["ram"], series=per["series"], tick_edges=b, times=per["times"])
+        return out
+
+    def save_series_histogram_summary(self, path: str, by: Any = None, *, bins: int = 64, series: Any = None, lo: Any = None,
+                                      width: Any = None, window_s: float | None = None, ticks_per_window: int | None = None,
+                                      tick_edges: Any = None) -> dict[str, np.ndarray]:
+        """Columnar dump of the series histograms with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas``, ``series_hist_count`` [G, W] and per selected series ``series_hist:<series>`` [G, W, bins],
+        ``series_hist_under:<series>`` and ``series_hist_over:<series>`` [G, W] (the group's replicas taken together) and
+        the per-file vector ``series_hist_bin_edges:<series>`` [bins + 1]; ``series_hist_tick_edges`` [W + 1] and
+        ``series_hist_times`` [W] are per-file vectors too.  A series may be selected once.  ``.npz`` or ``.parquet``;
+        :func:`load_summary` reads it back."""
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        pooled = self.series_histogram_summary(bins, tick_edges=b, by=ids, series=series, lo=lo, width=width)
+        if len(set(pooled["series"])) != len(pooled["series"]):
+            msg = "a series may be selected once in a saved histogram summary (the columns are named after it)"
+            raise ValueError(msg)
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(pooled["replicas"], dtype=np.int64)
+        cols["series_hist_count"] = np.ascontiguousarray(pooled["count"].cpu().numpy()[:n_groups], dtype=np.int64)
+        hist, under, over = (pooled[k].cpu().numpy()[:n_groups] for k in ("hist", "under", "over"))
+        for c, name in enumerate(pooled["series"]):
+            cols[f"series_hist:{name}"] = np.ascontiguousarray(hist[:, :, c], dtype=np.int64)
+            cols[f"series_hist_under:{name}"] = np.ascontiguousarray(under[:, :, c], dtype=np.int64)
+            cols[f"series_hist_over:{name}"] = np.ascontiguousarray(over[:, :, c], dtype=np.int64)
+            cols[f"series_hist_bin_edges:{name}"] = np.ascontiguousarray(pooled["bin_edges"][c], dtype=np.float64)
+        cols["series_hist_tick_edges"] = np.asarray(b, dtype=np.float64)
+        cols["series_hist_times"] = np.asarray(pooled["times"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -1771,7 +2027,7 @@ def _write_columns(path: str, cols: dict[str, np.ndarray], n: int) -> None:
         import pyarrow as pa
         import pyarrow.parquet as pq
 
-        table = {k: (pa.array(list(v)) if v.ndim == 2 and v.shape[0] == n else pa.array(v))
+        table = {k: (pa.array(v.tolist()) if v.ndim > 2 else pa.array(list(v)) if v.ndim == 2 and v.shape[0] == n else pa.array(v))
                  for k, v in cols.items() if v.shape[:1] == (n,)}
         meta = {k: ",".join(map(str, v.tolist())) for k, v in cols.items() if v.shape[:1] != (n,)}
         pq.write_table(pa.table(table).replace_schema_metadata(meta), path)
@@ -1953,6 +2209,18 @@ class ShardedResults:
 
     def save_series_excursion_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_excursion_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_histogram_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_histogram_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_histogram_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_histogram_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_series_histogram_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_series_histogram_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:

@@ -586,6 +586,55 @@ typedef struct af_series_excursions {
 } af_series_excursions_t;
 int af_engine_summarize_series_excursions(af_engine_t* engine, const af_outputs_t* out, af_series_excursions_t* series_excursions);
 
+/* OCCUPANCY HISTOGRAMS OF THE SAMPLED SERIES per window of ticks, group and output column on the device
+ * (asyncflow_amd/csrc/af_series_histogram.hpp): P(queue length = k) per window and grid point, the distribution an M/M/c or
+ * Erlang check compares against; while no value falls outside the bins it also holds every quantile of an integer series.
+ * Cells: those of af_series_windows_t.  Window w of scenario s is its sample rows [min(b[w], m_s), min(b[w + 1], m_s)), with
+ * m_s = min(counts[s][AF_CNT_TICKS], tick_capacity); rows at or past m_s and the padding words of a row are never read.  The
+ * sample of (g, w, c) is series columns[c] over those rows of every member of g (group as in af_pooled_t).  Output column c
+ * has a binning of its own, lo[c] and width[c] (NULL, both: 0.0 and 1.0 each), so one series may appear twice with two
+ * binnings.  Bin of a value, bit for bit: x is the value as f64 exactly as af_series_windows_t.above takes it -- (double)word
+ * of an integer series, (double)(float) of a ram_in_use column --;
+ *     x < lo[c]                      -> under   (-0.0 is not below 0.0; a -2^-45 residue is)
+ *     t = (x - lo[c]) / width[c]     one f64 subtraction and one f64 division, each rounded to nearest
+ *     t >= (double)n_bins            -> over
+ *     otherwise                      -> bin (uint32_t)t
+ * Outputs, u32: count [G][W] the values in the cell per column; hist [G][W][C][n_bins]; under, over [G][W][C], with
+ * under + sum(hist) + over == count for every cell and column.  A NULL count / under / over skips that output.  An empty
+ * cell, or a group without members: zeros everywhere.
+ * Exactness: one streaming pass; every combining operation is an integer + (integer atomics on zeroed outputs): the result
+ * does not depend on the launch, on the batch a scenario sits in, on which other columns the call holds, or on the run.
+ * Refused, no output buffer touched: n_bins == 0 or more than AF_MAX_SERIES_HISTOGRAM_BINS, a width that is <= 0, NaN or
+ * infinite, a lo that is NaN or infinite, exactly one of lo / width NULL, tick_edges NULL or not strictly increasing or
+ * n_windows == 0, a column index >= af_series_count, n_columns == 0 with columns != NULL or the reverse, a group id >=
+ * n_groups, outputs.samples or outputs.counts NULL, hist NULL (AF_ERR_INVALID); a cell of 2^32 or more values, n_groups *
+ * n_windows >= 2^32 - 1, tick_capacity >= 2^31 (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).  `out` needs
+ * samples, tick_capacity and counts; clock is not read.
+ * Scratch kept by the engine (shared with the other analyzers): 4 B per edge + 4 B per series + 24 B per output column +
+ * 1 544 B -- the edges, the columns sorted by series with their lo / width and the passes they are read in; the group ids are
+ * read where the caller keeps them.  No per-element and no per-cell records.  Synchronous; the struct is written back. */
+#define AF_MAX_SERIES_HISTOGRAM_BINS 1024
+typedef struct af_series_histogram {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing */
+    uint32_t n_columns;
+    const uint32_t* columns;     /* HOST [n_columns] series indices < af_series_count, any order, duplicates allowed;
+                                    NULL with n_columns == 0: every series, in device order */
+    uint32_t n_bins;             /* 1 .. AF_MAX_SERIES_HISTOGRAM_BINS */
+    const double* lo;            /* HOST [C] finite, C = n_columns or af_series_count; NULL (with width): 0.0 each */
+    const double* width;         /* HOST [C] finite and > 0; NULL (with lo): 1.0 each */
+    uint32_t* count;             /* DEVICE [n_groups][n_windows]; NULL skips */
+    uint32_t* hist;              /* DEVICE [n_groups][n_windows][C][n_bins] */
+    uint32_t* under;             /* DEVICE [n_groups][n_windows][C]; NULL skips */
+    uint32_t* over;              /* DEVICE [n_groups][n_windows][C]; NULL skips */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_series_histogram_t;
+int af_engine_summarize_series_histogram(af_engine_t* engine, const af_outputs_t* out, af_series_histogram_t* series_histogram);
+
 /* Arbitrary latency QUANTILES and SLO counts per group and time window on the device (asyncflow_amd/csrc/af_quantiles.hpp):
  * p99.9 at a grid point, p90 during an outage, how many requests met a 200 ms objective in every 10 s window.  The cells and
  * their samples are af_windows_t's: cell c = g * n_windows + w holds, in ascending scenario index over the members of g,
