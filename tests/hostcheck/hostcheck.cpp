@@ -4,7 +4,8 @@
 // HIP kernel runs) with g++ for ONE lane, so that the CPU test-suite
 // (-m "not gpu") can differential-test the kernel logic against the oracle
 // without a GPU.  It is built into tests/hostcheck/libaf_hostcheck.so by
-// tests/hostcheck/build.py, loaded only by tests/, and is NOT a fallback: the
+// tests/hostcheck/build.py (and, with sancheck_main.cpp, into a stand-alone program under
+// AddressSanitizer + UBSan: build_sanitized), loaded only by tests/, and is NOT a fallback: the
 // asyncflow_amd package neither builds, loads nor knows about it, and raises if
 // the HIP library or a GPU is missing.
 #include <algorithm>
@@ -12,11 +13,19 @@
 #include <cstring>
 #include <vector>
 
+#if defined(HC_FLOW_SLICE)
+// af_core.hpp holds one free function that is not inline (cold_endpoint_pick, AF_CORE_NOINLINE): each slice of a build in several
+// translation units (HC_FLOW_VARIANTS below) keeps its copy under a name of its own
+#define HC_CAT2(a, b) a##b
+#define HC_CAT(a, b) HC_CAT2(a, b)
+#define cold_endpoint_pick HC_CAT(cold_endpoint_pick_slice, HC_FLOW_SLICE)
+#endif
 #include "../../asyncflow_amd/csrc/af_plan_pack.hpp"
 #include "../../asyncflow_amd/csrc/af_flow_host.hpp"
 #include "../../asyncflow_amd/csrc/af_pregen.hpp"
 #include "wave_emul.hpp"
 
+#if !defined(HC_FLOW_SLICE)   // (a slice holds Flow<> instantiations only: see HC_FLOW_VARIANTS below)
 namespace {
 
 struct MemHost {
@@ -26,6 +35,7 @@ struct MemHost {
 };
 
 int g_two_pass = 0, g_reruns = 0;
+int g_sim_variant = -1;   // what the last hc_simulate ran: 0 lean lane only, 1 SimPy-order lane, 2 lean lane, then the SimPy-order rerun
 uint32_t *g_online_hist = nullptr, *g_online_rps = nullptr;
 uint32_t g_online_bins = 0, g_online_buckets = 0;
 double g_online_scale = 0.0;
@@ -104,6 +114,7 @@ extern "C" int hc_simulate(const af_plan_t* p, uint64_t seed, uint32_t n_ovr, co
     if (g_online_rps) std::memset(g_online_rps, 0, 4u * g_online_buckets);
     std::vector<uint64_t> tie(L.tie_words, 0ull);
     af::PreDraws D{draws.data(), n_draw, flags_in, tie.data()};
+    g_sim_variant = 1;
     if (g_two_pass && !V.every_event_in_order) {  // what af_engine_run does: lean variant first, SimPy-order variant on demand
         af::Lane<MemHost, false> lean(V, L, MemHost{w.data()}, O, D, seed);
         lean.init(ovr_param, idx.data(), n_ovr, [&](uint32_t k) { return ovr_value[k]; });
@@ -111,6 +122,7 @@ extern "C" int hc_simulate(const af_plan_t* p, uint64_t seed, uint32_t n_ovr, co
         }
         lean.write_counts();
         g_reruns += (lean.flags & af::FLAG_SHARED_INSTANT) ? 1 : 0;
+        g_sim_variant = (lean.flags & af::FLAG_SHARED_INSTANT) ? 2 : 0;
         if (!(lean.flags & af::FLAG_SHARED_INSTANT)) return 0;
         std::fill(w.begin(), w.end(), 0xDEADBEEFDEADBEEFull);  // the second pass starts over
         if (g_online_hist) std::memset(g_online_hist, 0, 4u * g_online_bins);
@@ -137,18 +149,89 @@ extern "C" void hc_set_online(uint32_t* hist, uint32_t bins, double hist_max, ui
     g_online_buckets = buckets;
 }
 extern "C" int hc_reruns(void) { return g_reruns; }
+extern "C" int hc_sim_variant(void) { return g_sim_variant; }
 
 extern "C" uint64_t hc_bytes_per_lane(uint32_t cap, uint32_t fcap, uint32_t n_edges, uint32_t n_servers,
                                       uint32_t n_lb, uint32_t n_rows, uint32_t mask) {
     return af::layout_bytes_per_lane(af::make_layout(cap, fcap, n_edges, n_servers, n_lb, n_rows, mask));
 }
 
+#endif  // !HC_FLOW_SLICE
+
 // ---- the stage-parallel kernel (af_flow.hpp) on the 64-fibre wave emulator ---------------------------
+// The instantiations the engine can launch (engine.hip: plan_flow and the second chance), by dispatch id.  hc_flow_simulate
+// picks one and records its id (hc_flow_variant); a build that compiles them in several translation units
+// (build.py: build_sanitized) takes its slices from the same table.
+namespace hcv {
+constexpr uint32_t kAll = aff::FEAT_ALL, kRobust = aff::FEAT_ALL | aff::FEAT_TIEBREAK | aff::FEAT_BIGLIST, kLC = aff::FEAT_LC;
+constexpr uint32_t kGen = aff::FEAT_GENSRV, kChain = aff::FEAT_CHAIN;
+template <uint32_t IPL, uint32_t FEAT>
+void run_flow(const aff::FlowArgs& a, uint64_t* lds) {
+    aff::Flow<emu::WaveEmu, IPL, FEAT> f(a);
+    f.run(lds, 0u);
+}
+}  // namespace hcv
+#define HC_FLOW_VARIANTS(X) \
+    X( 0, 1, hcv::kAll | aff::FEAT_BIGLIST | hcv::kGen | hcv::kLC | hcv::kChain) \
+    X( 1, 1, hcv::kRobust | hcv::kGen | hcv::kLC | hcv::kChain) \
+    X( 2, 1, hcv::kAll | aff::FEAT_BIGLIST | hcv::kGen | hcv::kChain) \
+    X( 3, 1, hcv::kRobust | hcv::kGen | hcv::kChain) \
+    X( 4, 1, hcv::kRobust | hcv::kLC | hcv::kChain) \
+    X( 5, 1, hcv::kAll | hcv::kLC | hcv::kChain) \
+    X( 6, 2, hcv::kAll | hcv::kLC | hcv::kChain) \
+    X( 7, 4, hcv::kAll | hcv::kLC | hcv::kChain) \
+    X( 8, 1, hcv::kRobust | hcv::kChain) \
+    X( 9, 1, hcv::kAll | hcv::kChain) \
+    X(10, 2, hcv::kAll | hcv::kChain) \
+    X(11, 4, hcv::kAll | hcv::kChain) \
+    X(12, 1, hcv::kAll | aff::FEAT_BIGLIST | hcv::kLC | hcv::kGen) \
+    X(13, 1, hcv::kAll | aff::FEAT_BIGLIST | hcv::kGen) \
+    X(14, 1, hcv::kRobust | hcv::kLC | hcv::kGen) \
+    X(15, 1, hcv::kRobust | hcv::kGen) \
+    X(16, 1, hcv::kRobust | hcv::kLC) \
+    X(17, 1, hcv::kRobust) \
+    X(18, 1, hcv::kAll | hcv::kLC) \
+    X(19, 2, hcv::kAll | hcv::kLC) \
+    X(20, 4, hcv::kAll | hcv::kLC) \
+    X(21, 1, 0u) \
+    X(22, 1, aff::FEAT_FAR) \
+    X(23, 1, aff::FEAT_MARKS | aff::FEAT_FAR) \
+    X(24, 1, hcv::kAll) \
+    X(25, 2, 0u) \
+    X(26, 2, aff::FEAT_FAR) \
+    X(27, 2, aff::FEAT_MARKS | aff::FEAT_FAR) \
+    X(28, 2, hcv::kAll) \
+    X(29, 4, hcv::kAll)
+#define HC_FLOW_VARIANT_COUNT 30
+
+#if defined(HC_FLOW_SLICE)
+// One slice of the table as a translation unit of its own: -DHC_FLOW_SLICE=k -DHC_FLOW_SLICES=n instantiates the variants
+// with id % n == k and nothing else of this file.
+namespace {
+template <bool On, uint32_t IPL, uint32_t FEAT>
+void* slice_entry() {
+    if constexpr (On) return reinterpret_cast<void*>(&hcv::run_flow<IPL, FEAT>);
+    else return nullptr;
+}
+#define HC_X(ID, IPL, FEAT) slice_entry<(ID % HC_FLOW_SLICES) == HC_FLOW_SLICE, IPL, FEAT>(),
+__attribute__((used)) void* const g_slice[] = {HC_FLOW_VARIANTS(HC_X) nullptr};
+#undef HC_X
+}  // namespace
+#else
+#if defined(HC_FLOW_SLICES)   // the variants live in the slices
+#define HC_X(ID, IPL, FEAT) extern template void hcv::run_flow<IPL, FEAT>(const aff::FlowArgs&, uint64_t*);
+HC_FLOW_VARIANTS(HC_X)
+#undef HC_X
+#endif
+
 namespace {
 std::string g_flow_reason;
+int g_flow_variant = -1;
 }
 
 extern "C" const char* hc_flow_reason(void) { return g_flow_reason.c_str(); }
+// dispatch id (HC_FLOW_VARIANTS) of the last hc_flow_simulate that ran a scenario, -1: none yet
+extern "C" int hc_flow_variant(void) { return g_flow_variant; }
 
 // Returns 0 when the scenario ran (counts[AF_CNT_FLAGS] may carry FLAG_FLOW_FALLBACK = 1 << 8 and the reason
 // bits 9..12: the product then re-runs the scenario on the sequential kernels), 1 when the plan is not
@@ -161,11 +244,13 @@ extern "C" int hc_flow_simulate(const af_plan_t* p, uint64_t seed, uint32_t n_ov
     // the second-chance instantiation (FEAT_TIEBREAK | FEAT_BIGLIST): send times + lists of their own lengths;
     // bits 16..31 = entries of the long list(s) (0: 256), bits 12..14 = which list is long (0: all four; else index + 1, the others hold 256)
     const bool gen_srv = aff::flow_needs_general_servers(*p);   // (several endpoints per server, ...: the long-list instantiation with the general server station)
-    const bool robust = (ipl & 0x100u) != 0u || gen_srv;
+    // general servers: the second-chance form unless bit 10 asks for the compact first launch below (engine.hip launches that one first)
+    const bool compact = gen_srv && (ipl & 0x500u) == 0x400u;
+    const bool robust = (ipl & 0x100u) != 0u || (gen_srv && !compact);
     const bool near_only = (ipl & 0x200u) != 0u;   // the lean instantiations without FEAT_FAR (the sender enters both ends of every message)
     const uint32_t big_cap = (ipl >> 16) ? (ipl >> 16) : 256u, big_which = (ipl >> 12) & 7u;
     ipl &= 0xFFu;
-    if (robust) ipl = 4;
+    if (robust || compact) ipl = 4;
     if (ipl != 1 && ipl != 2 && ipl != 4) return AF_ERR_INVALID;
     g_flow_reason = aff::flow_ineligible_reason(*p);
     if (!g_flow_reason.empty()) return 1;
@@ -273,46 +358,52 @@ extern "C" int hc_flow_simulate(const af_plan_t* p, uint64_t seed, uint32_t n_ov
     if (g_online_rps) std::memset(g_online_rps, 0, 4u * g_online_buckets);
     a.n_fallback = nullptr;
 
-    std::vector<uint64_t> lds(pk.words.size() + a.L.n_words + 2u, 0xDEADBEEFDEADBEEFull);
+    std::vector<uint64_t> lds(pk.words.size() + a.L.n_words, 0xDEADBEEFDEADBEEFull);
     // the instantiation the engine would launch: the lean one when the launch needs none of the optional features
     const bool lean = p->n_edge_marks == 0 && p->n_srv_marks == 0 && !g_online_hist && !g_online_rps && (a.L.ring_rows != 0 || !samples);
     const bool lc = a.lb_least_connections != 0u;
     const bool marks_only = !lean && !g_online_hist && !g_online_rps && (a.L.ring_rows != 0 || !samples);   // (engine.hip: config-4-like launches)
-    constexpr uint32_t kAll = aff::FEAT_ALL, kRobust = aff::FEAT_ALL | aff::FEAT_TIEBREAK | aff::FEAT_BIGLIST, kLC = aff::FEAT_LC;
-    constexpr uint32_t kGen = aff::FEAT_GENSRV;
     const bool chain = aff::flow_needs_chain(*p);   // servers feed servers: the FEAT_CHAIN instantiations (engine.hip: plan_flow)
-    constexpr uint32_t kChain = aff::FEAT_CHAIN;
+    uint32_t id;
+    if (chain && gen_srv && lc && !robust) id = 0u;
+    else if (chain && gen_srv && lc) id = 1u;
+    else if (chain && gen_srv && !robust) id = 2u;
+    else if (chain && gen_srv) id = 3u;
+    else if (chain && lc && robust) id = 4u;
+    else if (chain && lc && ipl == 1) id = 5u;
+    else if (chain && lc && ipl == 2) id = 6u;
+    else if (chain && lc) id = 7u;
+    else if (chain && robust) id = 8u;
+    else if (chain && ipl == 1) id = 9u;
+    else if (chain && ipl == 2) id = 10u;
+    else if (chain) id = 11u;
+    else if (gen_srv && lc && !robust) id = 12u;
+    else if (gen_srv && !robust) id = 13u;
+    else if (gen_srv && lc) id = 14u;
+    else if (gen_srv) id = 15u;
+    else if (robust && lc) id = 16u;
+    else if (robust) id = 17u;
+    else if (lc && ipl == 1) id = 18u;
+    else if (lc && ipl == 2) id = 19u;
+    else if (lc) id = 20u;
+    else if (ipl == 1 && lean && near_only) id = 21u;
+    else if (ipl == 1 && lean) id = 22u;
+    else if (ipl == 1 && marks_only) id = 23u;
+    else if (ipl == 1) id = 24u;
+    else if (ipl == 2 && lean && near_only) id = 25u;
+    else if (ipl == 2 && lean) id = 26u;
+    else if (ipl == 2 && marks_only) id = 27u;
+    else if (ipl == 2) id = 28u;
+    else id = 29u;
+    g_flow_variant = (int)id;
+    uint64_t* const smem = lds.data();
     auto body = [&]() {
-        if (chain && gen_srv && lc && !robust) { aff::Flow<emu::WaveEmu, 1, kAll | aff::FEAT_BIGLIST | kGen | kLC | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && gen_srv && lc) { aff::Flow<emu::WaveEmu, 1, kRobust | kGen | kLC | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && gen_srv && !robust) { aff::Flow<emu::WaveEmu, 1, kAll | aff::FEAT_BIGLIST | kGen | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && gen_srv) { aff::Flow<emu::WaveEmu, 1, kRobust | kGen | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && lc && robust) { aff::Flow<emu::WaveEmu, 1, kRobust | kLC | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && lc && ipl == 1) { aff::Flow<emu::WaveEmu, 1, kAll | kLC | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && lc && ipl == 2) { aff::Flow<emu::WaveEmu, 2, kAll | kLC | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && lc) { aff::Flow<emu::WaveEmu, 4, kAll | kLC | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && robust) { aff::Flow<emu::WaveEmu, 1, kRobust | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && ipl == 1) { aff::Flow<emu::WaveEmu, 1, kAll | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain && ipl == 2) { aff::Flow<emu::WaveEmu, 2, kAll | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (chain) { aff::Flow<emu::WaveEmu, 4, kAll | kChain> f(a); f.run(lds.data(), 0u); }
-        else if (gen_srv && lc && !robust) { aff::Flow<emu::WaveEmu, 1, kAll | aff::FEAT_BIGLIST | kLC | kGen> f(a); f.run(lds.data(), 0u); }
-        else if (gen_srv && !robust) { aff::Flow<emu::WaveEmu, 1, kAll | aff::FEAT_BIGLIST | kGen> f(a); f.run(lds.data(), 0u); }
-        else if (gen_srv && lc) { aff::Flow<emu::WaveEmu, 1, kRobust | kLC | kGen> f(a); f.run(lds.data(), 0u); }
-        else if (gen_srv) { aff::Flow<emu::WaveEmu, 1, kRobust | kGen> f(a); f.run(lds.data(), 0u); }
-        else if (robust && lc) { aff::Flow<emu::WaveEmu, 1, kRobust | kLC> f(a); f.run(lds.data(), 0u); }
-        else if (robust) { aff::Flow<emu::WaveEmu, 1, kRobust> f(a); f.run(lds.data(), 0u); }
-        else if (lc && ipl == 1) { aff::Flow<emu::WaveEmu, 1, kAll | kLC> f(a); f.run(lds.data(), 0u); }
-        else if (lc && ipl == 2) { aff::Flow<emu::WaveEmu, 2, kAll | kLC> f(a); f.run(lds.data(), 0u); }
-        else if (lc) { aff::Flow<emu::WaveEmu, 4, kAll | kLC> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 1 && lean && near_only) { aff::Flow<emu::WaveEmu, 1, 0u> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 1 && lean) { aff::Flow<emu::WaveEmu, 1, aff::FEAT_FAR> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 1 && marks_only) { aff::Flow<emu::WaveEmu, 1, aff::FEAT_MARKS | aff::FEAT_FAR> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 1) { aff::Flow<emu::WaveEmu, 1> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 2 && lean && near_only) { aff::Flow<emu::WaveEmu, 2, 0u> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 2 && lean) { aff::Flow<emu::WaveEmu, 2, aff::FEAT_FAR> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 2 && marks_only) { aff::Flow<emu::WaveEmu, 2, aff::FEAT_MARKS | aff::FEAT_FAR> f(a); f.run(lds.data(), 0u); }
-        else if (ipl == 2) { aff::Flow<emu::WaveEmu, 2> f(a); f.run(lds.data(), 0u); }
-        else { aff::Flow<emu::WaveEmu, 4> f(a); f.run(lds.data(), 0u); }
+        switch (id) {
+#define HC_X(ID, IPL, FEAT) case ID: hcv::run_flow<IPL, FEAT>(a, smem); break;
+            HC_FLOW_VARIANTS(HC_X)
+#undef HC_X
+            default: std::abort();
+        }
     };
     emu::run_wave(body);
     return 0;
@@ -369,3 +460,4 @@ extern "C" int64_t hc_arrivals(int which, uint64_t seed, uint32_t dist, double m
     *flags = L.flags;
     return L.k;
 }
+#endif  // HC_FLOW_SLICE

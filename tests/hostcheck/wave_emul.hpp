@@ -7,7 +7,7 @@
 // anyone may overwrite the exchange buffer.  Deterministic, no data races, and it checks the
 // discipline the GPU needs as well: every lane must reach the SAME sequence of cross-lane operations
 // (a lane that takes a different path trips the `site` assertion instead of hanging the wave).
-// Built into tests/hostcheck/libaf_hostcheck.so only; never part of the product.
+// Built into tests/hostcheck/libaf_hostcheck.so and the sanitized stand-alone program (sancheck_main.cpp) only; never part of the product.
 #pragma once
 
 #include <execinfo.h>
@@ -19,19 +19,34 @@
 #include <functional>
 #include <vector>
 
+// AddressSanitizer keeps a shadow of the CURRENT stack: every swapcontext is announced with the bounds of the stack it goes to
+// (without that: "doesn't fully support makecontext/swapcontext ... may produce false positives").  Nothing in other builds.
+#if defined(__SANITIZE_ADDRESS__)
+#include <sanitizer/common_interface_defs.h>
+#define EMU_ASAN 1
+#else
+#define EMU_ASAN 0
+#endif
+
 namespace emu {
 
 struct WaveState {
     static constexpr int kLanes = 64;
     ucontext_t main_ctx;
     ucontext_t ctx[kLanes];
-    std::vector<char> stacks;
+    std::vector<char> stacks[kLanes];   // (one allocation each: a sanitized build has redzones between them)
     bool done[kLanes];
     int n_done = 0;
     int current = -1;
     uint64_t xbuf[kLanes];
     uint32_t site[kLanes];
     std::function<void()> body;
+#if EMU_ASAN
+    void* fake_main = nullptr;          // the sanitizer's fake-stack handles of the scheduler and of each fibre
+    void* fake[kLanes] = {};
+    const void* main_bottom = nullptr;  // the scheduler's stack, learnt when the first fibre starts
+    size_t main_size = 0;
+#endif
 };
 
 inline WaveState*& cur() {
@@ -39,31 +54,46 @@ inline WaveState*& cur() {
     return w;
 }
 
-inline void yield_lane() {
-    WaveState* w = cur();
+// fibre -> scheduler; `last`: the fibre never runs again (its fake stack is released)
+inline void to_scheduler(WaveState* w, bool last) {
+#if EMU_ASAN
+    __sanitizer_start_switch_fiber(last ? nullptr : &w->fake[w->current], w->main_bottom, w->main_size);
+#else
+    (void)last;
+#endif
     swapcontext(&w->ctx[w->current], &w->main_ctx);
+#if EMU_ASAN
+    __sanitizer_finish_switch_fiber(w->fake[w->current], nullptr, nullptr);
+#endif
 }
+
+inline void yield_lane() { to_scheduler(cur(), false); }
 
 inline void fibre_entry() {
     WaveState* w = cur();
+#if EMU_ASAN
+    __sanitizer_finish_switch_fiber(nullptr, &w->main_bottom, &w->main_size);
+#endif
     w->body();
     w->done[w->current] = true;
     w->n_done += 1;
-    swapcontext(&w->ctx[w->current], &w->main_ctx);
+    to_scheduler(w, true);
 }
 
 // run `body` on 64 fibres until all of them return
 inline void run_wave(const std::function<void()>& body) {
     WaveState w;
-    constexpr size_t kStack = 512u * 1024u;
-    w.stacks.resize(kStack * WaveState::kLanes);
+    // A fibre uses ~5 KB (measured high-water mark, sanitized -O1 build, the largest instantiations).  AddressSanitizer's swapcontext
+    // clears the shadow of the whole stack it switches to, twice per switch, so its stacks are kept small: 2 MiB ones made a run 18x slower.
+    constexpr size_t kStack = (EMU_ASAN ? 64u : 512u) * 1024u;
     w.body = body;
     WaveState* prev = cur();
     cur() = &w;
     for (int i = 0; i < WaveState::kLanes; ++i) {
         w.done[i] = false;
         getcontext(&w.ctx[i]);
-        w.ctx[i].uc_stack.ss_sp = w.stacks.data() + kStack * (size_t)i;
+        w.stacks[i].resize(kStack);
+        w.ctx[i].uc_stack.ss_sp = w.stacks[i].data();
         w.ctx[i].uc_stack.ss_size = kStack;
         w.ctx[i].uc_link = &w.main_ctx;
         makecontext(&w.ctx[i], fibre_entry, 0);
@@ -72,7 +102,13 @@ inline void run_wave(const std::function<void()>& body) {
         for (int i = 0; i < WaveState::kLanes; ++i) {
             if (w.done[i]) continue;
             w.current = i;
+#if EMU_ASAN
+            __sanitizer_start_switch_fiber(&w.fake_main, w.ctx[i].uc_stack.ss_sp, w.ctx[i].uc_stack.ss_size);
+#endif
             swapcontext(&w.main_ctx, &w.ctx[i]);
+#if EMU_ASAN
+            __sanitizer_finish_switch_fiber(w.fake_main, nullptr, nullptr);
+#endif
         }
     }
     cur() = prev;

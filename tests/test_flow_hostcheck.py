@@ -428,7 +428,9 @@ def test_general_servers_compact_first_launch():
     """Round 4: the FIRST launch of a plan with general servers uses the long-list instantiation WITHOUT send times and with
     lists sized by the load (128 entries here) -- 20 instead of 41 KB of LDS per wave, 7 instead of 3 waves per compute unit for a
     station that is one busy lane per server (engine.hip: plan_flow, gen_compact).  Exact or handed back to the second-chance
-    form (256-entry lists with send times), never different; LDS tick ring or differences in HBM."""
+    form (256-entry lists with send times), never different; LDS tick ring or differences in HBM.
+    (These runs take the second-chance instantiation: hc_flow_simulate sends every plan with general servers there unless
+    `compact=True` asks for the first launch -- test_general_servers_compact_form_is_what_runs_when_asked_for does.)"""
     import random
 
     from asyncflow_amd.workloads import _endpoint
@@ -445,6 +447,51 @@ def test_general_servers_compact_first_launch():
         exact += _run(random_payload(random.Random(31000 + case), horizon=8), 17 * case, ipl=1, ring_rows=0)[0] == "exact"
         exact += _run(tie_storm(random.Random(7000 + case), horizon=8), 3 * case + 1, ipl=1, ring_rows=32)[0] == "exact"
     assert exact >= 16, f"only {exact} of 32 fuzzed general-server payloads stayed on the compact form"
+
+
+COMPACT_IDS = {0, 2, 12, 13}     # tests/hostcheck/hostcheck.cpp, HC_FLOW_VARIANTS: FEAT_GENSRV | FEAT_BIGLIST without FEAT_TIEBREAK
+
+
+def test_general_servers_compact_form_is_what_runs_when_asked_for():
+    """hc_flow_simulate sends a plan with general servers to the second-chance instantiation whatever `robust` says -- the
+    runs with ipl=1 and no `robust` in the tests above are second-chance runs too --, so the compact first launch (engine.hip:
+    plan_flow, gen_compact: 128-entry lists without send times) is asked for by name, `compact=True`, and the recorded dispatch
+    id shows that it ran.  Against the oracle: exact, or handed back for a list that is too short or a tie (the form has no send
+    times to order one with) -- never for the ring (FEAT_FAR) or for RAM (the station keeps the RAM queue itself), never
+    different.  Two endpoints on LB-2 stay on it in every seed; of the fuzzed payloads at least eight must stay, which says
+    nothing about the kernel and only keeps the comparison from being empty."""
+    from asyncflow_amd.workloads import _endpoint
+    from oracle.scenarios import random_payload, tie_storm
+
+    report = lb_two_servers(horizon=20)
+    for s in report["topology_graph"]["nodes"]["servers"]:
+        s["endpoints"].append(_endpoint("/report", [("io_db", 0.004), ("ram", 64), ("cpu_bound_operation", 0.0015),
+                                                     ("io_wait", 0.006), ("cpu_bound_operation", 0.0005)]))
+    for ring in (0, 32):
+        for seed in range(3):
+            assert _run(report, 0x5EED0000 + seed, ipl=1, ring_rows=ring, compact=True)[0] == "exact"
+            assert hc.flow_variant() == 13
+            assert _run(report, 0x5EED0000 + seed, ipl=1, ring_rows=ring)[0] == "exact" and hc.flow_variant() == 15
+    ran = stayed = 0
+    payloads = [(random_payload(random.Random(31000 + case), horizon=8), 17 * case, 0) for case in range(16)]
+    payloads += [(tie_storm(random.Random(7000 + case), horizon=8), 3 * case + 1, 32) for case in range(16)]
+    payloads += [(server_tiers(random.Random(93000 + case), general=True), 500 + case, 32) for case in range(12)]
+    payloads += [(server_tiers(random.Random(94024 + case), general=True, algo="least_connection"), 724 + case, 32) for case in range(8)]
+    for payload, seed, ring in payloads:
+        status, info = _run(payload, seed, ipl=1, ring_rows=ring, compact=True)
+        if hc.flow_variant() not in COMPACT_IDS:          # (a fuzzed payload without general servers)
+            continue
+        ran += 1
+        stayed += status == "exact"
+        assert status == "exact" or info <= {"list", "tie"}, (seed, info)
+    assert ran >= 30 and stayed >= 8, (ran, stayed)
+    seen = set()
+    for payload, seed, kw in ((gateway_lb(front=1, general=True, algo="least_connection", users=150, horizon=10), 5, dict(ring_rows=32)),
+                              (gateway_lb(front=2, general=True, backend=True, users=150, horizon=10), 6, dict(ring_rows=32)),
+                              (wide_fanout(16, "least_connection", horizon=10, users=100), 83, dict(ring_rows=0))):
+        assert _run(payload, seed, ipl=1, compact=True, **kw)[0] == "exact"
+        seen.add(hc.flow_variant())
+    assert seen == {0, 2, 12}
 
 
 def test_general_servers_shared_instants_follow_simpy_order():
