@@ -396,11 +396,13 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize",
     "af_engine_summarize_pooled",
     "af_engine_summarize_windows",
+    "af_engine_summarize_arrival_windows",
     "af_engine_summarize_series_windows",
     "af_engine_summarize_series_quantiles",
     "af_engine_summarize_series_excursions",
     "af_engine_summarize_series_histogram",
     "af_engine_summarize_quantiles",
+    "af_engine_summarize_arrival_quantiles",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
     "af_engine_set_kernels",
@@ -437,6 +439,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_pooled.restype = C.c_int
     lib.af_engine_summarize_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfWindows)]
     lib.af_engine_summarize_windows.restype = C.c_int
+    lib.af_engine_summarize_arrival_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfWindows)]
+    lib.af_engine_summarize_arrival_windows.restype = C.c_int
     lib.af_engine_summarize_series_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesWindows)]
     lib.af_engine_summarize_series_windows.restype = C.c_int
     lib.af_engine_summarize_series_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesQuantiles)]
@@ -447,6 +451,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_series_histogram.restype = C.c_int
     lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_quantiles.restype = C.c_int
+    lib.af_engine_summarize_arrival_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
+    lib.af_engine_summarize_arrival_quantiles.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]
     lib.af_engine_run_summarized.restype = C.c_int
     lib.af_engine_jit_spec.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.c_char_p, C.c_size_t]

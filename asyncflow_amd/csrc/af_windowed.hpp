@@ -50,7 +50,7 @@ struct WinArgs {
     uint32_t n_scen, n_win;
     const double* edges;      // [W + 1]
     uint32_t* bounds;         // [n][W + 1]  r_s[k]
-    const uint32_t* pre;      // [n][W] latencies of cell (group[s], w) that come from members before s
+    uint32_t* pre;            // [n][W] latencies of cell (group[s], w) that come from members before s (af_arrival.hpp advances it)
     const uint64_t* cell_off; // [C + 1] first latency of every cell in the compacted array
     double* lat;              // compacted latencies
     uint32_t* err;            // [1] smallest scenario index with an inversion (kNoError: none)

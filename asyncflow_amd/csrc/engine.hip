@@ -55,6 +55,7 @@
 #include "af_series_excursions.hpp"
 #include "af_series_histogram.hpp"
 #include "af_windowed.hpp"
+#include "af_arrival.hpp"
 #include "af_quantiles.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
@@ -2755,11 +2756,13 @@ int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_poole
     return AF_OK;
 }
 
-// The cells (group g, window w) of a request with windows by finish time (af_windowed.hpp): layout_window_cells finds the row
-// bounds on the device and from them the cells' places; the caller sorts the cells into its tiers and adds its own parts to the
-// scratch layout; compact_window_cells brings the latencies to their cells.
+// The cells (group g, window w) of a request with windows by finish time (af_windowed.hpp) or by arrival time (af_arrival.hpp):
+// layout_window_cells finds the row bounds (by arrival: the cumulative counts) on the device and from them the cells' places; the
+// caller sorts the cells into its tiers and adds its own parts to the scratch layout; compact_window_cells brings the latencies
+// to their cells.  By arrival nothing rests on the rows' order: it is not checked.
 struct WindowCells {
-    afw::WinArgs a;                   // what af_win_bounds / af_win_compact take (the analyzer's kernels too, where they take a WinArgs)
+    afw::WinArgs a;                   // what the bounds / compaction kernels take (the analyzer's kernels too, where they take a WinArgs)
+    bool by_arrival;
     const double* edges;              // the caller's, [W + 1]
     uint32_t* row_bounds;             // the caller's, or null: the bounds lie in the scratch
     size_t o_edges, o_err, o_bounds, o_lat, o_pre, o_off;
@@ -2772,9 +2775,10 @@ static void bind_window_bounds(const af_engine_t* e, WindowCells& wc) {
     wc.a.bounds = wc.row_bounds ? wc.row_bounds : reinterpret_cast<uint32_t*>(e->d_pool + wc.o_bounds);
 }
 static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const uint32_t* group, const std::vector<uint32_t>& grp, uint32_t n, uint32_t G,
-                               uint32_t W, const double* edges, uint32_t* row_bounds, ScratchLayout& lay, WindowCells& wc) {
+                               uint32_t W, const double* edges, uint32_t* row_bounds, bool by_arrival, ScratchLayout& lay, WindowCells& wc) {
     const size_t C = (size_t)G * W, NE = (size_t)n * (W + 1u);
     hipStream_t st = e->stream;
+    wc.by_arrival = by_arrival;
     wc.edges = edges;
     wc.row_bounds = row_bounds;
     // scratch, first part: edges, the error word, the bounds (unless the caller takes them)
@@ -2792,7 +2796,12 @@ static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const ui
     wc.a.n_win = W;
     bind_window_bounds(e, wc);
     HIP_TRY(hipMemcpyAsync(e->d_pool + wc.o_edges, edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, wc.a);
+    if (!by_arrival)
+        hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, wc.a);
+    else if (W <= afw::kLdsArrivalWindows)
+        hipLaunchKernelGGL(afw::af_arrival_counts<true>, dim3(n), dim3(afw::kThreads), ((size_t)W + 1u) * 12u, st, wc.a);
+    else
+        hipLaunchKernelGGL(afw::af_arrival_counts<false>, dim3(n), dim3(afw::kThreads), 0, st, wc.a);
     HIP_TRY(hipGetLastError());
     wc.hb.resize(NE);
     HIP_TRY(hipMemcpyAsync(wc.hb.data(), wc.a.bounds, NE * 4u, hipMemcpyDeviceToHost, st));
@@ -2807,7 +2816,7 @@ static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const ui
         uint64_t* sz = wc.cell_off.data() + 1u + (size_t)g * W;
         uint32_t* ps = wc.pre.data() + (size_t)s * W;
         for (uint32_t w = 0; w < W; ++w) {
-            if (r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
+            if (!by_arrival && r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
                 return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
             if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
             ps[w] = (uint32_t)sz[w];
@@ -2836,13 +2845,17 @@ static int compact_window_cells(af_engine_t* e, const ScratchLayout& lay, Window
     }
     unsigned char* b = e->d_pool;
     wc.a.lat = reinterpret_cast<double*>(b + wc.o_lat);
-    wc.a.pre = reinterpret_cast<const uint32_t*>(b + wc.o_pre);
+    wc.a.pre = reinterpret_cast<uint32_t*>(b + wc.o_pre);
     wc.a.cell_off = reinterpret_cast<const uint64_t*>(b + wc.o_off);
     const uint32_t no_error = afw::kNoError;
     HIP_TRY(hipMemcpyAsync(b + wc.o_pre, wc.pre.data(), wc.pre.size() * 4u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b + wc.o_off, wc.cell_off.data(), wc.cell_off.size() * 8u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(wc.a.err, &no_error, 4u, hipMemcpyHostToDevice, st));
-    if (W <= afw::kLdsWindows)
+    if (wc.by_arrival && W <= afw::kLdsArrivalWindows)
+        hipLaunchKernelGGL(afw::af_arrival_compact<true>, dim3(n), dim3(afw::kArrivalCompactThreads), ((size_t)W + 1u) * 8u + (size_t)W * 8u, st, wc.a);
+    else if (wc.by_arrival)
+        hipLaunchKernelGGL(afw::af_arrival_compact<false>, dim3(n), dim3(afw::kArrivalCompactThreads), 0, st, wc.a);
+    else if (W <= afw::kLdsWindows)
         hipLaunchKernelGGL(afw::af_win_compact<true>, dim3(n), dim3(afw::kThreads), (size_t)W * 8u + ((size_t)W + 1u) * 4u, st, wc.a);
     else
         hipLaunchKernelGGL(afw::af_win_compact<false>, dim3(n), dim3(afw::kThreads), 0, st, wc.a);
@@ -2864,10 +2877,10 @@ static int launch_tiny_tier(uint64_t C, uint32_t tiny_waves, const std::function
     return AF_OK;
 }
 
-// Windowed analyzer (af_windowed.hpp).  The host reads the row bounds back and lays out the cells (group g, window w) of the
-// compacted array; cells of at most one numpy piece are reduced by one workgroup each, larger ones by the pooled analyzer's
-// tiled passes.
-int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) {
+// Windowed analyzer (af_windowed.hpp; windows by arrival: af_arrival.hpp).  The host reads the row bounds back and lays out the
+// cells (group g, window w) of the compacted array; cells of at most one numpy piece are reduced by one workgroup each, larger
+// ones by the pooled analyzer's tiled passes.
+static int summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win, bool by_arrival) {
     if (!e || !out || !win) return fail(AF_ERR_INVALID, "NULL argument");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
     if (win->n_scenarios == 0 || win->n_groups == 0 || win->n_windows == 0)
@@ -2887,7 +2900,7 @@ int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_wind
     if (int rc = read_groups(win->group, n, G, grp)) return rc;
     ScratchLayout lay;
     WindowCells wc;
-    if (int rc = layout_window_cells(e, out, win->group, grp, n, G, W, win->edges, win->row_bounds, lay, wc)) return rc;
+    if (int rc = layout_window_cells(e, out, win->group, grp, n, G, W, win->edges, win->row_bounds, by_arrival, lay, wc)) return rc;
     std::vector<afp::PoolGroup> groups;
     std::vector<afp::PoolTile> tiles;
     std::vector<uint32_t> stat_row, small;
@@ -2934,12 +2947,16 @@ int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_wind
     win->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
+int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) { return summarize_windows(e, out, win, false); }
+int af_engine_summarize_arrival_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) { return summarize_windows(e, out, win, true); }
 
 // Quantile analyzer (af_quantiles.hpp).  The cells are laid out and compacted as the windowed analyzer's (n_windows > 0) or the
-// pooled one's (n_windows == 0: a cell per group); a cell then goes to the tier of its size.
-int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) {
+// pooled one's (n_windows == 0: a cell per group; not by arrival: a whole run has no window); a cell then goes to the tier of
+// its size.
+static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr, bool by_arrival) {
     if (!e || !out || !qr) return fail(AF_ERR_INVALID, "NULL argument");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (by_arrival && qr->n_windows == 0) return fail(AF_ERR_INVALID, "quantiles by arrival time need windows (n_windows must be > 0)");
     if (qr->n_scenarios == 0 || qr->n_groups == 0) return fail(AF_ERR_INVALID, "empty quantiles request (n_scenarios and n_groups must be > 0)");
     const uint32_t n = qr->n_scenarios, G = qr->n_groups, W = qr->n_windows, cap = out->clock_capacity, Q = qr->n_levels, T = qr->n_thresholds;
     if (Q > AF_MAX_QUANTILE_LEVELS) return fail(AF_ERR_INVALID, "more than AF_MAX_QUANTILE_LEVELS (" + std::to_string(AF_MAX_QUANTILE_LEVELS) + ") levels");
@@ -2970,7 +2987,7 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
     WindowCells wc;     // the cells with windows
     PooledCells pc;     // ... and without
     if (W) {
-        if (int rc = layout_window_cells(e, out, qr->group, grp, n, G, W, qr->edges, nullptr, lay, wc)) return rc;
+        if (int rc = layout_window_cells(e, out, qr->group, grp, n, G, W, qr->edges, nullptr, by_arrival, lay, wc)) return rc;
     } else {
         if (int rc = layout_pooled_cells(out, grp, n, G, "holds", pc)) return rc;
         lay.part(8u), lay.part(4u);   // (an edge and the error word, as with windows: the scratch of a request is as large as it was)
@@ -3092,6 +3109,8 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
     qr->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
+int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) { return summarize_quantiles(e, out, qr, false); }
+int af_engine_summarize_arrival_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) { return summarize_quantiles(e, out, qr, true); }
 
 // Sampled-series analyzer per (group, window of ticks) (af_series_windows.hpp).  The host reads the group ids and the counts
 // back, checks them and builds the groups' member lists; one streaming pass over the sample rows, then -- unless every group

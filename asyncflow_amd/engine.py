@@ -282,11 +282,16 @@ class Engine:
         return float(req.elapsed_ms)
 
     def summarize_windows(self, n: int, n_groups: int, edges: Any, *, clock_ptr: int, clock_capacity: int, counts_ptr: int,
-                          stats_ptr: int, group_ptr: int = 0, row_bounds_ptr: int = 0) -> tuple[float, int]:
+                          stats_ptr: int, group_ptr: int = 0, row_bounds_ptr: int = 0, window_of: str = "finish") -> tuple[float, int]:
         """Windowed analyzer on the device (``af_engine_summarize_windows``): the eight latency statistics of every
         (group, window by finish time) into ``stats`` [n_groups, W, 8] f64, W = len(edges) - 1 (``edges``: HOST float64,
         strictly increasing).  ``group_ptr`` as in :meth:`summarize_pooled`; ``row_bounds_ptr``: optional DEVICE uint32
-        [n, W + 1] for the windows' row ranges.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        [n, W + 1] for the windows' row ranges.  ``window_of="arrival"``: windows by start time
+        (``af_engine_summarize_arrival_windows``; ``row_bounds`` then receives cumulative arrival counts).  Returns the
+        call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_window_of
+
+        name = "af_engine_summarize_arrival_windows" if check_window_of(window_of) == "arrival" else "af_engine_summarize_windows"
         e = np.ascontiguousarray(edges, dtype=np.float64)
         if e.ndim != 1 or e.shape[0] < 2:
             msg = f"window edges must be a vector of at least two values, not of shape {e.shape}"
@@ -295,20 +300,25 @@ class Engine:
         req = _abi.AfWindows(int(n), int(n_groups), int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
                              e.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(stats_ptr or None),
                              C.c_void_p(row_bounds_ptr or None), 0.0, 0)
-        _check(self._lib, self._lib.af_engine_summarize_windows(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_windows")
+        _check(self._lib, getattr(self._lib, name)(self._h, C.byref(out), C.byref(req)), name)
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
     def summarize_quantiles(self, n: int, n_groups: int, levels: Any, *, edges: Any = None, thresholds: Any = None,
                             clock_ptr: int, clock_capacity: int, counts_ptr: int, count_ptr: int = 0, quantiles_ptr: int = 0,
-                            within_ptr: int = 0, group_ptr: int = 0) -> tuple[float, int]:
+                            within_ptr: int = 0, group_ptr: int = 0, window_of: str = "finish") -> tuple[float, int]:
         """Quantile analyzer on the device (``af_engine_summarize_quantiles``): per (group, window by finish time)
         ``count`` uint32 [n_groups, W], ``quantiles`` f64 [n_groups, W, Q] and ``within`` uint32 [n_groups, W, T] (the
         latencies <= each threshold); a NULL pointer skips an output.  ``levels``: HOST float64 in [0, 1]; ``thresholds``:
         HOST float64 seconds or None; ``edges``: HOST float64, strictly increasing, W = len(edges) - 1, or None: the whole
-        run, one cell per group (W = 1).  ``group_ptr`` as in :meth:`summarize_pooled`.  Returns the call's wall time in
-        ms and the engine's scratch size in bytes."""
-        from .results import check_levels, check_slo_thresholds
+        run, one cell per group (W = 1).  ``group_ptr`` as in :meth:`summarize_pooled`.  ``window_of="arrival"``: windows
+        by start time (``af_engine_summarize_arrival_quantiles``; needs ``edges``).  Returns the call's wall time in ms and
+        the engine's scratch size in bytes."""
+        from .results import check_levels, check_slo_thresholds, check_window_of
 
+        name = "af_engine_summarize_arrival_quantiles" if check_window_of(window_of) == "arrival" else "af_engine_summarize_quantiles"
+        if name == "af_engine_summarize_arrival_quantiles" and edges is None:
+            msg = "window_of='arrival' needs windows: the whole run has none"
+            raise ValueError(msg)
         q, th = np.ascontiguousarray(check_levels(levels)), np.ascontiguousarray(check_slo_thresholds(thresholds))
         if q.shape[0] == 0 and th.shape[0] == 0:
             msg = "at least one quantile level or one threshold is needed"
@@ -326,7 +336,7 @@ class Engine:
                                int(q.shape[0]), q.ctypes.data_as(pd) if q.shape[0] else None,
                                int(th.shape[0]), th.ctypes.data_as(pd) if th.shape[0] else None,
                                C.c_void_p(count_ptr or None), C.c_void_p(quantiles_ptr or None), C.c_void_p(within_ptr or None), 0.0, 0)
-        _check(self._lib, self._lib.af_engine_summarize_quantiles(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_quantiles")
+        _check(self._lib, getattr(self._lib, name)(self._h, C.byref(out), C.byref(req)), name)
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
     def summarize_series_windows(self, n: int, n_groups: int, tick_edges: Any, *, samples_ptr: int, tick_capacity: int,

@@ -73,21 +73,51 @@ def latency_stats_row(arr: np.ndarray) -> np.ndarray:
                      np.percentile(arr, 99), np.min(arr), np.max(arr)], dtype=np.float64)
 
 
-def latency_window_stats(clock: np.ndarray, edges: Any) -> np.ndarray:
+WINDOW_OF = ("finish", "arrival")
+
+
+def check_window_of(window_of: str) -> str:
+    """``window_of`` if it is ``"finish"`` or ``"arrival"``, or ValueError."""
+    if window_of not in WINDOW_OF:
+        msg = f"window_of must be 'finish' or 'arrival', not {window_of!r}"
+        raise ValueError(msg)
+    return window_of
+
+
+def _window_latencies(ck: np.ndarray, e: np.ndarray, window_of: str) -> list[np.ndarray]:
+    """Per window of ``e`` the latencies of ONE scenario's rows ``ck`` [m, 2] that belong to it, in row order."""
+    n_win = e.shape[0] - 1
+    finish = ck[:, 1]
+    lat = finish - ck[:, 0]
+    if window_of == "arrival":
+        b = np.searchsorted(e, ck[:, 0], side="left")           # #{edges < start}: window b - 1 where 1 <= b <= W
+        order = np.argsort(b, kind="stable")                    # (stable: a window's rows stay in row order)
+        r = np.searchsorted(b[order], np.arange(1, n_win + 2), side="left")
+        return [lat[order[r[w]:r[w + 1]]] for w in range(n_win)]
+    if finish.size > 1 and (np.diff(finish) < 0.0).any():
+        msg = "rqs_clock is not in completion order (finish decreases): windows by finish time need it"
+        raise ValueError(msg)
+    r = np.searchsorted(finish, e, side="right")
+    return [lat[r[w]:r[w + 1]] for w in range(n_win)]
+
+
+def latency_window_stats(clock: np.ndarray, edges: Any, window_of: str = "finish") -> np.ndarray:
     """Latency statistics per time window of ONE scenario's ``rqs_clock`` [m, 2] (start, finish): float64 [W, 8] in
     LATENCY_KEYS order.  Window w holds the rows with ``edges[w] < finish <= edges[w + 1]`` (the bucket rule of the
     throughput series); rows are in completion order, so that is the row range between two ``np.searchsorted(finish,
     edges, side="right")`` positions.  The definition the device analyzer (``af_engine_summarize_windows``) is
-    bit-equal to."""
+    bit-equal to.
+
+    ``window_of="arrival"``: the same bucket rule on column 0, ``lat[(start > edges[w]) & (start <= edges[w + 1])]`` with
+    the latencies in row (completion) order -- the cohort of the requests SENT in the window, the one an objective is
+    written against (``af_engine_summarize_arrival_windows``).  A start equal to an edge belongs to the window that ends
+    there; rows with ``start <= edges[0]`` or ``start > edges[W]`` belong to no window; completion order is not needed and
+    not checked.  The cohorts are RIGHT-CENSORED: a request that arrived in a window but had not completed when the run
+    ended, or was dropped, is in no row, so ``total`` is the cohort's completions, not its arrivals, and the last windows
+    of a run under-report slow requests."""
     e = check_edges(edges)
     ck = np.asarray(clock, dtype=np.float64).reshape(-1, 2)
-    finish = ck[:, 1]
-    if finish.size > 1 and (np.diff(finish) < 0.0).any():
-        msg = "rqs_clock is not in completion order (finish decreases): windows by finish time need it"
-        raise ValueError(msg)
-    lat = finish - ck[:, 0]
-    r = np.searchsorted(finish, e, side="right")
-    return np.stack([latency_stats_row(lat[r[w]:r[w + 1]]) for w in range(e.shape[0] - 1)])
+    return np.stack([latency_stats_row(x) for x in _window_latencies(ck, e, check_window_of(window_of))])
 
 
 def check_levels(levels: Any) -> np.ndarray:
@@ -150,26 +180,26 @@ def latency_within(lat: Any, thresholds: Any) -> np.ndarray:
     return np.array([np.count_nonzero(x <= t) for t in th], dtype=np.uint32)
 
 
-def latency_window_quantiles(clock: np.ndarray, edges: Any, levels: Any, thresholds: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+def latency_window_quantiles(clock: np.ndarray, edges: Any, levels: Any, thresholds: Any = None,
+                             window_of: str = "finish") -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """Quantiles and SLO counts per time window of ONE scenario's ``rqs_clock`` [m, 2]: ``(count`` uint32 [W], ``quantiles``
     float64 [W, Q], ``within`` uint32 [W, T]``)``; the windows are :func:`latency_window_stats`'s (``edges[w] < finish <=
-    edges[w + 1]``, rows in completion order).  ``edges=None``: the whole run as one window, in any row order."""
+    edges[w + 1]``, rows in completion order).  ``edges=None``: the whole run as one window, in any row order.
+    ``window_of="arrival"``: that function's windows by start time (right-censored cohorts: ``count`` is the cohort's
+    completions, not its arrivals); it needs ``edges`` -- the whole run has no window."""
     q, th = check_levels(levels), check_slo_thresholds(thresholds)
     ck = np.asarray(clock, dtype=np.float64).reshape(-1, 2)
-    finish = ck[:, 1]
-    lat = finish - ck[:, 0]
     if edges is None:
-        r = np.array([0, lat.shape[0]])
-    else:
-        e = check_edges(edges)
-        if finish.size > 1 and (np.diff(finish) < 0.0).any():
-            msg = "rqs_clock is not in completion order (finish decreases): windows by finish time need it"
+        if check_window_of(window_of) == "arrival":
+            msg = "window_of='arrival' needs edges: the whole run has no window"
             raise ValueError(msg)
-        r = np.searchsorted(finish, e, side="right")
-    n_win = r.shape[0] - 1
-    count = np.diff(r).astype(np.uint32)
-    quant = np.stack([latency_quantiles(lat[r[w]:r[w + 1]], q) for w in range(n_win)]).reshape(n_win, q.shape[0])
-    within = np.stack([latency_within(lat[r[w]:r[w + 1]], th) for w in range(n_win)]).reshape(n_win, th.shape[0])
+        cells = [ck[:, 1] - ck[:, 0]]
+    else:
+        cells = _window_latencies(ck, check_edges(edges), check_window_of(window_of))
+    n_win = len(cells)
+    count = np.array([x.shape[0] for x in cells], dtype=np.uint32)
+    quant = np.stack([latency_quantiles(x, q) for x in cells]).reshape(n_win, q.shape[0])
+    within = np.stack([latency_within(x, th) for x in cells]).reshape(n_win, th.shape[0])
     return count, quant, within
 
 
@@ -655,25 +685,28 @@ class ScenarioResults:
             return self.throughput_series or ([], [])
         return self._throughput(float(window_s))
 
-    def get_latency_window_stats(self, window_s: float | None = None, edges: Any = None) -> np.ndarray:
-        """Latency statistics per time window (by finish time): float64 [W, 8] in LATENCY_KEYS order, for windows of
-        ``window_s`` seconds (default 1 s, :func:`window_edges`) or explicit ``edges``: :func:`latency_window_stats`."""
-        return latency_window_stats(self.rqs_clock, _resolve_edges(window_s, edges, self._plan.total_time))
+    def get_latency_window_stats(self, window_s: float | None = None, edges: Any = None, *, window_of: str = "finish") -> np.ndarray:
+        """Latency statistics per time window (by finish time; ``window_of="arrival"``: by start time): float64 [W, 8] in
+        LATENCY_KEYS order, for windows of ``window_s`` seconds (default 1 s, :func:`window_edges`) or explicit ``edges``:
+        :func:`latency_window_stats`."""
+        return latency_window_stats(self.rqs_clock, _resolve_edges(window_s, edges, self._plan.total_time), window_of)
 
     def get_latency_quantiles(self, levels: Any, *, window_s: float | None = None, edges: Any = None,
-                              thresholds: Any = None) -> dict[str, Any]:
+                              thresholds: Any = None, window_of: str = "finish") -> dict[str, Any]:
         """Any latency quantiles (``levels`` in [0, 1]) and, with ``thresholds`` (seconds), how many requests met each
         objective: :func:`latency_window_quantiles`.  Neither ``window_s`` nor ``edges``: the whole run (``count`` scalar,
         ``quantiles`` [Q], ``within`` [T]); otherwise per window of ``window_s`` seconds or explicit ``edges`` (``count``
-        [W], ``quantiles`` [W, Q], ``within`` [W, T]).  ``share`` = within / count (NaN where empty)."""
+        [W], ``quantiles`` [W, Q], ``within`` [W, T]).  ``share`` = within / count (NaN where empty).
+        ``window_of="arrival"``: windows by start time (needs windows)."""
         whole = window_s is None and edges is None
         e = None if whole else _resolve_edges(window_s, edges, self._plan.total_time)
-        count, quant, within = latency_window_quantiles(self.rqs_clock, e, levels, thresholds)
+        count, quant, within = latency_window_quantiles(self.rqs_clock, e, levels, thresholds, window_of)
         with np.errstate(invalid="ignore", divide="ignore"):
             share = np.where(count[:, None] > 0, within / count[:, None].astype(np.float64), np.nan)
         if whole:
-            return {"count": int(count[0]), "quantiles": quant[0], "within": within[0], "share": share[0], "edges": None}
-        return {"count": count, "quantiles": quant, "within": within, "share": share, "edges": e}
+            return {"count": int(count[0]), "quantiles": quant[0], "within": within[0], "share": share[0], "edges": None,
+                    "window_of": window_of}
+        return {"count": count, "quantiles": quant, "within": within, "share": share, "edges": e, "window_of": window_of}
 
     def get_series_window_stats(self, window_s: float | None = None, *, ticks_per_window: int | None = None,
                                 tick_edges: Any = None, thresholds: Any = None) -> dict[str, np.ndarray]:
@@ -1102,7 +1135,7 @@ class BatchedResults:
         return resolve_groups(by, len(self))
 
     def window_summary(self, window_s: float | None = None, *, edges: Any = None, by: Any = None,
-                       row_bounds: bool = False) -> dict[str, Any]:
+                       row_bounds: bool = False, window_of: str = "finish") -> dict[str, Any]:
         """The eight latency statistics of every (group, time window): the requests that FINISHED in the window
         (``edges[w] < finish <= edges[w + 1]``), over all scenarios of the group taken as one sample -- p95 during an
         outage, how fast it recovers.  Computed by the HIP windowed analyzer (``af_engine_summarize_windows``), bit-equal
@@ -1110,12 +1143,20 @@ class BatchedResults:
         (:func:`window_edges`; default 1 s) or explicit ``edges``.  ``by`` as in :meth:`pooled_summary`, or
         ``"scenario"`` (every scenario its own group).  Returns ``stats`` float64 [G, W, 8] on the run's device (an empty
         window: total 0, the rest NaN), ``edges`` [W + 1], ``keys``, ``replicas`` [G], ``window_ms``, ``scratch_bytes``
-        and, with ``row_bounds=True``, ``row_bounds`` int32 [n, W + 1] (the windows' row ranges)."""
+        and, with ``row_bounds=True``, ``row_bounds`` int32 [n, W + 1] (the windows' row ranges).
+
+        ``window_of="arrival"``: the requests that were SENT in the window (``edges[w] < start <= edges[w + 1]``), the
+        cohort an objective is written against -- by finish time the slow requests of an outage are charged to the
+        recovery.  ``af_engine_summarize_arrival_windows``, bit-equal to :func:`latency_window_stats` with that keyword;
+        ``row_bounds`` are then cumulative arrival counts, not row ranges.  The cohorts are right-censored: a request that
+        had not completed when the run ended, or was dropped, is in no row, so ``total`` is the cohort's completions and
+        the last windows of a run under-report slow requests.  The returned dict carries ``window_of``."""
         import torch
 
         from .engine import Engine
 
         self._require_clock()
+        check_window_of(window_of)
         e = _resolve_edges(window_s, edges, self.plan.total_time)
         ids, n_groups = self._window_groups(by)
         n_win = int(e.shape[0] - 1)
@@ -1130,38 +1171,40 @@ class BatchedResults:
         ms, scratch = self._summ_engine.summarize_windows(
             len(self), n_groups, e, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
             counts_ptr=self._counts_t.data_ptr(), stats_ptr=stats.data_ptr(), group_ptr=grp.data_ptr(),
-            row_bounds_ptr=rb.data_ptr() if rb is not None else 0)
-        out: dict[str, Any] = {"stats": stats, "edges": e, "keys": LATENCY_KEYS,
+            row_bounds_ptr=rb.data_ptr() if rb is not None else 0, window_of=window_of)
+        out: dict[str, Any] = {"stats": stats, "edges": e, "keys": LATENCY_KEYS, "window_of": window_of,
                                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "window_ms": ms, "scratch_bytes": scratch}
         if rb is not None:
             out["row_bounds"] = rb
         return out
 
     def window_bands(self, window_s: float | None = None, *, edges: Any = None, by: Any = None, level: float = 0.95,
-                     q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+                     q: tuple[float, float] = (0.05, 0.95), window_of: str = "finish") -> dict[str, Any]:
         """Bands over the replicas of the windowed latency statistics (the reference's roadmap: "confidence intervals and
         bands over time series").  Every scenario's own window statistics (``window_summary(by="scenario")``), then per
         group (``by``) and window, over the group's replicas whose window is not empty (``n`` [G, W] of them): ``mean``,
         unbiased ``std``, normal confidence half-width ``ci_halfwidth`` at ``level`` and the linear quantiles ``q_lo`` /
         ``q_hi`` (``q``) of each of the eight statistics, numpy float64 [G, W, 8] each (NaN where no replica has a
         completion in the window; ``std`` NaN below two).  Reduced on the device; ``pooled`` is
-        ``window_summary(by=by)["stats"]`` as numpy."""
+        ``window_summary(by=by)["stats"]`` as numpy.  ``window_of`` as in :meth:`window_summary`, for both."""
         e = _resolve_edges(window_s, edges, self.plan.total_time)
         ids, n_groups = self._window_groups(by)
-        per = self.window_summary(edges=e, by="scenario")["stats"]
+        per = self.window_summary(edges=e, by="scenario", window_of=window_of)["stats"]
         out = window_bands_by_group(per, ids, n_groups, level, q)
-        pooled = self.window_summary(edges=e, by=ids)
+        pooled = self.window_summary(edges=e, by=ids, window_of=window_of)
         out["pooled"] = pooled["stats"].cpu().numpy()[:n_groups]
         out["edges"] = e
+        out["window_of"] = window_of
         return out
 
     def save_window_summary(self, path: str, by: Any = None, *, window_s: float | None = None, edges: Any = None,
-                            level: float = 0.95) -> dict[str, np.ndarray]:
+                            level: float = 0.95, window_of: str = "finish") -> dict[str, np.ndarray]:
         """Columnar dump of the windowed statistics with one row per group (grid point): ``param:<axis>`` (for a Sweep),
         ``replicas``, and per latency key the [G, W] columns ``window_pooled:<key>`` (the group's replicas pooled),
         ``window_mean:<key>``, ``window_q05:<key>`` and ``window_q95:<key>`` (over the replicas, :meth:`window_bands`);
-        ``window_edges`` [W + 1] is a per-file vector.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
-        bands = self.window_bands(window_s, edges=edges, by=by, level=level, q=(0.05, 0.95))
+        ``window_edges`` [W + 1] and ``window_of`` (``"finish"`` or ``"arrival"``, as in :meth:`window_summary`) are
+        per-file values.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        bands = self.window_bands(window_s, edges=edges, by=by, level=level, q=(0.05, 0.95), window_of=window_of)
         n_groups = int(bands["replicas"].shape[0])
         cols: dict[str, np.ndarray] = {}
         if hasattr(by, "point_columns"):
@@ -1174,11 +1217,12 @@ class BatchedResults:
             cols[f"window_q05:{k}"] = np.ascontiguousarray(bands["q_lo"][:, :, j])
             cols[f"window_q95:{k}"] = np.ascontiguousarray(bands["q_hi"][:, :, j])
         cols["window_edges"] = np.asarray(bands["edges"], dtype=np.float64)
+        cols["window_of"] = np.asarray(window_of)
         _write_columns(str(path), cols, n_groups)
         return cols
 
     def quantile_summary(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
-                         by: Any = None) -> dict[str, Any]:
+                         by: Any = None, window_of: str = "finish") -> dict[str, Any]:
         """Any latency quantiles and SLO shares of every (group, time window): p99.9 at a grid point, p90 during an
         outage, the share of requests that met a 200 ms objective in every 10 s window.  Computed by the HIP quantile
         analyzer (``af_engine_summarize_quantiles``), bit-equal to :func:`latency_window_quantiles` / ``np.quantile`` on
@@ -1188,7 +1232,9 @@ class BatchedResults:
         :meth:`window_summary`.  ``by`` as there, ``"scenario"`` included.  Returns, on the run's device, ``quantiles``
         float64 [G, W, Q] (NaN where empty), ``count`` int64 [G, W], ``within`` int64 [G, W, T] and ``share`` float64
         [G, W, T] (= within / count, NaN where empty); ``levels``, ``thresholds``, ``edges``, ``replicas`` [G],
-        ``quantile_ms`` and ``scratch_bytes``."""
+        ``quantile_ms``, ``scratch_bytes`` and ``window_of``.  ``window_of="arrival"``: windows by start time as in
+        :meth:`window_summary` (``af_engine_summarize_arrival_quantiles``; right-censored cohorts: ``count`` is the cohort's
+        completions); it needs windows -- the whole run has none."""
         import torch
 
         from .engine import Engine
@@ -1199,6 +1245,9 @@ class BatchedResults:
             msg = "quantile_summary needs at least one level or one threshold"
             raise ValueError(msg)
         whole = window_s is None and edges is None
+        if check_window_of(window_of) == "arrival" and whole:
+            msg = "window_of='arrival' needs window_s or edges: the whole run has no window"
+            raise ValueError(msg)
         e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
         ids, n_groups = self._window_groups(by)
         n_win = 1 if e is None else int(e.shape[0] - 1)
@@ -1214,45 +1263,50 @@ class BatchedResults:
         ms, scratch = self._summ_engine.summarize_quantiles(
             len(self), n_groups, q, edges=e, thresholds=th, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
             counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(), quantiles_ptr=quant.data_ptr() if q.shape[0] else 0,
-            within_ptr=within.data_ptr() if th.shape[0] else 0, group_ptr=grp.data_ptr())
+            within_ptr=within.data_ptr() if th.shape[0] else 0, group_ptr=grp.data_ptr(), window_of=window_of)
         cnt = count.to(torch.int64) & 0xFFFFFFFF   # (the device's words are uint32)
         wth = within.to(torch.int64) & 0xFFFFFFFF
         nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
         share = torch.where((cnt > 0)[:, :, None], wth.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)[:, :, None], nan)
         return {"quantiles": quant, "count": cnt, "within": wth, "share": share, "levels": q, "thresholds": th, "edges": e,
-                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "quantile_ms": ms, "scratch_bytes": scratch}
+                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "quantile_ms": ms, "scratch_bytes": scratch,
+                "window_of": window_of}
 
     def quantile_bands(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
-                       by: Any = None, level: float = 0.95, q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+                       by: Any = None, level: float = 0.95, q: tuple[float, float] = (0.05, 0.95),
+                       window_of: str = "finish") -> dict[str, Any]:
         """Bands over the replicas of the quantiles and SLO shares: every scenario's own values
         (``quantile_summary(by="scenario")``), then per group (``by``) and window, over the group's replicas whose window
         is not empty (``n`` [G, W] of them), ``mean``, ``std``, ``ci_halfwidth`` (at ``level``) and the linear quantiles
         ``q_lo`` / ``q_hi`` (``q``) as :func:`window_bands_by_group` gives them: numpy float64 [G, W, Q + T], the levels'
         columns first, then the thresholds' shares.  ``pooled_quantiles`` [G, W, Q], ``pooled_share`` [G, W, T] and
-        ``pooled_count`` [G, W] are ``quantile_summary(by=by)`` as numpy."""
+        ``pooled_count`` [G, W] are ``quantile_summary(by=by)`` as numpy.  ``window_of`` as there, for both."""
         import torch
 
         whole = window_s is None and edges is None
         e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
         ids, n_groups = self._window_groups(by)
-        per = self.quantile_summary(levels, thresholds=thresholds, edges=e, by="scenario")
+        per = self.quantile_summary(levels, thresholds=thresholds, edges=e, by="scenario", window_of=window_of)
         out = window_bands_by_group(torch.cat([per["quantiles"], per["share"]], dim=2), ids, n_groups, level, q, valid=per["count"] > 0)
-        pooled = self.quantile_summary(levels, thresholds=thresholds, edges=e, by=ids)
+        pooled = self.quantile_summary(levels, thresholds=thresholds, edges=e, by=ids, window_of=window_of)
         out["pooled_quantiles"] = pooled["quantiles"].cpu().numpy()[:n_groups]
         out["pooled_share"] = pooled["share"].cpu().numpy()[:n_groups]
         out["pooled_count"] = pooled["count"].cpu().numpy()[:n_groups]
-        out["levels"], out["thresholds"], out["edges"] = per["levels"], per["thresholds"], e
+        out["levels"], out["thresholds"], out["edges"], out["window_of"] = per["levels"], per["thresholds"], e, window_of
         return out
 
     def save_quantile_summary(self, path: str, by: Any = None, *, levels: Any, thresholds: Any = None,
-                              window_s: float | None = None, edges: Any = None, level: float = 0.95) -> dict[str, np.ndarray]:
+                              window_s: float | None = None, edges: Any = None, level: float = 0.95,
+                              window_of: str = "finish") -> dict[str, np.ndarray]:
         """Columnar dump of the quantiles and SLO shares with one row per group (grid point): ``param:<axis>`` (for a
         Sweep), ``replicas``, ``quantile_count`` [G, W], and per level i / threshold j the [G, W] columns
         ``quantile_pooled:<i>`` / ``share_pooled:<j>`` (the group's replicas pooled) and ``quantile_mean:<i>``,
         ``quantile_q05:<i>``, ``quantile_q95:<i>`` / ``share_mean:<j>``, ``share_q05:<j>``, ``share_q95:<j>`` (over the
         replicas, :meth:`quantile_bands`); ``quantile_levels`` [Q], ``slo_thresholds`` [T] and ``window_edges`` [W + 1]
-        (empty for the whole run) are per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
-        bands = self.quantile_bands(levels, thresholds=thresholds, window_s=window_s, edges=edges, by=by, level=level, q=(0.05, 0.95))
+        (empty for the whole run) and ``window_of`` (``"finish"`` or ``"arrival"``, as in :meth:`quantile_summary`) are
+        per-file values.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        bands = self.quantile_bands(levels, thresholds=thresholds, window_s=window_s, edges=edges, by=by, level=level, q=(0.05, 0.95),
+                                    window_of=window_of)
         n_groups = int(bands["replicas"].shape[0])
         n_lev = int(bands["levels"].shape[0])
         cols: dict[str, np.ndarray] = {}
@@ -1271,6 +1325,7 @@ class BatchedResults:
         cols["quantile_levels"] = np.asarray(bands["levels"], dtype=np.float64)
         cols["slo_thresholds"] = np.asarray(bands["thresholds"], dtype=np.float64)
         cols["window_edges"] = np.zeros(0, dtype=np.float64) if bands["edges"] is None else np.asarray(bands["edges"], dtype=np.float64)
+        cols["window_of"] = np.asarray(window_of)
         _write_columns(str(path), cols, n_groups)
         return cols
 
@@ -2029,7 +2084,7 @@ def _write_columns(path: str, cols: dict[str, np.ndarray], n: int) -> None:
 
         table = {k: (pa.array(v.tolist()) if v.ndim > 2 else pa.array(list(v)) if v.ndim == 2 and v.shape[0] == n else pa.array(v))
                  for k, v in cols.items() if v.shape[:1] == (n,)}
-        meta = {k: ",".join(map(str, v.tolist())) for k, v in cols.items() if v.shape[:1] != (n,)}
+        meta = {k: ",".join(map(str, np.atleast_1d(v).tolist())) for k, v in cols.items() if v.shape[:1] != (n,)}
         pq.write_table(pa.table(table).replace_schema_metadata(meta), path)
     else:
         np.savez_compressed(path, **cols)
@@ -2254,6 +2309,8 @@ def load_summary(path: str) -> dict[str, np.ndarray]:
             key, text = k.decode(), v.decode()
             if key == "series_names":
                 cols[key] = np.asarray(text.split(","))
+            elif key == "window_of":
+                cols[key] = np.asarray(text)
             else:
                 cols[key] = np.asarray([float(x) for x in text.split(",")] if text else [], dtype=np.float64)
         return cols

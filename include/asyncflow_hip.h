@@ -438,6 +438,20 @@ typedef struct af_windows {
 } af_windows_t;
 int af_engine_summarize_windows(af_engine_t* engine, const af_outputs_t* out, af_windows_t* windows);
 
+/* The same statistics with windows by ARRIVAL time (asyncflow_amd/csrc/af_arrival.hpp): window w of scenario s holds its rows
+ * with edges[w] < start <= edges[w + 1] (a start equal to an edge belongs to the window that ends there; rows with start <=
+ * edges[0] or > edges[n_windows] belong to no window) -- the cohort of the requests SENT in the window, which is what an
+ * objective is written against: by finish time the slow requests of an outage are charged to the recovery.  start is not
+ * sorted in rqs_clock, so a window is a scattered subset of a scenario's rows; they stay in row (completion) order, and the
+ * sample of (group g, window w) is their concatenation in ascending scenario index over the members of g, on which stats
+ * are numpy's bit for bit.  The request, its refusals and the scratch are af_engine_summarize_windows's, except: nothing rests
+ * on completion order, so it is not checked and there is no such error; row_bounds, if given, receives
+ * c_s[k] = #{ i < m_s : start[s, i] <= edges[k] }, CUMULATIVE ARRIVAL COUNTS (not row ranges), also of skipped scenarios.
+ * The cohorts are RIGHT-CENSORED: a request that arrived in a window but had not completed when the run ended, or was
+ * dropped, is in no row; total is the cohort's completions, not its arrivals, and the last windows of a run under-report
+ * slow requests. */
+int af_engine_summarize_arrival_windows(af_engine_t* engine, const af_outputs_t* out, af_windows_t* windows);
+
 /* Statistics of every SAMPLED SERIES per window of ticks and group on the device (asyncflow_amd/csrc/af_series_windows.hpp):
  * how long the ready queue of a server is DURING an outage, at each grid point.  Windows are on TICK INDICES: sample k of
  * scenario s is row k of its outputs.samples block, k = 0 .. m_s - 1, m_s = min(counts[s][AF_CNT_TICKS], tick_capacity); the
@@ -678,6 +692,12 @@ typedef struct af_quantiles {
     uint64_t scratch_bytes;    /* out: size of the engine's scratch after the call */
 } af_quantiles_t;
 int af_engine_summarize_quantiles(af_engine_t* engine, const af_outputs_t* out, af_quantiles_t* quantiles);
+
+/* The same quantiles and SLO counts with windows by ARRIVAL time: the cells and their samples are
+ * af_engine_summarize_arrival_windows's (edges[w] < start <= edges[w + 1], rows in stored order, right-censored cohorts: count
+ * is the cohort's completions).  n_windows > 0 is required (a whole run has no window: AF_ERR_INVALID); completion order is
+ * neither needed nor checked.  Everything else as af_engine_summarize_quantiles. */
+int af_engine_summarize_arrival_quantiles(af_engine_t* engine, const af_outputs_t* out, af_quantiles_t* quantiles);
 
 /* af_engine_run followed by af_engine_summarize, in one call and with the same results (replaces SimulationRunner.run +
  * ResultsAnalyzer.process_all_metrics, simulation_runner.py:349-376 + analyzer.py:75-81, for the whole sweep).
