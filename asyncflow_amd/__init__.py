@@ -8,7 +8,7 @@ executed over thousands of independent scenarios by a hand-written HIP kernel
 
 from .payload import load_yaml, normalize_payload
 from .plan import DevicePlan, lower
-from .results import BatchedResults, ScenarioResults, latency_quantiles, latency_window_quantiles, latency_window_stats, series_histogram_quantiles, series_window_excursions, series_window_histogram, series_window_quantiles, window_edges
+from .results import BatchedResults, ScenarioResults, latency_quantiles, latency_state_cells, latency_state_quantiles, latency_state_stats, latency_window_quantiles, latency_window_stats, series_histogram_quantiles, series_window_excursions, series_window_histogram, series_window_quantiles, window_edges
 from .runner import SimulationRunner
 from .sweep import Sweep, expand_grid
 
@@ -20,6 +20,9 @@ __all__ = [
     "Sweep",
     "expand_grid",
     "latency_quantiles",
+    "latency_state_cells",
+    "latency_state_quantiles",
+    "latency_state_stats",
     "latency_window_quantiles",
     "latency_window_stats",
     "load_yaml",

@@ -389,6 +389,19 @@ class AfSeriesHistogram(C.Structure):
     ]
 
 
+class AfStateBins(C.Structure):
+    """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
+    ``af_engine_summarize_state_quantiles``."""
+
+    _fields_ = [
+        ("column", C.c_uint32),
+        ("n_bins", C.c_uint32),
+        ("lo", C.c_double),
+        ("width", C.c_double),
+        ("sample_period", C.c_double),
+    ]
+
+
 #: every symbol include/asyncflow_hip.h declares
 EXPORTED_SYMBOLS = (
     "af_engine_create",
@@ -403,6 +416,8 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_series_histogram",
     "af_engine_summarize_quantiles",
     "af_engine_summarize_arrival_quantiles",
+    "af_engine_summarize_state_windows",
+    "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
     "af_engine_jit_spec",
     "af_engine_set_kernels",
@@ -453,6 +468,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_summarize_arrival_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_arrival_quantiles.restype = C.c_int
+    lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
+    lib.af_engine_summarize_state_windows.restype = C.c_int
+    lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]
+    lib.af_engine_summarize_state_quantiles.restype = C.c_int
     lib.af_engine_run_summarized.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.POINTER(AfSummary)]
     lib.af_engine_run_summarized.restype = C.c_int
     lib.af_engine_jit_spec.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfOutputs), C.c_char_p, C.c_size_t]

@@ -45,13 +45,67 @@ __device__ __forceinline__ uint32_t edges_below(const double* e, uint32_t ne, do
     return lo;
 }
 
+// The block's prefix over ne counters: out[k] = hist[0] + ... + hist[k].  A run of consecutive counters per thread, the runs' sums
+// through the block; hist may BE out (the counters in global memory: every thread reads and writes its own run only).
+template <bool kLds>
+__device__ __forceinline__ void counters_prefix(uint32_t* hist, uint32_t* out, uint32_t ne, uint32_t* wave_total /* LDS [kWaves] */) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const auto counter = [&](uint32_t k) -> uint32_t {   // (global counters were written by atomics: read them where those went)
+        return kLds ? hist[k] : __hip_atomic_load(&hist[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    };
+    const uint32_t per = (ne + (uint32_t)kThreads - 1u) / (uint32_t)kThreads;
+    const uint32_t k0 = min((uint32_t)tid * per, ne), k1 = min(k0 + per, ne);
+    uint32_t sum = 0u;
+    for (uint32_t k = k0; k < k1; ++k) sum += counter(k);
+    uint32_t incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    if (lane == 63) wave_total[wave] = incl;
+    __syncthreads();
+    uint32_t run = incl - sum;
+    for (int v = 0; v < wave; ++v) run += wave_total[v];
+    for (uint32_t k = k0; k < k1; ++k) {
+        run += counter(k);
+        out[k] = run;
+    }
+}
+
+// The place of a row in the STABLE partition of a wave's 64 rows by key v (`in`: the lane has a row with a key): one turn per
+// distinct key of the 64 rows (start is nearly sorted: one or two), lowest row first; a lane's rank is the number of lanes below
+// it with its key, and the leader lane alone advances the key's cursor (the turns of a wave are in program order).  kLds: lcur[v]
+// is the next place of key v; otherwise goff[v] + gcur[v].  Wave-wide: every lane of the wave calls it.
+template <bool kLds>
+__device__ __forceinline__ uint64_t partition_place(bool in, uint32_t w, uint64_t* lcur, uint32_t* gcur, const uint64_t* goff, int lane) {
+    const unsigned long long below = (1ull << lane) - 1ull;
+    uint64_t place = 0u;
+    unsigned long long todo = __ballot(in);
+    while (todo) {
+        const int leader = __ffsll((long long)todo) - 1;
+        const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)w, leader);
+        const unsigned long long same = __ballot(in && w == v);
+        uint64_t first = 0u;
+        if (lane == leader) {   // one lane takes the key's rows off its cursor
+            if (kLds) first = atomicAdd(reinterpret_cast<unsigned long long*>(&lcur[v]), (unsigned long long)__popcll(same));
+            else first = goff[v] + atomicAdd(&gcur[v], (uint32_t)__popcll(same));
+        }
+        const uint32_t f_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, leader);
+        const uint32_t f_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(first >> 32), leader);
+        if (in && w == v) place = (((uint64_t)f_hi << 32) | f_lo) + (uint64_t)__popcll(same & below);
+        todo &= ~same;
+    }
+    return place;
+}
+
 // c_s[k] = #{ i < m_s : start[s, i] <= e[k] } of scenario blockIdx.x (skipped ones too) into bounds[s][0 .. W]
 template <bool kLds>
 __global__ __launch_bounds__(kThreads) void af_arrival_counts(WinArgs a) {
     extern __shared__ __attribute__((aligned(8))) unsigned char dyn[];   // kLds: [W + 1] f64 edges, then [W + 1] u32 counters
     __shared__ uint32_t wave_total[kWaves];
     const uint32_t s = blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const uint32_t ne = a.n_win + 1u;
     uint32_t m = a.counts[(size_t)s * 8u + a.cnt_completed_slot];
     if (m > a.clock_cap) m = a.clock_cap;
@@ -75,28 +129,7 @@ __global__ __launch_bounds__(kThreads) void af_arrival_counts(WinArgs a) {
         afs::wave_agg_add(hist, b, b < ne);
     }
     __syncthreads();
-    // the prefix over the counters: a run of consecutive edges per thread, the runs' sums through the block
-    const auto counter = [&](uint32_t k) -> uint32_t {   // (global counters were written by atomics: read them where those went)
-        return kLds ? hist[k] : __hip_atomic_load(&hist[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    const uint32_t per = (ne + (uint32_t)kThreads - 1u) / (uint32_t)kThreads;
-    const uint32_t k0 = min((uint32_t)tid * per, ne), k1 = min(k0 + per, ne);
-    uint32_t sum = 0u;
-    for (uint32_t k = k0; k < k1; ++k) sum += counter(k);
-    uint32_t incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    if (lane == 63) wave_total[wave] = incl;
-    __syncthreads();
-    uint32_t run = incl - sum;
-    for (int v = 0; v < wave; ++v) run += wave_total[v];
-    for (uint32_t k = k0; k < k1; ++k) {
-        run += counter(k);
-        out[k] = run;
-    }
+    counters_prefix<kLds>(hist, out, ne, wave_total);
 }
 
 // the stable partition of scenario blockIdx.x's stored rows by the window of start: finish - start to the cells, by ONE wave
@@ -121,7 +154,6 @@ __global__ __launch_bounds__(kArrivalCompactThreads) void af_arrival_compact(Win
         __syncthreads();
     }
     const double* e = kLds ? le : a.edges;
-    const unsigned long long below = (1ull << lane) - 1ull;
     constexpr uint32_t kU = 4;
     for (uint32_t base = 0; base < m; base += kU * 64u) {   // (uniform trip count: the ballots below are wave-wide)
         double2 c[kU];
@@ -133,21 +165,8 @@ __global__ __launch_bounds__(kArrivalCompactThreads) void af_arrival_compact(Win
             const uint32_t b = i < m ? edges_below(e, ne, c[u].x) : 0u;
             const bool in = b >= 1u && b <= W;   // lanes past m_s and rows outside (e[0], e[W]] take no part
             const uint32_t w = b - 1u;
-            unsigned long long todo = __ballot(in);
-            while (todo) {   // one turn per distinct window of the 64 rows (start is nearly sorted: one or two), lowest row first
-                const int leader = __ffsll((long long)todo) - 1;
-                const uint32_t v = (uint32_t)__builtin_amdgcn_readlane((int)w, leader);
-                const unsigned long long same = __ballot(in && w == v);
-                uint64_t first = 0u;
-                if (lane == leader) {   // one lane takes the window's rows off its cursor (the turns of a wave are in program order)
-                    if (kLds) first = atomicAdd(reinterpret_cast<unsigned long long*>(&lcur[v]), (unsigned long long)__popcll(same));
-                    else first = goff[v] + atomicAdd(&gcur[v], (uint32_t)__popcll(same));
-                }
-                const uint32_t f_lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)first, leader);
-                const uint32_t f_hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(first >> 32), leader);
-                if (in && w == v) a.lat[(((uint64_t)f_hi << 32) | f_lo) + (uint64_t)__popcll(same & below)] = c[u].y - c[u].x;
-                todo &= ~same;
-            }
+            const uint64_t d = partition_place<kLds>(in, w, lcur, gcur, goff, lane);
+            if (in) a.lat[d] = c[u].y - c[u].x;
         }
     }
 }

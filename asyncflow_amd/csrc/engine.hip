@@ -56,6 +56,7 @@
 #include "af_series_histogram.hpp"
 #include "af_windowed.hpp"
 #include "af_arrival.hpp"
+#include "af_state.hpp"
 #include "af_quantiles.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
@@ -2756,13 +2757,18 @@ int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_poole
     return AF_OK;
 }
 
-// The cells (group g, window w) of a request with windows by finish time (af_windowed.hpp) or by arrival time (af_arrival.hpp):
-// layout_window_cells finds the row bounds (by arrival: the cumulative counts) on the device and from them the cells' places; the
-// caller sorts the cells into its tiers and adds its own parts to the scratch layout; compact_window_cells brings the latencies
-// to their cells.  By arrival nothing rests on the rows' order: it is not checked.
+// The cells (group g, window w) of a request with windows by finish time (af_windowed.hpp), by arrival time (af_arrival.hpp) or
+// by arrival time and the state met on arrival (af_state.hpp: W is then the number of keys, max(n_time, 1) * n_bins, and the edges
+// are the n_time + 1 of the arrival windows, or none): layout_window_cells finds the row bounds (by arrival: the cumulative counts;
+// by state: the cumulative cell counts) on the device and from them the cells' places; the caller sorts the cells into its tiers
+// and adds its own parts to the scratch layout; compact_window_cells brings the latencies to their cells.  By arrival and by state
+// nothing rests on the rows' order: it is not checked.
+enum class CellsBy { kFinish, kArrival, kState };
 struct WindowCells {
     afw::WinArgs a;                   // what the bounds / compaction kernels take (the analyzer's kernels too, where they take a WinArgs)
-    bool by_arrival;
+    CellsBy by;
+    afst::StateArgs state;            // kState: the key (its WinArgs is bound at each launch)
+    size_t n_edge;                    // the edges the request has: W + 1, by state n_time + 1 or none
     const double* edges;              // the caller's, [W + 1]
     uint32_t* row_bounds;             // the caller's, or null: the bounds lie in the scratch
     size_t o_edges, o_err, o_bounds, o_lat, o_pre, o_off;
@@ -2775,14 +2781,18 @@ static void bind_window_bounds(const af_engine_t* e, WindowCells& wc) {
     wc.a.bounds = wc.row_bounds ? wc.row_bounds : reinterpret_cast<uint32_t*>(e->d_pool + wc.o_bounds);
 }
 static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const uint32_t* group, const std::vector<uint32_t>& grp, uint32_t n, uint32_t G,
-                               uint32_t W, const double* edges, uint32_t* row_bounds, bool by_arrival, ScratchLayout& lay, WindowCells& wc) {
+                               uint32_t W, const double* edges, uint32_t* row_bounds, CellsBy by, const afst::StateArgs* state, ScratchLayout& lay,
+                               WindowCells& wc) {
     const size_t C = (size_t)G * W, NE = (size_t)n * (W + 1u);
     hipStream_t st = e->stream;
-    wc.by_arrival = by_arrival;
+    const bool by_arrival = by == CellsBy::kArrival, by_state = by == CellsBy::kState;
+    wc.by = by;
+    wc.state = by_state ? *state : afst::StateArgs{};
+    wc.n_edge = !by_state ? (size_t)W + 1u : state->n_time ? (size_t)state->n_time + 1u : 0u;
     wc.edges = edges;
     wc.row_bounds = row_bounds;
     // scratch, first part: edges, the error word, the bounds (unless the caller takes them)
-    wc.o_edges = lay.part(((size_t)W + 1u) * 8u);
+    wc.o_edges = lay.part(std::max<size_t>(wc.n_edge, 1u) * 8u);
     wc.o_err = lay.part(4u);
     wc.o_bounds = row_bounds ? 0u : lay.part(NE * 4u);
     if (int rc = pool_reserve(e, lay.at)) return rc;
@@ -2795,8 +2805,14 @@ static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const ui
     wc.a.n_scen = n;
     wc.a.n_win = W;
     bind_window_bounds(e, wc);
-    HIP_TRY(hipMemcpyAsync(e->d_pool + wc.o_edges, edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
-    if (!by_arrival)
+    if (wc.n_edge) HIP_TRY(hipMemcpyAsync(e->d_pool + wc.o_edges, edges, wc.n_edge * 8u, hipMemcpyHostToDevice, st));
+    if (by_state) {
+        wc.state.w = wc.a;
+        if (W <= afst::kLdsStateCells)
+            hipLaunchKernelGGL(afst::af_state_counts<true>, dim3(n), dim3(afst::kThreads), wc.n_edge * 8u + ((size_t)W + 1u) * 4u, st, wc.state);
+        else
+            hipLaunchKernelGGL(afst::af_state_counts<false>, dim3(n), dim3(afst::kThreads), 0, st, wc.state);
+    } else if (!by_arrival)
         hipLaunchKernelGGL(afw::af_win_bounds, dim3((uint32_t)((NE + afw::kBoundsThreads - 1u) / afw::kBoundsThreads)), dim3(afw::kBoundsThreads), 0, st, wc.a);
     else if (W <= afw::kLdsArrivalWindows)
         hipLaunchKernelGGL(afw::af_arrival_counts<true>, dim3(n), dim3(afw::kThreads), ((size_t)W + 1u) * 12u, st, wc.a);
@@ -2816,15 +2832,15 @@ static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const ui
         uint64_t* sz = wc.cell_off.data() + 1u + (size_t)g * W;
         uint32_t* ps = wc.pre.data() + (size_t)s * W;
         for (uint32_t w = 0; w < W; ++w) {
-            if (!by_arrival && r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
+            if (by == CellsBy::kFinish && r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
                 return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
-            if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
+            if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, std::string(by_state ? "cell " : "window ") + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
             ps[w] = (uint32_t)sz[w];
             sz[w] += r[w + 1u] - r[w];
         }
     }
     for (size_t c = 0; c < C; ++c) {
-        if (wc.cell_off[c + 1u] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(c % W) + " of group " + std::to_string(c / W) + " holds 2^32 or more latencies");
+        if (wc.cell_off[c + 1u] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, std::string(by_state ? "cell " : "window ") + std::to_string(c % W) + " of group " + std::to_string(c / W) + " holds 2^32 or more latencies");
         wc.cell_off[c + 1u] += wc.cell_off[c];
     }
     // scratch, second part: the compacted latencies, pre, the cells' offsets; the caller's parts follow
@@ -2840,7 +2856,7 @@ static int compact_window_cells(af_engine_t* e, const ScratchLayout& lay, Window
     if (lay.at > e->pool_cap) {   // the scratch moves: its first part again
         if (int rc = pool_reserve(e, lay.at)) return rc;
         bind_window_bounds(e, wc);
-        HIP_TRY(hipMemcpyAsync(e->d_pool + wc.o_edges, wc.edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+        if (wc.n_edge) HIP_TRY(hipMemcpyAsync(e->d_pool + wc.o_edges, wc.edges, wc.n_edge * 8u, hipMemcpyHostToDevice, st));
         if (!wc.row_bounds) HIP_TRY(hipMemcpyAsync(wc.a.bounds, wc.hb.data(), NE * 4u, hipMemcpyHostToDevice, st));
     }
     unsigned char* b = e->d_pool;
@@ -2851,9 +2867,16 @@ static int compact_window_cells(af_engine_t* e, const ScratchLayout& lay, Window
     HIP_TRY(hipMemcpyAsync(b + wc.o_pre, wc.pre.data(), wc.pre.size() * 4u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(b + wc.o_off, wc.cell_off.data(), wc.cell_off.size() * 8u, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(wc.a.err, &no_error, 4u, hipMemcpyHostToDevice, st));
-    if (wc.by_arrival && W <= afw::kLdsArrivalWindows)
+    const bool by_arrival = wc.by == CellsBy::kArrival;
+    if (wc.by == CellsBy::kState) {
+        wc.state.w = wc.a;
+        if (W <= afst::kLdsStateCells)
+            hipLaunchKernelGGL(afst::af_state_compact<true>, dim3(n), dim3(afst::kStateCompactThreads), wc.n_edge * 8u + (size_t)W * 8u, st, wc.state);
+        else
+            hipLaunchKernelGGL(afst::af_state_compact<false>, dim3(n), dim3(afst::kStateCompactThreads), 0, st, wc.state);
+    } else if (by_arrival && W <= afw::kLdsArrivalWindows)
         hipLaunchKernelGGL(afw::af_arrival_compact<true>, dim3(n), dim3(afw::kArrivalCompactThreads), ((size_t)W + 1u) * 8u + (size_t)W * 8u, st, wc.a);
-    else if (wc.by_arrival)
+    else if (by_arrival)
         hipLaunchKernelGGL(afw::af_arrival_compact<false>, dim3(n), dim3(afw::kArrivalCompactThreads), 0, st, wc.a);
     else if (W <= afw::kLdsWindows)
         hipLaunchKernelGGL(afw::af_win_compact<true>, dim3(n), dim3(afw::kThreads), (size_t)W * 8u + ((size_t)W + 1u) * 4u, st, wc.a);
@@ -2868,6 +2891,36 @@ static int compact_window_cells(af_engine_t* e, const ScratchLayout& lay, Window
     return AF_OK;
 }
 
+// The key of a request by the state met on arrival (af_state.hpp), checked: the binning, the series, the sample rows.  K: the keys
+// per group, max(n_time, 1) * n_bins.
+static int check_state_bins(const af_engine_t* e, const af_outputs_t* out, const af_state_bins_t* sb, uint32_t n_time, uint32_t G, afst::StateArgs& sa, uint32_t& K) {
+    if (sb->n_bins == 0) return fail(AF_ERR_INVALID, "state bins: n_bins must be > 0");
+    if (!(std::isfinite(sb->width) && sb->width > 0.0)) return fail(AF_ERR_INVALID, "state bins: width must be finite and above 0");
+    if (!std::isfinite(sb->lo)) return fail(AF_ERR_INVALID, "state bins: lo must be finite");
+    if (!(std::isfinite(sb->sample_period) && sb->sample_period > 0.0)) return fail(AF_ERR_INVALID, "state bins: sample_period must be finite and above 0");
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch;
+    if (S == 0 || pitch < S) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    if (sb->column >= S) return fail(AF_ERR_INVALID, "state bins: column " + std::to_string(sb->column) + " is not a series (af_series_count " + std::to_string(S) + ")");
+    if (!out->samples || out->tick_capacity == 0) return fail(AF_ERR_INVALID, "latency by state needs outputs.samples");
+    const uint64_t wc = n_time ? n_time : 1u;
+    if ((uint64_t)G * wc >= 0xFFFFFFFFull || (uint64_t)G * wc * sb->n_bins >= 0xFFFFFFFFull)
+        return fail(AF_ERR_CAPACITY, "n_groups * max(n_windows, 1) * n_bins must be below 2^32 - 1");
+    K = (uint32_t)(wc * sb->n_bins);
+    sa = afst::StateArgs{};
+    sa.samples = out->samples;
+    sa.tick_cap = out->tick_capacity;
+    sa.pitch = pitch;
+    sa.cnt_ticks_slot = AF_CNT_TICKS;
+    sa.column = sb->column;
+    sa.is_float = sb->column >= e->args.n_edges && (sb->column - e->args.n_edges) % 3u == 2u ? 1u : 0u;
+    sa.n_time = n_time;
+    sa.n_bins = sb->n_bins;
+    sa.lo = sb->lo;
+    sa.width = sb->width;
+    sa.period = sb->sample_period;
+    return AF_OK;
+}
+
 // every cell of C to the wave kernel of a tiny tier, kTinyWaves cells per workgroup: launch(blocks, first cell)
 static int launch_tiny_tier(uint64_t C, uint32_t tiny_waves, const std::function<void(uint32_t, uint64_t)>& launch) {
     for (uint64_t c0 = 0; c0 < C; c0 += kBlocksPerLaunch * tiny_waves) {   // every cell: a wave takes it if it is tiny (or empty)
@@ -2877,20 +2930,28 @@ static int launch_tiny_tier(uint64_t C, uint32_t tiny_waves, const std::function
     return AF_OK;
 }
 
-// Windowed analyzer (af_windowed.hpp; windows by arrival: af_arrival.hpp).  The host reads the row bounds back and lays out the
-// cells (group g, window w) of the compacted array; cells of at most one numpy piece are reduced by one workgroup each, larger
-// ones by the pooled analyzer's tiled passes.
-static int summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win, bool by_arrival) {
-    if (!e || !out || !win) return fail(AF_ERR_INVALID, "NULL argument");
+// Windowed analyzer (af_windowed.hpp; windows by arrival: af_arrival.hpp; by the state met on arrival, `sb`: af_state.hpp, the
+// "windows" W of everything below are then the keys of a group and n_windows == 0 is one window over all time).  The host reads
+// the row bounds back and lays out the cells (group g, window w) of the compacted array; cells of at most one numpy piece are
+// reduced by one workgroup each, larger ones by the pooled analyzer's tiled passes.
+static int summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win, CellsBy by, const af_state_bins_t* sb = nullptr) {
+    if (!e || !out || !win || (by == CellsBy::kState && !sb)) return fail(AF_ERR_INVALID, "NULL argument");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
-    if (win->n_scenarios == 0 || win->n_groups == 0 || win->n_windows == 0)
+    if (win->n_scenarios == 0 || win->n_groups == 0 || (win->n_windows == 0 && !sb))
         return fail(AF_ERR_INVALID, "empty windows request (n_scenarios, n_groups and n_windows must be > 0)");
     if (!win->stats) return fail(AF_ERR_INVALID, "windows.stats is required");
-    if (!win->edges) return fail(AF_ERR_INVALID, "windows.edges is required");
+    if (win->n_windows > 0 && !win->edges) return fail(AF_ERR_INVALID, "windows.edges is required");
+    if (win->n_windows == 0 && win->edges) return fail(AF_ERR_INVALID, "windows.edges given with n_windows == 0 (one window over all time takes none)");
     if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
     if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "windowed summary needs outputs.clock");
-    const uint32_t n = win->n_scenarios, G = win->n_groups, W = win->n_windows;
-    if (int rc = check_window_edges(win->edges, W)) return rc;
+    const uint32_t n = win->n_scenarios, G = win->n_groups;
+    if (win->n_windows > 0)
+        if (int rc = check_window_edges(win->edges, win->n_windows)) return rc;
+    uint32_t W = win->n_windows;   // the cells of a group
+    afst::StateArgs sa{};
+    if (sb) {
+        if (int rc = check_state_bins(e, out, sb, win->n_windows, G, sa, W)) return rc;
+    }
     if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
     if ((uint64_t)n * ((uint64_t)W + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (n_windows + 1) must be below 2^32");
     const auto t0 = std::chrono::steady_clock::now();
@@ -2900,7 +2961,7 @@ static int summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows
     if (int rc = read_groups(win->group, n, G, grp)) return rc;
     ScratchLayout lay;
     WindowCells wc;
-    if (int rc = layout_window_cells(e, out, win->group, grp, n, G, W, win->edges, win->row_bounds, by_arrival, lay, wc)) return rc;
+    if (int rc = layout_window_cells(e, out, win->group, grp, n, G, W, win->edges, win->row_bounds, by, sb ? &sa : nullptr, lay, wc)) return rc;
     std::vector<afp::PoolGroup> groups;
     std::vector<afp::PoolTile> tiles;
     std::vector<uint32_t> stat_row, small;
@@ -2947,18 +3008,22 @@ static int summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows
     win->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
-int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) { return summarize_windows(e, out, win, false); }
-int af_engine_summarize_arrival_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) { return summarize_windows(e, out, win, true); }
+int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) { return summarize_windows(e, out, win, CellsBy::kFinish); }
+int af_engine_summarize_arrival_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) { return summarize_windows(e, out, win, CellsBy::kArrival); }
+int af_engine_summarize_state_windows(af_engine_t* e, const af_outputs_t* out, const af_state_bins_t* sb, af_windows_t* win) {
+    return summarize_windows(e, out, win, CellsBy::kState, sb);
+}
 
-// Quantile analyzer (af_quantiles.hpp).  The cells are laid out and compacted as the windowed analyzer's (n_windows > 0) or the
-// pooled one's (n_windows == 0: a cell per group; not by arrival: a whole run has no window); a cell then goes to the tier of
-// its size.
-static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr, bool by_arrival) {
-    if (!e || !out || !qr) return fail(AF_ERR_INVALID, "NULL argument");
+// Quantile analyzer (af_quantiles.hpp).  The cells are laid out and compacted as the windowed analyzer's (n_windows > 0; by the
+// state met on arrival, `sb`, always: W is then the keys of a group) or the pooled one's (n_windows == 0: a cell per group; not by
+// arrival: a whole run has no window); a cell then goes to the tier of its size.
+static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr, CellsBy by, const af_state_bins_t* sb = nullptr) {
+    if (!e || !out || !qr || (by == CellsBy::kState && !sb)) return fail(AF_ERR_INVALID, "NULL argument");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
-    if (by_arrival && qr->n_windows == 0) return fail(AF_ERR_INVALID, "quantiles by arrival time need windows (n_windows must be > 0)");
+    if (by == CellsBy::kArrival && qr->n_windows == 0) return fail(AF_ERR_INVALID, "quantiles by arrival time need windows (n_windows must be > 0)");
     if (qr->n_scenarios == 0 || qr->n_groups == 0) return fail(AF_ERR_INVALID, "empty quantiles request (n_scenarios and n_groups must be > 0)");
-    const uint32_t n = qr->n_scenarios, G = qr->n_groups, W = qr->n_windows, cap = out->clock_capacity, Q = qr->n_levels, T = qr->n_thresholds;
+    const uint32_t n = qr->n_scenarios, G = qr->n_groups, cap = out->clock_capacity, Q = qr->n_levels, T = qr->n_thresholds;
+    uint32_t W = qr->n_windows;   // the cells of a group laid out as windows (0: a cell per group over the whole run); by state: the keys
     if (Q > AF_MAX_QUANTILE_LEVELS) return fail(AF_ERR_INVALID, "more than AF_MAX_QUANTILE_LEVELS (" + std::to_string(AF_MAX_QUANTILE_LEVELS) + ") levels");
     if (T > AF_MAX_SLO_THRESHOLDS) return fail(AF_ERR_INVALID, "more than AF_MAX_SLO_THRESHOLDS (" + std::to_string(AF_MAX_SLO_THRESHOLDS) + ") thresholds");
     if (Q == 0 && T == 0) return fail(AF_ERR_INVALID, "quantiles request without levels and without thresholds");
@@ -2974,6 +3039,10 @@ static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quant
         if (int rc = check_window_edges(qr->edges, W)) return rc;
     if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
     if (!out->clock || cap == 0) return fail(AF_ERR_INVALID, "quantile summary needs outputs.clock");
+    afst::StateArgs sa{};
+    if (sb) {
+        if (int rc = check_state_bins(e, out, sb, qr->n_windows, G, sa, W)) return rc;
+    }
     const uint32_t Wc = W ? W : 1u;
     if ((uint64_t)G * Wc >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * max(n_windows, 1) must be below 2^32 - 1");
     if (W && (uint64_t)n * ((uint64_t)W + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (n_windows + 1) must be below 2^32");
@@ -2987,7 +3056,7 @@ static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quant
     WindowCells wc;     // the cells with windows
     PooledCells pc;     // ... and without
     if (W) {
-        if (int rc = layout_window_cells(e, out, qr->group, grp, n, G, W, qr->edges, nullptr, by_arrival, lay, wc)) return rc;
+        if (int rc = layout_window_cells(e, out, qr->group, grp, n, G, W, qr->edges, nullptr, by, sb ? &sa : nullptr, lay, wc)) return rc;
     } else {
         if (int rc = layout_pooled_cells(out, grp, n, G, "holds", pc)) return rc;
         lay.part(8u), lay.part(4u);   // (an edge and the error word, as with windows: the scratch of a request is as large as it was)
@@ -3109,8 +3178,11 @@ static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quant
     qr->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
-int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) { return summarize_quantiles(e, out, qr, false); }
-int af_engine_summarize_arrival_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) { return summarize_quantiles(e, out, qr, true); }
+int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) { return summarize_quantiles(e, out, qr, CellsBy::kFinish); }
+int af_engine_summarize_arrival_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) { return summarize_quantiles(e, out, qr, CellsBy::kArrival); }
+int af_engine_summarize_state_quantiles(af_engine_t* e, const af_outputs_t* out, const af_state_bins_t* sb, af_quantiles_t* qr) {
+    return summarize_quantiles(e, out, qr, CellsBy::kState, sb);
+}
 
 // Sampled-series analyzer per (group, window of ticks) (af_series_windows.hpp).  The host reads the group ids and the counts
 // back, checks them and builds the groups' member lists; one streaming pass over the sample rows, then -- unless every group

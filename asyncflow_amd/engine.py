@@ -339,6 +339,69 @@ class Engine:
         _check(self._lib, getattr(self._lib, name)(self._h, C.byref(out), C.byref(req)), name)
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def _state_request(self, column: int, bins: int, lo: float, width: float, sample_period: float, edges: Any) -> tuple[Any, Any]:
+        """``af_state_bins_t`` and the checked edges (or None) of the two latency-by-state calls."""
+        from .results import _check_series_columns, check_state_bins
+
+        n_bins, lo_f, width_f, period = check_state_bins(bins, lo, width, sample_period)
+        col = int(_check_series_columns([column], self.plan.n_series)[0])
+        e = None
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.float64)
+            if e.ndim != 1 or e.shape[0] < 2:
+                msg = f"window edges must be a vector of at least two values, not of shape {e.shape}"
+                raise ValueError(msg)
+        return _abi.AfStateBins(col, n_bins, lo_f, width_f, period), e
+
+    def summarize_state_windows(self, n: int, n_groups: int, *, column: int, bins: int, sample_period: float, lo: float = 0.0,
+                                width: float = 1.0, edges: Any = None, clock_ptr: int, clock_capacity: int, samples_ptr: int,
+                                tick_capacity: int, counts_ptr: int, stats_ptr: int, group_ptr: int = 0,
+                                row_bounds_ptr: int = 0) -> tuple[float, int]:
+        """Latency by the state met on arrival on the device (``af_engine_summarize_state_windows``): the eight latency
+        statistics of every (group, arrival window, bin of series ``column`` at the request's arrival tick) into ``stats``
+        [n_groups, W', bins, 8] f64.  ``bins`` bins of ``width`` from ``lo`` (the last takes the overflow); ``sample_period``:
+        the plan's; ``edges``: HOST float64, strictly increasing, W' = len(edges) - 1, or None: one window with no condition
+        on time (W' = 1).  ``group_ptr`` as in :meth:`summarize_pooled`; ``row_bounds_ptr``: optional DEVICE uint32
+        [n, W' * bins + 1] for the cumulative cell counts per scenario.  Returns the call's wall time in ms and the engine's
+        scratch size in bytes."""
+        sb, e = self._state_request(column, bins, lo, width, sample_period, edges)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), int(tick_capacity), C.c_void_p(samples_ptr or None),
+                             C.c_void_p(counts_ptr or None))
+        req = _abi.AfWindows(int(n), int(n_groups), 0 if e is None else int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
+                             e.ctypes.data_as(C.POINTER(C.c_double)) if e is not None else None, C.c_void_p(stats_ptr or None),
+                             C.c_void_p(row_bounds_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_state_windows(self._h, C.byref(out), C.byref(sb), C.byref(req)),
+               "af_engine_summarize_state_windows")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
+    def summarize_state_quantiles(self, n: int, n_groups: int, levels: Any, *, thresholds: Any = None, column: int, bins: int,
+                                  sample_period: float, lo: float = 0.0, width: float = 1.0, edges: Any = None, clock_ptr: int,
+                                  clock_capacity: int, samples_ptr: int, tick_capacity: int, counts_ptr: int, count_ptr: int = 0,
+                                  quantiles_ptr: int = 0, within_ptr: int = 0, group_ptr: int = 0) -> tuple[float, int]:
+        """Quantiles and SLO counts over the cells of :meth:`summarize_state_windows`
+        (``af_engine_summarize_state_quantiles``): ``count`` uint32 [n_groups, W', bins], ``quantiles`` f64
+        [n_groups, W', bins, Q] and ``within`` uint32 [n_groups, W', bins, T]; a pointer of 0 skips an output.  ``levels`` and
+        ``thresholds`` as in :meth:`summarize_quantiles`, the rest as in :meth:`summarize_state_windows`.  Returns the call's
+        wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_levels, check_slo_thresholds
+
+        q, th = np.ascontiguousarray(check_levels(levels)), np.ascontiguousarray(check_slo_thresholds(thresholds))
+        if q.shape[0] == 0 and th.shape[0] == 0:
+            msg = "at least one quantile level or one threshold is needed"
+            raise ValueError(msg)
+        sb, e = self._state_request(column, bins, lo, width, sample_period, edges)
+        pd = C.POINTER(C.c_double)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), int(tick_capacity), C.c_void_p(samples_ptr or None),
+                             C.c_void_p(counts_ptr or None))
+        req = _abi.AfQuantiles(int(n), int(n_groups), 0 if e is None else int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
+                               e.ctypes.data_as(pd) if e is not None else None,
+                               int(q.shape[0]), q.ctypes.data_as(pd) if q.shape[0] else None,
+                               int(th.shape[0]), th.ctypes.data_as(pd) if th.shape[0] else None,
+                               C.c_void_p(count_ptr or None), C.c_void_p(quantiles_ptr or None), C.c_void_p(within_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_state_quantiles(self._h, C.byref(out), C.byref(sb), C.byref(req)),
+               "af_engine_summarize_state_quantiles")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def summarize_series_windows(self, n: int, n_groups: int, tick_edges: Any, *, samples_ptr: int, tick_capacity: int,
                                  counts_ptr: int, count_ptr: int, mean_ptr: int, min_ptr: int = 0, max_ptr: int = 0,
                                  above_ptr: int = 0, group_ptr: int = 0, thresholds: Any = None) -> tuple[float, int]:

@@ -513,6 +513,125 @@ def series_window_histogram(samples: np.ndarray, tick_edges: Any, n_edges: int, 
             "bin_edges": lo_v[:, None] + np.arange(n_bins + 1, dtype=np.float64)[None, :] * width_v[:, None], "ram": ram}
 
 
+def check_state_bins(bins: Any, lo: Any = 0.0, width: Any = 1.0, sample_period: Any = None) -> tuple[int, float, float, float | None]:
+    """The binning of a latency-by-state call as ``(n_bins, lo, width, sample_period)``, or ValueError: ``bins`` a whole number
+    above 0, ``lo`` finite, ``width`` finite and above 0, ``sample_period`` (unless None) finite and above 0."""
+    if isinstance(bins, (bool, np.bool_)) or not isinstance(bins, (int, np.integer)) or int(bins) < 1:
+        msg = f"bins must be a whole number above 0, not {bins!r}"
+        raise ValueError(msg)
+    try:
+        lo_f, width_f = float(lo), float(width)
+        period_f = None if sample_period is None else float(sample_period)
+    except (TypeError, ValueError):
+        msg = f"lo, width and sample_period must be numbers, not {lo!r}, {width!r}, {sample_period!r}"
+        raise ValueError(msg) from None
+    if not np.isfinite(lo_f):
+        msg = f"lo must be finite, not {lo!r}"
+        raise ValueError(msg)
+    if not (np.isfinite(width_f) and width_f > 0.0):
+        msg = f"width must be finite and above 0, not {width!r}"
+        raise ValueError(msg)
+    if period_f is not None and not (np.isfinite(period_f) and period_f > 0.0):
+        msg = f"sample_period must be finite and above 0, not {sample_period!r}"
+        raise ValueError(msg)
+    return int(bins), lo_f, width_f, period_f
+
+
+def latency_state_cells(clock: np.ndarray, samples: np.ndarray, n_edges: int, sample_period: float, column: int, bins: int,
+                        lo: float = 0.0, width: float = 1.0, edges: Any = None) -> list[np.ndarray]:
+    """Per cell (arrival window w, bin b), at index ``w * bins + b``, the latencies of ONE scenario's rows ``clock`` [m, 2] that
+    belong to it, in row order: the latency of a request by the STATE it met on arrival.  ``samples``: the scenario's sampled
+    series as uint32 words [n_series, ticks]; ``column``: the series; ``n_edges``: the plan's (the ``ram_in_use`` columns are
+    float32 words, :func:`ram_columns`).  For a row with ``start = clock[i, 0]``:
+
+    * tick: ``q = floor(start / sample_period)`` in float64, ``k = q - 1``.  Sample ``k`` is taken at ``(k + 1) *
+      sample_period`` (the collector samples after its timeout), so ``k`` is the last sample taken at or before the arrival
+      AS THE FLOAT64 QUOTIENT SEES IT.  No state, no cell: ``q < 1`` (no sample yet), ``k >= ticks``, ``start`` NaN or negative.
+    * value: ``x`` = the word as float64 (the float32 value of a ``ram_in_use`` column), as :func:`series_window_histogram`.
+    * bin: ``x < lo``: no cell (-0.0 is not below 0.0); ``t = (x - lo) / width`` in float64; ``t >= bins``: the LAST bin (it
+      takes the overflow: "queue >= k" is a condition); otherwise bin ``floor(t)``.
+    * window: with ``edges`` the rule of ``window_of="arrival"``, ``edges[w] < start <= edges[w + 1]``, else no cell; with
+      ``edges=None`` one window with no condition on time.
+
+    The cohorts are right-censored like the arrival windows': a request that had not completed when the run ended, or was
+    dropped, is in no row.  The definition the device analyzers (``af_engine_summarize_state_windows`` /
+    ``af_engine_summarize_state_quantiles``) equal word for word."""
+    n_bins, lo_f, width_f, period = check_state_bins(bins, lo, width, sample_period)
+    ck = np.asarray(clock, dtype=np.float64).reshape(-1, 2)
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    n_series, ticks = words.shape
+    col = int(_check_series_columns([column], n_series)[0])
+    e = None if edges is None else check_edges(edges)
+    n_win = 1 if e is None else e.shape[0] - 1
+    start = ck[:, 0]
+    with np.errstate(invalid="ignore", over="ignore"):
+        lat = ck[:, 1] - start
+        q = np.floor(start / period)
+        ok = (start >= 0.0) & (q >= 1.0) & (q - 1.0 < float(ticks))
+        k = np.where(ok, q - 1.0, 0.0).astype(np.int64)
+        word = words[col, k] if ticks else np.zeros(k.shape, dtype=np.uint32)
+        x = word.view(np.float32).astype(np.float64) if ram_columns(n_series, n_edges)[col] else word.astype(np.float64)
+        ok &= x >= lo_f                                          # (a NaN, which no series holds: no cell)
+        t = (x - lo_f) / width_f
+        b = np.where(t >= float(n_bins), float(n_bins - 1), np.where(ok, t, 0.0)).astype(np.int64)
+    w = np.zeros(start.shape, dtype=np.int64)
+    if e is not None:
+        eb = np.searchsorted(e, start, side="left")              # #{edges < start}: window eb - 1 where 1 <= eb <= W
+        ok &= (eb >= 1) & (eb <= n_win)
+        w = eb - 1
+    key = np.where(ok, w * n_bins + b, n_win * n_bins)           # (rows without a cell: past the last key)
+    order = np.argsort(key, kind="stable")                       # (stable: a cell's rows stay in row order)
+    r = np.searchsorted(key[order], np.arange(n_win * n_bins + 1), side="left")
+    return [lat[order[r[c]:r[c + 1]]] for c in range(n_win * n_bins)]
+
+
+def latency_state_stats(clock: np.ndarray, samples: np.ndarray, n_edges: int, sample_period: float, column: int, bins: int,
+                        lo: float = 0.0, width: float = 1.0, edges: Any = None) -> np.ndarray:
+    """The eight latency statistics of every cell of :func:`latency_state_cells`: float64 [W', bins, 8] in LATENCY_KEYS order
+    (W' = 1 without ``edges``; an empty cell: total 0, the rest NaN)."""
+    cells = latency_state_cells(clock, samples, n_edges, sample_period, column, bins, lo, width, edges)
+    return np.stack([latency_stats_row(x) for x in cells]).reshape(-1, int(bins), 8)
+
+
+def latency_state_quantiles(clock: np.ndarray, samples: np.ndarray, n_edges: int, sample_period: float, column: int, bins: int,
+                            levels: Any, thresholds: Any = None, lo: float = 0.0, width: float = 1.0,
+                            edges: Any = None) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Quantiles and SLO counts of every cell of :func:`latency_state_cells`: ``(count`` uint32 [W', bins], ``quantiles``
+    float64 [W', bins, Q], ``within`` uint32 [W', bins, T]``)`` as :func:`latency_window_quantiles` gives them per window."""
+    q, th = check_levels(levels), check_slo_thresholds(thresholds)
+    cells = latency_state_cells(clock, samples, n_edges, sample_period, column, bins, lo, width, edges)
+    n_bins = int(bins)
+    count = np.array([x.shape[0] for x in cells], dtype=np.uint32).reshape(-1, n_bins)
+    quant = np.stack([latency_quantiles(x, q) for x in cells]).reshape(-1, n_bins, q.shape[0])
+    within = np.stack([latency_within(x, th) for x in cells]).reshape(-1, n_bins, th.shape[0])
+    return count, quant, within
+
+
+def series_names_of(plan: DevicePlan) -> list[str]:
+    """Names of the sampled series of a plan in device order: edges, then ready/io/ram per server."""
+    names = [f"{e}:edge_concurrent_connection" for e in plan.edge_ids]
+    for sid in plan.server_ids:
+        names += [f"{sid}:ready_queue_len", f"{sid}:event_loop_io_sleep", f"{sid}:ram_in_use"]
+    return names
+
+
+def _state_series(series: Any, names: list[str]) -> int:
+    """ONE series, a name of ``names`` or an index, as its index."""
+    if isinstance(series, (str, bytes)):
+        series = series.decode() if isinstance(series, bytes) else series
+        if series not in names:
+            msg = f"unknown series {series!r} (series_names(): {names})"
+            raise ValueError(msg)
+        return names.index(series)
+    if isinstance(series, (bool, np.bool_)) or not isinstance(series, (int, np.integer)):
+        msg = f"series must be one name of series_names() or one index, not {series!r}"
+        raise ValueError(msg)
+    return int(_check_series_columns([int(series)], len(names))[0])
+
+
 def series_histogram_quantiles(summary: dict[str, Any], levels: Any) -> np.ndarray:
     """Quantiles ``levels`` (any number of them, each in [0, 1]) read off a series histogram ``summary`` -- what
     :func:`series_window_histogram`, :meth:`ScenarioResults.get_series_histogram` or
@@ -765,6 +884,33 @@ class ScenarioResults:
         col = _check_series_columns(series, int(np.asarray(self._samples).shape[0]))
         out: dict[str, Any] = series_window_histogram(self._samples, b, self._plan.n_edges, bins, col, lo, width)
         out.update(series=col, tick_edges=b)
+        return out
+
+    def get_latency_by_state(self, series: Any, bins: int = 8, lo: float = 0.0, width: float = 1.0, window_s: float | None = None,
+                             edges: Any = None, levels: Any = None, thresholds: Any = None) -> dict[str, Any]:
+        """Latency by the state the request met on arrival (:func:`latency_state_cells`): the requests that arrived while
+        ``series`` (a name ``"<id>:<metric>"`` as in :meth:`BatchedResults.series_names`, or an index) was in bin ``b`` of
+        ``bins`` bins of ``width`` from ``lo`` (the last bin takes the overflow).  ``stats`` float64 [W', bins, 8] and ``count``
+        [W', bins]; with ``levels`` / ``thresholds`` also ``quantiles`` [W', bins, Q], ``within`` [W', bins, T] and ``share``.
+        Windows by ARRIVAL time of ``window_s`` seconds or explicit ``edges``; neither: one window (W' = 1, ``edges`` None).
+        ``bin_lo`` [bins] are the bins' lower edges, ``series`` the series index.  Right-censored cohorts, as
+        ``window_of="arrival"``."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        col = _state_series(series, series_names_of(self._plan))
+        n_bins, lo_f, width_f, period = check_state_bins(bins, lo, width, self._plan.sample_period)
+        e = None if window_s is None and edges is None else _resolve_edges(window_s, edges, self._plan.total_time)
+        args = (self.rqs_clock, self._samples, self._plan.n_edges, period, col, n_bins)
+        stats = latency_state_stats(*args, lo_f, width_f, e)
+        out: dict[str, Any] = {"stats": stats, "count": stats[:, :, 0].astype(np.int64), "keys": LATENCY_KEYS, "edges": e,
+                               "bin_lo": lo_f + np.arange(n_bins, dtype=np.float64) * width_f, "series": col}
+        if levels is not None or thresholds is not None:
+            count, quant, within = latency_state_quantiles(*args, [] if levels is None else levels, thresholds, lo_f, width_f, e)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                share = np.where(count[:, :, None] > 0, within / count[:, :, None].astype(np.float64), np.nan)
+            out.update(quantiles=quant, within=within, share=share, levels=check_levels([] if levels is None else levels),
+                       thresholds=check_slo_thresholds(thresholds))
         return out
 
     def get_sampled_metrics(self) -> dict[str, dict[str, list[float]]]:
@@ -1053,10 +1199,7 @@ class BatchedResults:
 
     def series_names(self) -> list[str]:
         """Names of the sampled series in device order: edges, then ready/io/ram per server."""
-        names = [f"{e}:edge_concurrent_connection" for e in self.plan.edge_ids]
-        for sid in self.plan.server_ids:
-            names += [f"{sid}:ready_queue_len", f"{sid}:event_loop_io_sleep", f"{sid}:ram_in_use"]
-        return names
+        return series_names_of(self.plan)
 
     def aggregate(self, level: float = 0.95, by: Any = None) -> dict[str, Any]:
         """Monte-Carlo aggregation over the scenarios of the sweep (the reference's roadmap
@@ -1326,6 +1469,113 @@ class BatchedResults:
         cols["slo_thresholds"] = np.asarray(bands["thresholds"], dtype=np.float64)
         cols["window_edges"] = np.zeros(0, dtype=np.float64) if bands["edges"] is None else np.asarray(bands["edges"], dtype=np.float64)
         cols["window_of"] = np.asarray(window_of)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
+    def _state_request(self, series: Any, bins: Any, lo: Any, width: Any, window_s: float | None, edges: Any, by: Any) -> dict[str, Any]:
+        """What the two latency-by-state calls share: the checked request and the device buffers of the group ids."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_clock()
+        self._require_samples()
+        col = _state_series(series, self.series_names())
+        n_bins, lo_f, width_f, period = check_state_bins(bins, lo, width, self.plan.sample_period)
+        e = None if window_s is None and edges is None else _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        dev = self._clock_t.device
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        kw = {"column": col, "bins": n_bins, "lo": lo_f, "width": width_f, "sample_period": period, "edges": e,
+              "clock_ptr": self._clock_t.data_ptr(), "clock_capacity": int(self._clock_t.shape[1]),
+              "samples_ptr": self._samples_t.data_ptr(), "tick_capacity": int(self._samples_t.shape[1]),
+              "counts_ptr": self._counts_t.data_ptr(), "group_ptr": grp.data_ptr()}
+        return {"kw": kw, "grp": grp, "ids": ids, "n_groups": n_groups, "n_win": 1 if e is None else int(e.shape[0] - 1), "dev": dev,
+                "meta": {"edges": e, "bin_lo": lo_f + np.arange(n_bins, dtype=np.float64) * width_f, "series": col,
+                         "replicas": np.bincount(ids[ids >= 0], minlength=n_groups)}}
+
+    def state_summary(self, series: Any, bins: int = 8, *, lo: float = 0.0, width: float = 1.0, window_s: float | None = None,
+                      edges: Any = None, by: Any = None) -> dict[str, Any]:
+        """Latency by the STATE A REQUEST MET ON ARRIVAL: the eight latency statistics of every (group, arrival window, bin of
+        ``series`` at the request's arrival tick) -- does p95 rise with the ready queue of a server, with RAM in use, with the
+        connections on an edge?  ``series``: one name of :meth:`series_names` or one index; ``bins`` bins of ``width`` from
+        ``lo``, the last bin taking the overflow; the sample period is the plan's.  The state of a request is the last sample
+        taken at or before its arrival as the float64 quotient ``start / sample_period`` sees it; requests that arrived before
+        the first sample, or whose value lies below ``lo``, are in no cell (:func:`latency_state_cells`, the definition the HIP
+        kernels of ``af_engine_summarize_state_windows`` equal bit for bit).  Windows by ARRIVAL time of ``window_s`` seconds
+        or explicit ``edges``; neither: one window with no condition on time (W' = 1, ``edges`` None).  ``by`` as in
+        :meth:`window_summary`.  Returns ``stats`` float64 [G, W', bins, 8] on the run's device (an empty cell: total 0, the rest
+        NaN), ``bin_lo`` [bins], ``edges``, ``series`` (the index), ``keys``, ``replicas`` [G], ``state_ms`` and
+        ``scratch_bytes``.  The cohorts are right-censored like ``window_of="arrival"``: ``total`` counts completions."""
+        import torch
+
+        rq = self._state_request(series, bins, lo, width, window_s, edges, by)
+        stats = torch.empty((rq["n_groups"], rq["n_win"], int(bins), 8), dtype=torch.float64, device=rq["dev"])
+        ms, scratch = self._summ_engine.summarize_state_windows(len(self), rq["n_groups"], stats_ptr=stats.data_ptr(), **rq["kw"])
+        return {"stats": stats, "keys": LATENCY_KEYS, "state_ms": ms, "scratch_bytes": scratch, **rq["meta"]}
+
+    def state_quantile_summary(self, series: Any, levels: Any, *, thresholds: Any = None, bins: int = 8, lo: float = 0.0,
+                               width: float = 1.0, window_s: float | None = None, edges: Any = None, by: Any = None) -> dict[str, Any]:
+        """Any latency quantiles and SLO shares over the cells of :meth:`state_summary` (``af_engine_summarize_state_quantiles``,
+        bit-equal to :func:`latency_state_quantiles` / ``np.quantile`` on the concatenated latencies): ``quantiles`` float64
+        [G, W', bins, Q] (NaN where empty), ``count`` int64 [G, W', bins], ``within`` int64 [G, W', bins, T] and ``share`` float64
+        (= within / count, NaN where empty) on the run's device; ``levels``, ``thresholds`` and the rest as there."""
+        import torch
+
+        q, th = check_levels(levels), check_slo_thresholds(thresholds)
+        if q.shape[0] == 0 and th.shape[0] == 0:
+            msg = "state_quantile_summary needs at least one level or one threshold"
+            raise ValueError(msg)
+        rq = self._state_request(series, bins, lo, width, window_s, edges, by)
+        shape, dev = (rq["n_groups"], rq["n_win"], int(bins)), rq["dev"]
+        quant = torch.empty((*shape, q.shape[0]), dtype=torch.float64, device=dev)
+        count = torch.empty(shape, dtype=torch.int32, device=dev)
+        within = torch.empty((*shape, th.shape[0]), dtype=torch.int32, device=dev)
+        ms, scratch = self._summ_engine.summarize_state_quantiles(
+            len(self), rq["n_groups"], q, thresholds=th, count_ptr=count.data_ptr(), quantiles_ptr=quant.data_ptr() if q.shape[0] else 0,
+            within_ptr=within.data_ptr() if th.shape[0] else 0, **rq["kw"])
+        cnt = count.to(torch.int64) & 0xFFFFFFFF   # (the device's words are uint32)
+        wth = within.to(torch.int64) & 0xFFFFFFFF
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        share = torch.where((cnt > 0)[..., None], wth.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)[..., None], nan)
+        return {"quantiles": quant, "count": cnt, "within": wth, "share": share, "levels": q, "thresholds": th, "state_ms": ms,
+                "scratch_bytes": scratch, **rq["meta"]}
+
+    def save_state_summary(self, path: str, by: Any = None, *, series: Any, bins: int = 8, lo: float = 0.0, width: float = 1.0,
+                           window_s: float | None = None, edges: Any = None, levels: Any = None,
+                           thresholds: Any = None) -> dict[str, np.ndarray]:
+        """Columnar dump of the latency-by-state statistics with one row per group (grid point): ``param:<axis>`` (for a
+        Sweep), ``replicas``, per latency key the [G, W', bins] column ``state_pooled:<key>`` (:meth:`state_summary`) and, with
+        ``levels`` / ``thresholds``, ``state_count`` and per level i / threshold j ``state_quantile:<i>`` / ``state_share:<j>``
+        (:meth:`state_quantile_summary`).  ``state_bin_lo`` [bins], ``state_series`` (the series index), ``window_edges``
+        [W' + 1] (empty: one window over all time), ``quantile_levels`` and ``slo_thresholds`` are per-file values.  ``.npz`` or
+        ``.parquet``; :func:`load_summary` reads it back.  (Bands over replicas are not written: most cells of one replica are
+        empty.)"""
+        summ = self.state_summary(series, bins, lo=lo, width=width, window_s=window_s, edges=edges, by=by)
+        n_groups = int(summ["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(summ["replicas"], dtype=np.int64)
+        st = summ["stats"].cpu().numpy()
+        for j, k in enumerate(LATENCY_KEYS):
+            cols[f"state_pooled:{k}"] = np.ascontiguousarray(st[..., j])
+        q, th = check_levels([] if levels is None else levels), check_slo_thresholds(thresholds)
+        if q.shape[0] or th.shape[0]:
+            qs = self.state_quantile_summary(series, q, thresholds=th, bins=bins, lo=lo, width=width, window_s=window_s, edges=edges, by=by)
+            cols["state_count"] = np.ascontiguousarray(qs["count"].cpu().numpy(), dtype=np.int64)
+            for i in range(q.shape[0]):
+                cols[f"state_quantile:{i}"] = np.ascontiguousarray(qs["quantiles"].cpu().numpy()[..., i])
+            for i in range(th.shape[0]):
+                cols[f"state_share:{i}"] = np.ascontiguousarray(qs["share"].cpu().numpy()[..., i])
+        cols["quantile_levels"], cols["slo_thresholds"] = q, th
+        cols["state_bin_lo"] = np.asarray(summ["bin_lo"], dtype=np.float64)
+        cols["state_series"] = np.asarray([summ["series"]], dtype=np.float64)
+        cols["window_edges"] = np.zeros(0, dtype=np.float64) if summ["edges"] is None else np.asarray(summ["edges"], dtype=np.float64)
         _write_columns(str(path), cols, n_groups)
         return cols
 
@@ -2276,6 +2526,18 @@ class ShardedResults:
 
     def save_series_histogram_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_histogram_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def state_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "state_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def state_quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "state_quantile_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_state_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_state_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:

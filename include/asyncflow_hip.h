@@ -699,6 +699,53 @@ int af_engine_summarize_quantiles(af_engine_t* engine, const af_outputs_t* out, 
  * neither needed nor checked.  Everything else as af_engine_summarize_quantiles. */
 int af_engine_summarize_arrival_quantiles(af_engine_t* engine, const af_outputs_t* out, af_quantiles_t* quantiles);
 
+/* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
+ * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
+ * use, with the connections on an edge?  A cell is (group g, arrival window w, bin b of ONE sampled series at the row's tick).
+ * For scenario s, m_s = min(counts[s][AF_CNT_COMPLETED], clock_capacity) rows and t_s = min(counts[s][AF_CNT_TICKS],
+ * tick_capacity) sample rows; a stored row i has start = clock[s][i][0].
+ *   tick    q = floor(start / sample_period) -- one f64 division rounded to nearest, then floor --, k = q - 1.  Sample row k is
+ *           taken at (k + 1) * sample_period (collector.py:53; see af_series_windows_t), so k is the last sample taken at or
+ *           before the arrival AS THE F64 QUOTIENT SEES IT (a start a rounding error below a multiple of the period may be
+ *           given that multiple's sample).  The row has no state and belongs to no cell when q < 1 (no sample yet), k >= t_s,
+ *           or start is NaN or negative.
+ *   value   x = the word samples[s][k][column] as f64 exactly as af_series_histogram_t takes it: (double)word of an integer
+ *           series, (double)(float) of a ram_in_use column.  Only that word of a row is read: never the padding, never a row
+ *           at or past t_s.
+ *   bin     x < lo -> no cell (-0.0 is not below 0.0; a -2^-45 residue is);  t = (x - lo) / width, one f64 subtraction and one
+ *           f64 division;  t >= (double)n_bins -> bin n_bins - 1 (the last bin takes the overflow, as af_summary_t.hist does:
+ *           "queue >= k" is a condition);  otherwise bin (uint32_t)t.
+ *   window  with n_windows > 0 af_engine_summarize_arrival_windows's rule, edges[w] < start <= edges[w + 1], else no cell; with
+ *           n_windows == 0 and edges == NULL ONE window with no condition on time.  W' = max(n_windows, 1).
+ * Cell (g, w, b) has index (g * W' + w) * n_bins + b; its sample is the concatenation, in ascending scenario index over the
+ * members of g, of finish - start over the member's rows of that cell IN ROW ORDER.
+ *   af_engine_summarize_state_windows    stats [n_groups][W'][n_bins][8]: numpy's eight statistics of the cell, bit for bit
+ *                                        (an empty cell: total 0, the rest NaN); row_bounds, if given, receives the CUMULATIVE
+ *                                        CELL COUNTS [n_scenarios][W' * n_bins + 1]: c_s[0] = 0, c_s[k + 1] - c_s[k] = the rows of
+ *                                        scenario s in cell (w, b) with w * n_bins + b = k (also of skipped scenarios)
+ *   af_engine_summarize_state_quantiles  count / quantiles / within of af_quantiles_t over the same cells ([C], [C][n_levels],
+ *                                        [C][n_thresholds] with C = n_groups * W' * n_bins): np.quantile and exact counts
+ * The cohorts are RIGHT-CENSORED like the arrival windows': a request that had not completed when the run ended, or was
+ * dropped, is in no row, so a cell's total / count is its cohort's completions.  A cell's result is identical from run to run
+ * and does not depend on the batch a scenario sits in (integer atomics only; a cell's rows are placed in row order by one wave).
+ * Refused, no output touched: n_bins == 0; a width that is <= 0, NaN or infinite; a lo that is NaN or infinite; a
+ * sample_period that is <= 0, NaN or infinite; column >= af_series_count; outputs.samples or outputs.counts NULL or
+ * tick_capacity == 0; edges given with n_windows == 0 or missing with n_windows > 0; the refusals of the arrival entry points
+ * (AF_ERR_INVALID); n_groups * W' * n_bins >= 2^32 - 1, n_scenarios * (W' * n_bins + 1) >= 2^32, a cell of 2^32 or more latencies
+ * (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).  `out` needs clock, samples, both capacities and counts.
+ * Scratch kept by the engine: af_engine_summarize_windows's / af_engine_summarize_quantiles's with W' * n_bins for n_windows (8 B per
+ * latency in a cell + 8 B per (scenario, cell) + at most 12 B per (group, cell) + 8 B per edge + the large cells' parts); the
+ * key of a row is recomputed by the second pass, not stored.  Synchronous; the request struct is written back. */
+typedef struct af_state_bins {
+    uint32_t column;        /* the sampled series, < af_series_count */
+    uint32_t n_bins;        /* > 0 */
+    double lo;              /* finite: the lower edge of bin 0 */
+    double width;           /* finite, > 0 */
+    double sample_period;   /* seconds, finite, > 0: the plan's */
+} af_state_bins_t;
+int af_engine_summarize_state_windows(af_engine_t* engine, const af_outputs_t* out, const af_state_bins_t* bins, af_windows_t* windows);
+int af_engine_summarize_state_quantiles(af_engine_t* engine, const af_outputs_t* out, const af_state_bins_t* bins, af_quantiles_t* quantiles);
+
 /* af_engine_run followed by af_engine_summarize, in one call and with the same results (replaces SimulationRunner.run +
  * ResultsAnalyzer.process_all_metrics, simulation_runner.py:349-376 + analyzer.py:75-81, for the whole sweep).
  * summary->n_scenarios must equal sweep->n_scenarios.  Where the sweep is ONE launch of the stage-parallel kernel, the analyzer
