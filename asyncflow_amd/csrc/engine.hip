@@ -988,6 +988,8 @@ struct af_engine {
                                    // [21..24], what the second chance (d_fb + 5) finds at that offset: always 0
     uint32_t* d_slot = nullptr;    // draw slots of a second pass over a subset
     size_t slot_cap = 0;
+    unsigned long long* d_prof = nullptr;   // AF_FLOW_PROF: shader-clock time per scenario and section of Flow::run
+    size_t prof_cap = 0;
     // host copy of what the layout heuristics need
     uint32_t has_lb = 0, cores_max = 1, ram_slots_max = 1;
     std::vector<double> edge_mean, edge_sigma, edge_spike;   // per edge: latency law, largest cumulative spike
@@ -1119,11 +1121,44 @@ uint32_t chunk_size(const af_engine* e, uint32_t n, size_t draw_bytes_per_scen, 
     return (n + n_chunks - 1u) / n_chunks;  // equal chunks: no short, latency-bound tail launch
 }
 
+// An engine-owned device buffer, grown on demand (the contents are lost then) and kept until the engine is destroyed.
+int reserve_device(void** ptr, size_t& cap, size_t need) {
+    if (need <= cap) return AF_OK;
+    if (*ptr) HIP_TRY(hipFree(*ptr));
+    *ptr = nullptr;
+    cap = 0;
+    HIP_TRY(hipMalloc(ptr, need));
+    cap = need;
+    return AF_OK;
+}
+
+uint32_t klog_of(uint32_t lanes) {
+    uint32_t klog = 0;
+    while ((1u << klog) < lanes) ++klog;
+    return klog;
+}
+
+// The columns a sweep overrides, as bits.  (Only a run reads the values: af_engine_jit_spec looks at them on the
+// stage-parallel path alone.)
+int sweep_override_mask(const af_sweep_t* sweep, bool values_required, uint32_t& mask) {
+    mask = 0;
+    for (uint32_t k = 0; k < sweep->n_overrides; ++k) {
+        const af_override_t& o = sweep->overrides[k];
+        if (o.param >= AF_PARAM_COUNT_ || (values_required && !o.values)) return fail(AF_ERR_INVALID, "bad override");
+        mask |= 1u << o.param;
+    }
+    return AF_OK;
+}
+
+// pre-generated draws per stream and scenario
+int draws_per_stream(const af_sweep_t* sweep, const af_outputs_t* out, uint32_t& n_draw) {
+    n_draw = sweep->draw_capacity ? sweep->draw_capacity : out->clock_capacity;
+    if (n_draw == 0) return fail(AF_ERR_INVALID, "draw_capacity (or clock_capacity) must be > 0");
+    return AF_OK;
+}
+
 
 // ---- stage-parallel kernel: what one af_engine_run launches -------------------------------------------------
-// List capacity and tick ring from what will be in flight at the heaviest point of the sweep, the instantiation
-// (IPL, FEAT) that covers the launch.  Shared by af_engine_run and af_engine_jit_spec (the plan-specialised build
-// bakes exactly this in).
 // Does this sweep run on the stage-parallel kernel?  flow_mode 0: whenever the plan is in its range; 2 = the same, but a sweep
 // it cannot be sized for is an error instead of a fall-back; 1 = never.
 // (Round 3 sent plans with general servers -- several endpoints per server, core re-entry -- there only as sweeps of <= 8
@@ -1136,13 +1171,8 @@ static bool flow_wanted(const af_engine_t* e, uint32_t n_scenarios) {
     return e->flow_ok && e->flow_mode != 1u;
 }
 
-// Sweeps with a users / rpm column: does af_arrival_groups still pay?  Its workgroup is as slow as its heaviest scenario (the
-// chain wave walks that scenario's draws; the lighter lanes idle, the producers skip them) and the kernel as slow as its slowest
-// workgroup -- one per CU, all resident --, so its time follows the HEAVIEST scenario of the chunk whatever the others are,
-// while the row kernel's follows the TOTAL number of draws at about twice the cost per draw.
-// Measured (MI355X): config 3 (users 10 .. 1000, heaviest / mean = 1.98): rows 14.8 ms, groups 11.3 ms; config 4: 103 -> 90 ms.
-// launch order of a chunk's scenarios for sweeps with a users / rpm column: heaviest first (stable)
-static std::vector<uint32_t> heaviest_first(const af_engine_t* e, const af_sweep_t* sweep, uint32_t lo, uint32_t nc) {
+// load (users x requests per minute) of the scenarios [lo, lo + nc) of a sweep: its users / rpm columns, else the plan's means
+static std::vector<double> chunk_loads(const af_engine_t* e, const af_sweep_t* sweep, uint32_t lo, uint32_t nc) {
     const double* users = nullptr;
     const double* rpm = nullptr;
     for (uint32_t k = 0; k < sweep->n_overrides; ++k) {
@@ -1152,22 +1182,24 @@ static std::vector<uint32_t> heaviest_first(const af_engine_t* e, const af_sweep
     }
     std::vector<double> load(nc);
     for (uint32_t i = 0; i < nc; ++i) load[i] = (users ? users[i] : e->users_mean) * (rpm ? rpm[i] : e->rpm_mean);
+    return load;
+}
+// launch order of a chunk's scenarios for sweeps with a users / rpm column: heaviest first (stable)
+static std::vector<uint32_t> heaviest_first(const af_engine_t* e, const af_sweep_t* sweep, uint32_t lo, uint32_t nc) {
+    const std::vector<double> load = chunk_loads(e, sweep, lo, nc);
     std::vector<uint32_t> order(nc);
     for (uint32_t i = 0; i < nc; ++i) order[i] = i;
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return load[x] > load[y]; });
     return order;
 }
+// Sweeps with a users / rpm column: does af_arrival_groups still pay?  Its workgroup is as slow as its heaviest scenario (the
+// chain wave walks that scenario's draws; the lighter lanes idle, the producers skip them) and the kernel as slow as its slowest
+// workgroup -- one per CU, all resident --, so its time follows the HEAVIEST scenario of the chunk whatever the others are,
+// while the row kernel's follows the TOTAL number of draws at about twice the cost per draw.
+// Measured (MI355X): config 3 (users 10 .. 1000, heaviest / mean = 1.98): rows 14.8 ms, groups 11.3 ms; config 4: 103 -> 90 ms.
 static bool load_spread_suits_groups(const af_engine_t* e, const af_sweep_t* sweep, uint32_t lo, uint32_t nc) {
-    const double* users = nullptr;
-    const double* rpm = nullptr;
-    for (uint32_t k = 0; k < sweep->n_overrides; ++k) {
-        const af_override_t& o = sweep->overrides[k];
-        if (o.param == AF_PARAM_GEN_USERS_MEAN) users = o.values + lo;
-        else if (o.param == AF_PARAM_GEN_RPM_MEAN) rpm = o.values + lo;
-    }
     double sum = 0.0, heaviest = 0.0;
-    for (uint32_t i = 0; i < nc; ++i) {
-        const double load = (users ? users[i] : e->users_mean) * (rpm ? rpm[i] : e->rpm_mean);
+    for (const double load : chunk_loads(e, sweep, lo, nc)) {
         heaviest = load > heaviest ? load : heaviest;
         sum += load;
     }
@@ -1185,6 +1217,9 @@ struct FlowPlan {
     bool gen_compact = false;      // general servers, first launch: long-list instantiation WITHOUT send times, lists sized by the load
 };
 
+// List capacity and tick ring from what will be in flight at the heaviest point of the sweep, the instantiation
+// (IPL, FEAT) that covers the launch.  Shared by af_engine_run and af_engine_jit_spec (the plan-specialised build
+// bakes exactly this in).
 int plan_flow(const af_engine* e, const KArgs& a, const af_sweep_t* sweep, const af_outputs_t* out, FlowPlan& P) {
     const uint32_t n = sweep->n_scenarios;
     aff::FlowLayout& FL = P.FL;
@@ -1822,7 +1857,46 @@ static int launch_summary_kernels(af_engine_t* e, const af_outputs_t* out, const
     return AF_OK;
 }
 
-int af_engine_run(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* out) {
+// ---- af_engine_run: one sweep as a sequence of steps -------------------------------------------------------------------
+// The totals of a run: what becomes e->stats at its end.
+struct RunTotals {
+    double ms_pregen = 0.0, ms_kernel = 0.0, ms_flow = 0.0;
+    float ms_h2d = 0.f;
+    uint32_t kl = 0, waves = 0, lds_bytes = 0;   // of the last next-event launch ...
+    bool lds_state = false;                      // ... and where its state lived
+    uint32_t n_chunks = 0, n_rerun = 0, n_jit = 0, n_jit_miss = 0;
+    uint32_t fb_total[5] = {0, 0, 0, 0, 0}, flow_scen = 0;
+    uint32_t flow_retried = 0, flow_to_next = 0;
+    size_t draw_bytes = 0;
+    uint32_t pregen_group = 0;
+    uint32_t fused_first = 0u;   // af_engine_run_summarized: scenarios whose analyzer ran beside the stage-parallel kernel's last round
+};
+
+// What is fixed once the sweep is validated, staged and sized.  The steps of a run take it and what else they need; all they
+// change in it are the totals.
+struct Run {
+    af_engine_t* e = nullptr;
+    const af_sweep_t* sweep = nullptr;
+    const af_outputs_t* out = nullptr;
+    uint32_t mask = 0;   // the columns the sweep overrides
+    uint32_t n = 0, n_draw = 0;
+    size_t draw_bytes_per_scen = 0;
+    af::Layout L{};
+    uint64_t bytes_per_lane = 0;
+    size_t tie_words = 0;
+    bool hetero_load = false;   // a users / rpm column: scenario lengths differ by orders of magnitude
+    // the staged sweep on the device
+    const uint64_t* d_seeds = nullptr;
+    const double* d_values = nullptr;   // [n_overrides][n]
+    const uint32_t* d_params = nullptr;
+    const uint32_t* d_idxs = nullptr;
+    bool use_flow = false;   // the sweep starts on the stage-parallel kernel, sized by FP
+    FlowPlan FP;
+    RunTotals t;
+};
+
+// The arguments and the override columns of a run; the columns' bits, the state layout they need.
+static int validate_sweep(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* out, Run& r) {
     if (!e || !sweep || !out) return fail(AF_ERR_INVALID, "NULL argument");
     if (sweep->n_scenarios == 0 || !sweep->seeds) return fail(AF_ERR_INVALID, "empty sweep");
     if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
@@ -1833,13 +1907,15 @@ int af_engine_run(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* o
     if (out->online_rps && out->online_rps_buckets == 0) return fail(AF_ERR_INVALID, "online_rps with zero buckets");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY): it cannot run");
     HIP_TRY(hipSetDevice(e->device));
-    KArgs a = e->args;
+    const KArgs& a = e->args;
     const uint32_t n = sweep->n_scenarios;
-
-    uint32_t mask = 0;
+    r.e = e;
+    r.sweep = sweep;
+    r.out = out;
+    r.n = n;
+    if (int rc = sweep_override_mask(sweep, true, r.mask)) return rc;
     for (uint32_t k = 0; k < sweep->n_overrides; ++k) {
         const af_override_t& o = sweep->overrides[k];
-        if (o.param >= AF_PARAM_COUNT_ || !o.values) return fail(AF_ERR_INVALID, "bad override");
         const uint32_t lim = (o.param >= AF_PARAM_EDGE_MEAN && o.param <= AF_PARAM_EDGE_DROPOUT) ? a.n_edges
                              : (o.param == AF_PARAM_STEP_TIME)                                   ? (uint32_t)e->row_of_step.size()
                              : (o.param == AF_PARAM_SRV_CORES || o.param == AF_PARAM_SRV_RAM_MB)  ? a.n_servers
@@ -1859,23 +1935,24 @@ int af_engine_run(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* o
             if (o.param == AF_PARAM_GEN_WINDOW && !(v > 0.0)) return fail(AF_ERR_INVALID, "user_sampling_window column must be positive");
             if (o.param == AF_PARAM_SRV_RAM_MB && !(v > 0.0)) return fail(AF_ERR_INVALID, "ram_mb column must be positive");
         }
-        mask |= 1u << o.param;
     }
-    a.L = af::make_layout(e->request_capacity, e->fifo_capacity, a.n_edges, a.n_servers, a.n_lb_edges, a.n_rows, mask, a.n_edge_marks, a.n_srv_marks);
-    const uint64_t bytes_per_lane = af::layout_bytes_per_lane(a.L);
+    r.L = af::make_layout(e->request_capacity, e->fifo_capacity, a.n_edges, a.n_servers, a.n_lb_edges, a.n_rows, r.mask, a.n_edge_marks, a.n_srv_marks);
+    r.bytes_per_lane = af::layout_bytes_per_lane(r.L);
+    r.tie_words = r.L.tie_words;
+    r.hetero_load = (r.mask & ((1u << AF_PARAM_GEN_USERS_MEAN) | (1u << AF_PARAM_GEN_RPM_MEAN))) != 0u;
+    return AF_OK;
+}
 
-    // ---- upload seeds + override tables (one staging buffer) -------------------
+// Upload seeds + override tables (one staging buffer).
+static int stage_sweep(Run& r) {
+    af_engine_t* e = r.e;
+    const af_sweep_t* sweep = r.sweep;
+    const uint32_t n = r.n;
     const size_t seeds_b = (size_t)n * 8;
     const size_t vals_b = (size_t)sweep->n_overrides * n * 8;
     const size_t tab_b = (size_t)(sweep->n_overrides ? sweep->n_overrides : 1) * 4;
     const size_t total = seeds_b + vals_b + 2 * ((tab_b + 7) & ~size_t(7));
-    if (total > e->sweep_cap) {
-        if (e->d_sweep) HIP_TRY(hipFree(e->d_sweep));
-        e->d_sweep = nullptr;
-        e->sweep_cap = 0;
-        HIP_TRY(hipMalloc(&e->d_sweep, total));
-        e->sweep_cap = total;
-    }
+    if (int rc = reserve_device(&e->d_sweep, e->sweep_cap, total)) return rc;
     unsigned char* ds = static_cast<unsigned char*>(e->d_sweep);
     HIP_TRY(hipEventRecord(e->ev0, e->stream));
     HIP_TRY(hipMemcpyAsync(ds, sweep->seeds, seeds_b, hipMemcpyHostToDevice, e->stream));
@@ -1892,544 +1969,631 @@ int af_engine_run(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* o
     HIP_TRY(hipMemcpyAsync(d_idxs, idxs.data(), tab_b, hipMemcpyHostToDevice, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));  // host staging vectors go out of scope below
     HIP_TRY(hipEventRecord(e->ev1, e->stream));
+    r.d_seeds = reinterpret_cast<const uint64_t*>(ds);
+    r.d_values = reinterpret_cast<const double*>(ds + seeds_b);
+    r.d_params = reinterpret_cast<const uint32_t*>(d_params);
+    r.d_idxs = reinterpret_cast<const uint32_t*>(d_idxs);
+    return AF_OK;
+}
 
-    a.n_ovr = sweep->n_overrides;
-    a.ovr_param = reinterpret_cast<const uint32_t*>(d_params);
-    a.ovr_index = reinterpret_cast<const uint32_t*>(d_idxs);
-    a.ovr_stride = n;
+// The kernel arguments of the chunk [lo, lo + nc) of the sweep.  Built once per chunk; a launch works on a copy of its own,
+// in which it sets where ITS scenarios, draws and state are (scen_map, draw_slot, draws_by_lane, n_scen, draws, pre_flags, tie,
+// state, state_bytes_per_wave).
+static KArgs chunk_kargs(const Run& r, uint32_t lo, uint32_t nc) {
+    const af_outputs_t* out = r.out;
+    KArgs a = r.e->args;
+    a.L = r.L;
+    a.n_ovr = r.sweep->n_overrides;
+    a.ovr_param = r.d_params;
+    a.ovr_index = r.d_idxs;
+    a.ovr_stride = r.n;
     a.clock_cap = out->clock_capacity;
     a.tick_cap = out->tick_capacity;
+    a.n_draw = r.n_draw;
+    a.n_shared = r.e->d_n_shared;
+    a.n_scen = nc;
+    a.scen_map = nullptr;
+    a.draw_slot = nullptr;
+    a.draws_by_lane = 0u;
+    a.seeds = r.d_seeds + lo;
+    a.ovr_values = r.d_values + lo;
+    a.clock = out->clock ? out->clock + (size_t)lo * out->clock_capacity * 2u : nullptr;
+    a.samples = out->samples ? out->samples + (size_t)lo * a.series_pitch * out->tick_capacity : nullptr;
+    a.counts = out->counts + (size_t)lo * AF_CNT_SLOTS;
+    a.online_hist = out->online_hist ? out->online_hist + (size_t)lo * out->online_hist_bins : nullptr;
+    a.online_rps = out->online_rps ? out->online_rps + (size_t)lo * out->online_rps_buckets : nullptr;
+    a.online_hist_bins = out->online_hist_bins;
+    a.online_rps_buckets = out->online_rps_buckets;
+    a.online_hist_scale = out->online_hist ? (double)out->online_hist_bins / out->online_hist_max : 0.0;
+    return a;
+}
 
-    // ---- buffers ------------------------------------------------------------------------------------
-    const uint32_t n_draw = sweep->draw_capacity ? sweep->draw_capacity : out->clock_capacity;
-    if (n_draw == 0) return fail(AF_ERR_INVALID, "draw_capacity (or clock_capacity) must be > 0");
-    const size_t draw_bytes_per_scen = (size_t)(1u + a.n_edges) * n_draw * sizeof(double);
+// Draws per stream, the kernel family the sweep starts on and its sizing, scenarios per chunk.
+static int size_run(Run& r, uint32_t& chunk) {
+    af_engine_t* e = r.e;
+    if (int rc = draws_per_stream(r.sweep, r.out, r.n_draw)) return rc;
+    r.draw_bytes_per_scen = (size_t)(1u + e->args.n_edges) * r.n_draw * sizeof(double);
     // (a sweep the stage-parallel kernel cannot be sized for -- a cpu_cores column above 64, lists that do not fit the LDS --
     // runs on the next-event kernels like a plan outside its range does, unless flow_mode 2 asked for that kernel: ADVICE r3)
-    bool use_flow = flow_wanted(e, n);
-    FlowPlan FP;
-    if (use_flow) {
-        const int rc = plan_flow(e, a, sweep, out, FP);
-        if (rc == AF_ERR_CAPACITY && e->flow_mode != 2u) use_flow = false;
+    r.use_flow = flow_wanted(e, r.n);
+    if (r.use_flow) {
+        const int rc = plan_flow(e, chunk_kargs(r, 0u, r.n), r.sweep, r.out, r.FP);
+        if (rc == AF_ERR_CAPACITY && e->flow_mode != 2u) r.use_flow = false;
         else if (rc) return rc;
     }
     size_t mem_free = 0, mem_total = 0;
     HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
     // the stage-parallel kernel only needs the arrival times of a chunk; the next-event kernels every draw
-    const uint32_t chunk = chunk_size(e, n, use_flow ? (size_t)n_draw * sizeof(double) : draw_bytes_per_scen,
-                                      mem_free + (use_flow ? e->arr_cap : 0));
+    chunk = chunk_size(e, r.n, r.use_flow ? (size_t)r.n_draw * sizeof(double) : r.draw_bytes_per_scen,
+                       mem_free + (r.use_flow ? e->arr_cap : 0));
     if (chunk == 0) return fail(AF_ERR_CAPACITY, "draw_capacity too large for the device memory budget");
-    auto grow = [&](void** ptr, size_t& cap, size_t need) -> int {
-        if (need <= cap) return AF_OK;
-        if (*ptr) HIP_TRY(hipFree(*ptr));
-        *ptr = nullptr;
-        cap = 0;
-        HIP_TRY(hipMalloc(ptr, need));
-        cap = need;
-        return AF_OK;
-    };
-    a.n_draw = n_draw;
-    a.n_shared = e->d_n_shared;
-    a.scen_map = nullptr;
-    a.draw_slot = nullptr;
-    a.draws_by_lane = 0u;
+    return AF_OK;
+}
 
-    double ms_pregen = 0.0, ms_kernel = 0.0, ms_flow = 0.0;
-    uint32_t kl = 0, waves = 0, lds_bytes = 0, n_chunks = 0, n_rerun = 0, n_jit = 0, n_jit_miss = 0;
-    uint32_t fused_first = 0u;   // af_engine_run_summarized: scenarios whose analyzer ran beside the stage-parallel kernel's last round
-    uint32_t fb_total[5] = {0, 0, 0, 0, 0}, flow_scen = 0;
-    uint32_t flow_retried = 0, flow_to_next = 0;
-    size_t draw_bytes = 0;
-    uint32_t pregen_group = 0;
-    bool lds_state = false;
+// One launch of the next-event kernel over `count` scenarios (all of the chunk, or the ones listed in a.scen_map).
+static int launch_next_event(Run& r, KArgs a, uint32_t count, bool faithful) {
+    af_engine_t* e = r.e;
+    RunTotals& t = r.t;
+    choose_lanes(e, count, a.blob_bytes, r.bytes_per_lane, t.kl, t.lds_state);
+    const uint32_t klog = klog_of(t.kl);
+    a.n_scen = count;
+    const uint64_t state_per_wave = r.bytes_per_lane * t.kl;
+    t.waves = (count + t.kl - 1) / t.kl;
+    t.lds_bytes = t.lds_state ? (uint32_t)(a.blob_bytes + state_per_wave) : a.blob_bytes;
+    a.state = nullptr;
+    a.state_bytes_per_wave = state_per_wave;
+    if (!t.lds_state) {
+        if (int rc = reserve_device((void**)&e->d_state, e->state_cap, (size_t)state_per_wave * t.waves)) return rc;
+        a.state = e->d_state;
+    }
+    // SimPy-order variant: when the waves do not all fit at 3 per SIMD anyway, the build with
+    // the larger register budget (2 per SIMD, no spills) is the faster one (measured: 6 400
+    // grid points 6.2 s -> 5.5 s; 2 500 waves that do fit: 2.7 s vs 4.3 s).  Sweeps over the load
+    // (scenario lengths differ by orders of magnitude) do not run as lock-step batches: there the
+    // per-wave speed decides and the roomy build wins even when everything would fit.
+    const bool roomy = faithful && (t.waves > 3072u || r.hetero_load);
+    const void* fn = des_kernel_for(t.lds_state, faithful, klog, roomy);
+    hipFunction_t jit_fn = nullptr;
+    if (e->jit_module && t.lds_bytes <= 64u * 1024u) {
+        if (jit_spec_string(a, t.lds_state, klog) == e->jit_spec) jit_fn = !faithful ? e->jit_lean : roomy ? e->jit_order2 : e->jit_order3;
+        else t.n_jit_miss += 1u;
+    }
+    if (std::getenv("AF_DEBUG"))
+        std::fprintf(stderr, "[af] launch: %u scenarios, %u waves x %u lanes, %s state, %s%s%s\n", count, t.waves, t.kl,
+                     t.lds_state ? "LDS" : "HBM", faithful ? "SimPy-order" : "lean", roomy ? " (2 waves/SIMD build)" : "",
+                     jit_fn ? ", plan-specialised" : "");
+    void* kargs[] = {&a};
+    if (jit_fn) {
+        HIP_TRY(hipModuleLaunchKernel(jit_fn, t.waves, 1, 1, kWave, 1, 1, t.lds_bytes, e->stream, kargs, nullptr));
+        t.n_jit += 1u;
+    } else {
+        if (t.lds_state) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds_bytes));
+        HIP_TRY(hipLaunchKernel(fn, dim3(t.waves), dim3(kWave), kargs, t.lds_bytes, e->stream));
+    }
+    return AF_OK;
+}
 
-    aff::FlowLayout& FL = FP.FL;
-    aff::FlowLayout& FL2 = FP.FL2;
-    const bool flow_big = FP.big;
-    const uint32_t flow_lds = FP.lds;
-
-    const size_t tie_words = a.L.tie_words;
-    const bool hetero_load = (mask & ((1u << AF_PARAM_GEN_USERS_MEAN) | (1u << AF_PARAM_GEN_RPM_MEAN))) != 0u;
-    // One launch of the next-event kernel over `count` scenarios (all of the chunk, or the ones listed in `map`).
-    auto launch_des = [&](uint32_t count, bool faithful) -> int {
-        choose_lanes(e, count, a.blob_bytes, bytes_per_lane, kl, lds_state);
-        uint32_t klog = 0;
-        while ((1u << klog) < kl) ++klog;
-        a.n_scen = count;
-        const uint64_t state_per_wave = bytes_per_lane * kl;
-        waves = (count + kl - 1) / kl;
-        lds_bytes = lds_state ? (uint32_t)(a.blob_bytes + state_per_wave) : a.blob_bytes;
-        a.state = nullptr;
-        a.state_bytes_per_wave = state_per_wave;
-        if (!lds_state) {
-            if (int rc = grow((void**)&e->d_state, e->state_cap, (size_t)state_per_wave * waves)) return rc;
-            a.state = e->d_state;
-        }
-        // SimPy-order variant: when the waves do not all fit at 3 per SIMD anyway, the build with
-        // the larger register budget (2 per SIMD, no spills) is the faster one (measured: 6 400
-        // grid points 6.2 s -> 5.5 s; 2 500 waves that do fit: 2.7 s vs 4.3 s).  Sweeps over the load
-        // (scenario lengths differ by orders of magnitude) do not run as lock-step batches: there the
-        // per-wave speed decides and the roomy build wins even when everything would fit.
-        const bool hetero = (mask & ((1u << AF_PARAM_GEN_USERS_MEAN) | (1u << AF_PARAM_GEN_RPM_MEAN))) != 0u;
-        const bool roomy = faithful && (waves > 3072u || hetero);
-        const void* fn = des_kernel_for(lds_state, faithful, klog, roomy);
-        hipFunction_t jit_fn = nullptr;
-        if (e->jit_module && lds_bytes <= 64u * 1024u) {
-            if (jit_spec_string(a, lds_state, klog) == e->jit_spec) jit_fn = !faithful ? e->jit_lean : roomy ? e->jit_order2 : e->jit_order3;
-            else n_jit_miss += 1u;
-        }
-        if (std::getenv("AF_DEBUG"))
-            std::fprintf(stderr, "[af] launch: %u scenarios, %u waves x %u lanes, %s state, %s%s%s\n", count, waves, kl,
-                         lds_state ? "LDS" : "HBM", faithful ? "SimPy-order" : "lean", roomy ? " (2 waves/SIMD build)" : "",
-                         jit_fn ? ", plan-specialised" : "");
-        void* kargs[] = {&a};
-        if (jit_fn) {
-            HIP_TRY(hipModuleLaunchKernel(jit_fn, waves, 1, 1, kWave, 1, 1, lds_bytes, e->stream, kargs, nullptr));
-            n_jit += 1u;
-        } else {
-            if (lds_state) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            HIP_TRY(hipLaunchKernel(fn, dim3(waves), dim3(kWave), kargs, lds_bytes, e->stream));
-        }
-        return AF_OK;
-    };
-
-    // The next-event kernels over `count` scenarios of the current chunk: all of them (h_map == nullptr) or the
-    // listed ones.  Draws are pre-generated per slot j = position in the list; pieces that fit the draw budget.
-    auto run_sequential = [&](uint32_t count, const uint32_t* h_map, const KArgs& chunk_args) -> int {
-        size_t mf = 0, mt = 0;
-        HIP_TRY(hipMemGetInfo(&mf, &mt));
-        // (per scenario: its draws, its scratch of the SimPy-order path and -- when the state does not fit the LDS: long wait
-        // queues -- its state words in HBM)
-        const size_t state_hbm = bytes_per_lane > 48u * 1024u ? (size_t)bytes_per_lane : 0u;
-        uint32_t piece = chunk_size(e, count, draw_bytes_per_scen + tie_words * 8u + state_hbm, mf);
-        if (piece == 0) return fail(AF_ERR_CAPACITY, "draw_capacity / fifo_capacity too large for the device memory budget");
-        if (const char* env = std::getenv("AF_SEQ_PIECE")) {   // test hook: force a whole chunk to run in pieces
-            const uint32_t v = (uint32_t)std::atoi(env);
-            if (v != 0u && v < piece) piece = v;
-        }
-        // A whole chunk (no list) that does not fit the draw budget in one piece -- the free memory is measured again
-        // here, after the scratch buffers of the chunk were allocated -- runs as pieces over an identity list: piece
-        // p0 simulates scenarios [p0, p0 + cnt) with its draws in slots [0, cnt).  (Round 2 ran [0, cnt) again: ADVICE r2.)
-        std::vector<uint32_t> ident;
-        if (h_map == nullptr && piece < count) {
-            ident.resize(count);
-            for (uint32_t i = 0; i < count; ++i) ident[i] = i;
-            h_map = ident.data();
-        }
-        const bool listed_subset = h_map != nullptr && ident.empty();
-        for (uint32_t p0 = 0; p0 < count; p0 += piece) {
-            const uint32_t cnt = count - p0 < piece ? count - p0 : piece;
-            a = chunk_args;
-            if (int rc = grow((void**)&e->d_draws, e->draws_cap, draw_bytes_per_scen * cnt)) return rc;
-            if (int rc = grow((void**)&e->d_pre_flags, e->pre_flags_cap, (size_t)cnt * 4u)) return rc;
-            if (int rc = grow((void**)&e->d_tie, e->tie_cap, (size_t)cnt * tie_words * 8u)) return rc;
-            if (draw_bytes_per_scen * cnt > draw_bytes) draw_bytes = draw_bytes_per_scen * cnt;
-            a.draws = e->d_draws;
-            a.pre_flags = e->d_pre_flags;
-            a.tie = e->d_tie;
-            a.draw_slot = nullptr;
-            if (h_map) {
-                if (int rc = grow((void**)&e->d_map, e->map_cap, (size_t)cnt * 4u)) return rc;
-                HIP_TRY(hipMemcpyAsync(e->d_map, h_map + p0, (size_t)cnt * 4u, hipMemcpyHostToDevice, e->stream));
-                a.scen_map = e->d_map;
-                a.draws_by_lane = 1u;
-            } else {
-                a.scen_map = nullptr;
-                a.draws_by_lane = 0u;
-            }
-            a.n_scen = cnt;
-            HIP_TRY(hipEventRecord(e->ev2, e->stream));
-            if (launch_pregen_arrivals(a, cnt, (uint32_t)((1u + a.n_edges) * n_draw), !hetero_load, e->stream))
-                return fail(AF_ERR_HIP, "af_pregen_arrivals: LDS attribute");
-            hipLaunchKernelGGL(af_pregen_edges, dim3((n_draw + 255u) / 256u, cnt, a.n_edges), dim3(256), 0, e->stream, a);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(e->ev3, e->stream));
-            if (listed_subset && (a.online_hist || a.online_rps)) {   // scenarios that start over: their online counters are cleared
-                hipLaunchKernelGGL(af_zero_online, dim3(cnt), dim3(256), 0, e->stream, a, cnt);
-                HIP_TRY(hipGetLastError());
-            }
-            // First pass: the lean kernel.  A scenario in which two timed events share an instant stops
-            // there and is simulated again, from its start, by the kernel that has SimPy's event-by-event
-            // path; engines whose plan keeps producing such scenarios go straight to that kernel.
-            // (a handful of scenarios handed back by the stage-parallel kernel -- usually for a tie -- go straight to the
-            // SimPy-order kernel: a second pass over them would cost a whole latency-bound launch more)
-            const bool faithful_first = e->shared_instants_likely || (listed_subset && (uint64_t)count * 50u < chunk_args.n_scen);
-            HIP_TRY(hipMemsetAsync(e->d_n_shared, 0, 4, e->stream));
-            if (int rc = launch_des(cnt, faithful_first)) return rc;
-            if (!faithful_first) {
-                uint32_t n_shared = 0;
-                HIP_TRY(hipMemcpyAsync(&n_shared, e->d_n_shared, 4, hipMemcpyDeviceToHost, e->stream));
-                HIP_TRY(hipStreamSynchronize(e->stream));
-                if (n_shared > 0u) {
-                    const uint32_t nc_all = chunk_args.n_scen;
-                    std::vector<uint32_t> cnt_host((size_t)nc_all * AF_CNT_SLOTS);
-                    HIP_TRY(hipMemcpy(cnt_host.data(), a.counts, cnt_host.size() * 4u, hipMemcpyDeviceToHost));
-                    std::vector<uint32_t> map2, slot2;
-                    for (uint32_t j = 0; j < cnt; ++j) {
-                        const uint32_t scn = h_map ? h_map[p0 + j] : j;
-                        if (cnt_host[(size_t)scn * AF_CNT_SLOTS + AF_CNT_FLAGS] & af::FLAG_SHARED_INSTANT) {
-                            map2.push_back(scn);
-                            slot2.push_back(j);
-                        }
-                    }
-                    if (!map2.empty()) {
-                        if (int rc = grow((void**)&e->d_map, e->map_cap, (size_t)nc_all * 4u)) return rc;
-                        if (int rc = grow((void**)&e->d_slot, e->slot_cap, map2.size() * 4u)) return rc;
-                        HIP_TRY(hipMemcpy(e->d_map, map2.data(), map2.size() * 4u, hipMemcpyHostToDevice));
-                        HIP_TRY(hipMemcpy(e->d_slot, slot2.data(), slot2.size() * 4u, hipMemcpyHostToDevice));
-                        a.scen_map = e->d_map;
-                        a.draw_slot = e->d_slot;
-                        if (a.online_hist || a.online_rps) {
-                            hipLaunchKernelGGL(af_zero_online, dim3((uint32_t)map2.size()), dim3(256), 0, e->stream, a, (uint32_t)map2.size());
-                            HIP_TRY(hipGetLastError());
-                        }
-                        if (int rc = launch_des((uint32_t)map2.size(), true)) return rc;
-                        n_rerun += (uint32_t)map2.size();
-                        // such plans keep producing them: later runs start with the SimPy-order kernel, which
-                        // is cheaper than a second pass over a few long scenarios in narrow, latency-bound waves
-                        e->shared_instants_likely = true;
-                    }
-                }
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipEventRecord(e->ev4, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            float ms_p = 0.f, ms_k = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms_p, e->ev2, e->ev3));
-            HIP_TRY(hipEventElapsedTime(&ms_k, e->ev3, e->ev4));
-            ms_pregen += ms_p;
-            ms_kernel += ms_k;
-        }
-        return AF_OK;
-    };
-
-    for (uint32_t lo = 0; lo < n; lo += chunk) {
-        const uint32_t nc = n - lo < chunk ? n - lo : chunk;
-        n_chunks += 1u;
-        a.n_scen = nc;
-        a.scen_map = nullptr;
-        a.draw_slot = nullptr;
-        a.draws_by_lane = 0u;
-        a.seeds = reinterpret_cast<const uint64_t*>(ds) + lo;
-        a.ovr_values = reinterpret_cast<const double*>(ds + seeds_b) + lo;
-        a.clock = out->clock ? out->clock + (size_t)lo * out->clock_capacity * 2u : nullptr;
-        a.samples = out->samples ? out->samples + (size_t)lo * a.series_pitch * out->tick_capacity : nullptr;
-        a.counts = out->counts + (size_t)lo * AF_CNT_SLOTS;
-        a.online_hist = out->online_hist ? out->online_hist + (size_t)lo * out->online_hist_bins : nullptr;
-        a.online_rps = out->online_rps ? out->online_rps + (size_t)lo * out->online_rps_buckets : nullptr;
-        a.online_hist_bins = out->online_hist_bins;
-        a.online_rps_buckets = out->online_rps_buckets;
-        a.online_hist_scale = out->online_hist ? (double)out->online_hist_bins / out->online_hist_max : 0.0;
-        const KArgs chunk_args = a;
-
-        if (!use_flow) {
-            if (int rc = run_sequential(nc, nullptr, chunk_args)) return rc;
-            continue;
-        }
-        // ---- stage-parallel kernel over the whole chunk; what it hands back goes to the next-event kernels
-        if (int rc = grow((void**)&e->d_arr, e->arr_cap, (size_t)nc * n_draw * sizeof(double))) return rc;
-        if (int rc = grow((void**)&e->d_arr_flags, e->arr_flags_cap, (size_t)nc * 4u)) return rc;
-        if ((size_t)nc * n_draw * sizeof(double) > draw_bytes) draw_bytes = (size_t)nc * n_draw * sizeof(double);
-        a.draws = e->d_arr;
-        a.pre_flags = e->d_arr_flags;
-        // grouped pre-generation (af_pregen.hpp): sweeps of alike scenarios -- a workgroup is as slow as its heaviest one -- with
-        // sampling windows long enough that a window start (a user draw by one wave, the pipeline refilled) does not count
-        const char* pregen_mode = std::getenv("AF_PREGEN_MODE");   // rows | groups: tests and measurements
-        const bool force_groups = pregen_mode && std::strcmp(pregen_mode, "groups") == 0;
-        const bool force_rows = pregen_mode && std::strcmp(pregen_mode, "rows") == 0;
-        // (sweeps over users / rpm -- BASELINE configs 3 / 4 -- as long as the heaviest scenario is within 2.5 x of the mean:
-        // load_spread_suits_groups)
-        const bool grouped = !force_rows && a.gen_window_s > 0.0 &&
-                             (force_groups || (!(mask & (1u << AF_PARAM_GEN_WINDOW)) && nc >= 3072u &&
-                                               (double)n_draw * a.gen_window_s >= 512.0 * a.total_time &&
-                                               (!hetero_load || load_spread_suits_groups(e, sweep, lo, nc))));
-        // Sweeps over the load: waves are dispatched in blockIdx order as slots free up, and a wave lasts as long as its scenario
-        // has events.  A users-major grid (BASELINE configs 3 / 4: users ascending with the index) is then the WORST order --
-        // the heaviest scenarios start last and the launch ends with a few long waves on an empty chip (list scheduling of
-        // 10 000 waves with times ~ users on 4 096 slots: 3.54 mean wave times ascending, 2.73 heaviest first, 2.44 ideal).  Wave j
-        // simulates scenario order[j]; everything the kernel reads or writes is indexed by the scenario.
-        const bool ordered = hetero_load && std::getenv("AF_FLOW_ORDER_OFF") == nullptr;
-        if (ordered) {
-            std::vector<uint32_t> order = heaviest_first(e, sweep, lo, nc);
-            if (int rc = grow((void**)&e->d_order, e->order_cap, (size_t)nc * 4u)) return rc;
-            HIP_TRY(hipMemcpyAsync(e->d_order, order.data(), (size_t)nc * 4u, hipMemcpyHostToDevice, e->stream));
-            HIP_TRY(hipStreamSynchronize(e->stream));   // (`order` leaves scope; 40 KB, before anything of this chunk is enqueued)
-        }
-        HIP_TRY(hipEventRecord(e->ev2, e->stream));
-        if (launch_pregen_arrivals(a, nc, n_draw, !hetero_load, e->stream, grouped, &pregen_group)) return fail(AF_ERR_HIP, "af_arrival_groups: LDS attribute");
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipEventRecord(e->ev3, e->stream));
-        aff::FlowArgs f = e->fargs;
-        f.L = FL;
-        f.n_scen = nc;
-        f.seeds = a.seeds;
-        f.n_ovr = a.n_ovr;
-        f.ovr_param = a.ovr_param;
-        f.ovr_index = a.ovr_index;
-        f.ovr_values = a.ovr_values;
-        f.ovr_stride = a.ovr_stride;
-        f.arrivals = e->d_arr;
-        f.n_draw = n_draw;
-        f.pre_flags = e->d_arr_flags;
-        if (ordered) f.scen_map = e->d_order;
-        f.clock = a.clock;
-        f.clock_cap = a.clock_cap;
-        f.samples = a.samples;
-        f.tick_cap = a.tick_cap;
-        f.counts = a.counts;
-        f.online_hist = a.online_hist;
-        f.online_rps = a.online_rps;
-        f.online_hist_bins = a.online_hist_bins;
-        f.online_rps_buckets = a.online_rps_buckets;
-        f.online_hist_scale = a.online_hist_scale;
-        f.n_fallback = e->d_fb;
-        HIP_TRY(hipMemsetAsync(e->d_fb, 0, 32u * 4u, e->stream));
-        // measurement hook (AF_FLOW_PROF=<file>, plan-specialised builds only): shader-clock time per section of Flow::run
-        unsigned long long* d_prof = nullptr;
-        const char* prof_path = std::getenv("AF_FLOW_PROF");
-        if (prof_path != nullptr) {
-            HIP_TRY(hipMalloc((void**)&d_prof, (size_t)nc * aff::kProfSections * 8u));
-            HIP_TRY(hipMemsetAsync(d_prof, 0, (size_t)nc * aff::kProfSections * 8u, e->stream));
-            f.prof = d_prof;
-        }
-        {
-            const uint32_t flow_lds_launch = spread_lds_bytes(flow_lds);
-            void* kargs[] = {&f};
-            // plan-specialised build of exactly this launch (af_engine_set_kernels), else the library's generic instantiation
-            const bool jit = e->flow_jit_fn != nullptr && flow_lds_launch <= 64u * 1024u &&
-                             flow_jit_spec_string(e, FP, out, sweep->n_overrides != 0u) == e->flow_jit_spec;
-            if (e->flow_jit_fn != nullptr && !jit) n_jit_miss += 1u;
-            if (std::getenv("AF_DEBUG")) std::fprintf(stderr, "[af] flow jit spec: %s\n", flow_jit_spec_string(e, FP, out, sweep->n_overrides != 0u).c_str());
-            if (std::getenv("AF_DEBUG"))
-                std::fprintf(stderr, "[af] flow launch: %u scenarios, %u list entries%s, %u ring rows, %u B LDS per wave, af_flow_kernel<%u, %#x>%s%s\n", nc,
-                             FL.cap, flow_big ? " (long-list instantiation)" : "", FL.ring_rows, flow_lds, FP.ipl, FP.feat,
-                             FP.lean ? (FP.far ? ", lean instantiation with far edges" : ", lean instantiation") : "", jit ? ", plan-specialised" : "");
-            const void* fn = jit ? nullptr : flow_kernel_for(FP.ipl, FP.feat);
-            if (!jit && fn == nullptr) return fail(AF_ERR_INVALID, "no stage-parallel instantiation for this launch");
-            if (!jit && flow_lds_launch > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flow_lds_launch));
-            // af_engine_run_summarized: the analyzer starts on a second stream once the scenarios of the kernel's full residency rounds
-            // have finished (hipStreamWaitValue32 on a counter its waves bump) and runs beside the last, partial round, which leaves
-            // most of the chip idle; the analyzer is HBM-bound where this kernel is VALU-bound.  A workgroup of the analyzer that
-            // meets a scenario still being simulated (its done flag is clear) puts it on a retry list and leaves.
-            // (Measured first, round 6: the kernel launched in two parts with the analyzer of the first beside the second --
-            // 51.9 instead of 48.4 ms per step on BASELINE config 2: the second part cannot start before the LAST wave of the first
-            // has ended and then lasts a whole scenario at low occupancy, 11 ms against the 7 ms of the natural tail.)
-            uint32_t gate = 0u;
-            if (e->fused_sum != nullptr && lo == 0u && nc == n && d_prof == nullptr) {
-                if (e->wait_value_ok < 0) {
-                    int v = 0;
-                    if (hipDeviceGetAttribute(&v, hipDeviceAttributeCanUseStreamWaitValue, e->device) != hipSuccess) { (void)hipGetLastError(); v = 0; }
-                    e->wait_value_ok = v;
-                }
-                int per_cu = 0;
-                hipDeviceProp_t prop;
-                HIP_TRY(hipGetDeviceProperties(&prop, e->device));
-                if (jit) HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, e->flow_jit_fn, (int)kWave, flow_lds_launch));
-                else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, (int)kWave, flow_lds_launch));
-                const uint32_t resident = (uint32_t)(per_cu > 0 ? per_cu : 0) * (uint32_t)prop.multiProcessorCount;
-                const uint32_t rem = resident ? nc % resident : 0u;
-                // (a tail of more than three quarters of a round leaves no room for the analyzer's workgroups; no tail, nothing to fill)
-                // (and only where the partial round is a good part of the launch -- at most six rounds --: the analyzer of a sweep of
-                // many rounds needs longer than the tail lasts, and beside a FULL round it only takes the kernel's slots: BASELINE
-                // config 5, 12.2 rounds, 227 instead of 223 ms per step, measured)
-                if (e->wait_value_ok > 0 && resident != 0u && nc > resident && nc <= 6u * resident && rem != 0u && rem * 4u <= resident * 3u) gate = nc - rem;
-                if (std::getenv("AF_DEBUG")) std::fprintf(stderr, "[af] analyzer beside the last round: %u resident waves, gate at %u of %u scenarios\n", resident, gate, nc);
-            }
-            if (gate != 0u) {
-                if (e->stream2 == nullptr) {
-                    HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
-                    HIP_TRY(hipEventCreate(&e->ev_s0));
-                    HIP_TRY(hipEventCreate(&e->ev_s1));
-                    HIP_TRY(hipHostMalloc((void**)&e->h_done_count, 64, hipHostMallocCoherent | hipHostMallocMapped));
-                    HIP_TRY(hipHostGetDevicePointer((void**)&e->d_done_count, e->h_done_count, 0));
-                }
-                if (int rc = grow((void**)&e->d_done_flags, e->done_flags_cap, (size_t)nc * 4u)) return rc;
-                if (int rc = grow((void**)&e->d_retry, e->retry_cap, 2u * ((size_t)nc + 1u) * 4u)) return rc;
-                *e->h_done_count = 0u;   // (nothing of this engine is in flight: af_engine_run is synchronous)
-                HIP_TRY(hipMemsetAsync(e->d_done_flags, 0, (size_t)nc * 4u, e->stream));
-                HIP_TRY(hipMemsetAsync(e->d_retry, 0, 2u * ((size_t)nc + 1u) * 4u, e->stream));
-                // (where the kernel's entry point finds them: behind the hand-over counters it already has a pointer to -- two more
-                // kernel arguments cost the general-server form 5 %, measured: its register allocation answers small changes chaotically)
-                e->done_ptrs[0] = reinterpret_cast<uint64_t>(e->d_done_flags);
-                e->done_ptrs[1] = reinterpret_cast<uint64_t>(e->d_done_count);
-                HIP_TRY(hipMemcpyAsync(e->d_fb + kDoneWords, e->done_ptrs, 16u, hipMemcpyHostToDevice, e->stream));
-            }
-            f.n_scen = nc;
-            if (jit) {
-                HIP_TRY(hipModuleLaunchKernel(e->flow_jit_fn, nc, 1, 1, kWave, 1, 1, flow_lds_launch, e->stream, kargs, nullptr));
-                n_jit += 1u;
-            } else {
-                HIP_TRY(hipLaunchKernel(fn, dim3(nc), dim3(kWave), kargs, flow_lds_launch, e->stream));
-            }
-            if (gate != 0u) {
-                // (from here on the second stream waits for the counter: whatever goes wrong below must still let it through)
-                auto release_side = [&]() { *e->h_done_count = 0xFFFFFFFFu; };
-                hipError_t err = hipStreamWaitValue32(e->stream2, e->d_done_count, gate, hipStreamWaitValueGte, 0xFFFFFFFFu);
-                if (err == hipSuccess) err = hipEventRecord(e->ev_s0, e->stream2);
-                int rc = AF_OK;
-                if (err == hipSuccess) rc = launch_summary_kernels(e, e->fused_out, e->fused_sum, 0u, nc, e->stream2, e->d_done_flags, e->d_retry, nullptr, 0u);
-                if (err == hipSuccess && rc == AF_OK) err = hipEventRecord(e->ev_s1, e->stream2);
-                if (err != hipSuccess || rc != AF_OK) {
-                    release_side();
-                    (void)hipStreamSynchronize(e->stream);
-                    (void)hipStreamSynchronize(e->stream2);
-                    if (rc != AF_OK) return rc;
-                    HIP_TRY(err);
-                }
-            }
-            fused_first = gate;
-        }
-        HIP_TRY(hipEventRecord(e->ev4, e->stream));
-        uint32_t fb[5] = {0, 0, 0, 0, 0};
-        HIP_TRY(hipMemcpyAsync(fb, e->d_fb, sizeof fb, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        if (fused_first != 0u) {
-            HIP_TRY(hipStreamSynchronize(e->stream2));
-            float ms_s = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms_s, e->ev_s0, e->ev_s1));
-            e->stats.summary_beside_ms = ms_s;
-            // (a scenario handed back is simulated again below and its outputs change: the sweep is then summarised again, in full)
-            e->fused_done = fb[0] == 0u;
-        }
-        if (d_prof != nullptr) {
-            std::vector<unsigned long long> hp((size_t)nc * aff::kProfSections);
-            HIP_TRY(hipMemcpy(hp.data(), d_prof, hp.size() * 8u, hipMemcpyDeviceToHost));
-            (void)hipFree(d_prof);
-            static const char* names[aff::kProfSections] = {"setup+end", "generator batch", "select", "series: delivery end (FAR)", "station logic",
-                                                            "servers_solve + claim", "server series", "draws (Philox, log)", "send: spike + series",
-                                                            "append + send_floor", "complete", "flush_ticks + round end",
-                                                            "general servers: lanes", "general servers: walk", "general servers: rank + relax", "general servers: state at the horizon",
-                                                            "COUNT rounds solved at once", "COUNT relaxation sweeps", "COUNT lanes in solved rounds", "COUNT rounds walked by event",
-                                                            "general servers: standing (ranks, RAM)", "general servers: commit walk (series)"};
-            double acc[aff::kProfSections] = {}, total = 0.0;
-            for (uint32_t i = 0; i < nc; ++i)
-                for (uint32_t k = 0; k < aff::kProfSections; ++k) acc[k] += (double)hp[(size_t)i * aff::kProfSections + k];
-            for (uint32_t k = 0; k < aff::kProfSections; ++k)
-                if (!names[k] || std::strncmp(names[k], "COUNT", 5) != 0) total += acc[k];
-            if (FILE* fp = std::fopen(prof_path, "a")) {
-                std::fprintf(fp, "af_flow_kernel<%u, %#x> sections, %u waves, mean cycles per wave %.0f:\n", FP.ipl, FP.feat, nc, total / nc);
-                for (uint32_t k = 0; k < aff::kProfSections; ++k)
-                    if (names[k]) std::fprintf(fp, "  %-28s %6.2f %%  %12.0f cycles per wave\n", names[k], 100.0 * acc[k] / total, acc[k] / nc);
-                std::fclose(fp);
-            }
-        }
-        float ms_p = 0.f, ms_f = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms_p, e->ev2, e->ev3));
-        HIP_TRY(hipEventElapsedTime(&ms_f, e->ev3, e->ev4));
-        ms_pregen += ms_p;
-        ms_flow += ms_f;
-        flow_scen += nc;
-        for (int k = 0; k < 5; ++k) fb_total[k] += fb[k];
-        if (fb[0] > 0u) {
-            std::vector<uint32_t> cnt_host((size_t)nc * AF_CNT_SLOTS);
-            HIP_TRY(hipMemcpy(cnt_host.data(), a.counts, cnt_host.size() * 4u, hipMemcpyDeviceToHost));
-            // Second chance on the stage-parallel kernel itself, in its most tolerant form: 256-entry lists, tick
-            // differences in HBM (no reach limit), messages carry their send time so that two deliveries of one station
-            // at the same instant are ordered the way SimPy orders them.  A wave costs tens of milliseconds; the same
-            // scenario on a next-event kernel is a latency-bound chain of ~1 s (LB-2).  Only what this launch hands
-            // back again -- or what can never fit its RAM model -- goes to the next-event kernels.
-            std::vector<uint32_t> retry, rest;
-            for (uint32_t i = 0; i < nc; ++i) {
-                const uint32_t fl = cnt_host[(size_t)i * AF_CNT_SLOTS + AF_CNT_FLAGS];
-                if (!(fl & aff::FLAG_FLOW_FALLBACK)) continue;
-                // (flow_big: that WAS the most tolerant form; a tie the general server station gives up on stops the second chance at
-                // the same instant: straight to the next-event kernels)
-                if ((fl & (aff::FLOW_WHY_RAM | aff::FLOW_WHY_GEN_TIE)) || (flow_big && !FP.gen_compact)) rest.push_back(i);
-                else retry.push_back(i);
-            }
-            if (!retry.empty()) {
-                if (int rc = grow((void**)&e->d_map, e->map_cap, retry.size() * 4u)) return rc;
-                HIP_TRY(hipMemcpyAsync(e->d_map, retry.data(), retry.size() * 4u, hipMemcpyHostToDevice, e->stream));
-                aff::FlowArgs f2 = f;
-                f2.L = FL2;
-                f2.n_scen = (uint32_t)retry.size();
-                f2.scen_map = e->d_map;
-                f2.n_fallback = e->d_fb + 5;
-                const uint32_t lds2 = a.blob_bytes + f2.L.n_words * 8u;
-                if (lds2 > kLdsLimit) return fail(AF_ERR_CAPACITY, "flow kernel layout exceeds the LDS of a compute unit");
-                if (a.online_hist || a.online_rps) {
-                    a.scen_map = e->d_map;
-                    hipLaunchKernelGGL(af_zero_online, dim3((uint32_t)retry.size()), dim3(256), 0, e->stream, a, (uint32_t)retry.size());
-                    HIP_TRY(hipGetLastError());
-                    a.scen_map = nullptr;
-                }
-                constexpr uint32_t kRobust = aff::FEAT_ALL | aff::FEAT_TIEBREAK | aff::FEAT_BIGLIST;
-                const void* fn2 = (FP.gen_compact && e->flow_chain && f2.lb_least_connections) ? reinterpret_cast<const void*>(af_flow_kernel<1, kRobust | aff::FEAT_GENSRV | aff::FEAT_LC | aff::FEAT_CHAIN>)
-                                  : (FP.gen_compact && e->flow_chain) ? reinterpret_cast<const void*>(af_flow_kernel<1, kRobust | aff::FEAT_GENSRV | aff::FEAT_CHAIN>)
-                                  : (FP.gen_compact && f2.lb_least_connections) ? reinterpret_cast<const void*>(af_flow_kernel<1, kRobust | aff::FEAT_LC | aff::FEAT_GENSRV>)
-                                  : FP.gen_compact        ? reinterpret_cast<const void*>(af_flow_kernel<1, kRobust | aff::FEAT_GENSRV>)
-                                  : (f2.lb_least_connections && e->flow_chain) ? reinterpret_cast<const void*>(af_flow_kernel<1, kRobust | aff::FEAT_LC | aff::FEAT_CHAIN>)
-                                  : f2.lb_least_connections ? reinterpret_cast<const void*>(af_flow_kernel<1, kRobust | aff::FEAT_LC>)
-                                  : e->flow_chain         ? reinterpret_cast<const void*>(af_flow_kernel<1, kRobust | aff::FEAT_CHAIN>)
-                                                          : reinterpret_cast<const void*>(af_flow_kernel<1, kRobust>);
-                if (lds2 > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-                HIP_TRY(hipEventRecord(e->ev3, e->stream));
-                void* kargs2[] = {&f2};
-                if (std::getenv("AF_DEBUG")) {
-                    std::fprintf(stderr, "[af] flow second chance: %zu scenarios (lists of %u/%u/%u/%u entries with send times, differences in HBM), %u B LDS:",
-                                 retry.size(), FL2.cap_of[0], FL2.cap_of[1], FL2.cap_of[2], FL2.cap_of[3], lds2);
-                    for (size_t q = 0; q < retry.size() && q < 16; ++q)
-                        std::fprintf(stderr, " %u(flags %#x)", lo + retry[q], cnt_host[(size_t)retry[q] * AF_CNT_SLOTS + AF_CNT_FLAGS]);
-                    std::fprintf(stderr, "\n");
-                }
-                HIP_TRY(hipLaunchKernel(fn2, dim3((uint32_t)retry.size()), dim3(kWave), kargs2, lds2, e->stream));
-                HIP_TRY(hipEventRecord(e->ev4, e->stream));
-                uint32_t fb2[5] = {0, 0, 0, 0, 0};
-                HIP_TRY(hipMemcpyAsync(fb2, e->d_fb + 5, sizeof fb2, hipMemcpyDeviceToHost, e->stream));
-                HIP_TRY(hipStreamSynchronize(e->stream));
-                float ms2 = 0.f;
-                HIP_TRY(hipEventElapsedTime(&ms2, e->ev3, e->ev4));
-                ms_flow += ms2;
-                flow_retried += (uint32_t)retry.size();
-                if (fb2[0] > 0u) {
-                    HIP_TRY(hipMemcpy(cnt_host.data(), a.counts, cnt_host.size() * 4u, hipMemcpyDeviceToHost));
-                    for (uint32_t i : retry)
-                        if (cnt_host[(size_t)i * AF_CNT_SLOTS + AF_CNT_FLAGS] & aff::FLAG_FLOW_FALLBACK) rest.push_back(i);
-                    std::sort(rest.begin(), rest.end());
-                }
-            }
-            flow_to_next += (uint32_t)rest.size();
-            if (!rest.empty())
-                if (int rc = run_sequential((uint32_t)rest.size(), rest.data(), chunk_args)) return rc;
-            // A plan whose scenarios mostly end on the next-event kernels anyway (general servers fed by edges with discrete
-            // latencies: arrivals that coincide with step ends) pays a flow pass, a second chance AND a next-event pass
-            // per scenario: once a chunk handed more than a quarter of its scenarios over, the chunks still to come go to the
-            // next-event kernels directly (results are the same either way; flow_mode 2 = "always" keeps the stage-parallel kernel).
-            if ((uint64_t)rest.size() * 4u > (uint64_t)nc && e->flow_mode != 2u) use_flow = false;
+// Second pass over a piece: the scenarios of `first` (the piece's first launch over `cnt` scenarios, those of `list` or, without a
+// list, [0, cnt)) that stopped at a shared instant run again, from their start, on the SimPy-order kernel, with the draws of
+// their slot in the piece.
+static int rerun_shared_instants(Run& r, const KArgs& first, uint32_t nc_all, const uint32_t* list, uint32_t cnt) {
+    af_engine_t* e = r.e;
+    std::vector<uint32_t> cnt_host((size_t)nc_all * AF_CNT_SLOTS);
+    HIP_TRY(hipMemcpy(cnt_host.data(), first.counts, cnt_host.size() * 4u, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> map2, slot2;
+    for (uint32_t j = 0; j < cnt; ++j) {
+        const uint32_t scn = list ? list[j] : j;
+        if (cnt_host[(size_t)scn * AF_CNT_SLOTS + AF_CNT_FLAGS] & af::FLAG_SHARED_INSTANT) {
+            map2.push_back(scn);
+            slot2.push_back(j);
         }
     }
+    if (map2.empty()) return AF_OK;
+    if (int rc = reserve_device((void**)&e->d_map, e->map_cap, (size_t)nc_all * 4u)) return rc;
+    if (int rc = reserve_device((void**)&e->d_slot, e->slot_cap, map2.size() * 4u)) return rc;
+    HIP_TRY(hipMemcpy(e->d_map, map2.data(), map2.size() * 4u, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_slot, slot2.data(), slot2.size() * 4u, hipMemcpyHostToDevice));
+    KArgs a = first;
+    a.scen_map = e->d_map;
+    a.draw_slot = e->d_slot;
+    if (a.online_hist || a.online_rps) {   // scenarios that start over: their online counters are cleared
+        hipLaunchKernelGGL(af_zero_online, dim3((uint32_t)map2.size()), dim3(256), 0, e->stream, a, (uint32_t)map2.size());
+        HIP_TRY(hipGetLastError());
+    }
+    if (int rc = launch_next_event(r, a, (uint32_t)map2.size(), true)) return rc;
+    r.t.n_rerun += (uint32_t)map2.size();
+    // such plans keep producing them: later runs start with the SimPy-order kernel, which
+    // is cheaper than a second pass over a few long scenarios in narrow, latency-bound waves
+    e->shared_instants_likely = true;
+    return AF_OK;
+}
 
-    float ms_h2d = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms_h2d, e->ev0, e->ev1));
-    e->stats.kernel_ms = ms_kernel + ms_flow;
-    e->stats.flow_kernel_ms = ms_flow;
-    e->stats.flow_scenarios = flow_scen;
-    e->stats.flow_fallback = fb_total[0];
-    e->stats.flow_fallback_tie = fb_total[1];
-    e->stats.flow_fallback_list = fb_total[2];
-    e->stats.flow_fallback_ring = fb_total[3];
-    e->stats.flow_fallback_ram = fb_total[4];
-    e->stats.flow_retried = flow_retried;
-    e->stats.flow_to_next_event = flow_to_next;
-    e->stats.flow_list_entries = flow_scen ? FL.cap : 0u;
-    e->stats.flow_ring_rows = flow_scen ? FL.ring_rows : 0u;
-    e->stats.flow_lds_bytes = flow_lds;
-    e->stats.jit_fallbacks = n_jit_miss;
-    e->stats.pregen_group = pregen_group;
-    e->stats.pregen_ms = ms_pregen;
-    e->stats.h2d_ms = ms_h2d;
-    e->stats.draw_bytes = draw_bytes;
-    e->stats.state_bytes_per_scenario = bytes_per_lane;
-    e->stats.state_in_lds = lds_state ? 1u : 0u;
-    e->stats.lds_bytes_per_wave = lds_bytes;
-    e->stats.waves = waves;
-    e->stats.lanes_per_wave = kl;
-    e->stats.chunks = n_chunks;
-    e->stats.shared_instant_scenarios = n_rerun;
-    e->stats.specialised_launches = n_jit;
+// The next-event kernels over `count` scenarios of a chunk: all of them (h_map == nullptr) or the
+// listed ones.  Draws are pre-generated per slot j = position in the list; pieces that fit the draw budget.
+static int run_next_event(Run& r, const KArgs& chunk, uint32_t count, const uint32_t* h_map) {
+    af_engine_t* e = r.e;
+    RunTotals& t = r.t;
+    size_t mf = 0, mt = 0;
+    HIP_TRY(hipMemGetInfo(&mf, &mt));
+    // (per scenario: its draws, its scratch of the SimPy-order path and -- when the state does not fit the LDS: long wait
+    // queues -- its state words in HBM)
+    const size_t state_hbm = r.bytes_per_lane > 48u * 1024u ? (size_t)r.bytes_per_lane : 0u;
+    uint32_t piece = chunk_size(e, count, r.draw_bytes_per_scen + r.tie_words * 8u + state_hbm, mf);
+    if (piece == 0) return fail(AF_ERR_CAPACITY, "draw_capacity / fifo_capacity too large for the device memory budget");
+    if (const char* env = std::getenv("AF_SEQ_PIECE")) {   // test hook: force a whole chunk to run in pieces
+        const uint32_t v = (uint32_t)std::atoi(env);
+        if (v != 0u && v < piece) piece = v;
+    }
+    // A whole chunk (no list) that does not fit the draw budget in one piece -- the free memory is measured again
+    // here, after the scratch buffers of the chunk were allocated -- runs as pieces over an identity list: piece
+    // p0 simulates scenarios [p0, p0 + cnt) with its draws in slots [0, cnt).  (Round 2 ran [0, cnt) again: ADVICE r2.)
+    std::vector<uint32_t> ident;
+    if (h_map == nullptr && piece < count) {
+        ident.resize(count);
+        for (uint32_t i = 0; i < count; ++i) ident[i] = i;
+        h_map = ident.data();
+    }
+    const bool listed_subset = h_map != nullptr && ident.empty();
+    // First pass: the lean kernel.  A scenario in which two timed events share an instant stops
+    // there and is simulated again, from its start, by the kernel that has SimPy's event-by-event
+    // path; engines whose plan keeps producing such scenarios go straight to that kernel.
+    // (a handful of scenarios handed back by the stage-parallel kernel -- usually for a tie -- go straight to the
+    // SimPy-order kernel: a second pass over them would cost a whole latency-bound launch more)
+    // (decided once for all pieces: what the first piece learns -- rerun_shared_instants -- must not make the others run
+    // differently, or the launches of a chunk and its shared_instant_scenarios would depend on the draw budget)
+    const bool faithful_first = e->shared_instants_likely || (listed_subset && (uint64_t)count * 50u < chunk.n_scen);
+    for (uint32_t p0 = 0; p0 < count; p0 += piece) {
+        const uint32_t cnt = count - p0 < piece ? count - p0 : piece;
+        if (int rc = reserve_device((void**)&e->d_draws, e->draws_cap, r.draw_bytes_per_scen * cnt)) return rc;
+        if (int rc = reserve_device((void**)&e->d_pre_flags, e->pre_flags_cap, (size_t)cnt * 4u)) return rc;
+        if (int rc = reserve_device((void**)&e->d_tie, e->tie_cap, (size_t)cnt * r.tie_words * 8u)) return rc;
+        if (r.draw_bytes_per_scen * cnt > t.draw_bytes) t.draw_bytes = r.draw_bytes_per_scen * cnt;
+        KArgs a = chunk;
+        a.draws = e->d_draws;
+        a.pre_flags = e->d_pre_flags;
+        a.tie = e->d_tie;
+        if (h_map) {
+            if (int rc = reserve_device((void**)&e->d_map, e->map_cap, (size_t)cnt * 4u)) return rc;
+            HIP_TRY(hipMemcpyAsync(e->d_map, h_map + p0, (size_t)cnt * 4u, hipMemcpyHostToDevice, e->stream));
+            a.scen_map = e->d_map;
+            a.draws_by_lane = 1u;
+        }
+        a.n_scen = cnt;
+        HIP_TRY(hipEventRecord(e->ev2, e->stream));
+        if (launch_pregen_arrivals(a, cnt, (uint32_t)((1u + a.n_edges) * r.n_draw), !r.hetero_load, e->stream))
+            return fail(AF_ERR_HIP, "af_pregen_arrivals: LDS attribute");
+        hipLaunchKernelGGL(af_pregen_edges, dim3((r.n_draw + 255u) / 256u, cnt, a.n_edges), dim3(256), 0, e->stream, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(e->ev3, e->stream));
+        if (listed_subset && (a.online_hist || a.online_rps)) {   // scenarios that start over: their online counters are cleared
+            hipLaunchKernelGGL(af_zero_online, dim3(cnt), dim3(256), 0, e->stream, a, cnt);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemsetAsync(e->d_n_shared, 0, 4, e->stream));
+        if (int rc = launch_next_event(r, a, cnt, faithful_first)) return rc;
+        if (!faithful_first) {
+            uint32_t n_shared = 0;
+            HIP_TRY(hipMemcpyAsync(&n_shared, e->d_n_shared, 4, hipMemcpyDeviceToHost, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            if (n_shared > 0u)
+                if (int rc = rerun_shared_instants(r, a, chunk.n_scen, h_map ? h_map + p0 : nullptr, cnt)) return rc;
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipEventRecord(e->ev4, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        float ms_p = 0.f, ms_k = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms_p, e->ev2, e->ev3));
+        HIP_TRY(hipEventElapsedTime(&ms_k, e->ev3, e->ev4));
+        t.ms_pregen += ms_p;
+        t.ms_kernel += ms_k;
+    }
+    return AF_OK;
+}
+
+// ---- one chunk on the stage-parallel kernel; what it hands back goes to the next-event kernels ----------------------------
+// The first launch of a chunk, as its steps hand it on.
+struct FlowLaunch {
+    aff::FlowArgs f{};
+    uint32_t lds = 0;            // bytes of LDS per wave asked for
+    bool jit = false;            // the plan-specialised build of exactly this launch, else `fn`
+    const void* fn = nullptr;    // the library's generic instantiation
+    const char* prof_path = nullptr;   // AF_FLOW_PROF's file (f.prof: its counters), else null
+    uint32_t gate = 0u;          // af_engine_run_summarized: the analyzer starts once this many scenarios are done (0: after the run)
+};
+
+// Arrival times of the chunk's scenarios; for sweeps over the load, their launch order (`ordered`: e->d_order holds it).
+static int pregen_flow_chunk(Run& r, const KArgs& chunk, uint32_t lo, bool& ordered) {
+    af_engine_t* e = r.e;
+    const uint32_t nc = chunk.n_scen, n_draw = r.n_draw;
+    if (int rc = reserve_device((void**)&e->d_arr, e->arr_cap, (size_t)nc * n_draw * sizeof(double))) return rc;
+    if (int rc = reserve_device((void**)&e->d_arr_flags, e->arr_flags_cap, (size_t)nc * 4u)) return rc;
+    if ((size_t)nc * n_draw * sizeof(double) > r.t.draw_bytes) r.t.draw_bytes = (size_t)nc * n_draw * sizeof(double);
+    KArgs a = chunk;
+    a.draws = e->d_arr;
+    a.pre_flags = e->d_arr_flags;
+    // grouped pre-generation (af_pregen.hpp): sweeps of alike scenarios -- a workgroup is as slow as its heaviest one -- with
+    // sampling windows long enough that a window start (a user draw by one wave, the pipeline refilled) does not count
+    const char* pregen_mode = std::getenv("AF_PREGEN_MODE");   // rows | groups: tests and measurements
+    const bool force_groups = pregen_mode && std::strcmp(pregen_mode, "groups") == 0;
+    const bool force_rows = pregen_mode && std::strcmp(pregen_mode, "rows") == 0;
+    // (sweeps over users / rpm -- BASELINE configs 3 / 4 -- as long as the heaviest scenario is within 2.5 x of the mean:
+    // load_spread_suits_groups)
+    const bool grouped = !force_rows && a.gen_window_s > 0.0 &&
+                         (force_groups || (!(r.mask & (1u << AF_PARAM_GEN_WINDOW)) && nc >= 3072u &&
+                                           (double)n_draw * a.gen_window_s >= 512.0 * a.total_time &&
+                                           (!r.hetero_load || load_spread_suits_groups(e, r.sweep, lo, nc))));
+    // Sweeps over the load: waves are dispatched in blockIdx order as slots free up, and a wave lasts as long as its scenario
+    // has events.  A users-major grid (BASELINE configs 3 / 4: users ascending with the index) is then the WORST order --
+    // the heaviest scenarios start last and the launch ends with a few long waves on an empty chip (list scheduling of
+    // 10 000 waves with times ~ users on 4 096 slots: 3.54 mean wave times ascending, 2.73 heaviest first, 2.44 ideal).  Wave j
+    // simulates scenario order[j]; everything the kernel reads or writes is indexed by the scenario.
+    ordered = r.hetero_load && std::getenv("AF_FLOW_ORDER_OFF") == nullptr;
+    if (ordered) {
+        std::vector<uint32_t> order = heaviest_first(e, r.sweep, lo, nc);
+        if (int rc = reserve_device((void**)&e->d_order, e->order_cap, (size_t)nc * 4u)) return rc;
+        HIP_TRY(hipMemcpyAsync(e->d_order, order.data(), (size_t)nc * 4u, hipMemcpyHostToDevice, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));   // (`order` leaves scope; 40 KB, before anything of this chunk is enqueued)
+    }
+    HIP_TRY(hipEventRecord(e->ev2, e->stream));
+    if (launch_pregen_arrivals(a, nc, n_draw, !r.hetero_load, e->stream, grouped, &r.t.pregen_group)) return fail(AF_ERR_HIP, "af_arrival_groups: LDS attribute");
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e->ev3, e->stream));
+    return AF_OK;
+}
+
+// The stage-parallel kernel's arguments for the first launch over a chunk.
+static aff::FlowArgs flow_chunk_args(const Run& r, const KArgs& a, bool ordered) {
+    const af_engine_t* e = r.e;
+    aff::FlowArgs f = e->fargs;
+    f.L = r.FP.FL;
+    f.n_scen = a.n_scen;
+    f.seeds = a.seeds;
+    f.n_ovr = a.n_ovr;
+    f.ovr_param = a.ovr_param;
+    f.ovr_index = a.ovr_index;
+    f.ovr_values = a.ovr_values;
+    f.ovr_stride = a.ovr_stride;
+    f.arrivals = e->d_arr;
+    f.n_draw = r.n_draw;
+    f.pre_flags = e->d_arr_flags;
+    if (ordered) f.scen_map = e->d_order;
+    f.clock = a.clock;
+    f.clock_cap = a.clock_cap;
+    f.samples = a.samples;
+    f.tick_cap = a.tick_cap;
+    f.counts = a.counts;
+    f.online_hist = a.online_hist;
+    f.online_rps = a.online_rps;
+    f.online_hist_bins = a.online_hist_bins;
+    f.online_rps_buckets = a.online_rps_buckets;
+    f.online_hist_scale = a.online_hist_scale;
+    f.n_fallback = e->d_fb;
+    return f;
+}
+
+// Which build runs the launch: the plan-specialised one of exactly this launch (af_engine_set_kernels), else the library's
+// generic instantiation.
+static int pick_flow_kernel(Run& r, uint32_t nc, FlowLaunch& fl) {
+    af_engine_t* e = r.e;
+    const FlowPlan& FP = r.FP;
+    fl.lds = spread_lds_bytes(FP.lds);
+    fl.jit = e->flow_jit_fn != nullptr && fl.lds <= 64u * 1024u &&
+             flow_jit_spec_string(e, FP, r.out, r.sweep->n_overrides != 0u) == e->flow_jit_spec;
+    if (e->flow_jit_fn != nullptr && !fl.jit) r.t.n_jit_miss += 1u;
+    if (std::getenv("AF_DEBUG")) std::fprintf(stderr, "[af] flow jit spec: %s\n", flow_jit_spec_string(e, FP, r.out, r.sweep->n_overrides != 0u).c_str());
+    if (std::getenv("AF_DEBUG"))
+        std::fprintf(stderr, "[af] flow launch: %u scenarios, %u list entries%s, %u ring rows, %u B LDS per wave, af_flow_kernel<%u, %#x>%s%s\n", nc,
+                     FP.FL.cap, FP.big ? " (long-list instantiation)" : "", FP.FL.ring_rows, FP.lds, FP.ipl, FP.feat,
+                     FP.lean ? (FP.far ? ", lean instantiation with far edges" : ", lean instantiation") : "", fl.jit ? ", plan-specialised" : "");
+    fl.fn = fl.jit ? nullptr : flow_kernel_for(FP.ipl, FP.feat);
+    if (!fl.jit && fl.fn == nullptr) return fail(AF_ERR_INVALID, "no stage-parallel instantiation for this launch");
+    if (!fl.jit && fl.lds > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(fl.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fl.lds));
+    return AF_OK;
+}
+
+// The analyzer beside the last round: after how many finished scenarios of `nc` it starts, given the waves that are resident at
+// once (0: not beside the kernel).
+static uint32_t analyzer_gate(uint32_t nc, uint32_t resident) {
+    const uint32_t rem = resident ? nc % resident : 0u;
+    // (a tail of more than three quarters of a round leaves no room for the analyzer's workgroups; no tail, nothing to fill)
+    // (and only where the partial round is a good part of the launch -- at most six rounds --: the analyzer of a sweep of
+    // many rounds needs longer than the tail lasts, and beside a FULL round it only takes the kernel's slots: BASELINE
+    // config 5, 12.2 rounds, 227 instead of 223 ms per step, measured)
+    if (resident != 0u && nc > resident && nc <= 6u * resident && rem != 0u && rem * 4u <= resident * 3u) return nc - rem;
+    return 0u;
+}
+
+// af_engine_run_summarized: the analyzer starts on a second stream once the scenarios of the kernel's full residency rounds
+// have finished (hipStreamWaitValue32 on a counter its waves bump) and runs beside the last, partial round, which leaves
+// most of the chip idle; the analyzer is HBM-bound where this kernel is VALU-bound.  A workgroup of the analyzer that
+// meets a scenario still being simulated (its done flag is clear) puts it on a retry list and leaves.
+// (Measured first, round 6: the kernel launched in two parts with the analyzer of the first beside the second --
+// 51.9 instead of 48.4 ms per step on BASELINE config 2: the second part cannot start before the LAST wave of the first
+// has ended and then lasts a whole scenario at low occupancy, 11 ms against the 7 ms of the natural tail.)
+static int gate_for_launch(const Run& r, uint32_t nc, const FlowLaunch& fl, uint32_t& gate) {
+    af_engine_t* e = r.e;
+    gate = 0u;
+    if (e->wait_value_ok < 0) {
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeCanUseStreamWaitValue, e->device) != hipSuccess) { (void)hipGetLastError(); v = 0; }
+        e->wait_value_ok = v;
+    }
+    int per_cu = 0;
+    hipDeviceProp_t prop;
+    HIP_TRY(hipGetDeviceProperties(&prop, e->device));
+    if (fl.jit) HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, e->flow_jit_fn, (int)kWave, fl.lds));
+    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fl.fn, (int)kWave, fl.lds));
+    const uint32_t resident = (uint32_t)(per_cu > 0 ? per_cu : 0) * (uint32_t)prop.multiProcessorCount;
+    if (e->wait_value_ok > 0) gate = analyzer_gate(nc, resident);
+    if (std::getenv("AF_DEBUG")) std::fprintf(stderr, "[af] analyzer beside the last round: %u resident waves, gate at %u of %u scenarios\n", resident, gate, nc);
+    return AF_OK;
+}
+
+// The second stream, the done flags and the retry lists of the analyzer beside the kernel, cleared; the kernel told where they are.
+static int arm_side_stream(af_engine_t* e, uint32_t nc) {
+    if (e->stream2 == nullptr) {
+        HIP_TRY(hipStreamCreateWithFlags(&e->stream2, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreate(&e->ev_s0));
+        HIP_TRY(hipEventCreate(&e->ev_s1));
+        HIP_TRY(hipHostMalloc((void**)&e->h_done_count, 64, hipHostMallocCoherent | hipHostMallocMapped));
+        HIP_TRY(hipHostGetDevicePointer((void**)&e->d_done_count, e->h_done_count, 0));
+    }
+    if (int rc = reserve_device((void**)&e->d_done_flags, e->done_flags_cap, (size_t)nc * 4u)) return rc;
+    if (int rc = reserve_device((void**)&e->d_retry, e->retry_cap, 2u * ((size_t)nc + 1u) * 4u)) return rc;
+    *e->h_done_count = 0u;   // (nothing of this engine is in flight: af_engine_run is synchronous)
+    HIP_TRY(hipMemsetAsync(e->d_done_flags, 0, (size_t)nc * 4u, e->stream));
+    HIP_TRY(hipMemsetAsync(e->d_retry, 0, 2u * ((size_t)nc + 1u) * 4u, e->stream));
+    // (where the kernel's entry point finds them: behind the hand-over counters it already has a pointer to -- two more
+    // kernel arguments cost the general-server form 5 %, measured: its register allocation answers small changes chaotically)
+    e->done_ptrs[0] = reinterpret_cast<uint64_t>(e->d_done_flags);
+    e->done_ptrs[1] = reinterpret_cast<uint64_t>(e->d_done_count);
+    HIP_TRY(hipMemcpyAsync(e->d_fb + kDoneWords, e->done_ptrs, 16u, hipMemcpyHostToDevice, e->stream));
+    return AF_OK;
+}
+
+static int launch_flow(Run& r, uint32_t nc, FlowLaunch& fl) {
+    af_engine_t* e = r.e;
+    fl.f.n_scen = nc;
+    void* kargs[] = {&fl.f};
+    if (fl.jit) {
+        HIP_TRY(hipModuleLaunchKernel(e->flow_jit_fn, nc, 1, 1, kWave, 1, 1, fl.lds, e->stream, kargs, nullptr));
+        r.t.n_jit += 1u;
+    } else {
+        HIP_TRY(hipLaunchKernel(fl.fn, dim3(nc), dim3(kWave), kargs, fl.lds, e->stream));
+    }
+    return AF_OK;
+}
+
+// The analyzer on the second stream, behind a wait for the kernel's done counter.
+// (from here on the second stream waits for the counter: whatever goes wrong below must still let it through)
+static int enqueue_side_stream(af_engine_t* e, uint32_t nc, uint32_t gate) {
+    auto release_side = [&]() { *e->h_done_count = 0xFFFFFFFFu; };
+    hipError_t err = hipStreamWaitValue32(e->stream2, e->d_done_count, gate, hipStreamWaitValueGte, 0xFFFFFFFFu);
+    if (err == hipSuccess) err = hipEventRecord(e->ev_s0, e->stream2);
+    int rc = AF_OK;
+    if (err == hipSuccess) rc = launch_summary_kernels(e, e->fused_out, e->fused_sum, 0u, nc, e->stream2, e->d_done_flags, e->d_retry, nullptr, 0u);
+    if (err == hipSuccess && rc == AF_OK) err = hipEventRecord(e->ev_s1, e->stream2);
+    if (err != hipSuccess || rc != AF_OK) {
+        release_side();
+        (void)hipStreamSynchronize(e->stream);
+        (void)hipStreamSynchronize(e->stream2);
+        if (rc != AF_OK) return rc;
+        HIP_TRY(err);
+    }
+    return AF_OK;
+}
+
+// AF_FLOW_PROF: the launch's section times, appended to the file.
+static int dump_flow_profile(const FlowPlan& FP, uint32_t nc, const FlowLaunch& fl) {
+    std::vector<unsigned long long> hp((size_t)nc * aff::kProfSections);
+    HIP_TRY(hipMemcpy(hp.data(), fl.f.prof, hp.size() * 8u, hipMemcpyDeviceToHost));
+    static const char* names[aff::kProfSections] = {"setup+end", "generator batch", "select", "series: delivery end (FAR)", "station logic",
+                                                    "servers_solve + claim", "server series", "draws (Philox, log)", "send: spike + series",
+                                                    "append + send_floor", "complete", "flush_ticks + round end",
+                                                    "general servers: lanes", "general servers: walk", "general servers: rank + relax", "general servers: state at the horizon",
+                                                    "COUNT rounds solved at once", "COUNT relaxation sweeps", "COUNT lanes in solved rounds", "COUNT rounds walked by event",
+                                                    "general servers: standing (ranks, RAM)", "general servers: commit walk (series)"};
+    double acc[aff::kProfSections] = {}, total = 0.0;
+    for (uint32_t i = 0; i < nc; ++i)
+        for (uint32_t k = 0; k < aff::kProfSections; ++k) acc[k] += (double)hp[(size_t)i * aff::kProfSections + k];
+    for (uint32_t k = 0; k < aff::kProfSections; ++k)
+        if (!names[k] || std::strncmp(names[k], "COUNT", 5) != 0) total += acc[k];
+    if (FILE* fp = std::fopen(fl.prof_path, "a")) {
+        std::fprintf(fp, "af_flow_kernel<%u, %#x> sections, %u waves, mean cycles per wave %.0f:\n", FP.ipl, FP.feat, nc, total / nc);
+        for (uint32_t k = 0; k < aff::kProfSections; ++k)
+            if (names[k]) std::fprintf(fp, "  %-28s %6.2f %%  %12.0f cycles per wave\n", names[k], 100.0 * acc[k] / total, acc[k] / nc);
+        std::fclose(fp);
+    }
+    return AF_OK;
+}
+
+// Second chance on the stage-parallel kernel itself, in its most tolerant form: 256-entry lists, tick
+// differences in HBM (no reach limit), messages carry their send time so that two deliveries of one station
+// at the same instant are ordered the way SimPy orders them.  A wave costs tens of milliseconds; the same
+// scenario on a next-event kernel is a latency-bound chain of ~1 s (LB-2).  Only what this launch hands
+// back again -- or what can never fit its RAM model -- goes to the next-event kernels: those join `rest`.
+static int flow_second_chance(Run& r, const KArgs& chunk, const aff::FlowArgs& f, uint32_t lo, const std::vector<uint32_t>& retry,
+                              std::vector<uint32_t>& rest, std::vector<uint32_t>& cnt_host) {
+    af_engine_t* e = r.e;
+    const aff::FlowLayout& FL2 = r.FP.FL2;
+    if (int rc = reserve_device((void**)&e->d_map, e->map_cap, retry.size() * 4u)) return rc;
+    HIP_TRY(hipMemcpyAsync(e->d_map, retry.data(), retry.size() * 4u, hipMemcpyHostToDevice, e->stream));
+    aff::FlowArgs f2 = f;
+    f2.L = FL2;
+    f2.n_scen = (uint32_t)retry.size();
+    f2.scen_map = e->d_map;
+    f2.n_fallback = e->d_fb + 5;
+    const uint32_t lds2 = chunk.blob_bytes + f2.L.n_words * 8u;
+    if (lds2 > kLdsLimit) return fail(AF_ERR_CAPACITY, "flow kernel layout exceeds the LDS of a compute unit");
+    if (chunk.online_hist || chunk.online_rps) {   // scenarios that start over: their online counters are cleared
+        KArgs a = chunk;
+        a.scen_map = e->d_map;
+        hipLaunchKernelGGL(af_zero_online, dim3((uint32_t)retry.size()), dim3(256), 0, e->stream, a, (uint32_t)retry.size());
+        HIP_TRY(hipGetLastError());
+    }
+    constexpr uint32_t kRobust = aff::FEAT_ALL | aff::FEAT_TIEBREAK | aff::FEAT_BIGLIST;
+    const void* fn2 = flow_kernel_for(1u, kRobust | (r.FP.gen_compact ? (uint32_t)aff::FEAT_GENSRV : 0u) | (e->flow_chain ? (uint32_t)aff::FEAT_CHAIN : 0u) |
+                                              (f2.lb_least_connections ? (uint32_t)aff::FEAT_LC : 0u));
+    if (fn2 == nullptr) return fail(AF_ERR_INVALID, "no stage-parallel instantiation for this launch");
+    if (lds2 > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(fn2, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+    HIP_TRY(hipEventRecord(e->ev3, e->stream));
+    void* kargs2[] = {&f2};
+    if (std::getenv("AF_DEBUG")) {
+        std::fprintf(stderr, "[af] flow second chance: %zu scenarios (lists of %u/%u/%u/%u entries with send times, differences in HBM), %u B LDS:",
+                     retry.size(), FL2.cap_of[0], FL2.cap_of[1], FL2.cap_of[2], FL2.cap_of[3], lds2);
+        for (size_t q = 0; q < retry.size() && q < 16; ++q)
+            std::fprintf(stderr, " %u(flags %#x)", lo + retry[q], cnt_host[(size_t)retry[q] * AF_CNT_SLOTS + AF_CNT_FLAGS]);
+        std::fprintf(stderr, "\n");
+    }
+    HIP_TRY(hipLaunchKernel(fn2, dim3((uint32_t)retry.size()), dim3(kWave), kargs2, lds2, e->stream));
+    HIP_TRY(hipEventRecord(e->ev4, e->stream));
+    uint32_t fb2[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(fb2, e->d_fb + 5, sizeof fb2, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    float ms2 = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms2, e->ev3, e->ev4));
+    r.t.ms_flow += ms2;
+    r.t.flow_retried += (uint32_t)retry.size();
+    if (fb2[0] > 0u) {
+        HIP_TRY(hipMemcpy(cnt_host.data(), chunk.counts, cnt_host.size() * 4u, hipMemcpyDeviceToHost));
+        for (uint32_t i : retry)
+            if (cnt_host[(size_t)i * AF_CNT_SLOTS + AF_CNT_FLAGS] & aff::FLAG_FLOW_FALLBACK) rest.push_back(i);
+        std::sort(rest.begin(), rest.end());
+    }
+    return AF_OK;
+}
+
+// What the first launch over a chunk handed back: a second chance for what can have one, the next-event kernels for the rest.
+static int rerun_handed_back(Run& r, const KArgs& chunk, const aff::FlowArgs& f, uint32_t lo, bool& on_flow) {
+    af_engine_t* e = r.e;
+    const uint32_t nc = chunk.n_scen;
+    std::vector<uint32_t> cnt_host((size_t)nc * AF_CNT_SLOTS);
+    HIP_TRY(hipMemcpy(cnt_host.data(), chunk.counts, cnt_host.size() * 4u, hipMemcpyDeviceToHost));
+    std::vector<uint32_t> retry, rest;
+    for (uint32_t i = 0; i < nc; ++i) {
+        const uint32_t fl = cnt_host[(size_t)i * AF_CNT_SLOTS + AF_CNT_FLAGS];
+        if (!(fl & aff::FLAG_FLOW_FALLBACK)) continue;
+        // (flow_big: that WAS the most tolerant form; a tie the general server station gives up on stops the second chance at
+        // the same instant: straight to the next-event kernels)
+        if ((fl & (aff::FLOW_WHY_RAM | aff::FLOW_WHY_GEN_TIE)) || (r.FP.big && !r.FP.gen_compact)) rest.push_back(i);
+        else retry.push_back(i);
+    }
+    if (!retry.empty())
+        if (int rc = flow_second_chance(r, chunk, f, lo, retry, rest, cnt_host)) return rc;
+    r.t.flow_to_next += (uint32_t)rest.size();
+    if (!rest.empty())
+        if (int rc = run_next_event(r, chunk, (uint32_t)rest.size(), rest.data())) return rc;
+    // A plan whose scenarios mostly end on the next-event kernels anyway (general servers fed by edges with discrete
+    // latencies: arrivals that coincide with step ends) pays a flow pass, a second chance AND a next-event pass
+    // per scenario: once a chunk handed more than a quarter of its scenarios over, the chunks still to come go to the
+    // next-event kernels directly (results are the same either way; flow_mode 2 = "always" keeps the stage-parallel kernel).
+    if ((uint64_t)rest.size() * 4u > (uint64_t)nc && e->flow_mode != 2u) on_flow = false;
+    return AF_OK;
+}
+
+// The stage-parallel kernel over the whole chunk [lo, lo + chunk.n_scen).  `on_flow` turns false when the chunks still to come
+// are better off on the next-event kernels.
+static int run_flow_chunk(Run& r, const KArgs& chunk, uint32_t lo, bool& on_flow) {
+    af_engine_t* e = r.e;
+    RunTotals& t = r.t;
+    const uint32_t nc = chunk.n_scen;
+    bool ordered = false;
+    if (int rc = pregen_flow_chunk(r, chunk, lo, ordered)) return rc;
+    FlowLaunch fl;
+    fl.f = flow_chunk_args(r, chunk, ordered);
+    HIP_TRY(hipMemsetAsync(e->d_fb, 0, 32u * 4u, e->stream));
+    // measurement hook (AF_FLOW_PROF=<file>, plan-specialised builds only): shader-clock time per section of Flow::run
+    fl.prof_path = std::getenv("AF_FLOW_PROF");
+    if (fl.prof_path != nullptr) {
+        if (int rc = reserve_device((void**)&e->d_prof, e->prof_cap, (size_t)nc * aff::kProfSections * 8u)) return rc;
+        HIP_TRY(hipMemsetAsync(e->d_prof, 0, (size_t)nc * aff::kProfSections * 8u, e->stream));
+        fl.f.prof = e->d_prof;
+    }
+    if (int rc = pick_flow_kernel(r, nc, fl)) return rc;
+    if (e->fused_sum != nullptr && lo == 0u && nc == r.n && fl.f.prof == nullptr)
+        if (int rc = gate_for_launch(r, nc, fl, fl.gate)) return rc;
+    if (fl.gate != 0u)
+        if (int rc = arm_side_stream(e, nc)) return rc;
+    if (int rc = launch_flow(r, nc, fl)) return rc;
+    if (fl.gate != 0u)
+        if (int rc = enqueue_side_stream(e, nc, fl.gate)) return rc;
+    t.fused_first = fl.gate;
+    HIP_TRY(hipEventRecord(e->ev4, e->stream));
+    uint32_t fb[5] = {0, 0, 0, 0, 0};
+    HIP_TRY(hipMemcpyAsync(fb, e->d_fb, sizeof fb, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (t.fused_first != 0u) {
+        HIP_TRY(hipStreamSynchronize(e->stream2));
+        float ms_s = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms_s, e->ev_s0, e->ev_s1));
+        e->stats.summary_beside_ms = ms_s;
+        // (a scenario handed back is simulated again below and its outputs change: the sweep is then summarised again, in full)
+        e->fused_done = fb[0] == 0u;
+    }
+    if (fl.f.prof != nullptr)
+        if (int rc = dump_flow_profile(r.FP, nc, fl)) return rc;
+    float ms_p = 0.f, ms_f = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms_p, e->ev2, e->ev3));
+    HIP_TRY(hipEventElapsedTime(&ms_f, e->ev3, e->ev4));
+    t.ms_pregen += ms_p;
+    t.ms_flow += ms_f;
+    t.flow_scen += nc;
+    for (int k = 0; k < 5; ++k) t.fb_total[k] += fb[k];
+    if (fb[0] > 0u)
+        if (int rc = rerun_handed_back(r, chunk, fl.f, lo, on_flow)) return rc;
+    return AF_OK;
+}
+
+// The totals of the run become e->stats.
+static int write_stats(Run& r) {
+    af_engine_t* e = r.e;
+    RunTotals& t = r.t;
+    HIP_TRY(hipEventElapsedTime(&t.ms_h2d, e->ev0, e->ev1));
+    e->stats.kernel_ms = t.ms_kernel + t.ms_flow;
+    e->stats.flow_kernel_ms = t.ms_flow;
+    e->stats.flow_scenarios = t.flow_scen;
+    e->stats.flow_fallback = t.fb_total[0];
+    e->stats.flow_fallback_tie = t.fb_total[1];
+    e->stats.flow_fallback_list = t.fb_total[2];
+    e->stats.flow_fallback_ring = t.fb_total[3];
+    e->stats.flow_fallback_ram = t.fb_total[4];
+    e->stats.flow_retried = t.flow_retried;
+    e->stats.flow_to_next_event = t.flow_to_next;
+    e->stats.flow_list_entries = t.flow_scen ? r.FP.FL.cap : 0u;
+    e->stats.flow_ring_rows = t.flow_scen ? r.FP.FL.ring_rows : 0u;
+    e->stats.flow_lds_bytes = r.FP.lds;
+    e->stats.jit_fallbacks = t.n_jit_miss;
+    e->stats.pregen_group = t.pregen_group;
+    e->stats.pregen_ms = t.ms_pregen;
+    e->stats.h2d_ms = t.ms_h2d;
+    e->stats.draw_bytes = t.draw_bytes;
+    e->stats.state_bytes_per_scenario = r.bytes_per_lane;
+    e->stats.state_in_lds = t.lds_state ? 1u : 0u;
+    e->stats.lds_bytes_per_wave = t.lds_bytes;
+    e->stats.waves = t.waves;
+    e->stats.lanes_per_wave = t.kl;
+    e->stats.chunks = t.n_chunks;
+    e->stats.shared_instant_scenarios = t.n_rerun;
+    e->stats.specialised_launches = t.n_jit;
     e->stats.request_capacity = e->request_capacity;
     e->stats.fifo_capacity = e->fifo_capacity;
     return AF_OK;
+}
+
+int af_engine_run(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* out) {
+    Run r;
+    if (int rc = validate_sweep(e, sweep, out, r)) return rc;
+    if (int rc = stage_sweep(r)) return rc;
+    uint32_t chunk = 0;
+    if (int rc = size_run(r, chunk)) return rc;
+    bool on_flow = r.use_flow;
+    for (uint32_t lo = 0; lo < r.n; lo += chunk) {
+        const uint32_t nc = r.n - lo < chunk ? r.n - lo : chunk;
+        r.t.n_chunks += 1u;
+        const KArgs a = chunk_kargs(r, lo, nc);
+        if (int rc = on_flow ? run_flow_chunk(r, a, lo, on_flow) : run_next_event(r, a, nc, nullptr)) return rc;
+    }
+    return write_stats(r);
 }
 
 int af_engine_jit_spec(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* out, char* buf, size_t cap) {
@@ -2438,10 +2602,7 @@ int af_engine_jit_spec(af_engine_t* e, const af_sweep_t* sweep, const af_outputs
     if (!e->plan_only) HIP_TRY(hipSetDevice(e->device));
     KArgs a = e->args;
     uint32_t mask = 0;
-    for (uint32_t k = 0; k < sweep->n_overrides; ++k) {
-        if (sweep->overrides[k].param >= AF_PARAM_COUNT_) return fail(AF_ERR_INVALID, "bad override");
-        mask |= 1u << sweep->overrides[k].param;
-    }
+    if (int rc = sweep_override_mask(sweep, false, mask)) return rc;
     a.L = af::make_layout(e->request_capacity, e->fifo_capacity, a.n_edges, a.n_servers, a.n_lb_edges, a.n_rows, mask, a.n_edge_marks, a.n_srv_marks);
     a.clock_cap = out->clock_capacity;
     a.tick_cap = out->tick_capacity;
@@ -2449,8 +2610,7 @@ int af_engine_jit_spec(af_engine_t* e, const af_sweep_t* sweep, const af_outputs
     a.samples = out->samples;
     a.online_hist = out->online_hist;
     a.online_rps = out->online_rps;
-    a.n_draw = sweep->draw_capacity ? sweep->draw_capacity : out->clock_capacity;
-    if (a.n_draw == 0) return fail(AF_ERR_INVALID, "draw_capacity (or clock_capacity) must be > 0");
+    if (int rc = draws_per_stream(sweep, out, a.n_draw)) return rc;
     bool on_flow = flow_wanted(e, sweep->n_scenarios);
     FlowPlan FP;
     if (on_flow) {
@@ -2475,9 +2635,7 @@ int af_engine_jit_spec(af_engine_t* e, const af_sweep_t* sweep, const af_outputs
     uint32_t kl = 0;
     bool lds_state = false;
     choose_lanes(e, chunk, a.blob_bytes, af::layout_bytes_per_lane(a.L), kl, lds_state);
-    uint32_t klog = 0;
-    while ((1u << klog) < kl) ++klog;
-    const std::string spec = jit_spec_string(a, lds_state, klog);
+    const std::string spec = jit_spec_string(a, lds_state, klog_of(kl));
     if (spec.size() + 1 > cap) return fail(AF_ERR_CAPACITY, "spec buffer too small");
     std::memcpy(buf, spec.c_str(), spec.size() + 1);
     return AF_OK;
@@ -2553,15 +2711,7 @@ int af_engine_summarize(af_engine_t* e, const af_outputs_t* out, const af_summar
 }
 
 // The pooled analyzer's engine-owned scratch: grown on demand (the contents are lost then), kept until the engine is destroyed.
-static int pool_reserve(af_engine_t* e, size_t bytes) {
-    if (bytes <= e->pool_cap) return AF_OK;
-    if (e->d_pool) HIP_TRY(hipFree(e->d_pool));
-    e->d_pool = nullptr;
-    e->pool_cap = 0;
-    HIP_TRY(hipMalloc((void**)&e->d_pool, bytes));
-    e->pool_cap = bytes;
-    return AF_OK;
-}
+static int pool_reserve(af_engine_t* e, size_t bytes) { return reserve_device((void**)&e->d_pool, e->pool_cap, bytes); }
 
 // the layout of a request's scratch: 256-byte aligned parts, one after the other
 struct ScratchLayout {
@@ -3727,10 +3877,11 @@ int af_engine_summarize_series_quantiles(af_engine_t* e, const af_outputs_t* out
 }
 
 // af_engine_run + af_engine_summarize in one call, with the same results.  Where the sweep runs as ONE launch sequence of the
-// stage-parallel kernel over alike scenarios (no launch order), the kernel is launched in two parts -- the scenarios of its full
-// residency rounds, then the rest -- and the analyzer of the first part runs on a second stream beside the second: the last,
-// partial round leaves most of the chip idle (BASELINE config 2: 10 000 scenarios = 2.44 rounds of 4 096 waves; the 0.44 round
-// takes 8.5 ms), the analyzer is HBM-bound and the simulation kernel VALU-bound.  Scenarios the kernel hands back are simulated
+// stage-parallel kernel (one chunk), the kernel is launched ONCE and its waves bump a counter as their scenarios finish; the analyzer
+// waits on a second stream until that counter reaches the scenarios of the kernel's full residency rounds (gate_for_launch) and
+// then runs beside the last, partial round, which leaves most of the chip idle (BASELINE config 2: 10 000 scenarios = 2.44 rounds
+// of 4 096 waves; the 0.44 round takes 8.5 ms); the analyzer is HBM-bound and the simulation kernel VALU-bound.  Scenarios it
+// meets unfinished go on retry lists and are summarised after the run.  Scenarios the kernel hands back are simulated
 // again afterwards: their sweep is then summarised once more, in full.
 int af_engine_run_summarized(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* out, const af_summary_t* sum) {
     if (int rc = check_summary_request(e, out, sum)) return rc;
@@ -3816,6 +3967,7 @@ void af_engine_destroy(af_engine_t* e) {
     if (e->d_arr_flags) (void)hipFree(e->d_arr_flags);
     if (e->d_fb) (void)hipFree(e->d_fb);
     if (e->d_slot) (void)hipFree(e->d_slot);
+    if (e->d_prof) (void)hipFree(e->d_prof);
     if (e->jit_module) (void)hipModuleUnload(e->jit_module);
     if (e->flow_jit_module) (void)hipModuleUnload(e->flow_jit_module);
     if (e->stream) (void)hipStreamDestroy(e->stream);

@@ -159,6 +159,46 @@ def test_handed_back_scenarios_are_invisible_in_the_results():
     assert handed_back >= 3 and ran > 20     # (the kernel models more every round: 4 of 120 are left, all exact ties)
 
 
+def _assert_online_counters(res, bins, hist_max, horizon, what=""):
+    """Every scenario's kernel-side histogram and 1-s windows against the analyzer oracle on its own rqs_clock."""
+    from oracle import analyzer_oracle as ao
+
+    hist = res.online_hist.cpu().numpy().view(np.uint32)
+    rps = res.online_rps.cpu().numpy()
+    for i in range(len(res)):
+        ck = res[i].rqs_clock
+        assert np.array_equal(hist[i], ao.latency_histogram(ck, bins, hist_max)), f"{what} scenario {i}: online histogram"
+        assert np.array_equal(rps[i].astype(np.float64), ao.throughput_series(ck, horizon)[1]), f"{what} scenario {i}: online rps"
+
+
+def test_second_chance_starts_from_cleared_online_counters():
+    """The scenarios of test_a_ring_shorter_than_the_stay_in_a_server_hands_back, with the kernel-side summary on: what the first
+    launch counted of a scenario it handed back must not show in the second chance's histogram and windows."""
+    payload = single_server(horizon=30)
+    seeds = np.arange(48, dtype=np.uint64) + 5
+    online = {"hist_bins": 1024, "hist_max": 0.256}
+    res = _runner(payload, seeds=seeds, flow_ring_rows=4, online_summary=online).run()
+    st = res.engine_stats
+    assert st.flow_fallback_ring > 0 and st.flow_retried == st.flow_fallback and st.flow_to_next_event == 0
+    _assert_online_counters(res, 1024, 0.256, 30)
+    whole = _runner(payload, seeds=seeds, online_summary=online).run()
+    assert np.array_equal(res.online_hist.cpu().numpy(), whole.online_hist.cpu().numpy())
+    assert np.array_equal(res.online_rps.cpu().numpy(), whole.online_rps.cpu().numpy())
+
+
+def test_scenarios_handed_to_the_next_event_kernels_start_from_cleared_online_counters():
+    """The payloads of test_handed_back_scenarios_are_invisible_in_the_results with the kernel-side summary on."""
+    handed_back = 0
+    for case in range(24):
+        rng = random.Random(31000 + case)
+        payload = flow_payload(rng, horizon=6)
+        seeds = np.arange(5, dtype=np.uint64) + 900 + case
+        res = _runner(payload, seeds=seeds, online_summary={"hist_bins": 512, "hist_max": 0.256}).run()
+        handed_back += res.engine_stats.flow_to_next_event
+        _assert_online_counters(res, 512, 0.256, 6, f"case {case}")
+    assert handed_back >= 1
+
+
 def test_single_server_and_sweep_columns():
     res = _runner(single_server(horizon=120), seeds=[0, 1, 2]).run()
     assert res.engine_stats.flow_scenarios == 3 and res.engine_stats.flow_fallback == 0

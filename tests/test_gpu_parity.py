@@ -169,17 +169,25 @@ def test_parameter_sweep_columns():
     assert gen[users == 480.0].mean() > 30 * gen[users == 10.0].mean()
 
 
-def test_sweep_larger_than_the_draw_budget_runs_in_chunks_with_identical_results():
+@pytest.mark.parametrize("flow", [False, True], ids=["next-event", "flow"])
+def test_sweep_larger_than_the_draw_budget_runs_in_chunks_with_identical_results(flow):
+    """flow=True: the stage-parallel kernel over several chunks -- output and column pointers offset by the chunk's start, and
+    (a users column) the heaviest-first launch order of a chunk that does not start at scenario 0."""
     payload = lb_two_servers(horizon=20)
     n = 150
     users = np.linspace(20.0, 400.0, n)
     seeds = 0xABCD0000 + np.arange(n, dtype=np.uint64)
     sweep = {"rqs_input.avg_active_users.mean": users}
-    whole = _runner(payload, seeds=seeds, sweep=sweep).run()
+    whole = _runner(payload, seeds=seeds, sweep=sweep, flow=flow).run()
     # 1 MiB of draws per chunk: (1 + 6 edges) * clock_capacity * 8 B per scenario -> a handful of scenarios
-    parts = _runner(payload, seeds=seeds, sweep=sweep, draw_memory_mb=1,
+    # (flow=True: the stage-parallel kernel pre-generates arrival times only, clock_capacity * 8 B per scenario -> fewer chunks)
+    parts = _runner(payload, seeds=seeds, sweep=sweep, draw_memory_mb=1, flow=flow,
                     clock_capacity=whole._clock_t.shape[1]).run()  # noqa: SLF001
-    assert whole.engine_stats.chunks == 1 and parts.engine_stats.chunks > 3
+    assert whole.engine_stats.chunks == 1
+    if flow:
+        assert parts.engine_stats.chunks > 1 and parts.engine_stats.flow_scenarios == n
+    else:
+        assert parts.engine_stats.chunks > 3
     assert np.array_equal(whole.counts, parts.counts)
     for i in range(n):
         assert np.array_equal(whole[i].rqs_clock, parts[i].rqs_clock)
@@ -300,6 +308,35 @@ def test_handover_between_kernel_variants_is_invisible():
     assert auto2.engine_stats.shared_instant_scenarios == 0 and np.array_equal(auto1.counts, auto2.counts)
     calm = _runner(lb_two_servers(horizon=20), seeds=seeds).run()
     assert calm.engine_stats.shared_instant_scenarios == 0
+
+
+def test_a_chunk_in_pieces_with_reruns_equals_the_chunk_in_one_piece(monkeypatch):
+    """AF_SEQ_PIECE=3: one chunk of 7 scenarios as pieces of 3, 3 and 1 over an identity list.  Every scenario of this payload
+    meets shared instants (seeds 900..939 on the CPU oracle: 25 to 139 each), so every piece has its second pass on the
+    SimPy-order kernel, which starts from cleared online counters."""
+    from oracle import analyzer_oracle as ao
+
+    payload = tie_storm(random.Random(777003), horizon=12)
+    seeds = np.arange(7, dtype=np.uint64) + 900
+    kw = {"seeds": seeds, "expect_shared_instants": False, "online_summary": {"hist_bins": 512, "hist_max": 0.256}}
+    plain = _runner(payload, **kw).run()
+    monkeypatch.setenv("AF_SEQ_PIECE", "3")
+    pieces = _runner(payload, **kw).run()
+    monkeypatch.delenv("AF_SEQ_PIECE")
+    assert plain.engine_stats.chunks == 1 and pieces.engine_stats.chunks == 1
+    assert plain.engine_stats.shared_instant_scenarios == 7 and pieces.engine_stats.shared_instant_scenarios == 7
+    assert np.array_equal(plain.counts, pieces.counts)
+    for i in range(7):
+        assert np.array_equal(plain[i].rqs_clock.view(np.uint64), pieces[i].rqs_clock.view(np.uint64)), f"scenario {i}: rqs_clock"
+    assert np.array_equal(plain._samples_t.cpu().numpy(), pieces._samples_t.cpu().numpy())  # noqa: SLF001
+    for res in (plain, pieces):
+        hist = res.online_hist.cpu().numpy().view(np.uint32)
+        rps = res.online_rps.cpu().numpy()
+        for i in range(7):
+            ck = res[i].rqs_clock
+            assert np.array_equal(hist[i], ao.latency_histogram(ck, 512, 0.256)), f"scenario {i}: online histogram"
+            assert np.array_equal(rps[i].astype(np.float64), ao.throughput_series(ck, 12)[1]), f"scenario {i}: online rps"
+    _assert_scenario(pieces[4], ol.simulate(lower(payload), 904))      # in the second piece
 
 
 # ------------------------------------------------------------------ edge cases
