@@ -8,7 +8,7 @@ executed over thousands of independent scenarios by a hand-written HIP kernel
 
 from .payload import load_yaml, normalize_payload
 from .plan import DevicePlan, lower
-from .results import BatchedResults, ScenarioResults, latency_quantiles, latency_state_cells, latency_state_quantiles, latency_state_stats, latency_window_quantiles, latency_window_stats, series_histogram_quantiles, series_window_excursions, series_window_histogram, series_window_quantiles, window_edges
+from .results import BatchedResults, ScenarioResults, check_series_combinations, latency_quantiles, latency_state_cells, latency_state_quantiles, latency_state_stats, latency_window_quantiles, latency_window_stats, series_combined_values, series_combined_window_stats, series_histogram_quantiles, series_window_excursions, series_window_histogram, series_window_quantiles, window_edges
 from .runner import SimulationRunner
 from .sweep import Sweep, expand_grid
 
@@ -18,6 +18,7 @@ __all__ = [
     "ScenarioResults",
     "SimulationRunner",
     "Sweep",
+    "check_series_combinations",
     "expand_grid",
     "latency_quantiles",
     "latency_state_cells",
@@ -28,6 +29,8 @@ __all__ = [
     "load_yaml",
     "lower",
     "normalize_payload",
+    "series_combined_values",
+    "series_combined_window_stats",
     "series_histogram_quantiles",
     "series_window_excursions",
     "series_window_histogram",

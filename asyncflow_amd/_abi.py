@@ -389,6 +389,42 @@ class AfSeriesHistogram(C.Structure):
     ]
 
 
+MAX_SERIES_COMBINATIONS = 64   # AF_MAX_SERIES_COMBINATIONS
+#: AF_COMBINE_*: the op of a combination across the series of one sample row
+COMBINE_OPS = {"sum": 0, "min": 1, "max": 2, "spread": 3}
+
+
+class AfSeriesCombined(C.Structure):
+    """``af_series_combined_t``: request of ``af_engine_summarize_series_combined`` (``elapsed_ms`` and
+    ``scratch_bytes`` are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("n_combos", C.c_uint32),
+        ("op", C.POINTER(C.c_uint32)),
+        ("col_start", C.POINTER(C.c_uint32)),
+        ("cols", C.POINTER(C.c_uint32)),
+        ("thresholds", C.POINTER(C.c_double)),
+        ("n_bins", C.c_uint32),
+        ("lo", C.POINTER(C.c_double)),
+        ("width", C.POINTER(C.c_double)),
+        ("count", C.c_void_p),
+        ("mean", C.c_void_p),
+        ("minv", C.c_void_p),
+        ("maxv", C.c_void_p),
+        ("above", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("under", C.c_void_p),
+        ("over", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -414,6 +450,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_series_quantiles",
     "af_engine_summarize_series_excursions",
     "af_engine_summarize_series_histogram",
+    "af_engine_summarize_series_combined",
     "af_engine_summarize_quantiles",
     "af_engine_summarize_arrival_quantiles",
     "af_engine_summarize_state_windows",
@@ -464,6 +501,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_series_excursions.restype = C.c_int
     lib.af_engine_summarize_series_histogram.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesHistogram)]
     lib.af_engine_summarize_series_histogram.restype = C.c_int
+    lib.af_engine_summarize_series_combined.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesCombined)]
+    lib.af_engine_summarize_series_combined.restype = C.c_int
     lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_summarize_arrival_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]

@@ -22,6 +22,8 @@
 //                                          per (scenario, window of ticks, series) (af_series_excursions.hpp)
 //   af_shist_kernel                        af_engine_summarize_series_histogram: occupancy histograms of the sampled series
 //                                          per (group, window of ticks, output column) (af_series_histogram.hpp)
+//   af_scomb_partial / af_scomb_reduce     af_engine_summarize_series_combined: sum, min, max and spread across the series
+//                                          of a sample row per (group, window of ticks, combination) (af_series_combined.hpp)
 //
 // Memory plan
 //   LDS  : flow kernel: [plan blob, patched per scenario][station lists, select scratch / server segments, rings,
@@ -54,6 +56,7 @@
 #include "af_series_quantiles.hpp"
 #include "af_series_excursions.hpp"
 #include "af_series_histogram.hpp"
+#include "af_series_combined.hpp"
 #include "af_windowed.hpp"
 #include "af_arrival.hpp"
 #include "af_state.hpp"
@@ -3655,6 +3658,175 @@ int af_engine_summarize_series_histogram(af_engine_t* e, const af_outputs_t* out
     const size_t lds = (size_t)afsh::kWaves * lds_slots * (B + 2u) * 4u;
     hipLaunchKernelGGL(afsh::af_shist_kernel, dim3((uint32_t)((items + afsh::kWaves - 1u) / afsh::kWaves)), dim3(afsh::kThreads), lds, st, a);
     HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the host vectors are read by the copies until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Combinations across the sampled series per (group, window of ticks, combination) (af_series_combined.hpp).  The host checks
+// the combinations, reads the group ids and the counts back, builds the groups' member lists and zeroes the histogram outputs;
+// one streaming pass over the sample rows, then -- unless every group is a single scenario -- the fold of the members' records.
+static_assert(afsc::kMaxCombos == AF_MAX_SERIES_COMBINATIONS && afsc::kMaxBins == AF_MAX_SERIES_HISTOGRAM_BINS, "the kernel's limits are the header's");
+static_assert(afsc::kSum == AF_COMBINE_SUM && afsc::kMin == AF_COMBINE_MIN && afsc::kMax == AF_COMBINE_MAX && afsc::kSpread == AF_COMBINE_SPREAD,
+              "the kernel's ops are the header's");
+
+int af_engine_summarize_series_combined(af_engine_t* e, const af_outputs_t* out, af_series_combined_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty series combined request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "series_combined.tick_edges is required");
+    if (!req->mean) return fail(AF_ERR_INVALID, "series_combined.mean is required");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, cap = out->tick_capacity, B = req->n_bins, Cn = req->n_combos;
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch, n_edges = e->args.n_edges;
+    if (Cn == 0 || Cn > AF_MAX_SERIES_COMBINATIONS)
+        return fail(AF_ERR_INVALID, "series_combined.n_combos must be 1 .. AF_MAX_SERIES_COMBINATIONS (" + std::to_string(AF_MAX_SERIES_COMBINATIONS) + ")");
+    if (!req->op || !req->col_start || !req->cols) return fail(AF_ERR_INVALID, "series_combined.op, col_start and cols are required");
+    if (B > AF_MAX_SERIES_HISTOGRAM_BINS)
+        return fail(AF_ERR_INVALID, "series_combined.n_bins must be at most AF_MAX_SERIES_HISTOGRAM_BINS (" + std::to_string(AF_MAX_SERIES_HISTOGRAM_BINS) + ")");
+    if (B == 0 ? (req->hist || req->under || req->over) : !req->hist)
+        return fail(AF_ERR_INVALID, "series_combined.hist (with under and over) and n_bins must be given together");
+    if ((req->lo == nullptr) != (req->width == nullptr)) return fail(AF_ERR_INVALID, "series_combined.lo and width must be given together");
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    if (S == 0 || pitch < S || pitch % 4u) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    const auto is_ram = [&](uint32_t j) { return j >= n_edges && (j - n_edges) % 3u == 2u; };
+    std::vector<afsc::Combo> combos(Cn);
+    uint32_t max_cols = 0;
+    if (req->col_start[0] != 0u) return fail(AF_ERR_INVALID, "series_combined.col_start must begin at 0");
+    for (uint32_t c = 0; c < Cn; ++c) {
+        const std::string who = "combination " + std::to_string(c);
+        const uint32_t c0 = req->col_start[c], c1 = req->col_start[c + 1u];
+        if (req->op[c] > AF_COMBINE_SPREAD) return fail(AF_ERR_INVALID, who + " has an unknown op (" + std::to_string(req->op[c]) + ")");
+        if (c1 <= c0) return fail(AF_ERR_INVALID, who + " has no columns");
+        for (uint32_t k = c0; k < c1; ++k) {
+            if (req->cols[k] >= S) return fail(AF_ERR_INVALID, who + " names series " + std::to_string(req->cols[k]) + " of " + std::to_string(S));
+            if (k > c0 && !(req->cols[k - 1u] < req->cols[k])) return fail(AF_ERR_INVALID, who + ": the columns must be strictly increasing");
+            if (is_ram(req->cols[k]) != is_ram(req->cols[c0])) return fail(AF_ERR_INVALID, who + " mixes ram_in_use columns with integer series");
+        }
+        if (req->thresholds && std::isnan(req->thresholds[c])) return fail(AF_ERR_INVALID, "threshold of " + who + " is NaN");
+        if (req->lo) {
+            if (!std::isfinite(req->lo[c])) return fail(AF_ERR_INVALID, "lo of " + who + " is not finite");
+            if (!(std::isfinite(req->width[c]) && req->width[c] > 0.0)) return fail(AF_ERR_INVALID, "width of " + who + " is not a finite number above 0");
+        }
+        combos[c] = afsc::Combo{req->op[c], c0, c1, is_ram(req->cols[c0]) ? 1u : 0u, req->thresholds ? req->thresholds[c] : 0.0,
+                                req->lo ? req->lo[c] : 0.0, req->width ? req->width[c] : 1.0};
+        max_cols = std::max(max_cols, c1 - c0);
+    }
+    const uint32_t n_cols = req->col_start[Cn];
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->samples || cap == 0) return fail(AF_ERR_INVALID, "series combinations need outputs.samples");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp;
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    // the groups' members, ascending; may a cell reach 2^32 rows, or its rows times the longest column list?
+    std::vector<uint32_t> mem_off((size_t)G + 1u, 0u), members;
+    std::vector<uint64_t> g_ticks(G, 0u);
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = grp.empty() ? 0u : grp[s];
+        if (g == afsc::kSkip) continue;
+        mem_off[(size_t)g + 1u] += 1u;
+        g_ticks[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+    }
+    bool direct = true;
+    for (uint32_t g = 0; g < G; ++g) {
+        if (mem_off[(size_t)g + 1u] > 1u) direct = false;
+        mem_off[(size_t)g + 1u] += mem_off[g];
+    }
+    members.resize(std::max<size_t>(mem_off[G], 1u));
+    {
+        std::vector<uint32_t> cursor(mem_off.begin(), mem_off.end() - 1);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = grp.empty() ? 0u : grp[s];
+            if (g != afsc::kSkip) members[cursor[g]++] = s;
+        }
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+        if (g_ticks[g] * max_cols <= 0xFFFFFFFFull) continue;   // (no window of the group can reach either limit)
+        for (uint32_t w = 0; w < W; ++w) {
+            uint64_t c = 0;
+            for (uint32_t k = mem_off[g]; k < mem_off[(size_t)g + 1u]; ++k) {
+                const uint32_t m = std::min(counts[(size_t)members[k] * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+                c += std::min(req->tick_edges[w + 1u], m) - std::min(req->tick_edges[w], m);
+            }
+            if (c > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more samples");
+            if (c * max_cols > 0xFFFFFFFFull)
+                return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + ": its rows times the longest column list reach 2^32");
+        }
+    }
+    // scratch layout (256-byte aligned parts)
+    ScratchLayout lay;
+    const size_t R = direct ? 0u : (size_t)n * W * Cn;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u), o_combo = lay.part((size_t)Cn * sizeof(afsc::Combo)), o_cols = lay.part((size_t)n_cols * 4u),
+                 o_off = lay.part(((size_t)G + 1u) * 4u), o_mem = lay.part(members.size() * 4u), o_sum = lay.part(R * 8u), o_comp = lay.part(R * 8u),
+                 o_min = lay.part(R * 8u), o_max = lay.part(R * 8u), o_above = lay.part(R * 4u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    unsigned char* b = e->d_pool;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(b + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_combo, combos.data(), (size_t)Cn * sizeof(afsc::Combo), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_cols, req->cols, (size_t)n_cols * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_off, mem_off.data(), mem_off.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_mem, members.data(), members.size() * 4u, hipMemcpyHostToDevice, st));
+    const size_t cells = (size_t)G * W;
+    if (B) {
+        HIP_TRY(hipMemsetAsync(req->hist, 0, cells * Cn * B * 4u, st));
+        if (req->under) HIP_TRY(hipMemsetAsync(req->under, 0, cells * Cn * 4u, st));
+        if (req->over) HIP_TRY(hipMemsetAsync(req->over, 0, cells * Cn * 4u, st));
+    }
+    afsc::ScArgs a{};
+    a.samples = out->samples;
+    a.counts = out->counts;
+    a.tick_cap = cap;
+    a.pitch = pitch;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.group = req->group;
+    a.n_scen = n;
+    a.n_groups = G;
+    a.n_win = W;
+    a.direct = direct ? 1u : 0u;
+    a.edges = reinterpret_cast<const uint32_t*>(b + o_edges);
+    a.n_combos = Cn;
+    a.n_bins = B;
+    a.per = std::max(1u, std::min(afsc::kPer, afsc::kWaveLdsWords / (B + 2u)));
+    a.combos = reinterpret_cast<const afsc::Combo*>(b + o_combo);
+    a.cols = reinterpret_cast<const uint32_t*>(b + o_cols);
+    a.mem_off = reinterpret_cast<const uint32_t*>(b + o_off);
+    a.members = reinterpret_cast<const uint32_t*>(b + o_mem);
+    a.rec_sum = reinterpret_cast<unsigned long long*>(b + o_sum);
+    a.rec_comp = reinterpret_cast<double*>(b + o_comp);
+    a.rec_min = reinterpret_cast<unsigned long long*>(b + o_min);
+    a.rec_max = reinterpret_cast<unsigned long long*>(b + o_max);
+    a.rec_above = reinterpret_cast<uint32_t*>(b + o_above);
+    a.count = req->count;
+    a.mean = req->mean;
+    a.minv = req->minv;
+    a.maxv = req->maxv;
+    a.above = req->above;
+    a.hist = req->hist;
+    a.under = req->under;
+    a.over = req->over;
+    // a wave per (scenario, run of windows): runs as long as leave the chip some 32 768 waves (af_engine_summarize_series_windows' rule)
+    const uint32_t want_runs = (32768u + n - 1u) / n;
+    a.run = std::max(1u, W / want_runs);
+    const uint64_t items = (uint64_t)n * ((W + a.run - 1u) / a.run);
+    const size_t lds = B ? (size_t)afsc::kWaves * a.per * (B + 2u) * 4u : 0u;
+    hipLaunchKernelGGL(afsc::af_scomb_partial, dim3((uint32_t)((items + afsc::kWaves - 1u) / afsc::kWaves)), dim3(afsc::kThreads), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    if (!direct || mem_off[G] < G) {   // the members' fold; after a direct pass only the cells of groups without a member
+        const uint64_t entries = (uint64_t)G * W * Cn;
+        for (uint64_t f = 0; f < entries; f += kBlocksPerLaunch * afsc::kReduceThreads) {
+            const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (entries - f + afsc::kReduceThreads - 1u) / afsc::kReduceThreads);
+            hipLaunchKernelGGL(afsc::af_scomb_reduce, dim3((uint32_t)blocks), dim3(afsc::kReduceThreads), 0, st, a, f, entries);
+            HIP_TRY(hipGetLastError());
+        }
+    }
     HIP_TRY(hipStreamSynchronize(st));   // (the host vectors are read by the copies until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();

@@ -520,6 +520,51 @@ class Engine:
                "af_engine_summarize_series_histogram")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_series_combined(self, n: int, n_groups: int, tick_edges: Any, ops: Any, columns: Any, *, samples_ptr: int,
+                                  tick_capacity: int, counts_ptr: int, mean_ptr: int, count_ptr: int = 0, min_ptr: int = 0,
+                                  max_ptr: int = 0, above_ptr: int = 0, hist_ptr: int = 0, under_ptr: int = 0, over_ptr: int = 0,
+                                  group_ptr: int = 0, thresholds: Any = None, bins: int = 0, lo: Any = None,
+                                  width: Any = None) -> tuple[float, int]:
+        """Combinations across the series on the device (``af_engine_summarize_series_combined``): combination ``c`` is
+        ``ops[c]`` (an ``AF_COMBINE_*`` code) over the series ``columns[c]`` (strictly increasing indices, all integer
+        series or all ``ram_in_use`` columns) of one sample row.  Per (group, window of ticks) ``count`` uint32 [n_groups, W]
+        and per combination ``mean``, ``min``, ``max`` float64 and ``above`` uint32 [n_groups, W, C]; with ``bins`` above 0
+        also ``hist`` uint32 [n_groups, W, C, bins] and ``under`` / ``over`` uint32 [n_groups, W, C].  A pointer of 0 skips
+        every output but ``mean``.  ``tick_edges``: HOST uint32 tick indices, strictly increasing; ``thresholds``, ``lo``,
+        ``width``: HOST float64 [C] or None (0.0, 0.0 and 1.0 each).  ``group_ptr`` as in :meth:`summarize_pooled`.
+        The library checks the combinations.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_series_bins, check_tick_edges
+
+        b = check_tick_edges(tick_edges)
+        op = np.ascontiguousarray(ops, dtype=np.uint32).reshape(-1)
+        lists = [np.ascontiguousarray(c, dtype=np.uint32).reshape(-1) for c in columns]
+        if len(lists) != op.shape[0]:
+            msg = f"{op.shape[0]} ops for {len(lists)} column lists"
+            raise ValueError(msg)
+        n_c = int(op.shape[0])
+        start = np.ascontiguousarray(np.concatenate([[0], np.cumsum([x.shape[0] for x in lists])]), dtype=np.uint32)
+        cols = np.ascontiguousarray(np.concatenate(lists) if lists else np.zeros(0), dtype=np.uint32)
+        pd, pu = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+        thr = None if thresholds is None else np.ascontiguousarray(thresholds, dtype=np.float64)
+        if thr is not None and thr.shape != (n_c,):
+            msg = f"thresholds must be one value per combination ({n_c}), not of shape {thr.shape}"
+            raise ValueError(msg)
+        n_bins, lo_v, width_v = 0, None, None
+        if bins or lo is not None or width is not None:
+            n_bins, lo_v, width_v = check_series_bins(bins, n_c, lo, width)
+        plain = lo is None and width is None
+        out = _abi.AfOutputs(0, None, int(tick_capacity), C.c_void_p(samples_ptr or None), C.c_void_p(counts_ptr or None))
+        req = _abi.AfSeriesCombined(int(n), int(n_groups), int(b.shape[0] - 1), C.c_void_p(group_ptr or None), b.ctypes.data_as(pu),
+                                    n_c, op.ctypes.data_as(pu), start.ctypes.data_as(pu), cols.ctypes.data_as(pu),
+                                    None if thr is None else thr.ctypes.data_as(pd), n_bins,
+                                    None if plain else lo_v.ctypes.data_as(pd), None if plain else width_v.ctypes.data_as(pd),
+                                    C.c_void_p(count_ptr or None), C.c_void_p(mean_ptr or None), C.c_void_p(min_ptr or None),
+                                    C.c_void_p(max_ptr or None), C.c_void_p(above_ptr or None), C.c_void_p(hist_ptr or None),
+                                    C.c_void_p(under_ptr or None), C.c_void_p(over_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_series_combined(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_series_combined")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:
         """``af_engine_gather``: ONE grouped RCCL all-gather of the per-scenario summaries.

@@ -681,6 +681,205 @@ def series_histogram_quantiles(summary: dict[str, Any], levels: Any) -> np.ndarr
     return out
 
 
+COMBINE_OPS = ("sum", "min", "max", "spread")
+
+
+def check_series_combinations(combos: Any, names: list[str], n_edges: int) -> tuple[list[str], list[str], list[np.ndarray]]:
+    """The combinations of a series-combined call as ``(labels, ops, columns)``: ``combos`` is ``{label: (op, selection)}``
+    (or an iterable of ``(label, (op, selection))`` pairs), ``op`` one of ``"sum"``, ``"min"``, ``"max"``, ``"spread"`` and
+    ``selection`` a list of series names of ``names`` or of indices, ONE ``fnmatch`` pattern over ``names`` (such as
+    ``"*:ready_queue_len"``) or a list of such patterns.  ``columns[c]`` is the selection as strictly increasing int64
+    series indices.  ValueError for no combination or more than ``AF_MAX_SERIES_COMBINATIONS`` (64), an unknown op, a
+    duplicate label, a selection that matches no series, names a series twice or is out of range, and one that mixes
+    ``ram_in_use`` columns with integer series."""
+    import fnmatch
+
+    items = list(combos.items()) if isinstance(combos, dict) else [(k, v) for k, v in combos]
+    if not 1 <= len(items) <= _abi.MAX_SERIES_COMBINATIONS:
+        msg = f"a call takes 1 .. {_abi.MAX_SERIES_COMBINATIONS} combinations, not {len(items)}"
+        raise ValueError(msg)
+    ram = ram_columns(len(names), n_edges)
+    labels: list[str] = []
+    ops: list[str] = []
+    columns: list[np.ndarray] = []
+    for label, spec in items:
+        label = str(label)
+        if label in labels:
+            msg = f"combination {label!r} is given twice"
+            raise ValueError(msg)
+        if not isinstance(spec, (tuple, list)) or len(spec) != 2:
+            msg = f"combination {label!r} must be (op, selection), not {spec!r}"
+            raise ValueError(msg)
+        op, selection = spec
+        if op not in COMBINE_OPS:
+            msg = f"combination {label!r}: unknown op {op!r} (one of {COMBINE_OPS})"
+            raise ValueError(msg)
+        sel = [selection] if isinstance(selection, (str, bytes)) else list(np.asarray(selection).tolist() if isinstance(selection, np.ndarray) else selection)
+        picked: list[int] = []
+        patterns = False
+        for x in sel:
+            x = x.decode() if isinstance(x, bytes) else x
+            if isinstance(x, str) and any(ch in x for ch in "*?["):
+                hit = [j for j, nm in enumerate(names) if fnmatch.fnmatchcase(nm, x)]
+                if not hit:
+                    msg = f"combination {label!r}: pattern {x!r} matches no series (series_names(): {names})"
+                    raise ValueError(msg)
+                patterns = True
+                picked += hit
+            elif isinstance(x, str):
+                if x not in names:
+                    msg = f"combination {label!r}: unknown series {x!r} (series_names(): {names})"
+                    raise ValueError(msg)
+                picked.append(names.index(x))
+            elif isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < len(names):
+                msg = f"combination {label!r}: {x!r} is no series name, pattern or index below {len(names)}"
+                raise ValueError(msg)
+            else:
+                picked.append(int(x))
+        if patterns:
+            picked = sorted(set(picked))                 # (two patterns may match one series: their union)
+        if not picked:
+            msg = f"combination {label!r} selects no series"
+            raise ValueError(msg)
+        if len(set(picked)) != len(picked):
+            msg = f"combination {label!r} names a series twice"
+            raise ValueError(msg)
+        col = np.array(sorted(picked), dtype=np.int64)
+        if ram[col].any() and not ram[col].all():
+            msg = f"combination {label!r} mixes ram_in_use columns with integer series"
+            raise ValueError(msg)
+        labels.append(label)
+        ops.append(op)
+        columns.append(col)
+    return labels, ops, columns
+
+
+def _double_keys(x: np.ndarray) -> np.ndarray:
+    """uint64 keys that order like the float64 values ``x`` (no NaN) with -0.0 below +0.0: the IEEE total order."""
+    bits = np.ascontiguousarray(x, dtype=np.float64).view(np.uint64)
+    return np.where(bits >> np.uint64(63) != 0, ~bits, bits | np.uint64(1 << 63))
+
+
+def _combination_columns(op: str, columns: Any, n_series: int, n_edges: int) -> tuple[np.ndarray, bool]:
+    if op not in COMBINE_OPS:
+        msg = f"unknown op {op!r} (one of {COMBINE_OPS})"
+        raise ValueError(msg)
+    col = np.asarray(columns)
+    if col.ndim != 1 or col.shape[0] == 0 or col.dtype.kind not in "iu":
+        msg = "the columns of a combination must be a non-empty vector of series indices"
+        raise ValueError(msg)
+    col = col.astype(np.int64)
+    if col[0] < 0 or col[-1] >= n_series or not (np.diff(col) > 0).all():
+        msg = f"the columns of a combination must be strictly increasing series indices below {n_series}"
+        raise ValueError(msg)
+    ram = ram_columns(n_series, n_edges)[col]
+    if ram.any() and not ram.all():
+        msg = "a combination mixes ram_in_use columns with integer series"
+        raise ValueError(msg)
+    return col, bool(ram.all())
+
+
+def series_combined_values(samples: np.ndarray, n_edges: int, op: str, columns: Any) -> np.ndarray:
+    """The per-tick values of ONE combination ``(op, columns)`` across the sampled series of ONE scenario (``samples``:
+    uint32 words [n_series, ticks]): ``columns`` strictly increasing series indices, all integer series or all
+    ``ram_in_use`` columns.  Integer columns: the words as unsigned 32-bit integers, ``sum`` their exact sum, ``min`` /
+    ``max`` the smallest / largest word, ``spread`` their difference, as uint64 [ticks].  ``ram_in_use`` columns: every word
+    as the float64 of its float32 value; ``sum`` is added in ascending series index, left to right from the first column's
+    value, one rounding per addition (an explicit loop); ``min`` / ``max`` follow the IEEE total order (-0.0 below +0.0);
+    ``spread`` is ``max - min`` as one float64 subtraction; float64 [ticks]."""
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    col, is_ram = _combination_columns(op, columns, words.shape[0], n_edges)
+    if not is_ram:
+        w = words[col].astype(np.uint64)
+        if op == "sum":
+            acc = np.zeros(words.shape[1], dtype=np.uint64)
+            for row in w:
+                acc = acc + row                           # (at most 2^32 columns below 2^32: no wrap)
+            return acc
+        return w.min(axis=0) if op == "min" else w.max(axis=0) if op == "max" else w.max(axis=0) - w.min(axis=0)
+    x = words[col].view(np.float32).astype(np.float64)
+    if op == "sum":
+        acc = x[0].copy()
+        for row in x[1:]:                                 # (left to right: np.sum's order is not fixed)
+            acc = acc + row
+        return acc
+    keys = _double_keys(x)
+    tick = np.arange(x.shape[1])
+    mn, mx = x[np.argmin(keys, axis=0), tick], x[np.argmax(keys, axis=0), tick]
+    return mn if op == "min" else mx if op == "max" else mx - mn
+
+
+def series_combined_window_stats(samples: np.ndarray, tick_edges: Any, n_edges: int, combos: Any, thresholds: Any = None,
+                                 bins: int = 0, lo: Any = None, width: Any = None) -> dict[str, np.ndarray]:
+    """Statistics per window of ticks of combinations ACROSS the sampled series of ONE scenario (``samples``: uint32 words
+    [n_series, ticks]); the windows are :func:`series_window_stats`'s.  ``combos`` is a sequence of ``(op, columns)`` pairs
+    (:func:`check_series_combinations` makes them); ``v`` = :func:`series_combined_values` per tick and ``x`` = ``v`` as
+    float64.  Returns ``count`` int64 [W]; ``mean`` float64 [W, C] -- an integer combination: the exact integer sum of
+    ``v`` over the window, ``float(S) / float(count)``; a ``ram_in_use`` one: ``math.fsum(v) / count`` --; ``min`` / ``max``
+    float64 [W, C], the smallest / largest ``x`` in the IEEE total order (-0.0 below +0.0); ``above`` int64 [W, C], the
+    ticks with ``x > thresholds[c]`` (None: 0.0 each).  An empty window has NaN in the three float outputs and 0 in
+    ``above``.  With ``bins`` above 0 also ``hist`` int64 [W, C, bins], ``under``, ``over`` [W, C] by the rule of
+    :func:`series_window_histogram` on ``x`` with ``lo[c]``, ``width[c]`` (:func:`check_series_bins`), ``bin_edges``
+    float64 [C, bins + 1] and ``ram`` bool [C], so :func:`series_histogram_quantiles` reads exact quantiles of an integer
+    combination off the result.  The definition the device analyzer (``af_engine_summarize_series_combined``) matches:
+    bit for bit, but for the ``mean`` of a ``ram_in_use`` combination whose partial sums are not exact, which lies within
+    ``(count - 1) * 2^-53`` relative of it."""
+    import math
+
+    b = check_tick_edges(tick_edges)
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    n_series, ticks = words.shape
+    pairs = [(op, _combination_columns(op, col, n_series, n_edges)) for op, col in combos]
+    n_c = len(pairs)
+    if not 1 <= n_c <= _abi.MAX_SERIES_COMBINATIONS:
+        msg = f"a call takes 1 .. {_abi.MAX_SERIES_COMBINATIONS} combinations, not {n_c}"
+        raise ValueError(msg)
+    thr = np.zeros(n_c) if thresholds is None else np.asarray(thresholds, dtype=np.float64)
+    if thr.shape != (n_c,) or np.isnan(thr).any():
+        msg = f"thresholds must be {n_c} values, none of them NaN"
+        raise ValueError(msg)
+    n_bins = 0
+    if bins or lo is not None or width is not None:
+        n_bins, lo_v, width_v = check_series_bins(bins, n_c, lo, width)
+    n_win = b.shape[0] - 1
+    r = np.minimum(b.astype(np.int64), ticks)
+    count = np.diff(r)
+    mean, mn, mx = (np.full((n_win, n_c), np.nan) for _ in range(3))
+    above = np.zeros((n_win, n_c), dtype=np.int64)
+    hist = np.zeros((n_win, n_c, n_bins), dtype=np.int64)
+    under, over = (np.zeros((n_win, n_c), dtype=np.int64) for _ in range(2))
+    for c, (op, (col, is_ram)) in enumerate(pairs):
+        v = series_combined_values(words, n_edges, op, col)
+        x = v.astype(np.float64)
+        keys = _double_keys(x)
+        for w in range(n_win):
+            if count[w] == 0:
+                continue
+            seg, xs, ks = v[r[w]:r[w + 1]], x[r[w]:r[w + 1]], keys[r[w]:r[w + 1]]
+            total = 0.0 + math.fsum(seg.tolist()) if is_ram else float(sum(int(t) for t in seg.tolist()))
+            mean[w, c] = total / float(count[w])
+            mn[w, c], mx[w, c] = xs[np.argmin(ks)], xs[np.argmax(ks)]
+            above[w, c] = int((xs > thr[c]).sum())
+            if n_bins:
+                below = xs < lo_v[c]
+                t = (xs - lo_v[c]) / width_v[c]
+                past = ~below & (t >= float(n_bins))
+                inside = ~below & ~past
+                under[w, c], over[w, c] = int(below.sum()), int(past.sum())
+                hist[w, c] = np.bincount(t[inside].astype(np.int64), minlength=n_bins)
+    out = {"count": count, "mean": mean, "min": mn, "max": mx, "above": above}
+    if n_bins:
+        out.update(hist=hist, under=under, over=over, ram=np.array([p[1][1] for p in pairs], dtype=bool),
+                   bin_edges=lo_v[:, None] + np.arange(n_bins + 1, dtype=np.float64)[None, :] * width_v[:, None])
+    return out
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -884,6 +1083,24 @@ class ScenarioResults:
         col = _check_series_columns(series, int(np.asarray(self._samples).shape[0]))
         out: dict[str, Any] = series_window_histogram(self._samples, b, self._plan.n_edges, bins, col, lo, width)
         out.update(series=col, tick_edges=b)
+        return out
+
+    def get_series_combined(self, combos: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                            tick_edges: Any = None, thresholds: Any = None, bins: int = 0, lo: Any = None,
+                            width: Any = None) -> dict[str, Any]:
+        """Combinations across the sampled series per window of ticks (:func:`series_combined_window_stats`): ``combos`` is
+        ``{label: (op, selection)}`` over :func:`series_names_of` (:func:`check_series_combinations`), such as
+        ``{"imbalance": ("spread", "*:ready_queue_len")}``.  Returns ``count`` [W], ``mean``, ``min``, ``max``, ``above``
+        [W, C], with ``bins`` the histogram outputs, and ``names``, ``ops``, ``columns`` and ``tick_edges``.  Windows as in
+        :meth:`get_series_window_stats`; ``thresholds``: None (0.0) or one value per combination."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        labels, ops, columns = check_series_combinations(combos, series_names_of(self._plan), self._plan.n_edges)
+        out: dict[str, Any] = series_combined_window_stats(self._samples, b, self._plan.n_edges, list(zip(ops, columns)), thresholds,
+                                                           bins, lo, width)
+        out.update(names=labels, ops=ops, columns=columns, tick_edges=b)
         return out
 
     def get_latency_by_state(self, series: Any, bins: int = 8, lo: float = 0.0, width: float = 1.0, window_s: float | None = None,
@@ -2102,6 +2319,159 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    def _combined_thresholds(self, thresholds: Any, labels: list[str]) -> np.ndarray | None:
+        """``thresholds`` of a combined call -- None, one value per combination or ``{label: value}`` (missing: 0.0)."""
+        if thresholds is None:
+            return None
+        if isinstance(thresholds, dict):
+            for k in thresholds:
+                if k not in labels:
+                    msg = f"unknown combination {k!r} in thresholds (combinations: {labels})"
+                    raise ValueError(msg)
+            thr = np.array([float(thresholds.get(k, 0.0)) for k in labels], dtype=np.float64)
+        else:
+            thr = np.asarray(thresholds, dtype=np.float64)
+        if thr.shape != (len(labels),) or np.isnan(thr).any():
+            msg = f"thresholds must be one value per combination ({len(labels)}) or a dict, none of them NaN"
+            raise ValueError(msg)
+        return thr
+
+    def series_combined_summary(self, combos: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                                tick_edges: Any = None, by: Any = None, thresholds: Any = None, bins: int = 0, lo: Any = None,
+                                width: Any = None) -> dict[str, Any]:
+        """Combinations ACROSS the sampled series per tick -- the RAM of the whole fleet, the requests queued on all servers,
+        the imbalance (max - min) between the servers' queues -- and their statistics per (group, window of ticks), over all
+        scenarios of the group.  ``combos`` is ``{label: (op, selection)}``: ``op`` one of ``"sum"``, ``"min"``, ``"max"``,
+        ``"spread"``; ``selection`` series names or indices, one ``fnmatch`` pattern over :meth:`series_names` or a list of
+        patterns (:func:`check_series_combinations`).  Computed by the HIP analyzer
+        ``af_engine_summarize_series_combined`` in one pass over the sample rows, equal to
+        :func:`series_combined_window_stats` of the group's scenarios taken together.  Windows and ``by`` as in
+        :meth:`series_window_summary`; ``thresholds``: None (0.0), one value per combination or ``{label: value}``;
+        ``bins`` above 0 adds occupancy histograms of the per-tick values with ``lo`` / ``width`` (None: 0.0 / 1.0, a scalar
+        or one value per combination).  Returns torch tensors on the run's device: ``count`` int64 [G, W]; ``mean``,
+        ``min``, ``max`` and ``above_share`` float64 [G, W, C], NaN in empty cells; ``above`` int64 [G, W, C]; with ``bins``
+        ``hist`` int64 [G, W, C, bins], ``under``, ``over`` [G, W, C], ``bin_edges`` float64 [C, bins + 1] and ``ram``
+        bool [C], which :func:`series_histogram_quantiles` reads exact quantiles of an integer combination off; and
+        ``names``, ``ops``, ``columns``, ``tick_edges``, ``times``, ``replicas`` [G], ``series_combined_ms``,
+        ``scratch_bytes``."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_samples()
+        labels, ops, columns = check_series_combinations(combos, self.series_names(), self.plan.n_edges)
+        n_c = len(labels)
+        thr = self._combined_thresholds(thresholds, labels)
+        n_bins = 0
+        if bins or lo is not None or width is not None:
+            n_bins, lo_v, width_v = check_series_bins(bins, n_c, lo, width)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        n_win = int(b.shape[0] - 1)
+        samples = self._samples_t
+        dev = samples.device
+        count = torch.empty((n_groups, n_win), dtype=torch.int32, device=dev)
+        mean, mn, mx = (torch.empty((n_groups, n_win, n_c), dtype=torch.float64, device=dev) for _ in range(3))
+        ab = torch.empty((n_groups, n_win, n_c), dtype=torch.int32, device=dev)
+        hist = under = over = None
+        if n_bins:
+            hist = torch.empty((n_groups, n_win, n_c, n_bins), dtype=torch.int32, device=dev)
+            under, over = (torch.empty((n_groups, n_win, n_c), dtype=torch.int32, device=dev) for _ in range(2))
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_series_combined(
+            len(self), n_groups, b, [_abi.COMBINE_OPS[o] for o in ops], columns, samples_ptr=samples.data_ptr(),
+            tick_capacity=int(samples.shape[1]), counts_ptr=self._counts_t.data_ptr(), mean_ptr=mean.data_ptr(),
+            count_ptr=count.data_ptr(), min_ptr=mn.data_ptr(), max_ptr=mx.data_ptr(), above_ptr=ab.data_ptr(),
+            hist_ptr=hist.data_ptr() if n_bins else 0, under_ptr=under.data_ptr() if n_bins else 0,
+            over_ptr=over.data_ptr() if n_bins else 0, group_ptr=grp.data_ptr(), thresholds=thr, bins=n_bins,
+            lo=lo_v if n_bins and not (lo is None and width is None) else None,
+            width=width_v if n_bins and not (lo is None and width is None) else None)
+        cnt = count.to(torch.int64) & 0xFFFFFFFF
+        above = ab.to(torch.int64) & 0xFFFFFFFF
+        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+        share = torch.where((cnt == 0)[:, :, None], nan, above.to(torch.float64) / cnt.to(torch.float64)[:, :, None])
+        ram = ram_columns(self.plan.n_series, self.plan.n_edges)
+        out = {"count": cnt, "mean": mean, "min": mn, "max": mx, "above": above, "above_share": share}
+        if n_bins:
+            out.update(hist=hist.to(torch.int64) & 0xFFFFFFFF, under=under.to(torch.int64) & 0xFFFFFFFF,
+                       over=over.to(torch.int64) & 0xFFFFFFFF,
+                       bin_edges=lo_v[:, None] + np.arange(n_bins + 1, dtype=np.float64)[None, :] * width_v[:, None],
+                       ram=np.array([bool(ram[c[0]]) for c in columns], dtype=bool))
+        out.update(names=labels, ops=ops, columns=columns, tick_edges=b, times=b[:-1].astype(np.float64) * self.plan.sample_period,
+                   replicas=np.bincount(ids[ids >= 0], minlength=n_groups), series_combined_ms=ms, scratch_bytes=scratch)
+        return out
+
+    def series_combined_bands(self, combos: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                              tick_edges: Any = None, by: Any = None, thresholds: Any = None, of: str = "mean",
+                              level: float = 0.95, q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of a windowed statistic ``of`` (``"mean"``, ``"max"``, ``"min"`` or ``"above_share"``) of
+        the combinations: every scenario's own window values (``series_combined_summary(by="scenario")``), then per group
+        (``by``) and window, over the group's replicas whose window is not empty, what :meth:`series_window_bands` gives --
+        numpy float64 [G, W, C] each (:func:`window_bands_by_group`); ``pooled`` is the grouped call's value of the same
+        statistic."""
+        if of not in ("mean", "max", "min", "above_share"):
+            msg = f"of must be 'mean', 'max', 'min' or 'above_share', not {of!r}"
+            raise ValueError(msg)
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        return self._series_combined_bands(combos, b, by, thresholds, of, level, q)[0]
+
+    def _series_combined_bands(self, combos: Any, b: np.ndarray, by: Any, thresholds: Any, of: str, level: float,
+                               q: tuple[float, float], **hist: Any) -> tuple[dict[str, Any], dict[str, Any]]:
+        """:meth:`series_combined_bands` for resolved tick edges; also returns the grouped summary its ``pooled`` is from."""
+        ids, n_groups = self._window_groups(by)
+        per = self.series_combined_summary(combos, tick_edges=b, by="scenario", thresholds=thresholds)
+        out = window_bands_by_group(per[of], ids, n_groups, level, q, valid=per["count"] > 0)
+        pooled = self.series_combined_summary(combos, tick_edges=b, by=ids, thresholds=thresholds, **hist)
+        out["pooled"] = pooled[of].cpu().numpy()[:n_groups]
+        out.update(of=of, names=per["names"], ops=per["ops"], columns=per["columns"], tick_edges=b, times=per["times"])
+        return out, pooled
+
+    def save_series_combined_summary(self, path: str, by: Any = None, *, combos: Any, window_s: float | None = None,
+                                     ticks_per_window: int | None = None, tick_edges: Any = None, thresholds: Any = None,
+                                     bins: int = 0, lo: Any = None, width: Any = None, level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the combinations' statistics with one row per group (grid point): ``param:<axis>`` (for a
+        Sweep), ``replicas``, ``series_combined_count`` [G, W] and per combination the [G, W] columns
+        ``series_combined_mean:<label>``, ``series_combined_min:<label>``, ``series_combined_max:<label>``,
+        ``series_combined_above:<label>`` (the share above the threshold) -- the group's replicas taken together -- and
+        ``series_combined_q05:<label>`` / ``series_combined_q95:<label>`` (of the replicas' own means,
+        :meth:`series_combined_bands`); with ``bins`` also ``series_combined_hist:<label>`` [G, W, bins],
+        ``series_combined_under:<label>``, ``series_combined_over:<label>`` [G, W] and the per-file vector
+        ``series_combined_bin_edges:<label>`` [bins + 1].  ``series_combined_tick_edges`` [W + 1] and
+        ``series_combined_times`` [W] are per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        hist_kw = {"bins": bins, "lo": lo, "width": width} if bins or lo is not None or width is not None else {}
+        bands, pooled = self._series_combined_bands(combos, b, by, thresholds, "mean", level, (0.05, 0.95), **hist_kw)
+        n_groups = int(bands["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        cols["series_combined_count"] = np.ascontiguousarray(pooled["count"].cpu().numpy()[:n_groups], dtype=np.int64)
+        stat = {k: pooled[k].cpu().numpy()[:n_groups] for k in ("mean", "min", "max", "above_share")}
+        tables = {k: pooled[k].cpu().numpy()[:n_groups] for k in ("hist", "under", "over")} if "hist" in pooled else {}
+        for c, name in enumerate(bands["names"]):
+            cols[f"series_combined_mean:{name}"] = np.ascontiguousarray(stat["mean"][:, :, c])
+            cols[f"series_combined_min:{name}"] = np.ascontiguousarray(stat["min"][:, :, c])
+            cols[f"series_combined_max:{name}"] = np.ascontiguousarray(stat["max"][:, :, c])
+            cols[f"series_combined_above:{name}"] = np.ascontiguousarray(stat["above_share"][:, :, c])
+            cols[f"series_combined_q05:{name}"] = np.ascontiguousarray(bands["q_lo"][:, :, c])
+            cols[f"series_combined_q95:{name}"] = np.ascontiguousarray(bands["q_hi"][:, :, c])
+            if tables:
+                cols[f"series_combined_hist:{name}"] = np.ascontiguousarray(tables["hist"][:, :, c], dtype=np.int64)
+                cols[f"series_combined_under:{name}"] = np.ascontiguousarray(tables["under"][:, :, c], dtype=np.int64)
+                cols[f"series_combined_over:{name}"] = np.ascontiguousarray(tables["over"][:, :, c], dtype=np.int64)
+                cols[f"series_combined_bin_edges:{name}"] = np.ascontiguousarray(pooled["bin_edges"][c], dtype=np.float64)
+        cols["series_combined_tick_edges"] = np.asarray(b, dtype=np.float64)
+        cols["series_combined_times"] = np.asarray(bands["times"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -2526,6 +2896,18 @@ class ShardedResults:
 
     def save_series_histogram_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_histogram_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_combined_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_combined_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_combined_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_combined_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_series_combined_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_series_combined_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
     def state_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:

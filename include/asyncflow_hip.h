@@ -649,6 +649,82 @@ typedef struct af_series_histogram {
 } af_series_histogram_t;
 int af_engine_summarize_series_histogram(af_engine_t* engine, const af_outputs_t* out, af_series_histogram_t* series_histogram);
 
+/* COMBINATIONS ACROSS THE SAMPLED SERIES per tick, then per window of ticks and group, on the device
+ * (asyncflow_amd/csrc/af_series_combined.hpp): the RAM the whole fleet holds at its peak (the peak of a sum is not the sum of
+ * the peaks), the requests queued across all servers during an outage, the imbalance (max - min) of the servers' queues under
+ * a load-balancing algorithm, the connections open on the edges that end at one node.
+ * A COMBINATION c is (op[c], columns cols[col_start[c] .. col_start[c + 1] - 1]): op is AF_COMBINE_SUM, _MIN, _MAX or _SPREAD;
+ * the columns are a non-empty, strictly increasing list of series indices < af_series_count, either all integer series or all
+ * ram_in_use columns (index n_edges + 3 * server + 2).  At most AF_MAX_SERIES_COMBINATIONS a call.
+ * Per-tick value v of combination c at sample row k of scenario s:
+ *     integer columns   the words as unsigned 32-bit integers: sum their exact sum (64 bits), min / max the smallest / largest
+ *                       word, spread max - min; all exact integers; as f64, x = (double)v
+ *     ram_in_use        each word is (double)(float)word: sum the f64 sum in ascending series index, left to right from the
+ *                       first column's value, one rounding per addition (the sum of -0.0s is -0.0); min / max in the IEEE total
+ *                       order on the non-NaN values with -0.0 below +0.0, the order af_series_windows_t uses; spread max - min
+ *                       as one f64 subtraction; x = v
+ * Cells: those of af_series_windows_t.  Window w of scenario s is its sample rows [min(b[w], m_s), min(b[w + 1], m_s)), with
+ * m_s = min(counts[s][AF_CNT_TICKS], tick_capacity); rows at or past m_s and the padding words of a row are never read.  Groups
+ * as in af_pooled_t, AF_POOL_SKIP for a scenario left out.
+ * Outputs per (g, w) and per (g, w, c):
+ *     count  u32 [G][W]      the rows in the cell
+ *     mean   f64 [G][W][C]   integer combination: the exact integer sum S of v over the cell (64 bits), then (double)S /
+ *                            (double)count, the conversion rounded to nearest even.  ram combination: the f64 sum of the v in
+ *                            the fixed order af_series_windows_t documents for a ram_in_use mean (within a scenario's window a
+ *                            lane's rows top down -- lane l of 64 takes rows l, l + 64, ... of the window --, then a fixed tree
+ *                            over the lanes; across the members ascending scenario index) with the rounding errors of the
+ *                            additions carried along and added back once (a compensated sum), divided once: bit-equal to
+ *                            fsum(v) / count whenever every partial sum is exact, otherwise within (count - 1) * 2^-53
+ *                            relative of it
+ *     minv, maxv  f64 [G][W][C]   the smallest / largest x of the cell in the same total order
+ *     above  u32 [G][W][C]   the rows with x > thresholds[c], compared as f64 (NULL thresholds: 0.0 each)
+ *     hist   u32 [G][W][C][n_bins], under, over u32 [G][W][C]   optional: n_bins == 0 with all three NULL skips them.  The bin
+ *                            of x follows af_series_histogram_t's rule bit for bit with lo[c], width[c] per combination (NULL,
+ *                            both: 0.0 and 1.0), and under + sum(hist) + over == count; n_bins <= AF_MAX_SERIES_HISTOGRAM_BINS
+ * An empty cell has count 0, mean, minv and maxv NaN and every integer output 0.  A NULL count, minv, maxv, above, under or
+ * over skips that output.
+ * Determinism: every integer output is combined with integer +, min and max only (integer atomics on zeroed outputs for the
+ * histogram); nothing depends on the launch, the batch a scenario sits in, the other combinations of the call, or the run.
+ * Refused, no output buffer touched: n_combos == 0 or above the cap, an unknown op, an empty, unsorted, duplicate or
+ * out-of-range column list, a list that mixes ram_in_use with integer series, a NaN threshold, the binning refusals of
+ * af_series_histogram_t -- n_bins above the cap, a width that is <= 0, NaN or infinite, a lo that is NaN or infinite, exactly
+ * one of lo / width NULL --, hist, under or over given with n_bins == 0 or n_bins > 0 without hist, tick_edges NULL or not strictly
+ * increasing or n_windows == 0, a group id >= n_groups, outputs.samples, outputs.counts or mean NULL (AF_ERR_INVALID); a cell
+ * of 2^32 or more rows, the longest column list times the rows of a cell at or above 2^32 (below that the 64-bit sums cannot
+ * overflow), n_groups * n_windows >= 2^32 - 1, tick_capacity >= 2^31 (AF_ERR_CAPACITY); a planning-only engine
+ * (AF_ERR_NO_DEVICE).  `out` needs samples, tick_capacity and counts; clock is not read.
+ * Scratch kept by the engine (shared with the other analyzers): 4 B per edge + 40 B per combination + 4 B per listed column +
+ * 4 B per group + 4 B per scenario + 2 560 B of alignment, and -- unless every group holds at most one scenario -- 36 B per
+ * (scenario, window, combination).  Synchronous; the struct is written back. */
+#define AF_MAX_SERIES_COMBINATIONS 64
+enum { AF_COMBINE_SUM = 0, AF_COMBINE_MIN = 1, AF_COMBINE_MAX = 2, AF_COMBINE_SPREAD = 3 };
+typedef struct af_series_combined {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing */
+    uint32_t n_combos;           /* 1 .. AF_MAX_SERIES_COMBINATIONS */
+    const uint32_t* op;          /* HOST [n_combos] AF_COMBINE_* */
+    const uint32_t* col_start;   /* HOST [n_combos + 1] offsets into cols, col_start[0] == 0 */
+    const uint32_t* cols;        /* HOST [col_start[n_combos]] series indices, strictly increasing within a combination */
+    const double* thresholds;    /* HOST [n_combos] or NULL (0.0 each) */
+    uint32_t n_bins;             /* 0 (no histogram) .. AF_MAX_SERIES_HISTOGRAM_BINS */
+    const double* lo;            /* HOST [n_combos] finite; NULL (with width): 0.0 each */
+    const double* width;         /* HOST [n_combos] finite and > 0; NULL (with lo): 1.0 each */
+    uint32_t* count;             /* DEVICE [n_groups][n_windows]; NULL skips */
+    double* mean;                /* DEVICE [n_groups][n_windows][n_combos] f64 */
+    double* minv;                /* DEVICE, same shape, f64; NULL skips */
+    double* maxv;                /* DEVICE, same shape, f64; NULL skips */
+    uint32_t* above;             /* DEVICE, same shape, u32; NULL skips */
+    uint32_t* hist;              /* DEVICE [n_groups][n_windows][n_combos][n_bins]; NULL with n_bins == 0 */
+    uint32_t* under;             /* DEVICE [n_groups][n_windows][n_combos]; NULL skips */
+    uint32_t* over;              /* DEVICE [n_groups][n_windows][n_combos]; NULL skips */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_series_combined_t;
+int af_engine_summarize_series_combined(af_engine_t* engine, const af_outputs_t* out, af_series_combined_t* series_combined);
+
 /* Arbitrary latency QUANTILES and SLO counts per group and time window on the device (asyncflow_amd/csrc/af_quantiles.hpp):
  * p99.9 at a grid point, p90 during an outage, how many requests met a 200 ms objective in every 10 s window.  The cells and
  * their samples are af_windows_t's: cell c = g * n_windows + w holds, in ascending scenario index over the members of g,
