@@ -425,6 +425,34 @@ class AfSeriesCombined(C.Structure):
     ]
 
 
+MAX_SERIES_PAIRS = 64   # AF_MAX_SERIES_PAIRS
+
+
+class AfSeriesJoint(C.Structure):
+    """``af_series_joint_t``: request of ``af_engine_summarize_series_joint`` (``elapsed_ms`` and ``scratch_bytes`` are
+    written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("n_pairs", C.c_uint32),
+        ("a", C.POINTER(C.c_uint32)),
+        ("b", C.POINTER(C.c_uint32)),
+        ("lag", C.POINTER(C.c_uint32)),
+        ("n", C.c_void_p),
+        ("sx", C.c_void_p),
+        ("sy", C.c_void_p),
+        ("sxx", C.c_void_p),
+        ("syy", C.c_void_p),
+        ("sxy", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -451,6 +479,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_series_excursions",
     "af_engine_summarize_series_histogram",
     "af_engine_summarize_series_combined",
+    "af_engine_summarize_series_joint",
     "af_engine_summarize_quantiles",
     "af_engine_summarize_arrival_quantiles",
     "af_engine_summarize_state_windows",
@@ -503,6 +532,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_series_histogram.restype = C.c_int
     lib.af_engine_summarize_series_combined.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesCombined)]
     lib.af_engine_summarize_series_combined.restype = C.c_int
+    lib.af_engine_summarize_series_joint.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesJoint)]
+    lib.af_engine_summarize_series_joint.restype = C.c_int
     lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_summarize_arrival_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]

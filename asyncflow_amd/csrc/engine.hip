@@ -24,6 +24,8 @@
 //                                          per (group, window of ticks, output column) (af_series_histogram.hpp)
 //   af_scomb_partial / af_scomb_reduce     af_engine_summarize_series_combined: sum, min, max and spread across the series
 //                                          of a sample row per (group, window of ticks, combination) (af_series_combined.hpp)
+//   af_sjoint_partial / af_sjoint_fold     af_engine_summarize_series_joint: the six exact integer sums of pairs of series,
+//                                          lagged or not, per (group, window of ticks, pair) (af_series_joint.hpp)
 //
 // Memory plan
 //   LDS  : flow kernel: [plan blob, patched per scenario][station lists, select scratch / server segments, rings,
@@ -57,6 +59,7 @@
 #include "af_series_excursions.hpp"
 #include "af_series_histogram.hpp"
 #include "af_series_combined.hpp"
+#include "af_series_joint.hpp"
 #include "af_windowed.hpp"
 #include "af_arrival.hpp"
 #include "af_state.hpp"
@@ -3824,6 +3827,158 @@ int af_engine_summarize_series_combined(af_engine_t* e, const af_outputs_t* out,
         for (uint64_t f = 0; f < entries; f += kBlocksPerLaunch * afsc::kReduceThreads) {
             const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (entries - f + afsc::kReduceThreads - 1u) / afsc::kReduceThreads);
             hipLaunchKernelGGL(afsc::af_scomb_reduce, dim3((uint32_t)blocks), dim3(afsc::kReduceThreads), 0, st, a, f, entries);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // (the host vectors are read by the copies until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Joint moments of pairs of the sampled series per (group, window of ticks, pair) (af_series_joint.hpp).  The host checks the
+// pairs, reads the group ids and the counts back, builds the groups' member lists and picks the load form; one streaming pass
+// over the sample rows, then -- unless every group is a single scenario -- the fold of the members' records.
+static_assert(afsj::kMaxPairs == AF_MAX_SERIES_PAIRS, "the kernel's limit is the header's");
+
+int af_engine_summarize_series_joint(af_engine_t* e, const af_outputs_t* out, af_series_joint_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty series joint request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "series_joint.tick_edges is required");
+    if (!req->n || !req->sxy) return fail(AF_ERR_INVALID, "series_joint.n and sxy are required");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, cap = out->tick_capacity, Pn = req->n_pairs;
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch, n_edges = e->args.n_edges;
+    if (Pn == 0 || Pn > AF_MAX_SERIES_PAIRS)
+        return fail(AF_ERR_INVALID, "series_joint.n_pairs must be 1 .. AF_MAX_SERIES_PAIRS (" + std::to_string(AF_MAX_SERIES_PAIRS) + ")");
+    if (!req->a || !req->b || !req->lag) return fail(AF_ERR_INVALID, "series_joint.a, b and lag are required");
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    if (S == 0 || pitch < S || pitch % 4u) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    const auto is_ram = [&](uint32_t j) { return j >= n_edges && (j - n_edges) % 3u == 2u; };
+    std::vector<afsj::Pair> pairs(Pn);
+    for (uint32_t p = 0; p < Pn; ++p) {
+        const std::string who = "pair " + std::to_string(p);
+        for (const uint32_t j : {req->a[p], req->b[p]}) {
+            if (j >= S) return fail(AF_ERR_INVALID, who + " names series " + std::to_string(j) + " of " + std::to_string(S));
+            if (is_ram(j)) return fail(AF_ERR_INVALID, who + " names a ram_in_use column (series " + std::to_string(j) + "): pairs take integer series only");
+        }
+        if (req->lag[p] >= 0x80000000u) return fail(AF_ERR_INVALID, "the lag of " + who + " must be below 2^31");
+        pairs[p] = afsj::Pair{req->a[p], req->b[p], req->lag[p], 0u};
+    }
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->samples || cap == 0) return fail(AF_ERR_INVALID, "series joint moments need outputs.samples");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp;
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    // the groups' members, ascending; may a cell reach 2^32 rows?
+    std::vector<uint32_t> mem_off((size_t)G + 1u, 0u), members;
+    std::vector<uint64_t> g_ticks(G, 0u);
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = grp.empty() ? 0u : grp[s];
+        if (g == afsj::kSkip) continue;
+        mem_off[(size_t)g + 1u] += 1u;
+        g_ticks[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+    }
+    bool direct = true;
+    for (uint32_t g = 0; g < G; ++g) {
+        if (mem_off[(size_t)g + 1u] > 1u) direct = false;
+        mem_off[(size_t)g + 1u] += mem_off[g];
+    }
+    members.resize(std::max<size_t>(mem_off[G], 1u));
+    {
+        std::vector<uint32_t> cursor(mem_off.begin(), mem_off.end() - 1);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = grp.empty() ? 0u : grp[s];
+            if (g != afsj::kSkip) members[cursor[g]++] = s;
+        }
+    }
+    for (uint32_t g = 0; g < G; ++g) {
+        if (g_ticks[g] <= 0xFFFFFFFFull) continue;   // (no window of the group can reach the limit)
+        for (uint32_t w = 0; w < W; ++w) {
+            uint64_t c = 0;
+            for (uint32_t k = mem_off[g]; k < mem_off[(size_t)g + 1u]; ++k) {
+                const uint32_t m = std::min(counts[(size_t)members[k] * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+                c += std::min(req->tick_edges[w + 1u], m) - std::min(req->tick_edges[w], m);
+            }
+            if (c > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more samples");
+        }
+    }
+    // the load form: rows that fit a wave's LDS 64 at a time are staged, with as many rows after them as the largest lag that
+    // still fits asks for; the pairs with longer lags read their second word from global memory
+    const bool staged = pitch <= afsj::kMaxStagedPitch && reinterpret_cast<uintptr_t>(out->samples) % 16u == 0u;
+    uint32_t ring = 64u, lag_lds = 0u;
+    if (staged) {
+        for (uint32_t p = 0; p < Pn; ++p) {
+            uint32_t need = 64u;
+            while (need < 64u + (uint64_t)pairs[p].lag && need < afsj::kWaveLdsWords) need *= 2u;
+            if (need >= 64u + (uint64_t)pairs[p].lag && (uint64_t)need * (pitch + 1u) <= afsj::kWaveLdsWords && pairs[p].lag > lag_lds) {
+                lag_lds = pairs[p].lag;
+                ring = std::max(ring, need);
+            }
+        }
+    }
+    // scratch layout (256-byte aligned parts)
+    ScratchLayout lay;
+    const size_t R = direct ? 0u : (size_t)n * W * Pn;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u), o_pairs = lay.part((size_t)Pn * sizeof(afsj::Pair)), o_off = lay.part(((size_t)G + 1u) * 4u),
+                 o_mem = lay.part(members.size() * 4u), o_r64 = lay.part(R * 40u), o_r32 = lay.part(R * 12u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    unsigned char* b = e->d_pool;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(b + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_pairs, pairs.data(), (size_t)Pn * sizeof(afsj::Pair), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_off, mem_off.data(), mem_off.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_mem, members.data(), members.size() * 4u, hipMemcpyHostToDevice, st));
+    afsj::SjArgs a{};
+    a.samples = out->samples;
+    a.counts = out->counts;
+    a.tick_cap = cap;
+    a.pitch = pitch;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.group = req->group;
+    a.n_scen = n;
+    a.n_groups = G;
+    a.n_win = W;
+    a.direct = direct ? 1u : 0u;
+    a.edges = reinterpret_cast<const uint32_t*>(b + o_edges);
+    a.n_pairs = Pn;
+    while ((1u << a.p2_log) < Pn) a.p2_log += 1u;
+    a.pairs = reinterpret_cast<const afsj::Pair*>(b + o_pairs);
+    a.staged = staged ? 1u : 0u;
+    a.ring = ring;
+    a.lag_lds = lag_lds;
+    a.p4 = pitch / 4u;
+    a.q64 = 64u / a.p4;
+    a.r64 = 64u % a.p4;
+    a.mem_off = reinterpret_cast<const uint32_t*>(b + o_off);
+    a.members = reinterpret_cast<const uint32_t*>(b + o_mem);
+    a.rec64 = reinterpret_cast<unsigned long long*>(b + o_r64);
+    a.rec32 = reinterpret_cast<uint32_t*>(b + o_r32);
+    a.n = req->n;
+    a.sx = reinterpret_cast<unsigned long long*>(req->sx);
+    a.sy = reinterpret_cast<unsigned long long*>(req->sy);
+    a.sxx = reinterpret_cast<unsigned long long*>(req->sxx);
+    a.syy = reinterpret_cast<unsigned long long*>(req->syy);
+    a.sxy = reinterpret_cast<unsigned long long*>(req->sxy);
+    // a wave per (scenario, run of windows): runs as long as leave the chip some 32 768 waves (af_engine_summarize_series_windows' rule)
+    const uint32_t want_runs = (32768u + n - 1u) / n;
+    a.run = std::max(1u, W / want_runs);
+    const uint64_t items = (uint64_t)n * ((W + a.run - 1u) / a.run);
+    const size_t lds = staged ? (size_t)afsj::kWaves * ring * (pitch + 1u) * 4u : 0u;
+    hipLaunchKernelGGL(afsj::af_sjoint_partial, dim3((uint32_t)((items + afsj::kWaves - 1u) / afsj::kWaves)), dim3(afsj::kThreads), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    if (!direct || mem_off[G] < G) {   // the members' fold; after a direct pass only the cells of groups without a member
+        const uint64_t entries = (uint64_t)G * W * Pn;
+        for (uint64_t f = 0; f < entries; f += kBlocksPerLaunch * afsj::kFoldThreads) {
+            const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (entries - f + afsj::kFoldThreads - 1u) / afsj::kFoldThreads);
+            hipLaunchKernelGGL(afsj::af_sjoint_fold, dim3((uint32_t)blocks), dim3(afsj::kFoldThreads), 0, st, a, f, entries);
             HIP_TRY(hipGetLastError());
         }
     }

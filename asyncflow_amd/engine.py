@@ -565,6 +565,34 @@ class Engine:
                "af_engine_summarize_series_combined")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    #: the outputs of :meth:`summarize_series_joint`, in the order of ``af_series_joint_t``
+    JOINT_OUTPUTS = ("n", "sx", "sy", "sxx", "syy", "sxy")
+
+    def summarize_series_joint(self, n: int, n_groups: int, tick_edges: Any, a: Any, b: Any, lag: Any, *, samples_ptr: int,
+                               tick_capacity: int, counts_ptr: int, n_ptr: int, sxy_ptr: int, sx_ptr: int = 0, sy_ptr: int = 0,
+                               sxx_ptr: int = 0, syy_ptr: int = 0, group_ptr: int = 0) -> tuple[float, int]:
+        """Joint moments of pairs of series on the device (``af_engine_summarize_series_joint``): pair ``p`` is the integer
+        series ``a[p]`` at a row and ``b[p]`` ``lag[p]`` rows later, both inside one window.  Per (group, window of ticks,
+        pair) ``n`` uint32 [n_groups, W, P], ``sx`` / ``sy`` uint64 of the same shape and ``sxx`` / ``syy`` / ``sxy`` uint64
+        [n_groups, W, P, 2] (128-bit sums, low word first); a pointer of 0 skips every output but ``n`` and ``sxy``.
+        ``tick_edges``: HOST uint32 tick indices, strictly increasing.  ``group_ptr`` as in :meth:`summarize_pooled`.  The
+        library checks the pairs.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_tick_edges
+
+        e = check_tick_edges(tick_edges)
+        cols = [np.ascontiguousarray(v, dtype=np.uint32).reshape(-1) for v in (a, b, lag)]
+        if not cols[0].shape == cols[1].shape == cols[2].shape:
+            msg = f"a, b and lag must have one entry per pair each, not {[int(c.shape[0]) for c in cols]}"
+            raise ValueError(msg)
+        pu = C.POINTER(C.c_uint32)
+        out = _abi.AfOutputs(0, None, int(tick_capacity), C.c_void_p(samples_ptr or None), C.c_void_p(counts_ptr or None))
+        req = _abi.AfSeriesJoint(int(n), int(n_groups), int(e.shape[0] - 1), C.c_void_p(group_ptr or None), e.ctypes.data_as(pu),
+                                 int(cols[0].shape[0]), *(c.ctypes.data_as(pu) for c in cols),
+                                 *(C.c_void_p(p or None) for p in (n_ptr, sx_ptr, sy_ptr, sxx_ptr, syy_ptr, sxy_ptr)), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_series_joint(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_series_joint")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:
         """``af_engine_gather``: ONE grouped RCCL all-gather of the per-scenario summaries.

@@ -11,6 +11,7 @@ own plot helpers accept these objects through ``to_reference_analyzer``.
 
 from __future__ import annotations
 
+import math
 from collections import defaultdict
 from typing import Any, Iterator
 
@@ -880,6 +881,272 @@ def series_combined_window_stats(samples: np.ndarray, tick_edges: Any, n_edges: 
     return out
 
 
+JOINT_SUMS = ("sx", "sy", "sxx", "syy", "sxy")
+JOINT_STATISTICS = ("mean_x", "mean_y", "cov", "corr", "var_x", "var_y")
+
+
+def _select_series(selection: Any, names: list[str], what: str) -> list[int]:
+    """``selection`` -- a series name, an index, an ``fnmatch`` pattern over ``names`` or a list of those -- as series
+    indices in the order given (a pattern: its matches ascending), every series once."""
+    import fnmatch
+
+    sel = [selection] if isinstance(selection, (str, bytes, int, np.integer)) else list(np.asarray(selection).tolist() if isinstance(selection, np.ndarray) else selection)
+    picked: list[int] = []
+    for x in sel:
+        x = x.decode() if isinstance(x, bytes) else x
+        if isinstance(x, str) and any(ch in x for ch in "*?["):
+            hit = [j for j, nm in enumerate(names) if fnmatch.fnmatchcase(nm, x)]
+            if not hit:
+                msg = f"{what}: pattern {x!r} matches no series (series_names(): {names})"
+                raise ValueError(msg)
+            picked += [j for j in hit if j not in picked]
+        elif isinstance(x, str):
+            if x not in names:
+                msg = f"{what}: unknown series {x!r} (series_names(): {names})"
+                raise ValueError(msg)
+            picked.append(names.index(x))
+        elif isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < len(names):
+            msg = f"{what}: {x!r} is no series name, pattern or index below {len(names)}"
+            raise ValueError(msg)
+        else:
+            picked.append(int(x))
+    if not picked:
+        msg = f"{what} selects no series"
+        raise ValueError(msg)
+    if len(set(picked)) != len(picked):
+        msg = f"{what} names a series twice"
+        raise ValueError(msg)
+    return picked
+
+
+def check_series_pairs(pairs: Any, names: list[str], n_edges: int) -> tuple[list[str], np.ndarray, np.ndarray, np.ndarray]:
+    """The pairs of a series-joint call as ``(labels, a, b, lag)``: ``pairs`` is ``{label: (a, b)}`` or ``{label: (a, b,
+    lag)}`` (or an iterable of ``(label, spec)``), ``a`` and ``b`` series names of ``names`` or indices, ``lag`` a whole number
+    of ticks (default 0): the pair's samples are ``(a at tick k, b at tick k + lag)``.  ``a``, ``b`` and ``lag`` come back as
+    int64 vectors.  ValueError for everything ``af_engine_summarize_series_joint`` refuses in a pair -- no pair or more than
+    ``AF_MAX_SERIES_PAIRS`` (64), a series that is unknown or out of range, a ``ram_in_use`` column (integer series only in
+    this version), a lag that is negative, not whole or not below 2^31 -- and for a duplicate label."""
+    items = list(pairs.items()) if isinstance(pairs, dict) else [(k, v) for k, v in pairs]
+    if not 1 <= len(items) <= _abi.MAX_SERIES_PAIRS:
+        msg = f"a call takes 1 .. {_abi.MAX_SERIES_PAIRS} pairs, not {len(items)}"
+        raise ValueError(msg)
+    ram = ram_columns(len(names), n_edges)
+    labels: list[str] = []
+    cols: list[tuple[int, int, int]] = []
+    for label, spec in items:
+        label = str(label)
+        if label in labels:
+            msg = f"pair {label!r} is given twice"
+            raise ValueError(msg)
+        if not isinstance(spec, (tuple, list)) or len(spec) not in (2, 3):
+            msg = f"pair {label!r} must be (a, b) or (a, b, lag), not {spec!r}"
+            raise ValueError(msg)
+        ab = []
+        for x in spec[:2]:
+            x = x.decode() if isinstance(x, bytes) else x
+            if isinstance(x, str):
+                if x not in names:
+                    msg = f"pair {label!r}: unknown series {x!r} (series_names(): {names})"
+                    raise ValueError(msg)
+                j = names.index(x)
+            elif isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < len(names):
+                msg = f"pair {label!r}: {x!r} is no series name or index below {len(names)}"
+                raise ValueError(msg)
+            else:
+                j = int(x)
+            if ram[j]:
+                msg = f"pair {label!r}: {names[j]!r} is a ram_in_use column; pairs take integer series only"
+                raise ValueError(msg)
+            ab.append(j)
+        lag = spec[2] if len(spec) == 3 else 0
+        if isinstance(lag, (bool, np.bool_)) or not isinstance(lag, (int, np.integer)) or not 0 <= int(lag) < 2 ** 31:
+            msg = f"pair {label!r}: the lag must be a whole number of ticks in [0, 2^31), not {lag!r}"
+            raise ValueError(msg)
+        labels.append(label)
+        cols.append((ab[0], ab[1], int(lag)))
+    arr = np.array(cols, dtype=np.int64)
+    return labels, arr[:, 0].copy(), arr[:, 1].copy(), arr[:, 2].copy()
+
+
+def _check_pair_columns(pairs: Any, n_series: int, n_edges: int) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    a, b, lag = (np.asarray(v) for v in pairs)
+    if not (a.ndim == b.ndim == lag.ndim == 1 and a.shape == b.shape == lag.shape and 1 <= a.shape[0] <= _abi.MAX_SERIES_PAIRS):
+        msg = f"pairs must be (a, b, lag), three vectors of 1 .. {_abi.MAX_SERIES_PAIRS} entries"
+        raise ValueError(msg)
+    if any(v.dtype.kind not in "iu" for v in (a, b, lag)):
+        msg = "the series indices and the lags of the pairs must be integers"
+        raise ValueError(msg)
+    a, b, lag = a.astype(np.int64), b.astype(np.int64), lag.astype(np.int64)
+    ram = ram_columns(n_series, n_edges)
+    for col in (a, b):
+        if (col < 0).any() or (col >= n_series).any():
+            msg = f"the series of a pair must be indices below {n_series}"
+            raise ValueError(msg)
+        if ram[col].any():
+            msg = "a pair names a ram_in_use column; pairs take integer series only"
+            raise ValueError(msg)
+    if (lag < 0).any() or (lag >= 2 ** 31).any():
+        msg = "the lag of a pair must be in [0, 2^31)"
+        raise ValueError(msg)
+    return a, b, lag
+
+
+def series_joint_sums(samples: np.ndarray, tick_edges: Any, n_edges: int, pairs: Any) -> dict[str, np.ndarray]:
+    """The six sums of pairs of series per window of ticks of ONE scenario's sampled series ``samples`` (uint32 words
+    [n_series, ticks]); ``pairs`` is ``(a, b, lag)``, three integer vectors (:func:`check_series_pairs` makes them).  Window
+    ``w`` holds the rows ``[r0, r1) = [min(b[w], ticks), min(b[w + 1], ticks))`` of ``b = tick_edges``; the samples of pair
+    ``p`` in it are ``(x, y) = (samples[a[p], k], samples[b[p], k + lag[p]])`` for ``k`` in ``[r0, r1 - lag[p])``, the words as
+    unsigned integers: both ticks inside the window.  Returns ``n`` int64 [W, P] and ``sx``, ``sy``, ``sxx``, ``syy``,
+    ``sxy`` as object arrays [W, P] of Python integers: sum x, sum y, sum x^2, sum y^2, sum x y, exact.  Pooling the members
+    of a group is addition of these arrays.  The definition the device analyzer (``af_engine_summarize_series_joint``)
+    matches word for word."""
+    b = check_tick_edges(tick_edges)
+    words = np.ascontiguousarray(samples).view(np.uint32)
+    if words.ndim != 2:
+        msg = f"samples must be words [n_series, ticks], not of shape {words.shape}"
+        raise ValueError(msg)
+    n_series, ticks = words.shape
+    a, bb, lag = _check_pair_columns(pairs, n_series, n_edges)
+    n_win, n_p = b.shape[0] - 1, a.shape[0]
+    r = np.minimum(b.astype(np.int64), ticks)
+    out: dict[str, np.ndarray] = {"n": np.zeros((n_win, n_p), dtype=np.int64)}
+    for k in JOINT_SUMS:
+        out[k] = np.zeros((n_win, n_p), dtype=object)
+        out[k][...] = 0
+
+    def before(v: np.ndarray) -> np.ndarray:     # before(v)[k] = v[0] + ... + v[k - 1]: fewer than 2^32 terms below 2^32, exact in uint64
+        return np.concatenate([np.zeros(1, dtype=np.uint64), np.cumsum(v, dtype=np.uint64)])
+
+    low = np.uint64(0xFFFFFFFF)
+    for p in range(n_p):
+        step = int(lag[p])
+        pairs_all = max(ticks - step, 0)         # the pairs (k, k + step) of the whole block: k < pairs_all
+        x = words[a[p], :pairs_all].astype(np.uint64)
+        y = words[bb[p], step:step + pairs_all].astype(np.uint64)
+        cnt = np.maximum(r[1:] - r[:-1] - step, 0)
+        k0 = np.where(cnt > 0, r[:-1], 0)        # window w holds the pairs k0[w] <= k < k0[w] + cnt[w]
+        k1 = k0 + cnt
+        out["n"][:, p] = cnt
+        for key, v in (("sx", x), ("sy", y)):
+            run = before(v)
+            out[key][:, p] = (run[k1] - run[k0]).astype(object)
+        for key, v in (("sxx", x * x), ("syy", y * y), ("sxy", x * y)):      # 128-bit sums, 32 bits of the products at a time
+            top, bottom = before(v >> np.uint64(32)), before(v & low)
+            out[key][:, p] = (top[k1] - top[k0]).astype(object) * (1 << 32) + (bottom[k1] - bottom[k0]).astype(object)
+    return out
+
+
+def _joint_integers(v: Any, shape: tuple[int, ...]) -> np.ndarray:
+    """A sum of :func:`series_joint_sums` or of the device -- integers of ``shape``, or uint64 words ``shape + (2,)``, low
+    word first -- as a flat object array of Python integers."""
+    arr = np.asarray(v)
+    if arr.shape == (*shape, 2) and arr.shape != shape:
+        o = arr.astype(object)
+        arr = o[..., 0] + o[..., 1] * (1 << 64)
+    if arr.shape != shape:
+        msg = f"a sum of shape {arr.shape} next to n of shape {shape}"
+        raise ValueError(msg)
+    out = np.empty(int(np.prod(shape, dtype=np.int64)), dtype=object)
+    out[:] = [int(x) for x in arr.reshape(-1)]
+    return out
+
+
+def series_joint_statistics(sums: dict[str, Any], exact: bool = False) -> dict[str, np.ndarray]:
+    """Means, covariance, variances and the Pearson correlation from the six sums ``n``, ``sx``, ``sy``, ``sxx``, ``syy``,
+    ``sxy`` (arrays of one shape; a 128-bit sum may also be uint64 words ``[..., 2]``, low word first): the only place where
+    floats appear.  With the exact integers ``N = n sxy - sx sy``, ``Dx = n sxx - sx^2``, ``Dy = n syy - sy^2``:
+
+    * ``mean_x = sx / n``, ``mean_y = sy / n``, ``cov = N / n^2``, ``var_x = Dx / n^2``, ``var_y = Dy / n^2`` (the population
+      moments): each the correctly rounded float64 of the exact rational (Python's ``int / int``);
+    * ``corr = clamp(f(N) / sqrt(f(Dx) * f(Dy)), -1, 1)`` with ``f`` the correctly rounded conversion to float64 and every
+      operation IEEE float64; NaN where ``Dx == 0`` or ``Dy == 0`` (a constant column).  A pair ``(a, a, 0)`` of a
+      non-constant column has ``corr == 1.0`` exactly.
+
+    Everything is NaN where ``n == 0``.  Returns float64 arrays of the sums' shape.  Cells whose six products ``n sxx``,
+    ``n syy``, ``n sxy``, ``sx^2``, ``sy^2``, ``sx sy`` all stay below 2^63 take ``N``, ``Dx``, ``Dy`` in int64; of those, the
+    ones with ``|N|``, ``Dx``, ``Dy`` < 2^53 and ``n^2`` < 2^53 divide in float64, and the means divide in float64 where the
+    sum is below 2^53 -- the same bits as the definition, which ``exact=True`` applies to every cell."""
+    n_in = np.asarray(sums["n"])
+    shape = n_in.shape
+    n_o = _joint_integers(n_in, shape)
+    o = {k: _joint_integers(sums[k], shape) for k in JOINT_SUMS}
+    cells = n_o.shape[0]
+    out = {k: np.full(cells, np.nan) for k in JOINT_STATISTICS}
+    done_mean = np.zeros(cells, dtype=bool)
+    done_mom = np.zeros(cells, dtype=bool)
+    done_corr = np.zeros(cells, dtype=bool)
+    if not exact and cells:
+        top = (1 << 63) - 1
+        ok = (n_o > 0).astype(bool) & (n_o <= top).astype(bool)
+        for k in JOINT_SUMS:
+            ok &= (o[k] <= top).astype(bool)
+        i = {k: np.where(ok, o[k], 0).astype(np.int64) for k in JOINT_SUMS}
+        n = np.where(ok, n_o, 1).astype(np.int64)
+        per_n = top // n
+        ok &= (i["sxx"] <= per_n) & (i["syy"] <= per_n) & (i["sxy"] <= per_n)
+        ok &= (i["sx"] <= top // np.maximum(i["sx"], 1)) & (i["sy"] <= top // np.maximum(i["sy"], 1)) & (i["sy"] <= top // np.maximum(i["sx"], 1))
+        for k in JOINT_SUMS:
+            i[k] = np.where(ok, i[k], 0)
+        n = np.where(ok, n, 1)
+        num, dx, dy = n * i["sxy"] - i["sx"] * i["sy"], n * i["sxx"] - i["sx"] * i["sx"], n * i["syy"] - i["sy"] * i["sy"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            c = num.astype(np.float64) / np.sqrt(dx.astype(np.float64) * dy.astype(np.float64))
+        c = np.where((dx == 0) | (dy == 0), np.nan, np.minimum(np.maximum(c, -1.0), 1.0))
+        out["corr"] = np.where(ok, c, np.nan)
+        done_corr = ok
+        lim = 1 << 53
+        small = ok & (np.abs(num) < lim) & (dx < lim) & (dy < lim) & (n < 94906266)     # 94 906 266^2 is the first square above 2^53
+        ns = np.where(small, n, 1)
+        nn = (ns * ns).astype(np.float64)
+        for k, v in (("cov", num), ("var_x", dx), ("var_y", dy)):
+            out[k] = np.where(small, v.astype(np.float64) / nn, np.nan)
+        done_mom = small
+        means = ok & (i["sx"] < lim) & (i["sy"] < lim)
+        nf = n.astype(np.float64)
+        out["mean_x"] = np.where(means, i["sx"].astype(np.float64) / nf, np.nan)
+        out["mean_y"] = np.where(means, i["sy"].astype(np.float64) / nf, np.nan)
+        done_mean = means
+    for j in np.nonzero(~(done_mean & done_mom & done_corr))[0]:
+        n = n_o[j]
+        if n <= 0:
+            continue
+        sx, sy, sxx, syy, sxy = (o[k][j] for k in JOINT_SUMS)
+        num, dx, dy = n * sxy - sx * sy, n * sxx - sx * sx, n * syy - sy * sy
+        if not done_mean[j]:
+            out["mean_x"][j], out["mean_y"][j] = sx / n, sy / n
+        if not done_mom[j]:
+            out["cov"][j], out["var_x"][j], out["var_y"][j] = num / (n * n), dx / (n * n), dy / (n * n)
+        if not done_corr[j] and dx != 0 and dy != 0:
+            out["corr"][j] = min(max(float(num) / math.sqrt(float(dx) * float(dy)), -1.0), 1.0)
+    return {k: v.reshape(shape) for k, v in out.items()}
+
+
+def autocorrelation_time(acf: Any, n0: Any) -> dict[str, np.ndarray]:
+    """The integrated autocorrelation time of autocorrelation functions ``acf`` [..., L + 1] (lag 0 first) and the
+    effective sample size of cells of ``n0`` [...] samples: ``tau = 1 + 2 * (acf[1] + ... + acf[m])``, added left to right in
+    float64, with ``m`` the last lag before the first ``l >= 1`` at which ``acf[l] <= 0`` or is NaN (the initial positive
+    sequence); ``tau_truncated`` is true where no such lag exists up to ``L`` -- the lags were too few and ``tau`` is a
+    lower bound --; ``ess = n0 / tau``.  Where ``acf[0]`` is NaN (an empty cell or a constant series) ``tau`` and ``ess`` are
+    NaN and ``tau_truncated`` is false."""
+    f = np.asarray(acf, dtype=np.float64)
+    if f.ndim < 1 or f.shape[-1] < 1:
+        msg = "acf must hold lag 0"
+        raise ValueError(msg)
+    tail = f[..., 1:]
+    stop = ~(tail > 0.0)                                               # (NaN stops too)
+    found = stop.any(axis=-1)
+    total = np.zeros(f.shape[:-1])
+    if tail.shape[-1]:
+        m = np.where(found, np.argmax(stop, axis=-1), tail.shape[-1])  # the lags 1 .. m are summed
+        keep = np.arange(tail.shape[-1]) < m[..., None]
+        total = np.cumsum(np.where(keep, tail, 0.0), axis=-1)[..., -1]
+    valid = ~np.isnan(f[..., 0])
+    tau = np.where(valid, 1.0 + 2.0 * total, np.nan)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        ess = np.where(valid, np.asarray(n0, dtype=np.float64) / tau, np.nan)
+    return {"tau": tau, "tau_truncated": valid & ~found, "ess": ess}
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -1101,6 +1368,24 @@ class ScenarioResults:
         out: dict[str, Any] = series_combined_window_stats(self._samples, b, self._plan.n_edges, list(zip(ops, columns)), thresholds,
                                                            bins, lo, width)
         out.update(names=labels, ops=ops, columns=columns, tick_edges=b)
+        return out
+
+    def get_series_joint(self, pairs: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                         tick_edges: Any = None) -> dict[str, Any]:
+        """Covariance and correlation of pairs of integer series per window of ticks, lagged or not, from the host
+        definition: ``pairs`` is ``{label: (a, b)}`` or ``{label: (a, b, lag)}`` over :func:`series_names_of`
+        (:func:`check_series_pairs`), such as ``{"queues": ("srv-1:ready_queue_len", "srv-2:ready_queue_len")}``.  Returns
+        the sums of :func:`series_joint_sums` (``n`` and ``sx`` ... ``sxy`` [W, P]), the statistics of
+        :func:`series_joint_statistics` (``mean_x``, ``mean_y``, ``cov``, ``corr``, ``var_x``, ``var_y`` [W, P]) and
+        ``labels``, ``a``, ``b``, ``lag``, ``tick_edges``.  Windows as in :meth:`get_series_window_stats`."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        labels, ca, cb, lag = check_series_pairs(pairs, series_names_of(self._plan), self._plan.n_edges)
+        out: dict[str, Any] = series_joint_sums(self._samples, b, self._plan.n_edges, (ca, cb, lag))
+        out.update(series_joint_statistics(out))
+        out.update(labels=labels, a=ca, b=cb, lag=lag, tick_edges=b)
         return out
 
     def get_latency_by_state(self, series: Any, bins: int = 8, lo: float = 0.0, width: float = 1.0, window_s: float | None = None,
@@ -2472,6 +2757,171 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    def _series_joint_call(self, ca: np.ndarray, cb: np.ndarray, lag: np.ndarray, b: np.ndarray, ids: np.ndarray,
+                           n_groups: int) -> tuple[dict[str, np.ndarray], float, int]:
+        """One call of ``af_engine_summarize_series_joint``: the sums as numpy arrays [G, W, P] (``n`` int64, the others
+        Python integers), the call's wall time in ms and the engine's scratch size."""
+        import torch
+
+        from .engine import Engine
+
+        samples = self._samples_t
+        dev = samples.device
+        n_win, n_p = int(b.shape[0] - 1), int(ca.shape[0])
+        cnt = torch.empty((n_groups, n_win, n_p), dtype=torch.int32, device=dev)
+        one = {k: torch.empty((n_groups, n_win, n_p), dtype=torch.int64, device=dev) for k in ("sx", "sy")}
+        two = {k: torch.empty((n_groups, n_win, n_p, 2), dtype=torch.int64, device=dev) for k in ("sxx", "syy", "sxy")}
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_series_joint(
+            len(self), n_groups, b, ca, cb, lag, samples_ptr=samples.data_ptr(), tick_capacity=int(samples.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), n_ptr=cnt.data_ptr(), sx_ptr=one["sx"].data_ptr(), sy_ptr=one["sy"].data_ptr(),
+            sxx_ptr=two["sxx"].data_ptr(), syy_ptr=two["syy"].data_ptr(), sxy_ptr=two["sxy"].data_ptr(), group_ptr=grp.data_ptr())
+        out: dict[str, np.ndarray] = {"n": cnt.cpu().numpy().view(np.uint32).astype(np.int64)}
+        for k, t in one.items():
+            out[k] = t.cpu().numpy().view(np.uint64).astype(object)
+        for k, t in two.items():
+            w = t.cpu().numpy().view(np.uint64).astype(object)
+            out[k] = w[..., 0] + w[..., 1] * (1 << 64)
+        return out, ms, scratch
+
+    def series_joint_summary(self, pairs: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                             tick_edges: Any = None, by: Any = None) -> dict[str, Any]:
+        """How two sampled series move together per (group, window of ticks), over all scenarios of the group: do the
+        servers' queues rise together or in turn, does an edge's concurrency lead a server's queue and by how many ticks.
+        ``pairs`` is ``{label: (a, b)}`` or ``{label: (a, b, lag)}``, ``a`` and ``b`` names of :meth:`series_names` or indices
+        of INTEGER series (no ``ram_in_use`` column), at most 64 (:func:`check_series_pairs`); the samples of a pair are
+        ``(a at tick k, b at tick k + lag)`` with both ticks in the same window of the same scenario.  The HIP analyzer
+        ``af_engine_summarize_series_joint`` returns six exact integer sums per cell in one pass over the sample rows --
+        equal to :func:`series_joint_sums` added over the group's scenarios --, and :func:`series_joint_statistics` turns
+        them into floats on the host.  Windows and ``by`` as in :meth:`series_window_summary`.  Returns numpy arrays
+        [G, W, P]: ``n`` int64, the sums ``sx``, ``sy``, ``sxx``, ``syy``, ``sxy`` as Python integers (they pass 64 bits),
+        ``mean_x``, ``mean_y``, ``cov``, ``corr``, ``var_x``, ``var_y`` float64 (NaN in empty cells; ``corr`` NaN too where
+        a column is constant); and ``labels``, ``a``, ``b``, ``lag``, ``tick_edges``, ``times``, ``replicas`` [G],
+        ``series_joint_ms``, ``scratch_bytes``."""
+        self._require_samples()
+        labels, ca, cb, lag = check_series_pairs(pairs, self.series_names(), self.plan.n_edges)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        out: dict[str, Any]
+        out, ms, scratch = self._series_joint_call(ca, cb, lag, b, ids, n_groups)
+        out.update(series_joint_statistics(out))
+        out.update(labels=labels, a=ca, b=cb, lag=lag, tick_edges=b, times=b[:-1].astype(np.float64) * self.plan.sample_period,
+                   replicas=np.bincount(ids[ids >= 0], minlength=n_groups), series_joint_ms=ms, scratch_bytes=scratch)
+        return out
+
+    def series_autocorrelation_summary(self, series: Any, max_lag: int, window_s: float | None = None, *,
+                                       ticks_per_window: int | None = None, tick_edges: Any = None, by: Any = None) -> dict[str, Any]:
+        """The autocorrelation function of sampled series per (group, window of ticks) and what a time average over the
+        window is worth: ``series`` are names of :meth:`series_names`, indices, one ``fnmatch`` pattern or a list of those
+        (integer series only); the lags are ``0 .. max_lag`` ticks, issued to ``af_engine_summarize_series_joint`` as calls
+        of at most 64 pairs ``(c, c, l)``.  ``acf`` float64 [G, W, C, max_lag + 1]: ``acf[l]`` is the PEARSON correlation of
+        ``(x_k, x_{k + l})`` over the overlapping ticks of each window, each side with its own mean and variance over the
+        ticks it covers; it is NOT the estimator that divides the lagged products about the full-sample mean by the
+        full-sample variance -- the two differ by O(l / n) in a window of n ticks.  ``n`` int64 [G, W, C, max_lag + 1] are
+        the pairs per lag.  ``tau`` [G, W, C] is the integrated autocorrelation time ``1 + 2 * sum(acf[1 .. m])``, ``m`` the
+        last lag before the first ``acf[l] <= 0`` or NaN; ``tau_truncated`` is true where no such lag was found up to
+        ``max_lag`` (the lags were too few; ``tau`` is then a lower bound); ``ess = n[..., 0] / tau`` is the number of
+        independent samples the window's mean is worth (:func:`autocorrelation_time`).  Also ``series`` (the names),
+        ``columns``, ``lags``, ``tick_edges``, ``times``, ``replicas``, ``series_joint_ms`` (all calls), ``calls``."""
+        self._require_samples()
+        if isinstance(max_lag, (bool, np.bool_)) or not isinstance(max_lag, (int, np.integer)) or not 0 <= int(max_lag) < 2 ** 31:
+            msg = f"max_lag must be a whole number of ticks in [0, 2^31), not {max_lag!r}"
+            raise ValueError(msg)
+        names = self.series_names()
+        cols = _select_series(series, names, "series")
+        ram = ram_columns(len(names), self.plan.n_edges)
+        for j in cols:
+            if ram[j]:
+                msg = f"{names[j]!r} is a ram_in_use column; the autocorrelation takes integer series only"
+                raise ValueError(msg)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        n_lag, n_win = int(max_lag) + 1, int(b.shape[0] - 1)
+        every = [(c, lag) for c in cols for lag in range(n_lag)]
+        acf = np.empty((n_groups, n_win, len(every)))
+        cnt = np.empty((n_groups, n_win, len(every)), dtype=np.int64)
+        total_ms, scratch, calls = 0.0, 0, 0
+        for at in range(0, len(every), _abi.MAX_SERIES_PAIRS):
+            part = every[at:at + _abi.MAX_SERIES_PAIRS]
+            col = np.array([c for c, _ in part], dtype=np.int64)
+            sums, ms, scratch = self._series_joint_call(col, col, np.array([lag for _, lag in part], dtype=np.int64), b, ids, n_groups)
+            acf[:, :, at:at + len(part)] = series_joint_statistics(sums)["corr"]
+            cnt[:, :, at:at + len(part)] = sums["n"]
+            total_ms += ms
+            calls += 1
+        acf = acf.reshape(n_groups, n_win, len(cols), n_lag)
+        cnt = cnt.reshape(n_groups, n_win, len(cols), n_lag)
+        out: dict[str, Any] = {"acf": acf, "n": cnt}
+        out.update(autocorrelation_time(acf, cnt[..., 0]))
+        out.update(series=[names[j] for j in cols], columns=np.array(cols, dtype=np.int64), lags=np.arange(n_lag), tick_edges=b,
+                   times=b[:-1].astype(np.float64) * self.plan.sample_period, replicas=np.bincount(ids[ids >= 0], minlength=n_groups),
+                   series_joint_ms=total_ms, scratch_bytes=scratch, calls=calls)
+        return out
+
+    def series_joint_bands(self, pairs: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                           tick_edges: Any = None, by: Any = None, of: str = "corr", level: float = 0.95,
+                           q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of ``of`` (``"corr"`` or ``"cov"``) of the pairs: every scenario's own window values
+        (``series_joint_summary(by="scenario")``), then per group (``by``), window and pair, over the group's replicas whose
+        value is not NaN, what :meth:`series_window_bands` gives -- numpy float64 [G, W, P] each
+        (:func:`window_bands_by_group`, pair by pair: a pair's value may be NaN where another's is not); ``n`` int64
+        [G, W, P] are the replicas that count; ``pooled`` is the grouped call's value of the same statistic."""
+        if of not in ("corr", "cov"):
+            msg = f"of must be 'corr' or 'cov', not {of!r}"
+            raise ValueError(msg)
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        return self._series_joint_bands(pairs, b, by, of, level, q)[0]
+
+    def _series_joint_bands(self, pairs: Any, b: np.ndarray, by: Any, of: str, level: float,
+                            q: tuple[float, float]) -> tuple[dict[str, Any], dict[str, Any]]:
+        """:meth:`series_joint_bands` for resolved tick edges; also returns the grouped summary its ``pooled`` is from."""
+        import torch
+
+        ids, n_groups = self._window_groups(by)
+        per = self.series_joint_summary(pairs, tick_edges=b, by="scenario")
+        values = torch.from_numpy(np.ascontiguousarray(per[of]))       # (the statistics are made on the host)
+        parts = [window_bands_by_group(values[:, :, p:p + 1], ids, n_groups, level, q, valid=~torch.isnan(values[:, :, p]))
+                 for p in range(values.shape[2])]
+        out: dict[str, Any] = {k: np.concatenate([x[k] for x in parts], axis=2) for k in ("mean", "std", "ci_halfwidth", "q_lo", "q_hi")}
+        out["n"] = np.stack([x["n"] for x in parts], axis=2)
+        out.update(replicas=parts[0]["replicas"], level=level, q=parts[0]["q"])
+        pooled = self.series_joint_summary(pairs, tick_edges=b, by=ids)
+        out["pooled"] = pooled[of][:n_groups]
+        out.update(of=of, labels=per["labels"], a=per["a"], b=per["b"], lag=per["lag"], tick_edges=b, times=per["times"])
+        return out, pooled
+
+    def save_series_joint_summary(self, path: str, by: Any = None, *, pairs: Any, window_s: float | None = None,
+                                  ticks_per_window: int | None = None, tick_edges: Any = None, level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the pairs' statistics with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas`` and per pair the [G, W] columns ``series_joint_corr:<label>``, ``series_joint_cov:<label>``,
+        ``series_joint_n:<label>`` -- the group's replicas taken together -- and ``series_joint_q05:<label>`` /
+        ``series_joint_q95:<label>`` (of the replicas' own correlations, :meth:`series_joint_bands`).
+        ``series_joint_tick_edges`` [W + 1] and ``series_joint_times`` [W] are per-file vectors.  ``.npz`` or ``.parquet``;
+        :func:`load_summary` reads it back."""
+        self._require_samples()
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        bands, pooled = self._series_joint_bands(pairs, b, by, "corr", level, (0.05, 0.95))
+        n_groups = int(bands["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        for p, name in enumerate(bands["labels"]):
+            cols[f"series_joint_corr:{name}"] = np.ascontiguousarray(pooled["corr"][:n_groups, :, p])
+            cols[f"series_joint_cov:{name}"] = np.ascontiguousarray(pooled["cov"][:n_groups, :, p])
+            cols[f"series_joint_n:{name}"] = np.ascontiguousarray(pooled["n"][:n_groups, :, p], dtype=np.int64)
+            cols[f"series_joint_q05:{name}"] = np.ascontiguousarray(bands["q_lo"][:, :, p])
+            cols[f"series_joint_q95:{name}"] = np.ascontiguousarray(bands["q_hi"][:, :, p])
+        cols["series_joint_tick_edges"] = np.asarray(b, dtype=np.float64)
+        cols["series_joint_times"] = np.asarray(bands["times"], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -2908,6 +3358,22 @@ class ShardedResults:
 
     def save_series_combined_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_combined_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_joint_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_joint_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_autocorrelation_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_autocorrelation_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_joint_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_joint_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_series_joint_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_series_joint_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
     def state_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:

@@ -725,6 +725,59 @@ typedef struct af_series_combined {
 } af_series_combined_t;
 int af_engine_summarize_series_combined(af_engine_t* engine, const af_outputs_t* out, af_series_combined_t* series_combined);
 
+/* JOINT MOMENTS OF PAIRS OF THE SAMPLED SERIES per window of ticks and group on the device
+ * (asyncflow_amd/csrc/af_series_joint.hpp): do the servers' queues rise together or in turn (covariance, correlation), does an
+ * edge's concurrency lead a server's queue and by how many ticks (cross-correlation at a lag), how many independent samples
+ * does a time average hold (the autocorrelation function and the integrated autocorrelation time).  Every one of these is a
+ * closed form of SIX EXACT INTEGER SUMS per (pair, cell); the call returns the sums.
+ * A PAIR p is (a[p], b[p], lag[p]): a and b are series indices < af_series_count, both INTEGER series -- a ram_in_use column
+ * (index n_edges + 3 * server + 2) is refused in this version: second moments of floats need a rounding contract of their own
+ * --; a == b is allowed (the autocorrelation); pairs are ordered, (a, b, l) and (b, a, l) differ for l > 0; 0 <= lag < 2^31.
+ * At most AF_MAX_SERIES_PAIRS a call.
+ * Cells: those of af_series_windows_t, with its group / AF_POOL_SKIP rules, its tick_edges and m_s = min(counts[s]
+ * [AF_CNT_TICKS], tick_capacity).  Window w of scenario s is its rows [r0, r1) = [min(b[w], m_s), min(b[w + 1], m_s)).  The
+ * sample of pair p in that window is (x, y) = (word a of row k, word b of row k + lag) for k in [r0, r1 - lag), the words as
+ * unsigned 32-bit integers: both rows lie inside the same window of the same scenario.  A pair of rows that straddles a window
+ * edge or reaches past m_s is in no cell.  Rows at or past m_s and the padding words of a row are never read.
+ * Outputs per (g, w, p), over the windows of the members of g, all exact integers:
+ *     n             u32 [G][W][P]      the (x, y) samples
+ *     sx, sy        u64 [G][W][P]      sum x, sum y
+ *     sxx, syy, sxy u64 [G][W][P][2]   sum x * x, sum y * y, sum x * y as 128-bit sums, low word first: the low word is the
+ *                                      sum mod 2^64, the high word the carries out of it.  A cell holds < 2^32 samples of
+ *                                      products < 2^64, so the high word stays below 2^32
+ * A NULL sx, sy, sxx or syy skips that output; n and sxy are required.  An empty cell is all zeros.
+ * Determinism: the outputs are combined with integer + only (no atomics, no floating point): they depend on the data alone, not
+ * on the launch, the batch a scenario sits in, the other pairs of the call, or the run.
+ * Refused, no output word touched: n_pairs == 0 or above the cap, a, b or lag NULL, a column >= af_series_count or a ram_in_use
+ * column, a lag >= 2^31, tick_edges NULL or not strictly increasing or n_windows == 0, a group id >= n_groups,
+ * outputs.samples or outputs.counts NULL, n or sxy NULL (AF_ERR_INVALID); a cell of 2^32 or more rows, n_groups * n_windows >=
+ * 2^32 - 1, tick_capacity >= 2^31 (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).  `out` needs samples,
+ * tick_capacity and counts; clock is not read.
+ * Scratch kept by the engine (shared with the other analyzers): 4 B per edge + 16 B per pair + 4 B per group + 4 B per scenario
+ * + 1 536 B of alignment, and -- unless every group holds at most one scenario -- 52 B per (scenario, window, pair).
+ * Synchronous; the struct is written back. */
+#define AF_MAX_SERIES_PAIRS 64
+typedef struct af_series_joint {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing */
+    uint32_t n_pairs;            /* 1 .. AF_MAX_SERIES_PAIRS */
+    const uint32_t* a;           /* HOST [n_pairs] the series of x: an integer series < af_series_count */
+    const uint32_t* b;           /* HOST [n_pairs] the series of y, likewise */
+    const uint32_t* lag;         /* HOST [n_pairs] ticks between the row of x and the row of y, < 2^31 */
+    uint32_t* n;                 /* DEVICE [n_groups][n_windows][n_pairs] u32 */
+    uint64_t* sx;                /* DEVICE, same shape, u64; NULL skips */
+    uint64_t* sy;                /* DEVICE, same shape, u64; NULL skips */
+    uint64_t* sxx;               /* DEVICE [n_groups][n_windows][n_pairs][2] u64, low word first; NULL skips */
+    uint64_t* syy;               /* DEVICE, same shape; NULL skips */
+    uint64_t* sxy;               /* DEVICE, same shape */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_series_joint_t;
+int af_engine_summarize_series_joint(af_engine_t* engine, const af_outputs_t* out, af_series_joint_t* series_joint);
+
 /* Arbitrary latency QUANTILES and SLO counts per group and time window on the device (asyncflow_amd/csrc/af_quantiles.hpp):
  * p99.9 at a grid point, p90 during an outage, how many requests met a 200 ms objective in every 10 s window.  The cells and
  * their samples are af_windows_t's: cell c = g * n_windows + w holds, in ascending scenario index over the members of g,
