@@ -453,6 +453,33 @@ class AfSeriesJoint(C.Structure):
     ]
 
 
+MAX_SERIES_WARMUP_COLUMNS = 64   # AF_MAX_SERIES_WARMUP_COLUMNS
+
+
+class AfSeriesWarmup(C.Structure):
+    """``af_series_warmup_t``: request of ``af_engine_summarize_series_warmup`` (``elapsed_ms`` and ``scratch_bytes`` are
+    written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("n_columns", C.c_uint32),
+        ("columns", C.POINTER(C.c_uint32)),
+        ("batch", C.c_uint32),
+        ("batches", C.c_void_p),
+        ("trunc", C.c_void_p),
+        ("s1", C.c_void_p),
+        ("s2", C.c_void_p),
+        ("s1_all", C.c_void_p),
+        ("s2_all", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -480,6 +507,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_series_histogram",
     "af_engine_summarize_series_combined",
     "af_engine_summarize_series_joint",
+    "af_engine_summarize_series_warmup",
     "af_engine_summarize_quantiles",
     "af_engine_summarize_arrival_quantiles",
     "af_engine_summarize_state_windows",
@@ -534,6 +562,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_series_combined.restype = C.c_int
     lib.af_engine_summarize_series_joint.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesJoint)]
     lib.af_engine_summarize_series_joint.restype = C.c_int
+    lib.af_engine_summarize_series_warmup.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfSeriesWarmup)]
+    lib.af_engine_summarize_series_warmup.restype = C.c_int
     lib.af_engine_summarize_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_summarize_arrival_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]

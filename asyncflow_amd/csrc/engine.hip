@@ -26,6 +26,8 @@
 //                                          of a sample row per (group, window of ticks, combination) (af_series_combined.hpp)
 //   af_sjoint_partial / af_sjoint_fold     af_engine_summarize_series_joint: the six exact integer sums of pairs of series,
 //                                          lagged or not, per (group, window of ticks, pair) (af_series_joint.hpp)
+//   af_swarm_batches / af_swarm_cell       af_engine_summarize_series_warmup: the MSER truncation point of integer series per
+//                                          (group, window of ticks, column) in exact integers (af_series_warmup.hpp, af_wide.hpp)
 //
 // Memory plan
 //   LDS  : flow kernel: [plan blob, patched per scenario][station lists, select scratch / server segments, rings,
@@ -60,6 +62,7 @@
 #include "af_series_histogram.hpp"
 #include "af_series_combined.hpp"
 #include "af_series_joint.hpp"
+#include "af_series_warmup.hpp"
 #include "af_windowed.hpp"
 #include "af_arrival.hpp"
 #include "af_state.hpp"
@@ -3981,6 +3984,114 @@ int af_engine_summarize_series_joint(af_engine_t* e, const af_outputs_t* out, af
             hipLaunchKernelGGL(afsj::af_sjoint_fold, dim3((uint32_t)blocks), dim3(afsj::kFoldThreads), 0, st, a, f, entries);
             HIP_TRY(hipGetLastError());
         }
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // (the host vectors are read by the copies until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Warm-up truncation (MSER) of integer series per (group, window of ticks, column) (af_series_warmup.hpp).  The host checks the
+// columns and the width contract, reads the group ids back to check them and picks the load form; one streaming pass adds the
+// batch sums into a zeroed buffer and lowers the groups' batch counts, then a wave per cell finds the truncation point.
+static_assert(afwu::kMaxColumns == AF_MAX_SERIES_WARMUP_COLUMNS, "the kernel's limit is the header's");
+
+int af_engine_summarize_series_warmup(af_engine_t* e, const af_outputs_t* out, af_series_warmup_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty series warmup request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "series_warmup.tick_edges is required");
+    if (!req->batches || !req->trunc) return fail(AF_ERR_INVALID, "series_warmup.batches and trunc are required");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, cap = out->tick_capacity, Cn = req->n_columns, B = req->batch;
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch, n_edges = e->args.n_edges;
+    if (Cn == 0 || Cn > AF_MAX_SERIES_WARMUP_COLUMNS)
+        return fail(AF_ERR_INVALID, "series_warmup.n_columns must be 1 .. AF_MAX_SERIES_WARMUP_COLUMNS (" + std::to_string(AF_MAX_SERIES_WARMUP_COLUMNS) + ")");
+    if (!req->columns) return fail(AF_ERR_INVALID, "series_warmup.columns is required");
+    if (B == 0) return fail(AF_ERR_INVALID, "series_warmup.batch must be at least 1 tick");
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    if (S == 0 || pitch < S || pitch % 4u) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+    for (uint32_t c = 0; c < Cn; ++c) {
+        const uint32_t j = req->columns[c];
+        if (j >= S) return fail(AF_ERR_INVALID, "column " + std::to_string(c) + " names series " + std::to_string(j) + " of " + std::to_string(S));
+        if (j >= n_edges && (j - n_edges) % 3u == 2u)
+            return fail(AF_ERR_INVALID, "column " + std::to_string(c) + " names a ram_in_use column (series " + std::to_string(j) + "): the warm-up rule takes integer series only");
+    }
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->samples || cap == 0) return fail(AF_ERR_INVALID, "series warmup needs outputs.samples");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    if ((uint64_t)n * B > (1ull << 32)) return fail(AF_ERR_CAPACITY, "n_scenarios * batch must be at most 2^32 (a batch sum is 64 bits)");
+    // the batches a window can hold, and where its batches start in a (group, column)'s sequence
+    std::vector<uint32_t> boff((size_t)W + 1u, 0u);
+    for (uint32_t w = 0; w < W; ++w) {
+        const uint32_t nb = (std::min(req->tick_edges[w + 1u], cap) - std::min(req->tick_edges[w], cap)) / B;
+        if (nb >= afwu::kMaxWindowBatches) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " holds 2^25 or more batches");
+        boff[(size_t)w + 1u] = boff[w] + nb;   // (at most tick_capacity / B in all: below 2^31)
+    }
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    {
+        std::vector<uint32_t> grp;
+        if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    }
+    const uint32_t NB = boff[W];
+    const bool staged = pitch <= afwu::kMaxStagedPitch && reinterpret_cast<uintptr_t>(out->samples) % 16u == 0u;
+    // scratch layout (256-byte aligned parts)
+    ScratchLayout lay;
+    const size_t y_bytes = (size_t)G * Cn * NB * 8u, j_bytes = (size_t)G * W * 4u;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u), o_boff = lay.part(((size_t)W + 1u) * 4u), o_cols = lay.part((size_t)Cn * 4u),
+                 o_jmin = lay.part(j_bytes), o_y = lay.part(y_bytes);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    unsigned char* b = e->d_pool;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(b + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_boff, boff.data(), boff.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_cols, req->columns, (size_t)Cn * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(b + o_jmin, 0xFF, j_bytes, st));   // afwu::kNone: no member yet
+    if (y_bytes) HIP_TRY(hipMemsetAsync(b + o_y, 0, y_bytes, st));
+    afwu::SwArgs a{};
+    a.samples = out->samples;
+    a.counts = out->counts;
+    a.tick_cap = cap;
+    a.pitch = pitch;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.group = req->group;
+    a.n_scen = n;
+    a.n_groups = G;
+    a.n_win = W;
+    a.edges = reinterpret_cast<const uint32_t*>(b + o_edges);
+    a.boff = reinterpret_cast<const uint32_t*>(b + o_boff);
+    a.n_batches = NB;
+    a.batch = B;
+    a.n_cols = Cn;
+    a.cols = reinterpret_cast<const uint32_t*>(b + o_cols);
+    a.staged = staged ? 1u : 0u;
+    a.p4 = pitch / 4u;
+    a.q64 = 64u / a.p4;
+    a.r64 = 64u % a.p4;
+    a.y = reinterpret_cast<uint64_t*>(b + o_y);
+    a.jmin = reinterpret_cast<uint32_t*>(b + o_jmin);
+    a.batches = req->batches;
+    a.trunc = req->trunc;
+    a.s1 = req->s1;
+    a.s2 = req->s2;
+    a.s1_all = req->s1_all;
+    a.s2_all = req->s2_all;
+    // a wave per (scenario, run of windows): runs as long as leave the chip some 32 768 waves (af_engine_summarize_series_windows' rule)
+    const uint32_t want_runs = (32768u + n - 1u) / n;
+    a.run = std::max(1u, W / want_runs);
+    const uint64_t items = (uint64_t)n * ((W + a.run - 1u) / a.run);
+    const size_t lds = staged ? (size_t)afwu::kWaves * 64u * (pitch + 1u) * 4u : 0u;
+    hipLaunchKernelGGL(afwu::af_swarm_batches, dim3((uint32_t)((items + afwu::kWaves - 1u) / afwu::kWaves)), dim3(afwu::kThreads), lds, st, a);
+    HIP_TRY(hipGetLastError());
+    const uint64_t cells = (uint64_t)G * W * Cn;   // a wave each
+    for (uint64_t f = 0; f < cells; f += kBlocksPerLaunch * afwu::kWaves) {
+        const uint64_t blocks = std::min<uint64_t>(kBlocksPerLaunch, (cells - f + afwu::kWaves - 1u) / afwu::kWaves);
+        hipLaunchKernelGGL(afwu::af_swarm_cell, dim3((uint32_t)blocks), dim3(afwu::kThreads), 0, st, a, f, cells);
+        HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(st));   // (the host vectors are read by the copies until here)
     req->scratch_bytes = e->pool_cap;

@@ -593,6 +593,34 @@ class Engine:
                "af_engine_summarize_series_joint")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_series_warmup(self, n: int, n_groups: int, tick_edges: Any, columns: Any, batch: int = 5, *, samples_ptr: int,
+                                tick_capacity: int, counts_ptr: int, batches_ptr: int, trunc_ptr: int, s1_ptr: int = 0,
+                                s2_ptr: int = 0, s1_all_ptr: int = 0, s2_all_ptr: int = 0, group_ptr: int = 0) -> tuple[float, int]:
+        """Warm-up truncation of integer series on the device (``af_engine_summarize_series_warmup``): the MSER rule on
+        batches of ``batch`` ticks, pooled over the members of a group.  Per (group, window of ticks) ``batches`` uint32
+        [n_groups, W]; per column also ``trunc`` uint32 [n_groups, W, C], ``s1`` / ``s1_all`` uint64 [n_groups, W, C, 2] and
+        ``s2`` / ``s2_all`` uint64 [n_groups, W, C, 3] (the sums at the truncation point and at 0, low word first); a pointer
+        of 0 skips every output but ``batches`` and ``trunc``.  ``tick_edges``: HOST uint32 tick indices, strictly
+        increasing; ``columns``: HOST series indices, any order.  ``group_ptr`` as in :meth:`summarize_pooled`.  The library
+        checks the columns.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_tick_edges, check_warmup_batch
+
+        e = check_tick_edges(tick_edges)
+        n_b = check_warmup_batch(batch)
+        raw = np.asarray(columns)
+        if raw.ndim != 1 or raw.dtype.kind not in "iu" or (raw.size and (raw.min() < 0 or raw.max() > 0xFFFFFFFF)):
+            msg = "columns must be a vector of series indices"
+            raise ValueError(msg)
+        cols = np.ascontiguousarray(raw, dtype=np.uint32)
+        pu = C.POINTER(C.c_uint32)
+        out = _abi.AfOutputs(0, None, int(tick_capacity), C.c_void_p(samples_ptr or None), C.c_void_p(counts_ptr or None))
+        req = _abi.AfSeriesWarmup(int(n), int(n_groups), int(e.shape[0] - 1), C.c_void_p(group_ptr or None), e.ctypes.data_as(pu),
+                                  int(cols.shape[0]), cols.ctypes.data_as(pu), n_b,
+                                  *(C.c_void_p(p or None) for p in (batches_ptr, trunc_ptr, s1_ptr, s2_ptr, s1_all_ptr, s2_all_ptr)), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_series_warmup(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_series_warmup")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def gather(self, comm: "C.c_void_p | int", world_size: int, n_local: int, local: dict, gathered: dict, *,
                rps_buckets: int = 0, hist_bins: int = 0) -> _abi.AfStats:
         """``af_engine_gather``: ONE grouped RCCL all-gather of the per-scenario summaries.

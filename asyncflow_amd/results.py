@@ -1147,6 +1147,192 @@ def autocorrelation_time(acf: Any, n0: Any) -> dict[str, np.ndarray]:
     return {"tau": tau, "tau_truncated": valid & ~found, "ess": ess}
 
 
+WARMUP_SUMS = ("s1", "s2", "s1_all", "s2_all")
+WARMUP_STATISTICS = ("warmup_s", "mean_all", "mean_steady", "mser_all", "mser_steady")
+
+
+def check_warmup_batch(batch: Any) -> int:
+    """``batch``, the ticks of a batch of the warm-up rule, as an int, or ValueError: a whole number in [1, 2^32)."""
+    if isinstance(batch, (bool, np.bool_)) or not isinstance(batch, (int, np.integer)) or not 1 <= int(batch) < 2 ** 32:
+        msg = f"batch must be a whole number of ticks in [1, 2^32), not {batch!r}"
+        raise ValueError(msg)
+    return int(batch)
+
+
+def _warmup_columns(series: Any, names: list[str], n_edges: int) -> np.ndarray:
+    """``series`` -- None (every integer series), names of ``names`` or indices, any order, duplicates allowed -- as int64
+    series indices; ValueError for an unknown series, no series, and a ``ram_in_use`` column."""
+    ram = ram_columns(len(names), n_edges)
+    if series is None:
+        return np.nonzero(~ram)[0].astype(np.int64)
+    if isinstance(series, (str, bytes, int, np.integer)) and not isinstance(series, (bool, np.bool_)):
+        series = [series]
+    items = [x.decode() if isinstance(x, bytes) else x for x in series]
+    cols: list[int] = []
+    for x in items:
+        if isinstance(x, str):
+            if x not in names:
+                msg = f"unknown series {x!r} (series_names(): {names})"
+                raise ValueError(msg)
+            cols.append(names.index(x))
+        elif isinstance(x, (bool, np.bool_)) or not isinstance(x, (int, np.integer)) or not 0 <= int(x) < len(names):
+            msg = f"{x!r} is no series name or index below {len(names)}"
+            raise ValueError(msg)
+        else:
+            cols.append(int(x))
+    if not cols:
+        msg = "series selects no series"
+        raise ValueError(msg)
+    for j in cols:
+        if ram[j]:
+            msg = f"{names[j]!r} is a ram_in_use column; the warm-up rule takes integer series only"
+            raise ValueError(msg)
+    return np.array(cols, dtype=np.int64)
+
+
+def warmup_truncation(y: Any) -> tuple[int, int, int, int, int]:
+    """The MSER truncation point of ONE sequence of batch sums ``y`` (non-negative integers), in Python integers:
+    ``(d, S1(d), S2(d), S1(0), S2(0))`` with ``S1(d) = sum(y[d:])``, ``S2(d) = sum(v * v for v in y[d:])``, ``m = J - d``,
+    ``A(d) = m * S2(d) - S1(d) ** 2`` and ``d`` the smallest of ``0 .. J // 2`` that minimises ``A(d) / m ** 3``, compared
+    exactly as ``A(d1) * m2 ** 3 < A(d2) * m1 ** 3``.  No batch: all zeros."""
+    seq = [int(v) for v in y]
+    n_b = len(seq)
+    if n_b == 0:
+        return 0, 0, 0, 0, 0
+    s1 = s1_all = sum(seq)
+    s2 = s2_all = sum(v * v for v in seq)
+    best = (0, n_b * s2 - s1 * s1, n_b ** 3, s1, s2)                  # d, A, m^3 and the sums at d
+    for d in range(1, n_b // 2 + 1):
+        s1 -= seq[d - 1]
+        s2 -= seq[d - 1] * seq[d - 1]
+        m = n_b - d
+        a = m * s2 - s1 * s1
+        if a * best[2] < best[1] * m ** 3:                            # (strictly: the smaller d wins a tie)
+            best = (d, a, m ** 3, s1, s2)
+    return best[0], best[3], best[4], s1_all, s2_all
+
+
+def series_warmup_sums(members: Any, tick_edges: Any, n_edges: int, batch: Any, columns: Any = None) -> dict[str, np.ndarray]:
+    """The warm-up truncation (MSER on pooled batch sums) of ONE group per window of ticks and column, in Python integers:
+    the definition the device analyzer (``af_engine_summarize_series_warmup``) matches word for word.  ``members`` is one
+    scenario's sampled series (uint32 words [n_series, ticks]) or a list of them, one per replica of the group (an empty
+    list: a group without a member).  With ``b = tick_edges`` and ``B = batch`` (:func:`check_warmup_batch`): member ``s`` of
+    ``m_s`` ticks has the rows ``[r0, r1) = [min(b[w], m_s), min(b[w + 1], m_s))`` of window ``w``; its batch ``j`` is the
+    rows ``[b[w] + j B, b[w] + (j + 1) B)``, complete when inside ``[r0, r1)``; ``J`` is the minimum over the members of
+    their complete batches (0 without a member; a trailing partial batch is in no cell); ``Y_j`` is the sum over the
+    members and the ``B`` rows of batch ``j`` of the word as an unsigned integer; and the truncation point is
+    :func:`warmup_truncation` of ``Y_0 .. Y_{J - 1}``.  ``columns``: None (every integer series) or integer series indices,
+    any order, duplicates allowed; a ``ram_in_use`` column is refused.  Returns ``batches`` int64 [W] (``J``), ``trunc``
+    int64 [W, C] (``d*``), ``s1``, ``s2`` (the sums at ``d*``), ``s1_all``, ``s2_all`` (at ``d = 0``) as object arrays
+    [W, C] of Python integers, and ``columns``."""
+    b = check_tick_edges(tick_edges).astype(np.int64)
+    n_b = check_warmup_batch(batch)
+    arrs = [members] if isinstance(members, np.ndarray) else list(members)
+    words = [np.ascontiguousarray(m).view(np.uint32) for m in arrs]
+    for w in words:
+        if w.ndim != 2 or w.shape[0] != words[0].shape[0]:
+            msg = f"every member must be words [n_series, ticks] of one plan, not of shape {w.shape}"
+            raise ValueError(msg)
+    if words:
+        n_series = int(words[0].shape[0])
+        cols = _warmup_columns(None if columns is None else [int(c) for c in np.asarray(columns).reshape(-1)],
+                               [str(j) for j in range(n_series)], n_edges)
+    else:
+        cols = np.asarray([] if columns is None else columns, dtype=np.int64).reshape(-1)
+    n_win, n_c = b.shape[0] - 1, int(cols.shape[0])
+    out: dict[str, np.ndarray] = {"batches": np.zeros(n_win, dtype=np.int64), "trunc": np.zeros((n_win, n_c), dtype=np.int64)}
+    for k in WARMUP_SUMS:
+        out[k] = np.zeros((n_win, n_c), dtype=object)
+        out[k][...] = 0
+    out["columns"] = cols
+    for w in range(n_win):
+        complete = [(min(int(b[w + 1]), x.shape[1]) - min(int(b[w]), x.shape[1])) // n_b for x in words]
+        n_j = min(complete) if complete else 0
+        out["batches"][w] = n_j
+        if n_j == 0:
+            continue
+        lo, hi = int(b[w]), int(b[w]) + n_j * n_b                     # (a member with a complete batch has r0 = b[w])
+        for c, col in enumerate(cols):
+            parts = [x[col, lo:hi].astype(np.uint64).reshape(n_j, n_b).sum(axis=1, dtype=np.uint64) for x in words]   # B < 2^32 words below 2^32
+            if len(words) * n_b <= 2 ** 32:                           # the device's width contract: Y < 2^64, exact in uint64
+                y = np.sum(parts, axis=0, dtype=np.uint64).tolist()
+            else:
+                y = [sum(int(p[j]) for p in parts) for j in range(n_j)]
+            d, s1, s2, s1_all, s2_all = warmup_truncation(y)
+            out["trunc"][w, c] = d
+            out["s1"][w, c], out["s2"][w, c], out["s1_all"][w, c], out["s2_all"][w, c] = s1, s2, s1_all, s2_all
+    return out
+
+
+def _float_of(num: int, den: int) -> float:
+    """The correctly rounded float64 of the fraction ``num / den``; NaN for ``den == 0``."""
+    from fractions import Fraction
+
+    return float(Fraction(num, den)) if den else float("nan")
+
+
+def series_warmup_statistics(sums: dict[str, Any], batch: Any, replicas: Any, sample_period: float,
+                             tick_edges: Any) -> dict[str, np.ndarray]:
+    """What the warm-up sums mean, per cell: ``sums`` holds ``batches`` [..., W], ``trunc`` and ``s1``, ``s2``, ``s1_all``,
+    ``s2_all`` [..., W, C] as :func:`series_warmup_sums` or the device returns them; ``replicas`` is the number of members
+    ``R`` of the group (a scalar, or one value per leading index).  With ``J = batches``, ``d = trunc``, ``m = J - d``,
+    ``B = batch`` and ``b = tick_edges``:
+
+    * ``warmup_tick = b[w] + d * B`` (int64), the first tick of the steady regime; ``warmup_s = warmup_tick *
+      sample_period``;
+    * ``converged = trunc < batches // 2`` (bool): the usual MSER rule -- a minimum at the search limit means the window is
+      too short to show a steady regime;
+    * ``mean_all = S1(0) / (J B R)`` and ``mean_steady = S1(d) / (m B R)``: the mean per tick and replica over all complete
+      batches and over the steady ones;
+    * ``mser_all = A(0) / (J^3 (B R)^2)`` and ``mser_steady = A(d) / (m^3 (B R)^2)`` with ``A = m S2 - S1^2``: the MSER
+      statistic of the batch MEANS per tick and replica, ``sum (Z_j - mean)^2 / m^2``.
+
+    Every float is the correctly rounded float64 of its exact fraction (``fractions.Fraction``), NaN where ``J == 0`` (or
+    ``R == 0``).  Returns arrays of ``trunc``'s shape."""
+    from fractions import Fraction
+
+    n_b = check_warmup_batch(batch)
+    b = check_tick_edges(tick_edges).astype(np.int64)
+    trunc = np.asarray(sums["trunc"], dtype=np.int64)
+    nj = np.asarray(sums["batches"], dtype=np.int64)
+    if trunc.ndim < 2 or nj.shape != trunc.shape[:-1] or trunc.shape[-2] != b.shape[0] - 1:
+        msg = f"trunc of shape {trunc.shape} next to batches of shape {nj.shape} and {b.shape[0] - 1} windows"
+        raise ValueError(msg)
+    shape = trunc.shape
+    rep = np.broadcast_to(np.asarray(replicas, dtype=np.int64).reshape(np.shape(replicas) + (1,) * (trunc.ndim - np.ndim(replicas))), shape)
+    nj_c = np.broadcast_to(nj[..., None], shape)
+    tick = b[:-1][:, None] + trunc * n_b
+    period = Fraction(float(sample_period))
+    flat = {k: [int(v) for v in np.asarray(sums[k], dtype=object).reshape(-1)] for k in WARMUP_SUMS}
+    out = {k: np.full(trunc.size, np.nan) for k in WARMUP_STATISTICS}
+    for i, (j, d, r, t) in enumerate(zip(nj_c.reshape(-1).tolist(), trunc.reshape(-1).tolist(), rep.reshape(-1).tolist(),
+                                         tick.reshape(-1).tolist())):
+        if j == 0 or r == 0:
+            continue
+        m, scale = j - d, n_b * r
+        out["warmup_s"][i] = float(t * period)
+        out["mean_all"][i] = _float_of(flat["s1_all"][i], j * scale)
+        out["mean_steady"][i] = _float_of(flat["s1"][i], m * scale)
+        out["mser_all"][i] = _float_of(j * flat["s2_all"][i] - flat["s1_all"][i] ** 2, j ** 3 * scale * scale)
+        out["mser_steady"][i] = _float_of(m * flat["s2"][i] - flat["s1"][i] ** 2, m ** 3 * scale * scale)
+    res: dict[str, np.ndarray] = {k: v.reshape(shape) for k, v in out.items()}
+    res["warmup_tick"] = tick
+    res["converged"] = trunc < (nj_c // 2)
+    return res
+
+
+def series_warmup_cut(summary: dict[str, Any]) -> np.ndarray:
+    """Where to cut the transient away, per (group, window): the largest ``warmup_s`` of the selected series of ``summary``
+    (:func:`series_warmup_statistics`, :meth:`BatchedResults.series_warmup_summary`), NaN if any of them did not converge
+    (or the cell holds no batch) -- the ``t0`` to hand to ``edges=[t0, T]`` of the latency analyzers and, as a tick, to
+    ``tick_edges`` of the series analyzers.  float64 of ``warmup_s``'s shape without its last axis."""
+    s = np.asarray(summary["warmup_s"], dtype=np.float64)
+    ok = np.asarray(summary["converged"], dtype=bool).all(axis=-1) & ~np.isnan(s).any(axis=-1)
+    if s.shape[-1] == 0:
+        return np.full(s.shape[:-1], np.nan)
+    return np.where(ok, np.where(np.isnan(s), -np.inf, s).max(axis=-1), np.nan)
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -1386,6 +1572,29 @@ class ScenarioResults:
         out: dict[str, Any] = series_joint_sums(self._samples, b, self._plan.n_edges, (ca, cb, lag))
         out.update(series_joint_statistics(out))
         out.update(labels=labels, a=ca, b=cb, lag=lag, tick_edges=b)
+        return out
+
+    def get_series_warmup(self, batch: int = 5, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                          tick_edges: Any = None, series: Any = None) -> dict[str, Any]:
+        """Where this scenario's sampled series leave their initial transient, per window of ticks, from the host
+        definition: the MSER rule on batches of ``batch`` ticks (:func:`series_warmup_sums` with this scenario as the only
+        member, :func:`series_warmup_statistics`).  ``series``: None (every integer series), names of
+        :func:`series_names_of` or indices; no ``ram_in_use`` column.  Windows as in :meth:`get_series_window_stats`; none
+        given: one window over the whole run.  Returns ``batches`` [W], ``trunc``, the four sums, ``warmup_tick``,
+        ``warmup_s``, ``converged``, ``mean_all``, ``mean_steady``, ``mser_all``, ``mser_steady`` [W, C], ``cut`` [W]
+        (:func:`series_warmup_cut`) and ``series`` (the names), ``columns``, ``batch``, ``tick_edges``."""
+        if self._samples is None:
+            msg = "run(collect_samples=False) kept no sampled series"
+            raise RuntimeError(msg)
+        n_b = check_warmup_batch(batch)
+        if window_s is None and ticks_per_window is None and tick_edges is None:
+            tick_edges = [0, max(self._plan.tick_count, 1)]
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        names = series_names_of(self._plan)
+        cols = _warmup_columns(series, names, self._plan.n_edges)
+        out: dict[str, Any] = series_warmup_sums(np.asarray(self._samples), b, self._plan.n_edges, n_b, cols)
+        out.update(series_warmup_statistics(out, n_b, 1, self._plan.sample_period, b))
+        out.update(cut=series_warmup_cut(out), series=[names[j] for j in cols], batch=n_b, tick_edges=b)
         return out
 
     def get_latency_by_state(self, series: Any, bins: int = 8, lo: float = 0.0, width: float = 1.0, window_s: float | None = None,
@@ -2922,6 +3131,153 @@ class BatchedResults:
         _write_columns(str(path), cols, n_groups)
         return cols
 
+    def _series_warmup_call(self, cols: np.ndarray, batch: int, b: np.ndarray, ids: np.ndarray,
+                            n_groups: int) -> tuple[dict[str, np.ndarray], float, int]:
+        """One call of ``af_engine_summarize_series_warmup`` (at most 64 columns): ``batches`` int64 [G, W], ``trunc`` int64
+        [G, W, C] and the four sums as Python integers [G, W, C], the call's wall time in ms and the engine's scratch size."""
+        import torch
+
+        from .engine import Engine
+
+        samples = self._samples_t
+        dev = samples.device
+        n_win, n_c = int(b.shape[0] - 1), int(cols.shape[0])
+        nb = torch.empty((n_groups, n_win), dtype=torch.int32, device=dev)
+        trunc = torch.empty((n_groups, n_win, n_c), dtype=torch.int32, device=dev)
+        wide = {k: torch.empty((n_groups, n_win, n_c, 2 if k.startswith("s1") else 3), dtype=torch.int64, device=dev) for k in WARMUP_SUMS}
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        ms, scratch = self._summ_engine.summarize_series_warmup(
+            len(self), n_groups, b, cols, batch, samples_ptr=samples.data_ptr(), tick_capacity=int(samples.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), batches_ptr=nb.data_ptr(), trunc_ptr=trunc.data_ptr(), group_ptr=grp.data_ptr(),
+            **{f"{k}_ptr": t.data_ptr() for k, t in wide.items()})
+        out: dict[str, np.ndarray] = {"batches": nb.cpu().numpy().view(np.uint32).astype(np.int64),
+                                      "trunc": trunc.cpu().numpy().view(np.uint32).astype(np.int64)}
+        for k, t in wide.items():
+            w = t.cpu().numpy().view(np.uint64).astype(object)
+            out[k] = sum(w[..., i] * (1 << (64 * i)) for i in range(w.shape[-1]))
+        return out, ms, scratch
+
+    def series_warmup_summary(self, batch: int = 5, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                              tick_edges: Any = None, by: Any = None, series: Any = None) -> dict[str, Any]:
+        """Where the sampled series leave their initial transient, per (group, window of ticks, series): every sweep starts
+        from an empty system, and replicas shrink the band around a mean that still averages the ramp-up in.  The MSER rule
+        (White 1997; ``batch = 5`` is MSER-5) in pooled form: the batch sums ``Y_j`` of ``batch`` ticks are added over the
+        group's replicas, and the truncation point ``d*`` is the smallest ``d <= J / 2`` that minimises the variance of the
+        remaining batch means over their number.  The HIP analyzer ``af_engine_summarize_series_warmup`` computes it in
+        exact integers, equal word for word to :func:`series_warmup_sums` of the group's members;
+        :func:`series_warmup_statistics` makes the floats on the host.  One short member shortens a cell for all
+        (``batches``); leave a broken replica out with group id -1.  ``series``: None (every integer series), names of
+        :meth:`series_names` or indices, any order, duplicates allowed, no ``ram_in_use`` column; more than 64 are split
+        into several calls.  Windows and ``by`` as in :meth:`series_window_summary`; no window given: one window over the
+        whole run; a window that starts at an injected event answers how long the system takes to reach its new regime.
+        Returns numpy arrays: ``batches`` int64 [G, W]; ``trunc``, ``warmup_tick`` int64, ``warmup_s``, ``mean_all``,
+        ``mean_steady``, ``mser_all``, ``mser_steady`` float64 and ``converged`` bool [G, W, C]; the sums ``s1``, ``s2``,
+        ``s1_all``, ``s2_all`` as Python integers [G, W, C]; ``cut`` [G, W] (:func:`series_warmup_cut`: the ``t0`` for
+        ``edges=[t0, T]``); and ``series`` (the names), ``columns``, ``batch``, ``tick_edges``, ``times``, ``replicas`` [G],
+        ``series_warmup_ms`` (all calls), ``scratch_bytes``, ``calls``."""
+        self._require_samples()
+        n_b = check_warmup_batch(batch)
+        names = self.series_names()
+        cols = _warmup_columns(series, names, self.plan.n_edges)
+        if window_s is None and ticks_per_window is None and tick_edges is None:
+            tick_edges = [0, max(self.plan.tick_count, 1)]
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        parts, total_ms, scratch = [], 0.0, 0
+        for at in range(0, len(cols), _abi.MAX_SERIES_WARMUP_COLUMNS):
+            part, ms, scratch = self._series_warmup_call(cols[at:at + _abi.MAX_SERIES_WARMUP_COLUMNS], n_b, b, ids, n_groups)
+            parts.append(part)
+            total_ms += ms
+        out: dict[str, Any] = {"batches": parts[0]["batches"]}
+        for k in ("trunc", *WARMUP_SUMS):
+            out[k] = np.concatenate([p[k] for p in parts], axis=2)
+        replicas = np.bincount(ids[ids >= 0], minlength=n_groups)
+        out.update(series_warmup_statistics(out, n_b, replicas, self.plan.sample_period, b))
+        out.update(cut=series_warmup_cut(out), series=[names[j] for j in cols], columns=cols, batch=n_b, tick_edges=b,
+                   times=b[:-1].astype(np.float64) * self.plan.sample_period, replicas=replicas, series_warmup_ms=total_ms,
+                   scratch_bytes=scratch, calls=len(parts))
+        return out
+
+    def series_warmup_bands(self, batch: int = 5, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                            tick_edges: Any = None, by: Any = None, series: Any = None, level: float = 0.95,
+                            q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """How much the warm-up time varies from replica to replica: every scenario's own ``warmup_s``
+        (``series_warmup_summary(by="scenario")``), then per group (``by``), window and series, over the group's replicas
+        that hold a batch in the window, what :meth:`series_window_bands` gives -- numpy float64 [G, W, C] each
+        (:func:`window_bands_by_group`); ``n`` int64 [G, W] are the replicas that count; ``converged_share`` [G, W, C] is
+        the share of those whose own truncation point lies below the search limit (NaN without one); ``pooled`` is the
+        grouped call's ``warmup_s`` and ``pooled_converged`` its ``converged``."""
+        self._require_samples()
+        if window_s is None and ticks_per_window is None and tick_edges is None:
+            tick_edges = [0, max(self.plan.tick_count, 1)]
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        return self._series_warmup_bands(batch, b, by, series, level, q)[0]
+
+    def _series_warmup_bands(self, batch: int, b: np.ndarray, by: Any, series: Any, level: float,
+                             q: tuple[float, float]) -> tuple[dict[str, Any], dict[str, Any]]:
+        """:meth:`series_warmup_bands` for resolved tick edges; also returns the grouped summary its ``pooled`` is from."""
+        import torch
+
+        ids, n_groups = self._window_groups(by)
+        per = self.series_warmup_summary(batch, tick_edges=b, by="scenario", series=series)
+        valid = per["batches"] > 0
+        out = window_bands_by_group(torch.from_numpy(np.ascontiguousarray(per["warmup_s"])), ids, n_groups, level, q,
+                                    valid=torch.from_numpy(valid))
+        share = np.full((n_groups, *per["converged"].shape[1:]), np.nan)
+        for g in range(n_groups):
+            mem = ids == g
+            cnt = valid[mem].sum(axis=0)                                                   # [W]
+            hit = (per["converged"][mem] & valid[mem][:, :, None]).sum(axis=0)             # [W, C]
+            share[g] = np.where(cnt[:, None] > 0, hit / np.maximum(cnt, 1)[:, None], np.nan)
+        out["converged_share"] = share
+        pooled = self.series_warmup_summary(batch, tick_edges=b, by=ids, series=series)
+        out["pooled"] = pooled["warmup_s"][:n_groups]
+        out["pooled_converged"] = pooled["converged"][:n_groups]
+        out.update(series=per["series"], columns=per["columns"], batch=per["batch"], tick_edges=b, times=per["times"])
+        return out, pooled
+
+    def save_series_warmup_summary(self, path: str, by: Any = None, *, batch: int = 5, window_s: float | None = None,
+                                   ticks_per_window: int | None = None, tick_edges: Any = None, series: Any = None,
+                                   level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the warm-up truncation with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas``, ``series_warmup_batches`` and ``series_warmup_cut`` [G, W] and per series the [G, W] columns
+        ``series_warmup_tick:<name>``, ``series_warmup_s:<name>``, ``series_warmup_converged:<name>`` (0 / 1),
+        ``series_warmup_mean_all:<name>``, ``series_warmup_mean_steady:<name>`` -- the group's replicas taken together --
+        and ``series_warmup_q05:<name>`` / ``series_warmup_q95:<name>`` / ``series_warmup_converged_share:<name>`` (of the
+        replicas' own warm-up times, :meth:`series_warmup_bands`).  ``series_warmup_tick_edges`` [W + 1],
+        ``series_warmup_times`` [W] and ``series_warmup_batch`` [1] are per-file vectors.  ``.npz`` or ``.parquet``;
+        :func:`load_summary` reads it back."""
+        self._require_samples()
+        if window_s is None and ticks_per_window is None and tick_edges is None:
+            tick_edges = [0, max(self.plan.tick_count, 1)]
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        bands, pooled = self._series_warmup_bands(batch, b, by, series, level, (0.05, 0.95))
+        n_groups = int(bands["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        cols["series_warmup_batches"] = np.ascontiguousarray(pooled["batches"][:n_groups], dtype=np.int64)
+        cols["series_warmup_cut"] = np.ascontiguousarray(pooled["cut"][:n_groups], dtype=np.float64)
+        for c, name in enumerate(bands["series"]):
+            cols[f"series_warmup_tick:{name}"] = np.ascontiguousarray(pooled["warmup_tick"][:n_groups, :, c], dtype=np.int64)
+            cols[f"series_warmup_s:{name}"] = np.ascontiguousarray(pooled["warmup_s"][:n_groups, :, c])
+            cols[f"series_warmup_converged:{name}"] = np.ascontiguousarray(pooled["converged"][:n_groups, :, c], dtype=np.int64)
+            cols[f"series_warmup_mean_all:{name}"] = np.ascontiguousarray(pooled["mean_all"][:n_groups, :, c])
+            cols[f"series_warmup_mean_steady:{name}"] = np.ascontiguousarray(pooled["mean_steady"][:n_groups, :, c])
+            cols[f"series_warmup_q05:{name}"] = np.ascontiguousarray(bands["q_lo"][:, :, c])
+            cols[f"series_warmup_q95:{name}"] = np.ascontiguousarray(bands["q_hi"][:, :, c])
+            cols[f"series_warmup_converged_share:{name}"] = np.ascontiguousarray(bands["converged_share"][:, :, c])
+        cols["series_warmup_tick_edges"] = np.asarray(b, dtype=np.float64)
+        cols["series_warmup_times"] = np.asarray(bands["times"], dtype=np.float64)
+        cols["series_warmup_batch"] = np.asarray([pooled["batch"]], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
     def differing_scenarios(self, other: "BatchedResults", chunk: int = 512) -> np.ndarray:
         """Indices of the scenarios whose results differ from ``other``'s, compared ON THE DEVICE over the whole batch
         (see :func:`differing_scenarios`): two runs of one sweep by different kernel families must return an empty array."""
@@ -3374,6 +3730,18 @@ class ShardedResults:
 
     def save_series_joint_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_series_joint_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_warmup_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_warmup_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def series_warmup_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "series_warmup_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_series_warmup_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_series_warmup_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
 
     def state_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:

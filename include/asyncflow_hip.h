@@ -778,6 +778,63 @@ typedef struct af_series_joint {
 } af_series_joint_t;
 int af_engine_summarize_series_joint(af_engine_t* engine, const af_outputs_t* out, af_series_joint_t* series_joint);
 
+/* WARM-UP TRUNCATION OF THE SAMPLED SERIES per window of ticks and group on the device
+ * (asyncflow_amd/csrc/af_series_warmup.hpp): every sweep starts from an empty system, and every statistic of a window averages
+ * that transient in.  The initial-transient rule MSER (White 1997; MSER-5 with batch = 5) says where the steady regime begins,
+ * applied in pooled form to the batch sums of the ensemble over a group's members (Welch), and stated entirely in integers.
+ * Cells: (g, w, c) = those of af_series_windows_t, with its group / AF_POOL_SKIP rules, its tick_edges and m_s = min(counts[s]
+ * [AF_CNT_TICKS], tick_capacity); series columns[c] must be an INTEGER series -- a ram_in_use column (index n_edges + 3 * server
+ * + 2) is refused as in af_series_joint_t: second moments of floats need a rounding contract of their own.  Any order of the
+ * columns, duplicates allowed, at most AF_MAX_SERIES_WARMUP_COLUMNS a call.
+ * With B = batch >= 1 ticks: member s has the rows [r0, r1) = [min(b[w], m_s), min(b[w + 1], m_s)) of window w; its batch j is
+ * the rows [b[w] + j B, b[w] + (j + 1) B), complete when inside [r0, r1).  J = the minimum over the members of g of their
+ * complete batches -- the same for every column; 0 for a group without a member or with a member that stored no row of the
+ * window: one short member shortens the cell for all (`batches` shows it; leave a broken replica out with AF_POOL_SKIP).  A
+ * trailing partial batch is in no cell.  For j < J
+ *     Y_j = the sum over the members and the B rows of batch j of the word as an unsigned 32-bit integer
+ *     S1(d) = sum_{j >= d} Y_j,  S2(d) = sum_{j >= d} Y_j^2,  m = J - d,  A(d) = m S2(d) - S1(d)^2 >= 0,  MSER(d) = A(d) / m^3
+ *     d* = the smallest d in 0 .. J / 2 that minimises MSER(d), compared exactly by A(d1) m2^3 < A(d2) m1^3; J = 0: d* = 0.
+ * Width contract, checked statically: n_scenarios * B <= 2^32 (Y_j < 2^64) and every window holds fewer than 2^25 batches.
+ * Then S1 < 2^89, S2 < 2^153, A < 2^178, m^3 < 2^75 and every compared product is below 2^253: 256-bit arithmetic is exact.
+ * Outputs, all exact integers:
+ *     batches         u32 [G][W]         J
+ *     trunc           u32 [G][W][C]      d*: the steady regime of the window starts at tick b[w] + d* B
+ *     s1, s1_all      u64 [G][W][C][2]   S1(d*) and S1(0), low word first
+ *     s2, s2_all      u64 [G][W][C][3]   S2(d*) and S2(0), low word first
+ * A NULL s1, s2, s1_all or s2_all skips that output; batches and trunc are required.  A cell with J = 0 is all zeros.
+ * Determinism: integer additions and an integer minimum only (64-bit integer atomics into a zeroed buffer, no floating point):
+ * the outputs depend on the data alone, not on the launch, the batch a scenario sits in, the other columns of the call, or the
+ * run.
+ * Refused, no output word touched: batch == 0, n_columns == 0 or above the cap, columns NULL, a column >= af_series_count or a
+ * ram_in_use column, tick_edges NULL or not strictly increasing or n_windows == 0, a group id >= n_groups, outputs.samples or
+ * outputs.counts NULL, batches or trunc NULL (AF_ERR_INVALID); n_scenarios * batch > 2^32, a window of 2^25 or more batches,
+ * n_groups * n_windows >= 2^32 - 1, tick_capacity >= 2^31 (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).  `out`
+ * needs samples, tick_capacity and counts; clock is not read.
+ * Scratch kept by the engine (shared with the other analyzers): 8 B per (group, column, batch) -- batch over sum_w floor((min(
+ * b[w + 1], tick_capacity) - min(b[w], tick_capacity)) / B) --, 4 B per (group, window), 8 B per edge, 4 B per column + 1 280 B
+ * of alignment.
+ * Synchronous; the struct is written back. */
+#define AF_MAX_SERIES_WARMUP_COLUMNS 64
+typedef struct af_series_warmup {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing */
+    uint32_t n_columns;          /* 1 .. AF_MAX_SERIES_WARMUP_COLUMNS */
+    const uint32_t* columns;     /* HOST [n_columns] integer series < af_series_count; any order, duplicates allowed */
+    uint32_t batch;              /* B >= 1 ticks a batch (MSER-5: 5) */
+    uint32_t* batches;           /* DEVICE [n_groups][n_windows] u32 */
+    uint32_t* trunc;             /* DEVICE [n_groups][n_windows][n_columns] u32 */
+    uint64_t* s1;                /* DEVICE [n_groups][n_windows][n_columns][2] u64, low word first; NULL skips */
+    uint64_t* s2;                /* DEVICE [n_groups][n_windows][n_columns][3] u64, low word first; NULL skips */
+    uint64_t* s1_all;            /* DEVICE, the shape of s1; NULL skips */
+    uint64_t* s2_all;            /* DEVICE, the shape of s2; NULL skips */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_series_warmup_t;
+int af_engine_summarize_series_warmup(af_engine_t* engine, const af_outputs_t* out, af_series_warmup_t* series_warmup);
+
 /* Arbitrary latency QUANTILES and SLO counts per group and time window on the device (asyncflow_amd/csrc/af_quantiles.hpp):
  * p99.9 at a grid point, p90 during an outage, how many requests met a 200 ms objective in every 10 s window.  The cells and
  * their samples are af_windows_t's: cell c = g * n_windows + w holds, in ascending scenario index over the members of g,
