@@ -233,7 +233,9 @@ AF_HD double pre_edge_draw(uint64_t seed, uint32_t e, uint32_t idx, uint32_t dis
     const uint32_t stream = stream_edge(e);
     const U4 r = draw_block(seed, stream, idx, 0u);
     if (u53(r.x, r.y) < dropout) return -1.0;  // dropped: no latency draw
-    return test_quant(variate_from_u1(dist, mean, sigma, u53(r.z, r.w), seed, stream, idx));
+    const double K1 = k53(r.z, r.w);   // (the exponential law: 1 - u1 straight from the 53 bits, as Flow::edge_draw)
+    return test_quant(dist == DIST_EXPONENTIAL ? -(mean * af_log_unit(one_minus_unit_of(K1)))
+                                               : variate_from_u1(dist, mean, sigma, unit_of(K1), seed, stream, idx));
 }
 
 // The windowed arrival sampler: samplers/poisson_poisson.py:51-82, gaussian_poisson.py:63-94.

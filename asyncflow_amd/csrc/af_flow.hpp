@@ -664,14 +664,17 @@ struct Flow {
         // conversions, the multiply-add and the scaling of af::u53 (round 4)
         const uint64_t k53 = ((uint64_t)(rr.x >> 5) << 26) | (uint64_t)(rr.y >> 6);
         const bool sent = !(k53 < r[2]);   // (the latency draw is worked out all the same: one region less)
-        const double u1 = af::u53(rr.z, rr.w);
+        // (the exponential law takes 1 - u1 straight from the 53 bits: one fma on the device, af::one_minus_unit_of)
+        const double K1 = af::k53(rr.z, rr.w);
 #if defined(AF_FJ_DIST_ALL) && (AF_FJ_DIST_ALL != 255)
         // plan-specialised build of a plan whose edges all follow ONE law: the law is a constant, its variate code is
         // inlined and the call (with the registers it pins around the call site) is gone
-        transit = af::test_quant(af::variate_from_u1(AF_FJ_DIST_ALL, mean, sigma, u1, seed, stream, idx));
+        transit = af::test_quant(AF_FJ_DIST_ALL == af::DIST_EXPONENTIAL ? -(mean * af::af_log_unit(af::one_minus_unit_of(K1)))
+                                                                        : af::variate_from_u1(AF_FJ_DIST_ALL, mean, sigma, af::unit_of(K1), seed, stream, idx));
 #else
         const uint32_t dist = (uint32_t)(r[3] >> 16) & 0xFFu;
-        transit = af::test_quant(dist == af::DIST_EXPONENTIAL ? -(mean * af::af_log_unit(1.0 - u1)) : cold_variate(dist, mean, sigma, u1, seed, stream, idx));
+        transit = af::test_quant(dist == af::DIST_EXPONENTIAL ? -(mean * af::af_log_unit(af::one_minus_unit_of(K1)))
+                                                              : cold_variate(dist, mean, sigma, af::unit_of(K1), seed, stream, idx));
 #endif
         return sent;
     }

@@ -30,14 +30,40 @@ struct U4 {
     uint32_t x, y, z, w;
 };
 
+// Round 7: the same bits of a draw from fewer device instructions.  Each switch is a device-only
+// rewrite of ONE piece; 0 gives the text every other build has (the host pass of hipcc, g++ for tests/hostcheck, the
+// sanitizer programs).  Measurement builds: -DAF_DRAW_BITOP3=0 etc. (profiles/r07/ab_draws.txt).
+#if !defined(AF_DRAW_BITOP3)
+#define AF_DRAW_BITOP3 1         /* Philox: hi ^ c ^ key as one three-input bit operation (v_bitop3_b32, truth table 0x96) */
+#endif
+#if !defined(AF_DRAW_UNSCALED_DIV)
+#define AF_DRAW_UNSCALED_DIV 1   /* af_log_unit: f / (2 + f) without the scale / fix-up instructions of the IEEE sequence */
+#endif
+#if !defined(AF_DRAW_FMA_U53)
+#define AF_DRAW_FMA_U53 1        /* a x 2^26 + b and 1 - K x 2^-53 as one fma each */
+#endif
+
+// a ^ b ^ c.  gfx950 has a three-input bit operation; clang 22 does not form it from the two XORs on its own.
+AF_HD uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
+#if defined(__HIP_DEVICE_COMPILE__) && AF_DRAW_BITOP3
+#if __has_builtin(__builtin_amdgcn_bitop3_b32)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96u);
+#else
+    return a ^ b ^ c;
+#endif
+#else
+    return a ^ b ^ c;
+#endif
+}
+
 AF_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const uint64_t p0 = (uint64_t)0xD2511F53u * c0;
         const uint64_t p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0;
+        const uint32_t n0 = xor3((uint32_t)(p1 >> 32), c1, k0);
         const uint32_t n1 = (uint32_t)p1;
-        const uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        const uint32_t n2 = xor3((uint32_t)(p0 >> 32), c3, k1);
         const uint32_t n3 = (uint32_t)p0;
         c0 = n0;
         c1 = n1;
@@ -49,9 +75,27 @@ AF_HD U4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint3
     return U4{c0, c1, c2, c3};
 }
 
-AF_HD double u53(uint32_t hi, uint32_t lo) {
-    return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) * (1.0 / 9007199254740992.0);
+// The 53 bits of a uniform as the integer K = a x 2^26 + b in f64 (a = hi >> 5 < 2^27, b = lo >> 6 < 2^26), the uniform
+// u = K x 2^-53 and its complement 1 - u.  On the device the multiply-add pairs are one fma each, with the same bits:
+// a x 2^26 is a power-of-two scale of an integer below 2^27, so the product is exact, and K < 2^53 is an integer, so the sum
+// is exact too -- the fma's single rounding and the two separate ones all round nothing.  Likewise K x 2^-53 is exact (a
+// power-of-two scale, no underflow), so fma(K, -2^-53, 1) rounds the same real number 1 - K x 2^-53 as `1.0 - u` does.
+AF_HD double k53(uint32_t hi, uint32_t lo) {
+#if defined(__HIP_DEVICE_COMPILE__) && AF_DRAW_FMA_U53
+    return __builtin_fma((double)(hi >> 5), 67108864.0, (double)(lo >> 6));
+#else
+    return (double)(hi >> 5) * 67108864.0 + (double)(lo >> 6);
+#endif
 }
+AF_HD double unit_of(double K) { return K * (1.0 / 9007199254740992.0); }
+AF_HD double one_minus_unit_of(double K) {
+#if defined(__HIP_DEVICE_COMPILE__) && AF_DRAW_FMA_U53
+    return __builtin_fma(K, -(1.0 / 9007199254740992.0), 1.0);
+#else
+    return 1.0 - unit_of(K);
+#endif
+}
+AF_HD double u53(uint32_t hi, uint32_t lo) { return unit_of(k53(hi, lo)); }
 
 // Block (index, sub) of a stream: uniforms 2*sub and 2*sub+1 of logical draw `index`.
 AF_HD U4 draw_block(uint64_t seed, uint32_t stream, uint32_t index, uint32_t sub) {
@@ -67,6 +111,15 @@ AF_HD uint64_t f64_bits(double x) { return __builtin_bit_cast(uint64_t, x); }
 AF_HD double bits_f64(uint64_t u) { return __builtin_bit_cast(double, u); }
 
 AF_HD double af_sqrt(double x) { return __builtin_sqrt(x); }
+
+// the divisor's half of the IEEE division sequence: two Newton steps on the hardware's reciprocal estimate `r0`
+// (af_log_unit below; the division by lambda of the arrival kernel, af_pregen.hpp)
+AF_HD double refine_rcp(double d, double r0) {
+    const double e0 = __builtin_fma(-d, r0, 1.0);
+    const double r1 = __builtin_fma(r0, e0, r0);
+    const double e1 = __builtin_fma(-d, r1, 1.0);
+    return __builtin_fma(r1, e1, r1);
+}
 
 // Natural logarithm: argument reduction to [sqrt(2)/2, sqrt(2)) and the
 // classic degree-14 odd series in s = f/(2+f) (error < 1 ulp).
@@ -112,6 +165,18 @@ AF_HD double af_log(double x) {
 // operations without the checks for zero / negative / subnormal / infinite arguments (and without the x == 1 shortcut, whose
 // result the general path gives too: f = 0 makes every term +0).  Same bits as af_log on that domain
 // (tests/test_gpu_parity.py::test_device_math_matches_oracle_bit_for_bit, kind 7).
+//
+// The division (round 7).  On the device `f / (2.0 + f)` is the IEEE sequence: v_div_scale_f64 of divisor and numerator,
+// v_rcp_f64, two Newton steps (refine_rcp), q = n r, rem = fma(-d, q, n), v_div_fmas_f64(rem, r, q), v_div_fixup_f64.  Here
+// the reduced x lies in [0x3fe6a09e00000000, that + 2^52) = [0.70710.., 1.41421..), so the divisor d = 2 + f = 1 + x lies in
+// [1.7071, 2.4143) and the numerator f = x - 1 is +0 (x - 1.0 of x == 1; never -0) or, in magnitude, between 2^-53 and 0.4143:
+//   * v_div_scale scales only when an operand, the reciprocal or the quotient comes near the ends of the exponent range (a
+//     numerator below 2^-969, a divisor above 2^1021 ...): nothing of that here, both pass through and VCC is clear, so
+//     v_div_fmas is the plain fma(rem, r, q);
+//   * v_div_fixup replaces the result only for NaN, infinite, zero or denormal operands and for a quotient outside the normal
+//     range.  |f / d| is 0 or in [2^-55, 0.25).  For f = +0 it gives +0 -- and so do 0 x r, fma(-d, +0, +0) and fma(+0, r, +0).
+// The three instructions therefore compute nothing and are left out; the rest is the compiler's own sequence in its order
+// (afp::div_by in af_pregen.hpp is the same statement for the division by lambda).  Host builds keep `/`.
 AF_HD double af_log_unit(double x) {
     constexpr double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
     constexpr double L1 = 6.666666666666735130e-01, L2 = 3.999999999940941908e-01,
@@ -126,7 +191,14 @@ AF_HD double af_log_unit(double x) {
     x = bits_f64(((uint64_t)hx << 32) | (u & 0xffffffffull));
     const double f = x - 1.0;
     const double hfsq = 0.5 * f * f;
+#if defined(__HIP_DEVICE_COMPILE__) && AF_DRAW_UNSCALED_DIV
+    const double d = 2.0 + f;
+    const double r = refine_rcp(d, __builtin_amdgcn_rcp(d));
+    const double q = f * r;
+    const double s = __builtin_fma(__builtin_fma(-d, q, f), r, q);
+#else
     const double s = f / (2.0 + f);
+#endif
     const double z = s * s;
     const double w = z * z;
     const double t1 = w * (L2 + w * (L4 + w * L6));

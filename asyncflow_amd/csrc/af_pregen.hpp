@@ -35,19 +35,15 @@ constexpr uint32_t kChunk = kBatch * kRound;   // draws per lane and round
 // -log(1 - u) of draw `idx` of the generator's stream: the gap's numerator (poisson_poisson.py:69-70, u clamped at 1e-15)
 AF_HD double unit_variate(uint64_t seed, uint32_t idx) {
     const af::U4 r = af::draw_block(seed, af::STREAM_GENERATOR, idx, 0u);
-    double u = af::u53(r.x, r.y);
-    if (u < 1e-15) u = 1e-15;
-    return -af::af_log_unit(1.0 - u);
+    // `if (u < 1e-15) u = 1e-15; 1.0 - u` on the draw's 53 bits K: u = K x 2^-53 is exact, so u < c exactly when K < c x 2^53
+    // (a power-of-two scale of the constant: exact as well)
+    const double K = af::k53(r.x, r.y);
+    const double x = K < 1e-15 * 9007199254740992.0 ? 1.0 - 1e-15 : af::one_minus_unit_of(K);
+    return -af::af_log_unit(x);
 }
 
-// the divisor's half of the IEEE division sequence: two Newton steps on the hardware's reciprocal estimate `r0`
-AF_HD double refine_rcp(double d, double r0) {
-    const double e0 = __builtin_fma(-d, r0, 1.0);
-    const double r1 = __builtin_fma(r0, e0, r0);
-    const double e1 = __builtin_fma(-d, r1, 1.0);
-    return __builtin_fma(r1, e1, r1);
-}
-// ... and the numerator's: quotient estimate, remainder, correction (v_div_fmas without scaling is this fma)
+// the divisor's half of the IEEE division sequence is af::refine_rcp (af_math.hpp: the logarithm shares it); the
+// numerator's: quotient estimate, remainder, correction (v_div_fmas without scaling is this fma)
 AF_HD double div_by(double n, double d, double r2) {
     const double q = n * r2;
     const double rem = __builtin_fma(-d, q, n);
@@ -93,7 +89,7 @@ AF_HD void window_start(Lane& L, double T, double window_s, double rps_per_user,
         return;
     }
     L.fast_div = div_in_range(L.lam);
-    L.rinv = L.fast_div ? refine_rcp(L.lam, rcp_estimate(L.lam)) : 0.0;
+    L.rinv = L.fast_div ? af::refine_rcp(L.lam, rcp_estimate(L.lam)) : 0.0;
     L.state = LANE_RUN;
 }
 // One step of a running lane: e[j] = unit variate of draw index L.draws + j.  The sums are the sequential sampler's own

@@ -857,6 +857,17 @@ __global__ void af_probe_kernel(int kind, uint64_t seed, const double* in, const
         case 5: r = x / y; break;
         case 6: r = (double)af::af_poisson(x, seed, (uint32_t)y >> 16, (uint32_t)y & 0xFFFFu, 0u); break;
         case 7: r = af::af_log_unit(x); break;
+        // the draw's integer side, operands and results as BIT PATTERNS of the doubles (tests/test_gpu_draw_bits.py):
+        // 8 / 9: words (x, y) / (z, w) of block (index, 0) of stream `stream`, x = the 64-bit seed, y = stream << 32 | index
+        case 8:
+        case 9: {
+            const uint64_t sd = af::d2u(x), si = af::d2u(y);
+            const af::U4 b = af::draw_block(sd, (uint32_t)(si >> 32), (uint32_t)si, 0u);
+            r = af::u2d(kind == 8 ? ((uint64_t)b.x << 32) | b.y : ((uint64_t)b.z << 32) | b.w);
+            break;
+        }
+        // 10: 1 - u of the uniform made of the words x = hi << 32 | lo, as the exponential draws take it
+        case 10: r = af::one_minus_unit_of(af::k53((uint32_t)(af::d2u(x) >> 32), (uint32_t)af::d2u(x))); break;
         default: r = 0.0;
     }
     out[i] = r;

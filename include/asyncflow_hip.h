@@ -991,6 +991,9 @@ int af_abi_version(void);
  *   kind 0: uniform(seed,stream,index,j)
  *   kind 1: log(x)   kind 2: exp(x)   kind 3: norminv(x)   kind 4: sqrt(x)
  *   kind 5: x / y (x = in[i], y = in2[i])
+ *   kind 6: poisson(x)   kind 7: log of a normal number in (0, 1] (the exponential draws' logarithm)
+ *   kinds 8-10 take and give BIT PATTERNS: 8 / 9: Philox words x << 32 | y  /  z << 32 | w of block (index, 0),
+ *   in[i] = the 64-bit seed, in2[i] = stream << 32 | index; 10: 1 - u of the uniform made of the words in[i] = hi << 32 | lo
  * `in`, `in2`, `out` are HOST arrays of n doubles (kind 0: in[i] = index,
  * in2[i] = stream * 65536 + j, both exact small integers). */
 int af_probe_math(int device, int kind, uint64_t seed, const double* in, const double* in2,

@@ -1,6 +1,8 @@
-"""Disassembly of the plan-specialised af_flow_jit of `bench.py --config C` (no GPU needed): python scripts/jit_disasm.py C out.s"""
+"""Disassembly of the plan-specialised af_flow_jit of `bench.py --config C` (no GPU needed): python scripts/jit_disasm.py C out.s
+(prints the spec on stderr and one line of statistics: instructions by kind, registers, scratch bytes, spills)"""
 from __future__ import annotations
 
+import re
 import subprocess
 import sys
 import tempfile
@@ -35,4 +37,14 @@ with tempfile.NamedTemporaryFile(suffix=".hsaco") as f, tempfile.NamedTemporaryF
     subprocess.run([LLVM + "clang-offload-bundler", "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--input={f.name}",
                     f"--output={elf.name}", "--unbundle"], check=True)
     dis = subprocess.run([LLVM + "llvm-objdump", "-d", elf.name], capture_output=True, text=True, check=True).stdout
+    notes = subprocess.run([LLVM + "llvm-readelf", "--notes", elf.name], capture_output=True, text=True, check=True).stdout
 Path(sys.argv[2]).write_text(dis)
+# what an A/B of the kernel's source reports beside its time (profiles/r07/jit_disasm_c2_raw.txt): instructions of af_flow_jit
+# by kind, and the registers / scratch of its metadata
+body = re.search(r"^[0-9a-f]+ <af_flow_jit>:\n(.*?)(?=^[0-9a-f]+ <|\Z)", dis, re.S | re.M).group(1)
+ops = [ln.split()[0] for ln in body.splitlines() if re.match(r"\s+[a-z]", ln)]
+meta = next((part for part in re.split(r"\n\s+- \.agpr_count", notes) if re.search(r"\.name:\s+af_flow_jit\b", part)), "")
+print("insts", len(ops), *(f"{p} {sum(o.startswith(p) for o in ops)}" for p in ("v_", "v_readlane", "v_writelane", "v_xor_b32", "v_bitop3",
+                                                                                "v_mad_u64_u32", "v_div_", "v_fma_f64", "scratch_")),
+      *(f"{k} {' '.join(re.findall(re.escape(k) + ': +([0-9]+)', meta)) or '?'}"
+        for k in (".vgpr_count", ".sgpr_count", ".private_segment_fixed_size", ".vgpr_spill_count", ".sgpr_spill_count")))

@@ -76,6 +76,18 @@ if "cal_fma_f64" in sat and "cal_add_u32" in sat:
         "the x4 reading is right where the value is 1.00 and over- / under-states VALU busy time by that factor elsewhere; "
         f"one VALU wave-instruction costs a SIMD {f['simd_cycles_per_inst']:.2f} (v_fma_f64) / {u['simd_cycles_per_inst']:.2f} (v_add_u32) cycles "
         f"and is {f['active_per_inst']:.3f} / {u['active_per_inst']:.3f} counts.")
+# round 7: Philox's instructions.  8 waves per SIMD: what one instruction costs a SIMD; 1 wave per SIMD: the same with only the
+# wave's own eight chains to cover the latency of a dependent issue
+one = {t["kernel"]: t for t in table if t["waves_per_simd"] == 1}
+names = {"cal_xor_b32": "v_xor_b32", "cal_bitop3_b32": "v_bitop3_b32", "cal_mad_u64_u32": "v_mad_u64_u32", "cal_add_u32": "v_add_u32",
+         "cal_fma_f64": "v_fma_f64"}
+res["simd_cycles_per_inst_by_instruction"] = {
+    ins: {"saturated_8_waves_per_simd": sat[k]["simd_cycles_per_inst"], "one_wave_per_simd_eight_chains": one[k]["simd_cycles_per_inst"]}
+    for k, ins in names.items() if k in sat and k in one}
+if "cal_xor_b32" in sat and "cal_bitop3_b32" in sat:
+    x, b3 = sat["cal_xor_b32"]["simd_cycles_per_inst"], sat["cal_bitop3_b32"]["simd_cycles_per_inst"]
+    res["three_input_xor"] = {"one_v_bitop3_b32": b3, "two_v_xor_b32": 2.0 * x, "cheaper_than_the_pair": b3 < 2.0 * x,
+                              "reading": f"hi ^ c ^ key costs a SIMD {b3:.2f} cycles as one v_bitop3_b32 and {2.0 * x:.2f} as two v_xor_b32"}
 (out / "valu_calibration.json").write_text(json.dumps(res, indent=1))
 print(json.dumps({k: v for k, v in res.items() if k != "launches"}, indent=1))
 for t in table:

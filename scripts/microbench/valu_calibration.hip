@@ -50,6 +50,47 @@ __global__ void __launch_bounds__(64) cal_add_u32(double* out, uint32_t seed) {
     if ((a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7) == 0x7fffffffu) out[blockIdx.x] = 0;
 }
 
+// Round 7: what Philox is made of.  Same shape -- eight chains, every instruction takes the previous result of its chain --
+// for v_xor_b32 (the yardstick: two of them are one hi ^ c ^ key), v_bitop3_b32 with truth table 0x96 (the three-input XOR
+// that replaces the pair) and v_mad_u64_u32 (the 32 x 32 -> 64 products; the chain runs through the 64-bit addend).  At one
+// wave per SIMD the eight chains of a wave are all that covers an instruction's latency: the dependent-issue cost; at eight
+// waves per SIMD the issue cost proper.
+#define I_XOR_B32(k) "v_xor_b32 %" #k ", %" #k ", %8\n"
+#define I_BITOP3_B32(k) "v_bitop3_b32 %" #k ", %" #k ", %8, %9 bitop3:0x96\n"
+#define I_MAD_U64_U32(k) "v_mad_u64_u32 %" #k ", vcc, %8, %9, %" #k "\n"
+#define BODY8_VCC(INS)                                                                                 \
+    asm volatile(INS(0) INS(1) INS(2) INS(3) INS(4) INS(5) INS(6) INS(7)                                \
+                 : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7)       \
+                 : "v"(b), "v"(c)                                                                       \
+                 : "vcc")
+
+__global__ void __launch_bounds__(64) cal_xor_b32(double* out, uint32_t seed) {
+    uint32_t a0 = threadIdx.x + seed, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
+    uint32_t b = seed * 3u + 0x12345u, c = threadIdx.x | 1u;
+    for (int r = 0; r < REPS; ++r) {
+        BODY8(I_XOR_B32); BODY8(I_XOR_B32); BODY8(I_XOR_B32); BODY8(I_XOR_B32); BODY8(I_XOR_B32); BODY8(I_XOR_B32); BODY8(I_XOR_B32); BODY8(I_XOR_B32);
+    }
+    if ((a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7) == 0x7fffffffu) out[blockIdx.x] = 0;
+}
+
+__global__ void __launch_bounds__(64) cal_bitop3_b32(double* out, uint32_t seed) {
+    uint32_t a0 = threadIdx.x + seed, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
+    uint32_t b = seed * 3u + 0x12345u, c = threadIdx.x | 1u;
+    for (int r = 0; r < REPS; ++r) {
+        BODY8(I_BITOP3_B32); BODY8(I_BITOP3_B32); BODY8(I_BITOP3_B32); BODY8(I_BITOP3_B32); BODY8(I_BITOP3_B32); BODY8(I_BITOP3_B32); BODY8(I_BITOP3_B32); BODY8(I_BITOP3_B32);
+    }
+    if ((a0 + a1 + a2 + a3 + a4 + a5 + a6 + a7) == 0x7fffffffu) out[blockIdx.x] = 0;
+}
+
+__global__ void __launch_bounds__(64) cal_mad_u64_u32(double* out, uint32_t seed) {
+    uint64_t a0 = threadIdx.x + seed, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
+    uint32_t b = seed * 3u + 0x12345u, c = threadIdx.x | 1u;
+    for (int r = 0; r < REPS; ++r) {
+        BODY8_VCC(I_MAD_U64_U32); BODY8_VCC(I_MAD_U64_U32); BODY8_VCC(I_MAD_U64_U32); BODY8_VCC(I_MAD_U64_U32); BODY8_VCC(I_MAD_U64_U32); BODY8_VCC(I_MAD_U64_U32); BODY8_VCC(I_MAD_U64_U32); BODY8_VCC(I_MAD_U64_U32);
+    }
+    if ((a0 ^ a1 ^ a2 ^ a3 ^ a4 ^ a5 ^ a6 ^ a7) == 0x7fffffffffffffffull) out[blockIdx.x] = 0;
+}
+
 // half the lanes masked off: does the counter see lanes (it must not), does SQ_THREAD_CYCLES_VALU (it must)
 __global__ void __launch_bounds__(64) cal_fma_f64_half_lanes(double* out, uint32_t seed) {
     double a0 = threadIdx.x + seed + 1.0, a1 = a0 + 1, a2 = a0 + 2, a3 = a0 + 3, a4 = a0 + 4, a5 = a0 + 5, a6 = a0 + 6, a7 = a0 + 7;
@@ -68,7 +109,8 @@ struct K {
 };
 
 int main() {
-    const K ks[] = {{"cal_fma_f64", cal_fma_f64}, {"cal_add_u32", cal_add_u32}, {"cal_fma_f64_half_lanes", cal_fma_f64_half_lanes}};
+    const K ks[] = {{"cal_fma_f64", cal_fma_f64}, {"cal_add_u32", cal_add_u32}, {"cal_fma_f64_half_lanes", cal_fma_f64_half_lanes},
+                    {"cal_xor_b32", cal_xor_b32}, {"cal_bitop3_b32", cal_bitop3_b32}, {"cal_mad_u64_u32", cal_mad_u64_u32}};
     double* d = nullptr;
     const int n_simd = 256 * 4;
     hipMalloc(&d, n_simd * 8 * sizeof(double));
