@@ -480,6 +480,27 @@ class AfSeriesWarmup(C.Structure):
     ]
 
 
+class AfArrivals(C.Structure):
+    """``af_arrivals_t``: request of ``af_engine_summarize_arrivals`` (``elapsed_ms`` and ``scratch_bytes`` are written
+    back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("edges", C.POINTER(C.c_double)),
+        ("times", C.c_void_p),
+        ("times_given", C.c_uint32),
+        ("arrivals", C.c_void_p),
+        ("row_bounds", C.c_void_p),
+        ("generated", C.c_void_p),
+        ("flags", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -510,6 +531,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_series_warmup",
     "af_engine_summarize_quantiles",
     "af_engine_summarize_arrival_quantiles",
+    "af_engine_summarize_arrivals",
     "af_engine_summarize_state_windows",
     "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
@@ -568,6 +590,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_summarize_arrival_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_arrival_quantiles.restype = C.c_int
+    lib.af_engine_summarize_arrivals.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfArrivals)]
+    lib.af_engine_summarize_arrivals.restype = C.c_int
     lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
     lib.af_engine_summarize_state_windows.restype = C.c_int
     lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]

@@ -67,6 +67,7 @@
 #include "af_arrival.hpp"
 #include "af_state.hpp"
 #include "af_quantiles.hpp"
+#include "af_arrival_counts.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -1915,25 +1916,10 @@ struct Run {
     RunTotals t;
 };
 
-// The arguments and the override columns of a run; the columns' bits, the state layout they need.
-static int validate_sweep(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* out, Run& r) {
-    if (!e || !sweep || !out) return fail(AF_ERR_INVALID, "NULL argument");
-    if (sweep->n_scenarios == 0 || !sweep->seeds) return fail(AF_ERR_INVALID, "empty sweep");
-    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
-    if (out->clock && out->clock_capacity == 0) return fail(AF_ERR_INVALID, "clock buffer with zero capacity");
-    if (out->samples && out->tick_capacity == 0) return fail(AF_ERR_INVALID, "samples buffer with zero capacity");
-    if (out->online_hist && (out->online_hist_bins == 0 || !(out->online_hist_max > 0.0)))
-        return fail(AF_ERR_INVALID, "online_hist needs online_hist_bins > 0 and online_hist_max > 0");
-    if (out->online_rps && out->online_rps_buckets == 0) return fail(AF_ERR_INVALID, "online_rps with zero buckets");
-    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY): it cannot run");
-    HIP_TRY(hipSetDevice(e->device));
+// The override columns of a sweep: indices within the plan, integral columns integral, ranges the kernels rely on.
+static int check_override_columns(const af_engine_t* e, const af_sweep_t* sweep) {
     const KArgs& a = e->args;
     const uint32_t n = sweep->n_scenarios;
-    r.e = e;
-    r.sweep = sweep;
-    r.out = out;
-    r.n = n;
-    if (int rc = sweep_override_mask(sweep, true, r.mask)) return rc;
     for (uint32_t k = 0; k < sweep->n_overrides; ++k) {
         const af_override_t& o = sweep->overrides[k];
         const uint32_t lim = (o.param >= AF_PARAM_EDGE_MEAN && o.param <= AF_PARAM_EDGE_DROPOUT) ? a.n_edges
@@ -1956,6 +1942,29 @@ static int validate_sweep(af_engine_t* e, const af_sweep_t* sweep, const af_outp
             if (o.param == AF_PARAM_SRV_RAM_MB && !(v > 0.0)) return fail(AF_ERR_INVALID, "ram_mb column must be positive");
         }
     }
+    return AF_OK;
+}
+
+// The arguments and the override columns of a run; the columns' bits, the state layout they need.
+static int validate_sweep(af_engine_t* e, const af_sweep_t* sweep, const af_outputs_t* out, Run& r) {
+    if (!e || !sweep || !out) return fail(AF_ERR_INVALID, "NULL argument");
+    if (sweep->n_scenarios == 0 || !sweep->seeds) return fail(AF_ERR_INVALID, "empty sweep");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (out->clock && out->clock_capacity == 0) return fail(AF_ERR_INVALID, "clock buffer with zero capacity");
+    if (out->samples && out->tick_capacity == 0) return fail(AF_ERR_INVALID, "samples buffer with zero capacity");
+    if (out->online_hist && (out->online_hist_bins == 0 || !(out->online_hist_max > 0.0)))
+        return fail(AF_ERR_INVALID, "online_hist needs online_hist_bins > 0 and online_hist_max > 0");
+    if (out->online_rps && out->online_rps_buckets == 0) return fail(AF_ERR_INVALID, "online_rps with zero buckets");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY): it cannot run");
+    HIP_TRY(hipSetDevice(e->device));
+    const KArgs& a = e->args;
+    const uint32_t n = sweep->n_scenarios;
+    r.e = e;
+    r.sweep = sweep;
+    r.out = out;
+    r.n = n;
+    if (int rc = sweep_override_mask(sweep, true, r.mask)) return rc;
+    if (int rc = check_override_columns(e, sweep)) return rc;
     r.L = af::make_layout(e->request_capacity, e->fifo_capacity, a.n_edges, a.n_servers, a.n_lb_edges, a.n_rows, r.mask, a.n_edge_marks, a.n_srv_marks);
     r.bytes_per_lane = af::layout_bytes_per_lane(r.L);
     r.tie_words = r.L.tie_words;
@@ -2221,6 +2230,21 @@ struct FlowLaunch {
     uint32_t gate = 0u;          // af_engine_run_summarized: the analyzer starts once this many scenarios are done (0: after the run)
 };
 
+// Rows or groups (af_pregen.hpp) for the arrival times of the chunk [lo, lo + nc)?  Grouped pre-generation: sweeps of alike
+// scenarios -- a workgroup is as slow as its heaviest one -- with sampling windows long enough that a window start (a user draw
+// by one wave, the pipeline refilled) does not count.
+static bool pregen_grouped(const Run& r, const KArgs& a, uint32_t lo, uint32_t nc) {
+    const char* pregen_mode = std::getenv("AF_PREGEN_MODE");   // rows | groups: tests and measurements
+    const bool force_groups = pregen_mode && std::strcmp(pregen_mode, "groups") == 0;
+    const bool force_rows = pregen_mode && std::strcmp(pregen_mode, "rows") == 0;
+    // (sweeps over users / rpm -- BASELINE configs 3 / 4 -- as long as the heaviest scenario is within 2.5 x of the mean:
+    // load_spread_suits_groups)
+    return !force_rows && a.gen_window_s > 0.0 &&
+           (force_groups || (!(r.mask & (1u << AF_PARAM_GEN_WINDOW)) && nc >= 3072u &&
+                             (double)r.n_draw * a.gen_window_s >= 512.0 * a.total_time &&
+                             (!r.hetero_load || load_spread_suits_groups(r.e, r.sweep, lo, nc))));
+}
+
 // Arrival times of the chunk's scenarios; for sweeps over the load, their launch order (`ordered`: e->d_order holds it).
 static int pregen_flow_chunk(Run& r, const KArgs& chunk, uint32_t lo, bool& ordered) {
     af_engine_t* e = r.e;
@@ -2231,17 +2255,7 @@ static int pregen_flow_chunk(Run& r, const KArgs& chunk, uint32_t lo, bool& orde
     KArgs a = chunk;
     a.draws = e->d_arr;
     a.pre_flags = e->d_arr_flags;
-    // grouped pre-generation (af_pregen.hpp): sweeps of alike scenarios -- a workgroup is as slow as its heaviest one -- with
-    // sampling windows long enough that a window start (a user draw by one wave, the pipeline refilled) does not count
-    const char* pregen_mode = std::getenv("AF_PREGEN_MODE");   // rows | groups: tests and measurements
-    const bool force_groups = pregen_mode && std::strcmp(pregen_mode, "groups") == 0;
-    const bool force_rows = pregen_mode && std::strcmp(pregen_mode, "rows") == 0;
-    // (sweeps over users / rpm -- BASELINE configs 3 / 4 -- as long as the heaviest scenario is within 2.5 x of the mean:
-    // load_spread_suits_groups)
-    const bool grouped = !force_rows && a.gen_window_s > 0.0 &&
-                         (force_groups || (!(r.mask & (1u << AF_PARAM_GEN_WINDOW)) && nc >= 3072u &&
-                                           (double)n_draw * a.gen_window_s >= 512.0 * a.total_time &&
-                                           (!r.hetero_load || load_spread_suits_groups(e, r.sweep, lo, nc))));
+    const bool grouped = pregen_grouped(r, a, lo, nc);
     // Sweeps over the load: waves are dispatched in blockIdx order as slots free up, and a wave lasts as long as its scenario
     // has events.  A users-major grid (BASELINE configs 3 / 4: users ascending with the index) is then the WORST order --
     // the heaviest scenarios start last and the launch ends with a few long waves on an empty chip (list scheduling of
@@ -3357,6 +3371,118 @@ int af_engine_summarize_state_quantiles(af_engine_t* e, const af_outputs_t* out,
 // Sampled-series analyzer per (group, window of ticks) (af_series_windows.hpp).  The host reads the group ids and the counts
 // back, checks them and builds the groups' member lists; one streaming pass over the sample rows, then -- unless every group
 // is a single scenario -- the fold of the members' records.
+// Arrivals per window and group (af_arrival_counts.hpp).  The arrival times are generated as a run generates them -- the same
+// staged sweep, launch_pregen_arrivals with the same rows / groups choice, chunks by the same memory budget into the same
+// e->d_arr -- or taken from the caller; per chunk one launch for the bounds of every row and one for the group sums.
+static int summarize_arrivals(af_engine_t* e, const af_sweep_t* sweep, af_arrivals_t* req) {
+    const uint32_t n = req->n_scenarios, W = req->n_windows, G = req->n_groups, n_draw = sweep->draw_capacity;
+    const bool given = req->times && req->times_given != 0u;
+    Run r;
+    r.e = e;
+    r.sweep = sweep;
+    r.n = n;
+    r.n_draw = n_draw;
+    if (!given) {
+        if (int rc = sweep_override_mask(sweep, true, r.mask)) return rc;
+        if (int rc = check_override_columns(e, sweep)) return rc;
+        r.hetero_load = (r.mask & ((1u << AF_PARAM_GEN_USERS_MEAN) | (1u << AF_PARAM_GEN_RPM_MEAN))) != 0u;
+    }
+    std::vector<uint32_t> grp;
+    if (req->group)
+        if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    uint32_t chunk = n;
+    if (!req->times) {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        chunk = chunk_size(e, n, (size_t)n_draw * sizeof(double), mem_free + e->arr_cap);
+        if (chunk == 0) return fail(AF_ERR_CAPACITY, "draw_capacity too large for the device memory budget");
+    }
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 8u);
+    const size_t o_bounds = req->row_bounds ? 0u : lay.part((size_t)chunk * (W + 1u) * 4u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, req->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(req->arrivals, 0, (size_t)G * W * 8u, st));
+    if (given && req->flags) HIP_TRY(hipMemsetAsync(req->flags, 0, (size_t)n * 4u, st));
+    if (!given)
+        if (int rc = stage_sweep(r)) return rc;
+    for (uint32_t lo = 0; lo < n; lo += chunk) {
+        const uint32_t nc = std::min(chunk, n - lo);
+        double* rows = req->times;
+        if (!rows) {
+            if (int rc = reserve_device((void**)&e->d_arr, e->arr_cap, (size_t)nc * n_draw * sizeof(double))) return rc;
+            rows = e->d_arr;
+        }
+        if (!given) {
+            KArgs a = e->args;
+            a.n_ovr = sweep->n_overrides;
+            a.ovr_param = r.d_params;
+            a.ovr_index = r.d_idxs;
+            a.ovr_stride = n;
+            a.ovr_values = r.d_values + lo;
+            a.seeds = r.d_seeds + lo;
+            a.n_draw = n_draw;
+            a.n_scen = nc;
+            a.scen_map = nullptr;
+            a.draws = rows;
+            a.pre_flags = req->flags ? req->flags + lo : nullptr;
+            if (!a.pre_flags) {
+                if (int rc = reserve_device((void**)&e->d_arr_flags, e->arr_flags_cap, (size_t)nc * 4u)) return rc;
+                a.pre_flags = e->d_arr_flags;
+            }
+            if (launch_pregen_arrivals(a, nc, n_draw, !r.hetero_load, st, pregen_grouped(r, a, lo, nc)))
+                return fail(AF_ERR_HIP, "af_arrival_groups: LDS attribute");
+            HIP_TRY(hipGetLastError());
+        }
+        afac::CountArgs c{};
+        c.times = rows;
+        c.n_scen = nc;
+        c.n_draw = n_draw;
+        c.n_win = W;
+        c.n_groups = G;
+        c.edges = reinterpret_cast<const double*>(e->d_pool + o_edges);
+        c.group = req->group ? req->group + lo : nullptr;
+        c.first_group = lo;
+        c.bounds = req->row_bounds ? req->row_bounds + (size_t)lo * (W + 1u) : reinterpret_cast<uint32_t*>(e->d_pool + o_bounds);
+        c.generated = req->generated ? req->generated + lo : nullptr;
+        c.arrivals = reinterpret_cast<unsigned long long*>(req->arrivals);
+        const dim3 grid((nc + afac::kWavesPerBlock - 1u) / afac::kWavesPerBlock), block(64u * afac::kWavesPerBlock);
+        if (W + 1u <= afac::kMaxLdsEdges) hipLaunchKernelGGL(afac::af_arrival_bounds<true>, grid, block, ((size_t)W + 1u) * 8u, st, c);
+        else hipLaunchKernelGGL(afac::af_arrival_bounds<false>, grid, block, 0, st, c);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(afac::af_arrival_group_sums, dim3((nc + afac::kSumRows - 1u) / afac::kSumRows, (W + 255u) / 256u), dim3(256), 0, st, c);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // (the host edges are read by the copy until here)
+    return AF_OK;
+}
+
+static_assert(afac::kSkip == AF_POOL_SKIP, "the kernel's skip id is the header's");
+
+int af_engine_summarize_arrivals(af_engine_t* e, const af_sweep_t* sweep, af_arrivals_t* req) {
+    if (!e || !sweep || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_windows == 0 || req->n_groups == 0)
+        return fail(AF_ERR_INVALID, "empty arrivals request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (req->n_scenarios != sweep->n_scenarios) return fail(AF_ERR_INVALID, "arrivals.n_scenarios is not the sweep's");
+    if (sweep->draw_capacity == 0) return fail(AF_ERR_INVALID, "draw_capacity must be > 0 (pass the run's value)");
+    if (!req->arrivals) return fail(AF_ERR_INVALID, "arrivals.arrivals is required");
+    if (!req->edges) return fail(AF_ERR_INVALID, "arrivals.edges is required");
+    if (!(req->times && req->times_given) && !sweep->seeds) return fail(AF_ERR_INVALID, "empty sweep");
+    if (!req->group && req->n_groups != req->n_scenarios)
+        return fail(AF_ERR_INVALID, "group NULL means singletons: n_groups must be n_scenarios");
+    if (int rc = check_window_edges(req->edges, req->n_windows)) return rc;
+    if ((uint64_t)req->n_groups * req->n_windows >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (req->n_windows >= (1u << 24)) return fail(AF_ERR_CAPACITY, "n_windows must be below 2^24");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = summarize_arrivals(e, sweep, req)) return rc;
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
 int af_engine_summarize_series_windows(af_engine_t* e, const af_outputs_t* out, af_series_windows_t* req) {
     if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
     if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");

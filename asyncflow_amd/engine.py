@@ -339,6 +339,38 @@ class Engine:
         _check(self._lib, getattr(self._lib, name)(self._h, C.byref(out), C.byref(req)), name)
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_arrivals(self, seeds: Any, overrides: Sequence[tuple[int, int, np.ndarray]], n_groups: int, edges: Any, *,
+                           draw_capacity: int, arrivals_ptr: int, group_ptr: int = 0, row_bounds_ptr: int = 0,
+                           generated_ptr: int = 0, flags_ptr: int = 0, times_ptr: int = 0, times_given: bool = False,
+                           n: int | None = None) -> tuple[float, int]:
+        """Arrivals per window and group on the device (``af_engine_summarize_arrivals``): ``arrivals`` uint64
+        [n_groups, W], W = len(edges) - 1, the arrival times ``t`` of each group's scenarios with ``edges[w] < t <=
+        edges[w + 1]``.  ``seeds`` / ``overrides`` / ``draw_capacity``: the sweep as :meth:`run` takes it (pass the run's
+        ``draw_capacity``); nothing is simulated.  ``group_ptr``: DEVICE uint32 [n] (``_abi.POOL_SKIP`` leaves a scenario
+        out), 0 = every scenario its own group (``n_groups`` must then be n).  Optional DEVICE outputs: ``row_bounds_ptr``
+        uint32 [n, W + 1] (cumulative arrival counts at the edges), ``generated_ptr`` uint32 [n], ``flags_ptr`` uint32 [n]
+        (``FLAG_DRAW_OVERFLOW``).  ``times_ptr``: DEVICE float64 [n, draw_capacity]; with ``times_given=False`` it receives
+        the generated arrival times (+inf behind the last), with ``times_given=True`` its rows are counted instead of
+        generated ones (``seeds`` may then be None with ``n`` given).  Returns the call's wall time in ms and the engine's
+        scratch size in bytes."""
+        e = np.ascontiguousarray(edges, dtype=np.float64)
+        if e.ndim != 1 or e.shape[0] < 2:
+            msg = f"window edges must be a vector of at least two values, not of shape {e.shape}"
+            raise ValueError(msg)
+        if seeds is None:
+            if n is None or not (times_given and times_ptr):
+                msg = "summarize_arrivals without seeds needs n, times_ptr and times_given=True"
+                raise ValueError(msg)
+            sweep, _keep = _abi.AfSweep(int(n), None, 0, None, int(draw_capacity)), None
+        else:
+            sweep, _out, _keep = self._sweep_structs(seeds, overrides, 0, 0, 0, 0, 0, draw_capacity, 0, 0, 0.0, 0, 0)
+        req = _abi.AfArrivals(int(sweep.n_scenarios), int(n_groups), int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
+                              e.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(times_ptr or None), int(bool(times_given)),
+                              C.c_void_p(arrivals_ptr or None), C.c_void_p(row_bounds_ptr or None),
+                              C.c_void_p(generated_ptr or None), C.c_void_p(flags_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_arrivals(self._h, C.byref(sweep), C.byref(req)), "af_engine_summarize_arrivals")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def _state_request(self, column: int, bins: int, lo: float, width: float, sample_period: float, edges: Any) -> tuple[Any, Any]:
         """``af_state_bins_t`` and the checked edges (or None) of the two latency-by-state calls."""
         from .results import _check_series_columns, check_state_bins

@@ -204,6 +204,103 @@ def latency_window_quantiles(clock: np.ndarray, edges: Any, levels: Any, thresho
     return count, quant, within
 
 
+def spec_log(x: float) -> float:
+    """The natural logarithm as the engine's arrival sampler takes it (FreeBSD / fdlibm ``e_log.c``, every operation a
+    rounded float64 one in the order written): the gap of an arrival is ``-spec_log(1 - u) / rate``.  ``math.log`` is
+    the platform's and differs from it in the last digit now and then.  Positive finite ``x`` only."""
+    import struct
+
+    if not (x > 0.0) or x == float("inf"):
+        msg = f"spec_log takes a positive finite number, not {x!r}"
+        raise ValueError(msg)
+    k = 0
+    u = struct.unpack("<Q", struct.pack("<d", x))[0]
+    hx = u >> 32
+    if hx < 0x00100000:                       # subnormal: scale up
+        k -= 54
+        x *= 18014398509481984.0
+        u = struct.unpack("<Q", struct.pack("<d", x))[0]
+        hx = u >> 32
+    elif hx == 0x3FF00000 and (u & 0xFFFFFFFF) == 0:
+        return 0.0
+    hx = (hx + (0x3FF00000 - 0x3FE6A09E)) & 0xFFFFFFFF
+    k += (hx >> 20) - 0x3FF
+    hx = (hx & 0x000FFFFF) + 0x3FE6A09E
+    x = struct.unpack("<d", struct.pack("<Q", (hx << 32) | (u & 0xFFFFFFFF)))[0]
+    f = x - 1.0
+    hfsq = 0.5 * f * f
+    s = f / (2.0 + f)
+    z = s * s
+    w = z * z
+    t1 = w * (3.999999999940941908e-01 + w * (2.222219843214978396e-01 + w * 1.531383769920937332e-01))
+    t2 = z * (6.666666666666735130e-01 + w * (2.857142874366239149e-01 + w * (1.818357216161805012e-01 + w * 1.479819860511658591e-01)))
+    r = t2 + t1
+    dk = float(k)
+    return s * (hfsq + r) + dk * 1.90821492927058770002e-10 - hfsq + f + dk * 6.93147180369123816490e-01
+
+
+def arrival_times(rng: Any, dist: Any, mean: float, sigma: float, rpm: float, window_s: float, horizon: float,
+                  n_draw: int, *, log: Any = spec_log) -> tuple[np.ndarray, int]:
+    """The arrival times of one scenario on the host: the definition ``af_engine_summarize_arrivals`` counts.
+
+    The reference's windowed sampler (samplers/poisson_poisson.py:51-82, gaussian_poisson.py:63-94) with its TWO clocks:
+    the sampler's virtual clock ``now`` decides which sampling window a gap falls in and when the horizon is reached -- it
+    JUMPS to the window's end over a window nobody is active in and over the gap that crosses a window's end -- while the
+    simulation clock ``t`` only ever advances by the gaps that were yielded (rqs_generator.py:97-119: ``env.now + gap``).
+    Arrival k is ``t`` after the k-th yielded gap; the two clocks drift apart at every jump.
+    ``rng``: duck-typed like the reference's generator -- ``poisson(lam)``, ``normal(mean, sigma)``, ``random()`` -- one
+    call per draw in the sampler's order.  ``dist``: ``"poisson"`` / ``"normal"`` (or the codes 0 / 1) of the active
+    users, ``mean`` / ``sigma`` theirs, ``rpm`` requests per minute and user, ``window_s`` the user sampling window,
+    ``horizon`` the total simulation time.  ``log``: the logarithm of the gap (:func:`spec_log`, the engine's).
+    Returns ``times`` float64 [n_draw], ascending with ``+inf`` behind the last arrival, and ``flags``:
+    ``FLAG_DRAW_OVERFLOW`` when the sampler had a further arrival for a full row, else 0."""
+    normal = dist in (_abi.DIST_CODES["normal"], "normal")
+    if not normal and dist not in (_abi.DIST_CODES["poisson"], "poisson"):
+        msg = f"active users are 'poisson' or 'normal', not {dist!r}"
+        raise ValueError(msg)
+    n_draw = int(n_draw)
+    times = np.full(n_draw, np.inf, dtype=np.float64)
+    rps_per_user = float(rpm) / 60.0
+    now = window_end = lam = t = 0.0
+    k = 0
+    while now < horizon:
+        if now >= window_end:
+            window_end = now + float(window_s)
+            users = max(0.0, float(rng.normal(mean, sigma))) if normal else float(rng.poisson(mean))
+            lam = users * rps_per_user
+        if lam <= 0.0:
+            now = window_end
+            continue
+        u = max(float(rng.random()), 1e-15)
+        dt = -log(1.0 - u) / lam
+        if now + dt > horizon:
+            break
+        if now + dt >= window_end:
+            now = window_end
+            continue
+        if k == n_draw:
+            return times, _abi.FLAG_DRAW_OVERFLOW
+        now += dt
+        t = t + dt
+        times[k] = t
+        k += 1
+    return times, 0
+
+
+def arrival_window_counts(times: Any, edges: Any) -> np.ndarray:
+    """Cumulative arrival counts at the window edges: ``bounds[k] = #{ finite t in times : t <= edges[k] }``
+    (``np.searchsorted(side="right")``), int64 [W + 1]; window w holds ``bounds[w + 1] - bounds[w]`` arrivals, those with
+    ``edges[w] < t <= edges[w + 1]`` -- an arrival on an edge belongs to the window that ends there, the bucket rule of the
+    by-arrival latency windows.  ``times``: ascending, ``+inf`` (ignored) behind the last arrival."""
+    e = check_edges(edges)
+    t = np.asarray(times, dtype=np.float64).reshape(-1)
+    t = t[np.isfinite(t)]
+    if t.shape[0] > 1 and np.any(t[1:] < t[:-1]):
+        msg = "arrival times must be ascending"
+        raise ValueError(msg)
+    return np.searchsorted(t, e, side="right").astype(np.int64)
+
+
 def check_tick_edges(tick_edges: Any) -> np.ndarray:
     """``tick_edges`` as a uint32 vector, or ValueError: at least two tick indices, whole, in [0, 2^32), strictly increasing."""
     raw = np.asarray(tick_edges)
@@ -1347,6 +1444,7 @@ class ScenarioResults:
         self.latency_stats: dict[str, float] | None = None
         self.throughput_series: Series | None = None
         self.sampled_metrics: dict[str, dict[str, list[float]]] | None = None
+        self._arrival_times: Any = None   # () -> float64 arrival times: set by BatchedResults for get_arrival_counts
 
     # ---- counters -------------------------------------------------------------
     @property
@@ -1461,6 +1559,17 @@ class ScenarioResults:
         LATENCY_KEYS order, for windows of ``window_s`` seconds (default 1 s, :func:`window_edges`) or explicit ``edges``:
         :func:`latency_window_stats`."""
         return latency_window_stats(self.rqs_clock, _resolve_edges(window_s, edges, self._plan.total_time), window_of)
+
+    def get_arrival_counts(self, window_s: float | None = None, edges: Any = None) -> np.ndarray:
+        """Arrivals per time window, int64 [W]: the requests SENT with ``edges[w] < t <= edges[w + 1]``, completed or not
+        (:func:`arrival_window_counts` on the scenario's arrival times, which :meth:`BatchedResults.arrival_times`
+        regenerates on the device).  Windows as in :meth:`get_latency_window_stats`.  Only for a scenario taken from a
+        run's results: a hand-made object has no arrival times."""
+        if self._arrival_times is None:
+            msg = "this ScenarioResults does not come from a run: it has no arrival times"
+            raise ValueError(msg)
+        e = _resolve_edges(window_s, edges, self._plan.total_time)
+        return np.diff(arrival_window_counts(self._arrival_times(), e))
 
     def get_latency_quantiles(self, levels: Any, *, window_s: float | None = None, edges: Any = None,
                               thresholds: Any = None, window_of: str = "finish") -> dict[str, Any]:
@@ -1678,9 +1787,12 @@ class BatchedResults:
 
     def __init__(self, plan: DevicePlan, seeds: np.ndarray, counts: Any, clock: Any, samples: Any,
                  stats: _abi.AfStats, wall_s: float, overrides: dict[str, np.ndarray] | None = None, *,
-                 online_hist: Any = None, online_rps: Any = None, online_hist_max: float = 0.0) -> None:
+                 online_hist: Any = None, online_rps: Any = None, online_hist_max: float = 0.0, draw_capacity: int = 0) -> None:
         self.plan = plan
         self.seeds = seeds
+        #: the run's ``draw_capacity`` (0: the clock capacity, as the engine takes it): the arrivals it simulated are the
+        #: sampler's first that many (:meth:`arrival_summary` regenerates exactly those)
+        self.draw_capacity = int(draw_capacity)
         self._counts_t, self._clock_t, self._samples_t = counts, clock, samples
         self.counts = counts.cpu().numpy().view(np.uint32)
         self.kernel_ms = float(stats.kernel_ms)
@@ -1747,7 +1859,9 @@ class BatchedResults:
             k = min(int(counts[_abi.CNT_TICKS]), int(self._samples_t.shape[1]))
             rows = self._samples_t[i, :k, : self.plan.n_series].cpu().numpy().view(np.uint32)
             samples = np.ascontiguousarray(rows.T)
-        return ScenarioResults(self.plan, counts, clock, samples)
+        one = ScenarioResults(self.plan, counts, clock, samples)
+        one._arrival_times = lambda: self.arrival_times(i)   # noqa: SLF001
+        return one
 
     def __iter__(self) -> Iterator[ScenarioResults]:
         return (self[i] for i in range(len(self)))
@@ -2072,6 +2186,173 @@ class BatchedResults:
             cols[f"window_q95:{k}"] = np.ascontiguousarray(bands["q_hi"][:, :, j])
         cols["window_edges"] = np.asarray(bands["edges"], dtype=np.float64)
         cols["window_of"] = np.asarray(window_of)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
+    # ---- arrivals per window: the offered load and what became of each cohort ------------------------------------
+    #: the sweep keys that change a scenario's arrival times, and their engine columns
+    GENERATOR_COLUMNS = {"rqs_input.avg_active_users.mean": "gen_users_mean", "rqs_input.avg_active_users.variance": "gen_users_sigma",
+                         "rqs_input.avg_request_per_minute_per_user.mean": "gen_rpm_mean",
+                         "rqs_input.user_sampling_window": "gen_window"}
+
+    def _arrival_sweep(self, rows: Any = None) -> tuple[np.ndarray, list[tuple[int, int, np.ndarray]], int]:
+        """Seeds, generator columns and draw capacity of the run (of its scenarios ``rows``)."""
+        pick = slice(None) if rows is None else rows
+        cols = [(_abi.PARAM_CODES[name], 0, np.ascontiguousarray(np.asarray(self.overrides[key], dtype=np.float64)[pick]))
+                for key, name in self.GENERATOR_COLUMNS.items() if key in self.overrides]
+        cap = self.draw_capacity or (int(self._clock_t.shape[1]) if self._clock_t is not None else 0)
+        if cap <= 0:
+            msg = "the run's draw capacity is not known (BatchedResults(draw_capacity=...))"
+            raise ValueError(msg)
+        return np.ascontiguousarray(np.asarray(self.seeds, dtype=np.uint64)[pick]), cols, cap
+
+    def _arrival_engine(self) -> tuple[Any, Any]:
+        import torch
+
+        from .engine import Engine
+
+        dev = self._counts_t.device
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        return self._summ_engine, dev
+
+    def arrival_times(self, i: int) -> np.ndarray:
+        """The arrival times of scenario ``i``, float64 [generated], ascending: regenerated on the device from its seed
+        and generator parameters (``af_engine_summarize_arrivals`` with a ``times`` buffer), bit-equal to what the run
+        consumed and to :func:`arrival_times`.  Every ``start`` of the scenario's ``rqs_clock`` is one of them."""
+        import torch
+
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        seeds, cols, cap = self._arrival_sweep(slice(i, i + 1))
+        eng, dev = self._arrival_engine()
+        times = torch.empty((1, cap), dtype=torch.float64, device=dev)
+        arr = torch.empty((1, 1), dtype=torch.int64, device=dev)
+        eng.summarize_arrivals(seeds, cols, 1, np.asarray([0.0, max(float(self.plan.total_time), 1.0)]), draw_capacity=cap,
+                               arrivals_ptr=arr.data_ptr(), times_ptr=times.data_ptr())
+        t = times[0].cpu().numpy()
+        return t[np.isfinite(t)]
+
+    def arrival_summary(self, window_s: float | None = None, *, edges: Any = None, by: Any = None,
+                        thresholds: Any = None) -> dict[str, Any]:
+        """Arrivals per (group, time window), and what became of each window's cohort: the offered load, the share of the
+        requests SENT in a window that ever came back, and SLO shares with the ARRIVALS as the denominator -- the
+        by-arrival windows of :meth:`window_summary` / :meth:`quantile_summary` only see completions.  The arrival times are
+        regenerated on the device from the run's seeds, generator columns and draw capacity
+        (``af_engine_summarize_arrivals``: no simulation kernel runs) and counted in exact integers, equal to
+        :func:`arrival_window_counts` on :func:`arrival_times`.  Windows and ``by`` as in :meth:`window_summary`.
+        Returns, as numpy: ``edges`` [W + 1]; ``arrivals`` uint64 [G, W] (``edges[w] < t <= edges[w + 1]``);
+        ``offered_rps`` = arrivals / (members * window width); ``completed`` int64 [G, W], the by-arrival count of the same
+        cells (``af_engine_summarize_arrival_windows`` / ``_quantiles``); ``lost`` = arrivals - completed: the requests
+        that were DROPPED on an edge OR WERE STILL IN FLIGHT when the run ended -- the two are not told apart (drops per
+        window would need the simulation kernel to record them), so the last windows of a run always lose their slow
+        requests; ``completion_share`` = completed / arrivals (NaN without arrivals); with ``thresholds`` (seconds):
+        ``within`` int64 [G, W, T], the completions within each threshold, and ``within_share`` = within / arrivals;
+        ``truncated`` bool [G]: a member's arrival row was full (``FLAG_DRAW_OVERFLOW``) or its clock rows were cut, so its
+        counts are lower bounds; ``generated`` [n], ``flags`` [n], ``replicas`` [G], ``arrival_ms``.  Raises when a cell
+        of a group that is not truncated holds more completions than arrivals."""
+        import torch
+
+        self._require_clock()
+        e = _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        n, n_win = len(self), int(e.shape[0] - 1)
+        th = check_slo_thresholds(thresholds)
+        seeds, cols, cap = self._arrival_sweep()
+        eng, dev = self._arrival_engine()
+        arr = torch.empty((n_groups, n_win), dtype=torch.int64, device=dev)
+        gen = torch.empty(n, dtype=torch.int32, device=dev)
+        flg = torch.empty(n, dtype=torch.int32, device=dev)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        ms, _scratch = eng.summarize_arrivals(seeds, cols, n_groups, e, draw_capacity=cap, arrivals_ptr=arr.data_ptr(),
+                                              group_ptr=grp.data_ptr(), generated_ptr=gen.data_ptr(), flags_ptr=flg.data_ptr())
+        arrivals = arr.cpu().numpy().view(np.uint64)
+        generated = gen.cpu().numpy().view(np.uint32)
+        flags = flg.cpu().numpy().view(np.uint32)
+        out: dict[str, Any] = {"edges": e, "arrivals": arrivals, "generated": generated, "flags": flags, "arrival_ms": ms,
+                               "replicas": np.bincount(ids[ids >= 0], minlength=n_groups)}
+        if th.shape[0]:
+            qs = self.quantile_summary([], thresholds=th, edges=e, by=ids, window_of="arrival")
+            completed = qs["count"].cpu().numpy().astype(np.int64)
+            out["within"] = qs["within"].cpu().numpy().astype(np.int64)
+            out["thresholds"] = th
+        else:
+            completed = self.window_summary(edges=e, by=ids, window_of="arrival")["stats"][:, :, 0].cpu().numpy().astype(np.int64)
+        completed = completed[:n_groups]
+        cut = ((flags & _abi.FLAG_DRAW_OVERFLOW) != 0) | (self.counts[:, _abi.CNT_COMPLETED] > int(self._clock_t.shape[1]))
+        truncated = np.zeros(n_groups, dtype=bool)
+        truncated[ids[(ids >= 0) & cut]] = True
+        a = arrivals.astype(np.int64)
+        bad = (completed > a) & ~truncated[:, None]
+        if bad.any():
+            g, w = (int(v[0]) for v in np.nonzero(bad))
+            msg = (f"group {g}, window {w}: {int(completed[g, w])} completions of {int(a[g, w])} arrivals -- the arrival times "
+                   "regenerated are not the ones the run simulated (draw_capacity, seeds or generator columns differ)")
+            raise RuntimeError(msg)
+        width = np.diff(e)[None, :] * np.maximum(out["replicas"], 1)[:, None]
+        some = a > 0
+        out["offered_rps"] = a / width
+        out["completed"] = completed
+        out["lost"] = a - completed
+        out["completion_share"] = np.where(some, completed / np.maximum(a, 1), np.nan)
+        if th.shape[0]:
+            out["within"] = out["within"][:n_groups]
+            out["within_share"] = np.where(some[:, :, None], out["within"] / np.maximum(a, 1)[:, :, None], np.nan)
+        out["truncated"] = truncated
+        return out
+
+    def arrival_bands(self, window_s: float | None = None, *, edges: Any = None, by: Any = None, level: float = 0.95,
+                      q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of the offered load and the completion share: every scenario's own
+        ``offered_rps`` and ``completion_share`` (``arrival_summary(by="scenario")``), then per group (``by``) and window,
+        over the group's replicas with an arrival in the window (``n`` [G, W] of them), ``mean``, ``std``,
+        ``ci_halfwidth`` (at ``level``) and the linear quantiles ``q_lo`` / ``q_hi`` (``q``) as
+        :func:`window_bands_by_group` gives them: numpy float64 [G, W, 2], column 0 the offered load, 1 the share
+        (``keys``).  ``pooled`` is ``arrival_summary(by=by)``."""
+        import torch
+
+        e = _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        per = self.arrival_summary(edges=e, by="scenario")
+        dev = self._counts_t.device
+        body = torch.from_numpy(np.stack([per["offered_rps"], np.nan_to_num(per["completion_share"])], axis=2)).to(dev)
+        out = window_bands_by_group(body, ids, n_groups, level, q, valid=torch.from_numpy(per["arrivals"].astype(np.int64) > 0).to(dev))
+        out["keys"] = ("offered_rps", "completion_share")
+        out["pooled"] = self.arrival_summary(edges=e, by=ids)
+        out["edges"] = e
+        return out
+
+    def save_arrival_summary(self, path: str, by: Any = None, *, window_s: float | None = None, edges: Any = None,
+                             thresholds: Any = None, level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the arrivals with one row per group (grid point): ``param:<axis>`` (for a Sweep), ``replicas``,
+        ``truncated`` and the [G, W] columns ``arrivals``, ``offered_rps``, ``completed``, ``lost``, ``completion_share``
+        (the group's replicas pooled, :meth:`arrival_summary`), ``offered_rps_mean`` / ``_q05`` / ``_q95`` and
+        ``completion_share_mean`` / ``_q05`` / ``_q95`` (over the replicas, :meth:`arrival_bands`) and, per threshold j,
+        ``within:<j>`` and ``within_share:<j>``; ``window_edges`` [W + 1] and ``slo_thresholds`` [T] are per-file values.
+        ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        bands = self.arrival_bands(window_s, edges=edges, by=by, level=level, q=(0.05, 0.95))
+        pooled = bands["pooled"] if thresholds is None else self.arrival_summary(edges=bands["edges"], by=by, thresholds=thresholds)
+        n_groups = int(bands["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        cols["truncated"] = np.asarray(pooled["truncated"], dtype=bool)
+        cols["arrivals"] = pooled["arrivals"].astype(np.int64)
+        for k in ("offered_rps", "completed", "lost", "completion_share"):
+            cols[k] = np.ascontiguousarray(pooled[k])
+        for j, k in enumerate(bands["keys"]):
+            cols[f"{k}_mean"] = np.ascontiguousarray(bands["mean"][:, :, j])
+            cols[f"{k}_q05"] = np.ascontiguousarray(bands["q_lo"][:, :, j])
+            cols[f"{k}_q95"] = np.ascontiguousarray(bands["q_hi"][:, :, j])
+        for j in range(int(pooled["within"].shape[2]) if "within" in pooled else 0):
+            cols[f"within:{j}"] = np.ascontiguousarray(pooled["within"][:, :, j])
+            cols[f"within_share:{j}"] = np.ascontiguousarray(pooled["within_share"][:, :, j])
+        cols["window_edges"] = np.asarray(bands["edges"], dtype=np.float64)
+        cols["slo_thresholds"] = np.asarray(pooled.get("thresholds", np.zeros(0)), dtype=np.float64)
         _write_columns(str(path), cols, n_groups)
         return cols
 
@@ -3755,6 +4036,22 @@ class ShardedResults:
     def save_state_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_state_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
+
+    def arrival_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "arrival_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def arrival_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "arrival_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_arrival_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_arrival_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def arrival_times(self, i: int) -> np.ndarray:
+        k, j = self._where[int(i)]
+        return self.shards[int(k)].arrival_times(int(j))
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
         msg = "quantile_summary() of a sweep run on several devices: quantiles across devices are not implemented"

@@ -646,7 +646,7 @@ class SimulationRunner:
             user_cols = {k: np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype=np.float64), (n,))) for k, v in self.sweep.items()}
             res = BatchedResults(self.plan, self.seeds, counts, clock, samples, stats,
                                  time.perf_counter() - t0, user_cols,
-                                 online_hist=online_hist, online_rps=online_rps, online_hist_max=o_max)
+                                 online_hist=online_hist, online_rps=online_rps, online_hist_max=o_max, draw_capacity=clock_cap)
             res.flow_reason = flow_reason
             if summ_out is not None:
                 summ_out["summary_ms"] = float(stats.summary_ms)

@@ -885,6 +885,58 @@ int af_engine_summarize_quantiles(af_engine_t* engine, const af_outputs_t* out, 
  * neither needed nor checked.  Everything else as af_engine_summarize_quantiles. */
 int af_engine_summarize_arrival_quantiles(af_engine_t* engine, const af_outputs_t* out, af_quantiles_t* quantiles);
 
+/* ARRIVALS per window and group (asyncflow_amd/csrc/af_arrival_counts.hpp): the offered load, and the denominator the
+ * by-arrival cohorts above lack -- their count is the cohort's completions; a request that was dropped or was still in flight
+ * when the run ended is in no rqs_clock row.  Arrival times are a pure function of the seed and the generator's parameters;
+ * the engine works them out on the device before every run and this call does the same, WITHOUT a run: no simulation
+ * kernel is launched and no af_outputs_t is read.
+ * `sweep` is what af_engine_run takes; draw_capacity must be > 0 here (pass the run's value -- its clock_capacity where the
+ * run passed 0 -- so that the arrivals counted are exactly the ones simulated).  Let a_s[0 .. m_s) be the arrival times of
+ * scenario s: those of the sequential sampler (samplers/poisson_poisson.py:51-82, gaussian_poisson.py:63-94, summed on the
+ * simulation clock as rqs_generator.py:97-119 does) under seeds[s], the plan's generator parameters and the scenario's
+ * AF_PARAM_GEN_USERS_MEAN / _SIGMA / AF_PARAM_GEN_RPM_MEAN / AF_PARAM_GEN_WINDOW columns, cut at draw_capacity (m_s <=
+ * draw_capacity; other columns are checked like a run checks them and otherwise ignored).  With edges[0] < ... <
+ * edges[n_windows] (finite seconds):
+ *     row_bounds[s][k] = #{ i < m_s : a_s[i] <= edges[k] }      np.searchsorted(a_s, edges, side="right")
+ *     window w of s    = row_bounds[s][w + 1] - row_bounds[s][w] arrivals: edges[w] < t <= edges[w + 1], the bucket rule of
+ *                        the by-arrival latency windows (an arrival on an edge belongs to the window that ends there)
+ *     arrivals[g][w]   = the sum over the members of g;  generated[s] = m_s, which a run reports as counts[s][AF_CNT_GENERATED]
+ *     flags[s]         = AF_FLAG_DRAW_OVERFLOW where the sampler had a further arrival when the row was full, else 0
+ * Every output word is an exact integer (binary searches, integer atomics on zeroed outputs): the result does not depend on
+ * the launch, on the pre-generation kernel (AF_PREGEN_MODE, chosen as a run chooses it) or on the chunks.
+ * group: af_pooled_t's rule -- AF_POOL_SKIP leaves a scenario out of arrivals; its row_bounds / generated / flags are still
+ * written --, except that NULL means SINGLETONS here -- scenario s is group s, and n_groups must be n_scenarios.
+ * times / times_given:
+ *     times NULL                  the engine generates into its own scratch, in chunks sized by the memory budget of a run
+ *                                 (af_engine_options_t.draw_memory_mb), 8 B per scenario and draw;
+ *     times set, times_given 0    the engine generates into the caller's buffer (all scenarios at once), which the caller keeps:
+ *                                 a_s with +inf behind the last arrival, bit-equal to what the run consumed;
+ *     times set, times_given 1    the rows are READ and nothing is generated: they must be ascending with +inf behind the last
+ *                                 arrival (not checked: rows that are not give meaningless counts, nothing worse); seeds and
+ *                                 overrides of the sweep are ignored (seeds may be NULL), flags are 0.  For traces and tests.
+ * Refused, no output touched: n_scenarios == 0 or != sweep->n_scenarios, n_windows == 0, draw_capacity == 0, arrivals NULL,
+ * edges NULL / not finite / not strictly increasing, a group id >= n_groups, group NULL with n_groups != n_scenarios, a bad
+ * override, seeds NULL unless times_given (AF_ERR_INVALID); n_groups * n_windows >= 2^32 - 1, n_windows >= 2^24, a single
+ * scenario's row that does not fit the memory budget (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).
+ * Scratch kept by the engine: 8 B per edge and, without row_bounds, 4 B per (scenario of a chunk, edge), shared with the
+ * other analyzers; without times, the run's own arrival buffer.  Synchronous; the struct is written back. */
+typedef struct af_arrivals {
+    uint32_t n_scenarios;    /* = sweep->n_scenarios */
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;   /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: scenario s is group s */
+    const double* edges;     /* HOST [n_windows + 1] strictly increasing, finite */
+    double* times;           /* DEVICE [n_scenarios][draw_capacity] f64, optional (see above) */
+    uint32_t times_given;    /* 1: times holds the rows to count; 0: times, if set, receives the generated rows */
+    uint64_t* arrivals;      /* DEVICE [n_groups][n_windows] u64 out */
+    uint32_t* row_bounds;    /* DEVICE [n_scenarios][n_windows + 1] u32 out, optional */
+    uint32_t* generated;     /* DEVICE [n_scenarios] u32 out, optional */
+    uint32_t* flags;         /* DEVICE [n_scenarios] u32 out, optional */
+    double elapsed_ms;       /* out: wall time of the call */
+    uint64_t scratch_bytes;  /* out: size of the engine's scratch after the call */
+} af_arrivals_t;
+int af_engine_summarize_arrivals(af_engine_t* engine, const af_sweep_t* sweep, af_arrivals_t* arrivals);
+
 /* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
  * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
  * use, with the connections on an edge?  A cell is (group g, arrival window w, bin b of ONE sampled series at the row's tick).
