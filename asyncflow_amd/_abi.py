@@ -501,6 +501,35 @@ class AfArrivals(C.Structure):
     ]
 
 
+class AfInflight(C.Structure):
+    """``af_inflight_t``: request of ``af_engine_summarize_inflight`` (``elapsed_ms`` and ``scratch_bytes`` are written
+    back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("sample_period", C.c_double),
+        ("threshold", C.c_uint32),
+        ("n_bins", C.c_uint32),
+        ("lo", C.c_uint32),
+        ("count", C.c_void_p),
+        ("sum", C.c_void_p),
+        ("minv", C.c_void_p),
+        ("maxv", C.c_void_p),
+        ("above", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("under", C.c_void_p),
+        ("in_flight", C.c_void_p),
+        ("started", C.c_void_p),
+        ("finished", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -532,6 +561,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_quantiles",
     "af_engine_summarize_arrival_quantiles",
     "af_engine_summarize_arrivals",
+    "af_engine_summarize_inflight",
     "af_engine_summarize_state_windows",
     "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
@@ -592,6 +622,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_arrival_quantiles.restype = C.c_int
     lib.af_engine_summarize_arrivals.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfArrivals)]
     lib.af_engine_summarize_arrivals.restype = C.c_int
+    lib.af_engine_summarize_inflight.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfInflight)]
+    lib.af_engine_summarize_inflight.restype = C.c_int
     lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
     lib.af_engine_summarize_state_windows.restype = C.c_int
     lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]

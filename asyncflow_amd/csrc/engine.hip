@@ -68,6 +68,7 @@
 #include "af_state.hpp"
 #include "af_quantiles.hpp"
 #include "af_arrival_counts.hpp"
+#include "af_inflight.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -3478,6 +3479,114 @@ int af_engine_summarize_arrivals(af_engine_t* e, const af_sweep_t* sweep, af_arr
     const auto t0 = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(e->device));
     if (int rc = summarize_arrivals(e, sweep, req)) return rc;
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Requests in flight per tick, window of ticks and group (af_inflight.hpp).  The host checks the request, reads the group ids
+// and the counts back (may a cell reach 2^32 values?), uploads the edges and initialises the cells; one launch with a
+// workgroup per scenario, then the min of the empty cells.
+static_assert(afif::kSkip == AF_POOL_SKIP && afif::kMaxBins == AF_MAX_SERIES_HISTOGRAM_BINS, "the kernel's constants are the header's");
+
+int af_engine_summarize_inflight(af_engine_t* e, const af_outputs_t* out, af_inflight_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0)
+        return fail(AF_ERR_INVALID, "empty in-flight request (n_scenarios, n_groups and n_windows must be > 0)");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "inflight.tick_edges is required");
+    if (!req->count || !req->sum) return fail(AF_ERR_INVALID, "inflight.count and inflight.sum are required");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, cap = out->tick_capacity, B = req->hist ? req->n_bins : 0u;
+    if (req->hist && (B == 0 || B > AF_MAX_SERIES_HISTOGRAM_BINS))
+        return fail(AF_ERR_INVALID, "inflight.n_bins must be 1 .. AF_MAX_SERIES_HISTOGRAM_BINS (" + std::to_string(AF_MAX_SERIES_HISTOGRAM_BINS) + ")");
+    if (req->under && !req->hist) return fail(AF_ERR_INVALID, "inflight.under needs inflight.hist");
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    if (!(std::isfinite(req->sample_period) && req->sample_period > 0.0)) return fail(AF_ERR_INVALID, "inflight.sample_period must be a finite number above 0");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "requests in flight need outputs.clock");
+    if (cap == 0) return fail(AF_ERR_INVALID, "requests in flight need outputs.tick_capacity > 0");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS), grp;
+    HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+    if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    {   // may a cell reach 2^32 values?
+        std::vector<uint64_t> g_ticks(G, 0u);
+        bool big = false;
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = grp.empty() ? 0u : grp[s];
+            if (g == afif::kSkip) continue;
+            g_ticks[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+            big = big || g_ticks[g] > 0xFFFFFFFFull;
+        }
+        if (big) {   // (else no window of a group can hold 2^32 rows)
+            std::vector<uint64_t> cells((size_t)G * W, 0u);
+            for (uint32_t s = 0; s < n; ++s) {
+                const uint32_t g = grp.empty() ? 0u : grp[s];
+                if (g == afif::kSkip || g_ticks[g] <= 0xFFFFFFFFull) continue;
+                const uint32_t m = std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_TICKS], cap);
+                for (uint32_t w = 0; w < W && req->tick_edges[w] < m; ++w) {
+                    uint64_t& c = cells[(size_t)g * W + w];
+                    c += std::min(req->tick_edges[w + 1u], m) - req->tick_edges[w];
+                    if (c > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "window " + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more values");
+                }
+            }
+        }
+    }
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    const size_t cells = (size_t)G * W;
+    HIP_TRY(hipMemsetAsync(req->count, 0, cells * 4u, st));
+    HIP_TRY(hipMemsetAsync(req->sum, 0, cells * 8u, st));
+    if (req->minv) HIP_TRY(hipMemsetAsync(req->minv, 0xFF, cells * 4u, st));
+    if (req->maxv) HIP_TRY(hipMemsetAsync(req->maxv, 0, cells * 4u, st));
+    if (req->above) HIP_TRY(hipMemsetAsync(req->above, 0, cells * 4u, st));
+    if (req->hist) HIP_TRY(hipMemsetAsync(req->hist, 0, cells * B * 4u, st));
+    if (req->under) HIP_TRY(hipMemsetAsync(req->under, 0, cells * 4u, st));
+    afif::IfArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = out->clock_capacity;
+    a.tick_cap = cap;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.period = req->sample_period;
+    a.group = req->group;
+    a.n_win = W;
+    a.edges = reinterpret_cast<const uint32_t*>(e->d_pool + o_edges);
+    a.threshold = req->threshold;
+    a.n_bins = B;
+    a.lo = req->lo;
+    a.count = req->count;
+    a.sum = reinterpret_cast<unsigned long long*>(req->sum);
+    a.minv = req->minv;
+    a.maxv = req->maxv;
+    a.above = req->above;
+    a.hist = req->hist;
+    a.under = req->under;
+    a.in_flight = req->in_flight;
+    a.started = req->started;
+    a.finished = req->finished;
+    const bool both = req->started || req->finished;
+    const size_t lds = (size_t)afif::kChunkTicks * (both ? 8u : 4u);
+    const void* fn = both ? reinterpret_cast<const void*>(afif::af_inflight_kernel<WaveHip, true>)
+                          : reinterpret_cast<const void*>(afif::af_inflight_kernel<WaveHip, false>);
+    // (set before every launch: the attribute is per device and engines of several devices run in threads of one process)
+    if (lds > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void* kargs[] = {&a};
+    HIP_TRY(hipLaunchKernel(fn, dim3(n), dim3(afif::kThreads), kargs, lds, st));
+    if (req->minv) {
+        hipLaunchKernelGGL(afif::af_inflight_finish, dim3((uint32_t)((cells + 255u) / 256u)), dim3(256), 0, st, req->count, req->minv, (uint32_t)cells);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // (the host edges are read by the copy until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;

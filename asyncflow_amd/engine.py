@@ -371,6 +371,35 @@ class Engine:
         _check(self._lib, self._lib.af_engine_summarize_arrivals(self._h, C.byref(sweep), C.byref(req)), "af_engine_summarize_arrivals")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_inflight(self, n: int, n_groups: int, tick_edges: Any, sample_period: float, *, clock_ptr: int,
+                           clock_capacity: int, tick_capacity: int, counts_ptr: int, count_ptr: int, sum_ptr: int,
+                           min_ptr: int = 0, max_ptr: int = 0, above_ptr: int = 0, hist_ptr: int = 0, under_ptr: int = 0,
+                           in_flight_ptr: int = 0, started_ptr: int = 0, finished_ptr: int = 0, group_ptr: int = 0,
+                           threshold: int = 0, bins: int = 0, lo: int = 0) -> tuple[float, int]:
+        """Requests in flight on the device (``af_engine_summarize_inflight``): request i of a scenario's clock rows is
+        counted in the sample rows ``floor(start / sample_period) <= k < floor(finish / sample_period)`` (the host definition
+        is :func:`asyncflow_amd.results.in_flight_series`).  Per (group, window of ticks) ``count`` uint32, ``sum`` uint64 and,
+        each skipped by a pointer of 0, ``min`` / ``max`` / ``above`` (the values > ``threshold``) uint32 [n_groups, W], W =
+        len(tick_edges) - 1; with ``hist_ptr`` also ``hist`` uint32 [n_groups, W, bins] (bin b: the values equal to ``lo + b``,
+        the last bin takes everything above it) and ``under`` uint32 [n_groups, W]; per scenario ``in_flight`` / ``started``
+        / ``finished`` uint32 [n, tick_capacity] (rows at or past a scenario's ticks are left untouched).  ``tick_edges``:
+        HOST uint32 tick indices, strictly increasing; ``group_ptr`` as in :meth:`summarize_pooled`.  COMPLETED requests
+        only: dropped requests and requests still in flight at the end of the run are in no clock row.  Returns the call's
+        wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_in_flight_bins, check_tick_edges
+
+        b = check_tick_edges(tick_edges)
+        threshold, bins, lo = check_in_flight_bins(threshold, bins, lo)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), int(tick_capacity), None, C.c_void_p(counts_ptr or None))
+        req = _abi.AfInflight(int(n), int(n_groups), int(b.shape[0] - 1), C.c_void_p(group_ptr or None),
+                              b.ctypes.data_as(C.POINTER(C.c_uint32)), float(sample_period), int(threshold), int(bins), int(lo),
+                              C.c_void_p(count_ptr or None), C.c_void_p(sum_ptr or None), C.c_void_p(min_ptr or None),
+                              C.c_void_p(max_ptr or None), C.c_void_p(above_ptr or None), C.c_void_p(hist_ptr or None),
+                              C.c_void_p(under_ptr or None), C.c_void_p(in_flight_ptr or None), C.c_void_p(started_ptr or None),
+                              C.c_void_p(finished_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_inflight(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_inflight")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def _state_request(self, column: int, bins: int, lo: float, width: float, sample_period: float, edges: Any) -> tuple[Any, Any]:
         """``af_state_bins_t`` and the checked edges (or None) of the two latency-by-state calls."""
         from .results import _check_series_columns, check_state_bins

@@ -301,6 +301,83 @@ def arrival_window_counts(times: Any, edges: Any) -> np.ndarray:
     return np.searchsorted(t, e, side="right").astype(np.int64)
 
 
+def in_flight_series(clock_rows: Any, ticks: int, period: float) -> dict[str, np.ndarray]:
+    """Requests in flight end to end at every sample instant of one scenario: the host definition
+    ``af_engine_summarize_inflight`` is held to, word for word.
+
+    ``clock_rows``: float64 [m, 2], the stored ``(start, finish)`` rows; ``ticks``: the scenario's sample rows ``t_s``;
+    ``period``: the sample period ``p`` (sample row ``k`` is taken at ``(k + 1) * p``).  The tick of a time is ``q(t) =
+    floor(t / p)`` -- one float64 division, then floor, the rule of :func:`latency_state_cells` for ``start`` --, ``a_i =
+    q(start_i)``, ``f_i = q(finish_i)``.  Request i is counted in the rows ``a_i <= k < f_i``, clipped to ``[0, t_s)``: the
+    samples taken strictly after its start and at or before its finish, as the quotient sees them (the row a request "met
+    on arrival", ``q - 1``, does not contain it; the next one does).  Counted nowhere: ``start`` or ``finish`` NaN,
+    ``start < 0``, ``f_i <= a_i`` (a request that lived between two samples, or ``finish < start``), ``a_i >= t_s``; the
+    comparisons with ``t_s`` are made on the float64 quotients, so a huge ``finish / p`` clips.
+    Returns uint32 [t_s] each: ``started[k] = #{a_i == k}``, ``finished[k] = #{f_i == k}`` (a counted row with ``f_i >=
+    t_s`` is in none: still in flight at the last sample) and ``in_flight[k] = #{a_i <= k < f_i}``, which is also
+    ``cumsum(started - finished)``.  COMPLETED requests only: a dropped request and one still in flight when the run ended
+    are in no clock row, so the last seconds of a run under-count (``lost`` of :meth:`BatchedResults.arrival_summary`
+    says by how much)."""
+    p, t_s = float(period), int(ticks)
+    if not (np.isfinite(p) and p > 0.0):
+        msg = f"period must be a finite number above 0, not {period!r}"
+        raise ValueError(msg)
+    if t_s != ticks or not 0 <= t_s < 2 ** 31:
+        msg = f"ticks must be a whole number in [0, 2^31), not {ticks!r}"
+        raise ValueError(msg)
+    ck = np.asarray(clock_rows, dtype=np.float64).reshape(-1, 2)
+    start, finish = ck[:, 0], ck[:, 1]
+    with np.errstate(invalid="ignore", over="ignore"):
+        qa, qf = np.floor(start / p), np.floor(finish / p)
+        ok = (start >= 0.0) & ~np.isnan(finish) & (qa < float(t_s)) & (qf > qa)
+    a = qa[ok].astype(np.int64)
+    f = np.minimum(qf[ok], float(t_s)).astype(np.int64)
+    started = np.bincount(a, minlength=t_s)[:t_s]
+    finished = np.bincount(f, minlength=t_s + 1)[:t_s]
+    in_flight = np.cumsum(started - finished)
+    return {"started": started.astype(np.uint32), "finished": finished.astype(np.uint32), "in_flight": in_flight.astype(np.uint32)}
+
+
+def check_in_flight_bins(threshold: Any, bins: Any, lo: Any) -> tuple[int, int, int]:
+    """``threshold``, ``bins`` and ``lo`` of the in-flight statistics as whole numbers, or ValueError: ``threshold`` and ``lo``
+    in [0, 2^32), ``bins`` 0 (no histogram) .. 1024 (``AF_MAX_SERIES_HISTOGRAM_BINS``)."""
+    out = []
+    for name, v, top in (("threshold", threshold, 2 ** 32 - 1), ("bins", bins, 1024), ("lo", lo, 2 ** 32 - 1)):
+        if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+            msg = f"{name} must be a whole number in [0, {top}], not {v!r}"
+            raise ValueError(msg)
+        out.append(int(v))
+    return out[0], out[1], out[2]
+
+
+def in_flight_window_stats(members: Any, tick_edges: Any, threshold: int = 0, bins: int = 0, lo: int = 0) -> dict[str, np.ndarray]:
+    """The statistics of one cell row of ``af_engine_summarize_inflight`` on the host: ``members`` is the ``in_flight``
+    vector of every scenario of a group (one array, or a sequence of arrays of their own lengths ``t_s``), window w holds
+    the values ``in_flight[s][k]``, ``min(b[w], t_s) <= k < min(b[w + 1], t_s)``, of all of them.  Returns [W] each:
+    ``count`` int64, ``sum`` uint64, ``min``, ``max``, ``above`` (the values > ``threshold``) int64 and, with ``bins`` > 0,
+    ``hist`` int64 [W, bins] (bin b: the values equal to ``lo + b``; the last bin takes everything above it) and ``under``
+    (the values < ``lo``); an empty cell is all zeros."""
+    b = check_tick_edges(tick_edges).astype(np.int64)
+    thr, n_bins, lo_v = check_in_flight_bins(threshold, bins, lo)
+    rows = [np.asarray(members)] if isinstance(members, np.ndarray) and members.ndim == 1 else [np.asarray(v) for v in members]
+    n_win = int(b.shape[0] - 1)
+    out = {k: np.zeros(n_win, dtype=np.int64) for k in ("count", "min", "max", "above")}
+    out["sum"] = np.zeros(n_win, dtype=np.uint64)
+    if n_bins:
+        out["hist"] = np.zeros((n_win, n_bins), dtype=np.int64)
+        out["under"] = np.zeros(n_win, dtype=np.int64)
+    for w in range(n_win):
+        v = np.concatenate([r[min(int(b[w]), r.shape[0]): min(int(b[w + 1]), r.shape[0])].astype(np.int64) for r in rows] or [np.zeros(0, np.int64)])
+        if v.shape[0] == 0:
+            continue
+        out["count"][w], out["sum"][w], out["min"][w], out["max"][w] = v.shape[0], int(v.sum()), int(v.min()), int(v.max())
+        out["above"][w] = int((v > thr).sum())
+        if n_bins:
+            out["under"][w] = int((v < lo_v).sum())
+            out["hist"][w] = np.bincount(np.minimum(v[v >= lo_v] - lo_v, n_bins - 1), minlength=n_bins)
+    return out
+
+
 def check_tick_edges(tick_edges: Any) -> np.ndarray:
     """``tick_edges`` as a uint32 vector, or ValueError: at least two tick indices, whole, in [0, 2^32), strictly increasing."""
     raw = np.asarray(tick_edges)
@@ -1749,6 +1826,19 @@ class ScenarioResults:
         times = (np.arange(len(vals)) * self._plan.sample_period).tolist()
         return times, vals
 
+    def get_in_flight(self) -> Series:
+        """Requests in flight end to end at every sample instant, as a ``Series`` like :meth:`get_series`' (sample ``k``
+        carries the label ``k * sample_period``): :func:`in_flight_series` on the scenario's clock rows -- the "in-flight
+        requests" of a dashboard, which no sampled series holds.  COMPLETED requests only: dropped requests and those still
+        in flight when the run ended are missing, so the last seconds under-count
+        (:meth:`BatchedResults.arrival_summary`'s ``lost`` says by how much)."""
+        ticks = min(int(self.counts[_abi.CNT_TICKS]), max(int(self._plan.tick_count), 0))
+        if self._samples is not None:
+            ticks = min(ticks, int(self._samples.shape[1]))
+        vals = in_flight_series(self.rqs_clock, ticks, self._plan.sample_period)["in_flight"]
+        times = (np.arange(len(vals)) * self._plan.sample_period).tolist()
+        return times, vals.astype(np.float64).tolist()
+
     # ---- bridge to the reference's own analyzer / plots ----------------------------
     def to_reference_analyzer(self) -> Any:
         """Hydrate the reference's ``ResultsAnalyzer`` via duck-typed shims (needs `asyncflow`).
@@ -2355,6 +2445,179 @@ class BatchedResults:
         cols["slo_thresholds"] = np.asarray(pooled.get("thresholds", np.zeros(0)), dtype=np.float64)
         _write_columns(str(path), cols, n_groups)
         return cols
+
+    # ---- requests in flight end to end: L of Little's law ---------------------------------------------------------
+    def _in_flight_ticks(self) -> int:
+        """The tick capacity of the run's sample rows (without samples: the plan's tick count)."""
+        return int(self._samples_t.shape[1]) if self._samples_t is not None else max(int(self.plan.tick_count), 1)
+
+    def _in_flight_call(self, b: np.ndarray, ids: np.ndarray, n_groups: int, threshold: int, bins: int, lo: int) -> dict[str, Any]:
+        """One ``af_engine_summarize_inflight`` over resolved tick edges and group ids: the raw outputs on the host."""
+        import torch
+
+        self._require_clock()
+        thr, n_bins, lo_v = check_in_flight_bins(threshold, bins, lo)
+        eng, dev = self._arrival_engine()
+        n_win, clock = int(b.shape[0] - 1), self._clock_t
+        count, mn, mx, ab, under = (torch.empty((n_groups, n_win), dtype=torch.int32, device=dev) for _ in range(5))
+        total = torch.empty((n_groups, n_win), dtype=torch.int64, device=dev)
+        hist = torch.empty((n_groups, n_win, n_bins), dtype=torch.int32, device=dev) if n_bins else None
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        ms, scratch = eng.summarize_inflight(
+            len(self), n_groups, b, self.plan.sample_period, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
+            tick_capacity=self._in_flight_ticks(), counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(),
+            sum_ptr=total.data_ptr(), min_ptr=mn.data_ptr(), max_ptr=mx.data_ptr(), above_ptr=ab.data_ptr(),
+            hist_ptr=hist.data_ptr() if hist is not None else 0, under_ptr=under.data_ptr() if hist is not None else 0,
+            group_ptr=grp.data_ptr(), threshold=thr, bins=n_bins, lo=lo_v)
+
+        def host(t: Any) -> np.ndarray:
+            return t.cpu().numpy().view(np.uint32).astype(np.int64)
+
+        out: dict[str, Any] = {"count": host(count), "sum": total.cpu().numpy().view(np.uint64), "min": host(mn), "max": host(mx),
+                               "above": host(ab), "in_flight_ms": ms, "scratch_bytes": scratch}
+        if hist is not None:
+            out["hist"], out["under"] = host(hist), host(under)
+        return out
+
+    def in_flight_summary(self, window_s: float | None = None, *, ticks_per_window: int | None = None, tick_edges: Any = None,
+                          by: Any = None, threshold: int = 0, bins: int = 0, lo: int = 0) -> dict[str, Any]:
+        """Requests IN FLIGHT end to end per (group, window of ticks): the "in-flight requests" of a dashboard and L of
+        Little's law -- what sizes a client's connection pool or a global concurrency limit, and what builds up and drains
+        around an injected outage.  No sampled series or combination of them holds it (a request in a server's CPU step or
+        between two hops is in none).  Computed from the clock rows by ``af_engine_summarize_inflight``, every word equal to
+        :func:`in_flight_window_stats` on :func:`in_flight_series` of the group's scenarios: request i is counted at the
+        sample instants ``floor(start / p) <= k < floor(finish / p)``.  Windows and ``by`` as in
+        :meth:`series_window_summary` (``window_s`` seconds, default 1 s, ``ticks_per_window`` or ``tick_edges``).
+        Returns numpy arrays: ``count`` int64 [G, W] (the sample instants of the cell, over its members); ``sum`` uint64;
+        ``mean`` = ``float(sum) / float(count)`` (NaN in an empty cell); ``min`` / ``max`` int64 (0 in an empty cell);
+        ``above`` int64 and ``above_share`` = the share of the instants with more than ``threshold`` requests in flight
+        (NaN in an empty cell); with ``bins`` > 0 ``hist`` int64 [G, W, 1, bins] (bin b: exactly ``lo + b`` requests; the
+        LAST bin also holds everything above it, so choose ``bins > max - lo`` for exact quantiles), ``under`` [G, W, 1],
+        ``bin_edges`` [1, bins + 1] and ``ram`` -- the layout :func:`series_histogram_quantiles` reads exact quantiles off;
+        and ``series`` (``["in_flight"]``), ``tick_edges``, ``times`` (the windows' start labels in seconds), ``replicas``
+        [G], ``in_flight_ms``, ``scratch_bytes``.
+        COMPLETED requests only: a dropped request and one still in flight when the run ended are in no clock row, so the
+        last seconds of a run under-count as the by-arrival cohorts do; ``lost`` of :meth:`arrival_summary` sizes it."""
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        out = self._in_flight_call(b, ids, n_groups, threshold, bins, lo)
+        some = out["count"] > 0
+        cnt = np.maximum(out["count"], 1).astype(np.float64)
+        out["mean"] = np.where(some, out["sum"].astype(np.float64) / cnt, np.nan)
+        out["above_share"] = np.where(some, out["above"].astype(np.float64) / cnt, np.nan)
+        if "hist" in out:
+            n_bins = int(out["hist"].shape[2])
+            out["hist"], out["under"] = out["hist"][:, :, None, :], out["under"][:, :, None]
+            out["bin_edges"] = (float(lo) + np.arange(n_bins + 1, dtype=np.float64))[None, :]
+            out["ram"] = np.zeros(1, dtype=bool)
+        out.update(series=["in_flight"], threshold=int(threshold), tick_edges=b, times=b[:-1].astype(np.float64) * self.plan.sample_period,
+                   replicas=np.bincount(ids[ids >= 0], minlength=n_groups))
+        return out
+
+    def in_flight_bands(self, window_s: float | None = None, *, ticks_per_window: int | None = None, tick_edges: Any = None,
+                        by: Any = None, threshold: int = 0, of: str = "mean", level: float = 0.95,
+                        q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """Bands over the replicas of a windowed in-flight statistic ``of`` (``"mean"``, ``"max"`` or ``"above_share"``), as
+        :meth:`series_window_bands` gives them for the sampled series: every scenario's own window values
+        (``in_flight_summary(by="scenario")``), then per group (``by``) and window, over the group's replicas whose window
+        is not empty (``n`` [G, W] of them), ``mean``, ``std``, ``ci_halfwidth`` (at ``level``) and the linear quantiles
+        ``q_lo`` / ``q_hi`` (``q``): numpy float64 [G, W].  ``pooled`` is the grouped call's value of the same statistic."""
+        import torch
+
+        if of not in ("mean", "max", "above_share"):
+            msg = f"of must be 'mean', 'max' or 'above_share', not {of!r}"
+            raise ValueError(msg)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        per = self.in_flight_summary(tick_edges=b, by="scenario", threshold=threshold)
+        dev = self._counts_t.device
+        body = torch.from_numpy(np.nan_to_num(per[of].astype(np.float64))[:, :, None]).to(dev)
+        out = window_bands_by_group(body, ids, n_groups, level, q, valid=torch.from_numpy(per["count"] > 0).to(dev))
+        for k in ("mean", "std", "ci_halfwidth", "q_lo", "q_hi"):
+            out[k] = out[k][:, :, 0]
+        pooled = self.in_flight_summary(tick_edges=b, by=ids, threshold=threshold)
+        out["pooled"] = pooled[of][:n_groups].astype(np.float64)
+        out.update(of=of, summary=pooled, tick_edges=b, times=per["times"])
+        return out
+
+    def save_in_flight_summary(self, path: str, by: Any = None, *, window_s: float | None = None,
+                               ticks_per_window: int | None = None, threshold: int = 0, bins: int = 0, lo: int = 0,
+                               level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the requests in flight with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas`` and the [G, W] columns ``in_flight_count``, ``in_flight_mean``, ``in_flight_min``, ``in_flight_max``,
+        ``in_flight_above`` (the share above ``threshold``) -- the group's replicas taken together, :meth:`in_flight_summary`
+        --, ``in_flight_q05`` / ``in_flight_q95`` (of the replicas' own means, :meth:`in_flight_bands`) and, with ``bins``,
+        ``in_flight_hist`` [G, W, bins] and ``in_flight_under``; ``in_flight_tick_edges`` [W + 1], ``in_flight_times`` [W]
+        and ``in_flight_binning`` (threshold, lo) are per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary`
+        reads it back."""
+        b = self._series_tick_edges(window_s, ticks_per_window, None)
+        bands = self.in_flight_bands(tick_edges=b, by=by, threshold=threshold, level=level, q=(0.05, 0.95))
+        pooled = bands["summary"] if not bins else self.in_flight_summary(tick_edges=b, by=by, threshold=threshold, bins=bins, lo=lo)
+        n_groups = int(bands["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for k, v in by.point_columns().items():
+                cols[f"param:{k}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(bands["replicas"], dtype=np.int64)
+        for name, key in (("count", "count"), ("mean", "mean"), ("min", "min"), ("max", "max"), ("above", "above_share")):
+            cols[f"in_flight_{name}"] = np.ascontiguousarray(pooled[key][:n_groups])
+        cols["in_flight_q05"] = np.ascontiguousarray(bands["q_lo"])
+        cols["in_flight_q95"] = np.ascontiguousarray(bands["q_hi"])
+        if bins:
+            cols["in_flight_hist"] = np.ascontiguousarray(pooled["hist"][:n_groups, :, 0, :])
+            cols["in_flight_under"] = np.ascontiguousarray(pooled["under"][:n_groups, :, 0])
+        cols["in_flight_tick_edges"] = np.asarray(b, dtype=np.float64)
+        cols["in_flight_times"] = np.asarray(bands["times"], dtype=np.float64)
+        cols["in_flight_binning"] = np.asarray([threshold, lo], dtype=np.float64)
+        _write_columns(str(path), cols, n_groups)
+        return cols
+
+    def in_flight(self, i: int) -> dict[str, np.ndarray]:
+        """The per-tick arrays of scenario ``i``, uint32 [its ticks] each: ``in_flight`` (requests in flight end to end at
+        sample instant k), ``started`` and ``finished`` (``in_flight == cumsum(started - finished)``), written by
+        ``af_engine_summarize_inflight`` and equal to :func:`in_flight_series` on the scenario's clock rows."""
+        import torch
+
+        i = int(i)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        self._require_clock()
+        eng, dev = self._arrival_engine()
+        cap, clock = self._in_flight_ticks(), self._clock_t
+        rows = torch.empty((3, cap), dtype=torch.int32, device=dev)   # (rows at or past t_s are not written and not returned)
+        count = torch.empty((1, 1), dtype=torch.int32, device=dev)
+        total = torch.empty((1, 1), dtype=torch.int64, device=dev)
+        eng.summarize_inflight(1, 1, np.asarray([0, cap], dtype=np.uint32), self.plan.sample_period, clock_ptr=clock[i].data_ptr(),
+                               clock_capacity=int(clock.shape[1]), tick_capacity=cap, counts_ptr=self._counts_t[i].data_ptr(),
+                               count_ptr=count.data_ptr(), sum_ptr=total.data_ptr(), in_flight_ptr=rows[0].data_ptr(),
+                               started_ptr=rows[1].data_ptr(), finished_ptr=rows[2].data_ptr())
+        t_s = min(int(self.counts[i, _abi.CNT_TICKS]), cap)
+        words = rows[:, :t_s].cpu().numpy().view(np.uint32)
+        return {"in_flight": words[0].copy(), "started": words[1].copy(), "finished": words[2].copy()}
+
+    def littles_law(self, window_s: float | None = None, *, by: Any = None) -> dict[str, Any]:
+        """L, lambda and W of Little's law side by side per (group, window), each from its own exact analyzer -- informational:
+        nothing asserts that they agree, and over a window they only do as far as the requests open at its two ends allow.
+        Window w is the sample instants ``(k + 1) p`` of its ticks and the arrival cohort ``t0 < start <= t1`` over the same
+        span of ``window_s`` seconds (a multiple of the sample period; default 1 s).  Returns numpy float64 [G, W]: ``L``,
+        the mean number in flight (:meth:`in_flight_summary`); ``lambda_eff``, the COMPLETIONS of the window's arrival
+        cohort per second and replica (``window_summary(window_of="arrival")``: dropped requests and those still in flight at
+        the end of the run are in neither side); ``W``, the mean latency of that cohort in seconds (NaN without
+        completions); ``ratio`` = ``L / (lambda_eff * W)`` (NaN where that product is 0 or NaN); and ``completed`` int64,
+        ``edges`` (seconds) [W + 1], ``tick_edges``, ``replicas`` [G]."""
+        b = self._series_tick_edges(window_s, None, None)
+        ids, n_groups = self._window_groups(by)
+        edges = b.astype(np.float64) * float(self.plan.sample_period)
+        inf = self.in_flight_summary(tick_edges=b, by=ids)
+        stats = self.window_summary(edges=edges, by=ids, window_of="arrival")["stats"].cpu().numpy()[:n_groups]
+        completed = stats[:, :, 0].astype(np.int64)
+        width = np.diff(edges)[None, :] * np.maximum(inf["replicas"], 1)[:, None]
+        lam = completed / width
+        with np.errstate(invalid="ignore", divide="ignore"):
+            demand = lam * stats[:, :, 1]
+            ratio = np.where(demand > 0.0, inf["mean"][:n_groups] / demand, np.nan)
+        return {"L": inf["mean"][:n_groups], "lambda_eff": lam, "W": stats[:, :, 1], "ratio": ratio, "completed": completed,
+                "edges": edges, "tick_edges": b, "replicas": inf["replicas"]}
 
     def quantile_summary(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
                          by: Any = None, window_of: str = "finish") -> dict[str, Any]:
@@ -4052,6 +4315,26 @@ class ShardedResults:
     def arrival_times(self, i: int) -> np.ndarray:
         k, j = self._where[int(i)]
         return self.shards[int(k)].arrival_times(int(j))
+
+    def in_flight_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "in_flight_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def in_flight_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "in_flight_bands() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_in_flight_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_in_flight_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def littles_law(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "littles_law() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def in_flight(self, i: int) -> dict[str, np.ndarray]:
+        k, j = self._where[int(i)]
+        return self.shards[int(k)].in_flight(int(j))
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
         msg = "quantile_summary() of a sweep run on several devices: quantiles across devices are not implemented"

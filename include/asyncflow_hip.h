@@ -937,6 +937,67 @@ typedef struct af_arrivals {
 } af_arrivals_t;
 int af_engine_summarize_arrivals(af_engine_t* engine, const af_sweep_t* sweep, af_arrivals_t* arrivals);
 
+/* Requests IN FLIGHT end to end per tick, window of ticks and group, from the clock rows (asyncflow_amd/csrc/af_inflight.hpp):
+ * L of Little's law beside the arrivals per window (lambda, above) and the by-arrival latency windows (W).  No sampled series
+ * or combination of them holds it: a request in a server's CPU step or between two hops is in none of them.  Reads
+ * outputs.clock and outputs.counts only; no simulation kernel runs.
+ * Per scenario s: m_s = min(counts[s][AF_CNT_COMPLETED], clock_capacity) stored rows (start_i, finish_i), t_s =
+ * min(counts[s][AF_CNT_TICKS], tick_capacity) sample rows, p = sample_period.
+ *     tick of a time   q(t) = floor(t / p): one f64 division rounded to nearest, then floor -- the rule af_state_bins_t uses
+ *                      for `start`;  a_i = q(start_i), f_i = q(finish_i)
+ *     rows counted     sample row k is taken at (k + 1) p (af_series_windows_t): request i is counted in the rows
+ *                      a_i <= k < f_i, clipped to [0, t_s) -- the samples taken strictly after its start and at or before its
+ *                      finish, as the quotient sees them; the row a request "met on arrival" (q - 1 of af_state_bins_t) does not
+ *                      contain it, the next one does
+ *     counted nowhere  start or finish NaN; start < 0; f_i <= a_i (a request that lived between two samples, or a negative-delay
+ *                      residue with finish < start); a_i >= t_s.  The comparisons with t_s are made on the f64 quotients before
+ *                      any conversion to an integer: a huge finish / p clips, it does not wrap
+ *     started[s][k]    = #{ counted i : max(a_i, 0) == k }
+ *     finished[s][k]   = #{ counted i : f_i == k }; a counted row with f_i >= t_s is in none: still in flight at the last sample
+ *     in_flight[s][k]  = #{ counted i : a_i <= k < f_i } = the running sum of started - finished, finished[s][k] taken before
+ *                      row k is read;  all three u32
+ * Windows and groups: af_series_windows_t's -- tick_edges on tick indices, group / AF_POOL_SKIP, a cell of 2^32 or more values
+ * refused.  Cell (g, w) holds the values in_flight[s][k] of the members s of g, min(b[w], t_s) <= k < min(b[w + 1], t_s):
+ *     count u32, sum u64, minv / maxv u32, above u32 = the values > threshold;  with hist: hist[b] = the values == lo + b, the
+ *     LAST bin taking everything above it, under = the values < lo;  an empty cell: count 0 and every other output 0.
+ * in_flight / started / finished: optional DEVICE [n_scenarios][tick_capacity]; rows k < t_s are written, rows at or past t_s are
+ * left untouched; written for skipped scenarios too (as row_bounds elsewhere).
+ * COMPLETED REQUESTS ONLY: a dropped request, and a request still in flight when the run ended, is in no row, so the last
+ * seconds of a run under-count as the by-arrival cohorts do -- `lost` of the arrivals call sizes the under-count.
+ * Integer add / min / max atomics on initialised outputs only: every word is identical from run to run and does not depend on
+ * the batch a scenario sits in.
+ * Refused, no output touched: n_scenarios, n_groups or n_windows == 0, tick_edges NULL or not strictly increasing, a
+ * sample_period that is <= 0, NaN or infinite, a group id >= n_groups, outputs.clock or outputs.counts NULL, clock_capacity or
+ * tick_capacity == 0, count or sum NULL, with hist n_bins == 0 or above AF_MAX_SERIES_HISTOGRAM_BINS, under without hist
+ * (AF_ERR_INVALID); n_groups * n_windows >= 2^32 - 1, tick_capacity >= 2^31, a cell of 2^32 or more values (AF_ERR_CAPACITY);
+ * a planning-only engine (AF_ERR_NO_DEVICE).
+ * outputs.clock must be 16-byte aligned: a row is read as one (start, finish) pair by a 16-byte load (any device allocation is).
+ * Scratch kept by the engine: 4 B per edge, shared with the other analyzers.  Synchronous; the struct is written back. */
+typedef struct af_inflight {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing tick indices */
+    double sample_period;        /* p: seconds per tick, > 0 and finite */
+    uint32_t threshold;          /* above counts the values > threshold */
+    uint32_t n_bins;             /* with hist: 1 .. AF_MAX_SERIES_HISTOGRAM_BINS; ignored without */
+    uint32_t lo;                 /* the value of bin 0 */
+    uint32_t* count;             /* DEVICE [n_groups][n_windows] u32 out */
+    uint64_t* sum;               /* DEVICE [n_groups][n_windows] u64 out */
+    uint32_t* minv;              /* DEVICE [n_groups][n_windows] u32 out, optional */
+    uint32_t* maxv;              /* DEVICE [n_groups][n_windows] u32 out, optional */
+    uint32_t* above;             /* DEVICE [n_groups][n_windows] u32 out, optional */
+    uint32_t* hist;              /* DEVICE [n_groups][n_windows][n_bins] u32 out, optional */
+    uint32_t* under;             /* DEVICE [n_groups][n_windows] u32 out, optional, with hist only */
+    uint32_t* in_flight;         /* DEVICE [n_scenarios][tick_capacity] u32 out, optional */
+    uint32_t* started;           /* DEVICE [n_scenarios][tick_capacity] u32 out, optional */
+    uint32_t* finished;          /* DEVICE [n_scenarios][tick_capacity] u32 out, optional */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_inflight_t;
+int af_engine_summarize_inflight(af_engine_t* engine, const af_outputs_t* out, af_inflight_t* inflight);
+
 /* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
  * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
  * use, with the connections on an edge?  A cell is (group g, arrival window w, bin b of ONE sampled series at the row's tick).
