@@ -530,6 +530,30 @@ class AfInflight(C.Structure):
     ]
 
 
+class AfExemplars(C.Structure):
+    """``af_exemplars_t``: request of ``af_engine_summarize_exemplars`` (``elapsed_ms`` and ``scratch_bytes`` are written
+    back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("edges", C.POINTER(C.c_double)),
+        ("by_arrival", C.c_uint32),
+        ("k", C.c_uint32),
+        ("sample_period", C.c_double),
+        ("total", C.c_void_p),
+        ("kept", C.c_void_p),
+        ("scenario", C.c_void_p),
+        ("row", C.c_void_p),
+        ("clock", C.c_void_p),
+        ("state", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -562,6 +586,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_arrival_quantiles",
     "af_engine_summarize_arrivals",
     "af_engine_summarize_inflight",
+    "af_engine_summarize_exemplars",
     "af_engine_summarize_state_windows",
     "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
@@ -624,6 +649,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_arrivals.restype = C.c_int
     lib.af_engine_summarize_inflight.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfInflight)]
     lib.af_engine_summarize_inflight.restype = C.c_int
+    lib.af_engine_summarize_exemplars.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfExemplars)]
+    lib.af_engine_summarize_exemplars.restype = C.c_int
     lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
     lib.af_engine_summarize_state_windows.restype = C.c_int
     lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]

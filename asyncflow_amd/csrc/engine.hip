@@ -69,6 +69,7 @@
 #include "af_quantiles.hpp"
 #include "af_arrival_counts.hpp"
 #include "af_inflight.hpp"
+#include "af_exemplars.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -3587,6 +3588,121 @@ int af_engine_summarize_inflight(af_engine_t* e, const af_outputs_t* out, af_inf
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(st));   // (the host edges are read by the copy until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// The k slowest requests per window and group with their identity (af_exemplars.hpp).  The host checks the request, reads the
+// group ids back and lists each group's members in ascending scenario index; three launches: the per-(scenario, window) lists by a
+// wave per scenario, the cells by a wave per cell, the optional state gather.
+static_assert(afex::kSkip == AF_POOL_SKIP && afex::kMaxK == AF_MAX_EXEMPLARS, "the kernel's constants are the header's");
+
+int af_engine_summarize_exemplars(af_engine_t* e, const af_outputs_t* out, af_exemplars_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0) return fail(AF_ERR_INVALID, "empty exemplars request (n_scenarios and n_groups must be > 0)");
+    if (req->k == 0 || req->k > AF_MAX_EXEMPLARS) return fail(AF_ERR_INVALID, "exemplars.k must be 1 .. AF_MAX_EXEMPLARS (" + std::to_string(AF_MAX_EXEMPLARS) + ")");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, K = req->k;
+    if (W > 0 && !req->edges) return fail(AF_ERR_INVALID, "exemplars.edges is required with n_windows > 0");
+    if (W == 0 && req->edges) return fail(AF_ERR_INVALID, "exemplars.edges must be NULL with n_windows == 0");
+    if (W == 0 && req->by_arrival) return fail(AF_ERR_INVALID, "windows by arrival time need n_windows > 0");
+    if (W > 0)
+        if (int rc = check_window_edges(req->edges, W)) return rc;
+    if (!req->total || !req->scenario || !req->row || !req->clock) return fail(AF_ERR_INVALID, "exemplars.total, scenario, row and clock are required");
+    if (reinterpret_cast<uintptr_t>(req->clock) % 16u) return fail(AF_ERR_INVALID, "exemplars.clock must be 16-byte aligned");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "the slowest requests need outputs.clock");
+    const uint32_t S = e->args.n_edges + 3u * e->args.n_servers, pitch = e->args.series_pitch;
+    if (req->state) {
+        if (S == 0 || pitch < S) return fail(AF_ERR_INVALID, "the plan has no sampled series");
+        if (!out->samples || out->tick_capacity == 0) return fail(AF_ERR_INVALID, "exemplars.state needs outputs.samples");
+        if (!(std::isfinite(req->sample_period) && req->sample_period > 0.0)) return fail(AF_ERR_INVALID, "exemplars.sample_period must be a finite number above 0");
+    }
+    const uint64_t wins = W ? W : 1u;
+    if ((uint64_t)G * wins >= 0x100000000ull || (uint64_t)G * wins * K >= 0x100000000ull) return fail(AF_ERR_CAPACITY, "n_groups * max(n_windows, 1) * k must be below 2^32");
+    if ((uint64_t)n * wins >= 0x100000000ull || (uint64_t)n * wins * K >= 0x100000000ull) return fail(AF_ERR_CAPACITY, "n_scenarios * max(n_windows, 1) * k must be below 2^32");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> grp;
+    if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    std::vector<uint32_t> g_off((size_t)G + 1u, 0u), members;   // a counting sort: ascending scenario index within a group
+    for (uint32_t s = 0; s < n; ++s) {
+        const uint32_t g = grp.empty() ? 0u : grp[s];
+        if (g != afex::kSkip) g_off[(size_t)g + 1u] += 1u;
+    }
+    for (uint32_t g = 0; g < G; ++g) g_off[(size_t)g + 1u] += g_off[g];
+    members.resize(std::max<size_t>(g_off[G], 1u));
+    {
+        std::vector<uint32_t> next(g_off.begin(), g_off.end() - 1);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = grp.empty() ? 0u : grp[s];
+            if (g != afex::kSkip) members[next[g]++] = s;
+        }
+    }
+    const bool lds = wins <= afex::kLdsExemplarWindows;
+    const size_t NW = (size_t)n * wins, cells = (size_t)G * wins;
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 8u);
+    const size_t o_members = lay.part(members.size() * 4u);
+    const size_t o_goff = lay.part(g_off.size() * 4u);
+    const size_t o_cnt = lay.part(NW * 4u);
+    const size_t o_thr = lay.part(lds ? 0u : NW * 8u);
+    const size_t o_lrow = lay.part(NW * K * 4u);
+    const size_t o_lkey = lay.part(NW * K * 8u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    hipStream_t st = e->stream;
+    unsigned char* b = e->d_pool;
+    if (W) HIP_TRY(hipMemcpyAsync(b + o_edges, req->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_members, members.data(), members.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_goff, g_off.data(), g_off.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(b + o_cnt, 0, NW * 4u, st));   // (a skipped scenario writes none of its counts)
+    if (!lds) HIP_TRY(hipMemsetAsync(b + o_thr, 0, NW * 8u, st));
+    afex::ExArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = out->clock_capacity;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.group = req->group;
+    a.n_win = W;
+    a.wins = (uint32_t)wins;
+    a.edges = reinterpret_cast<const double*>(b + o_edges);
+    a.by_arrival = req->by_arrival ? 1u : 0u;
+    a.k = K;
+    a.lkey = reinterpret_cast<unsigned long long*>(b + o_lkey);
+    a.lrow = reinterpret_cast<uint32_t*>(b + o_lrow);
+    a.cnt = reinterpret_cast<uint32_t*>(b + o_cnt);
+    a.thr = lds ? nullptr : reinterpret_cast<unsigned long long*>(b + o_thr);
+    a.members = reinterpret_cast<const uint32_t*>(b + o_members);
+    a.g_off = reinterpret_cast<const uint32_t*>(b + o_goff);
+    a.cells = cells;
+    a.total = reinterpret_cast<unsigned long long*>(req->total);
+    a.kept = req->kept;
+    a.scenario = req->scenario;
+    a.row = req->row;
+    a.pair = req->clock;
+    a.samples = out->samples;
+    a.tick_cap = out->tick_capacity;
+    a.pitch = pitch;
+    a.n_series = S;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.period = req->sample_period;
+    a.state = req->state;
+    if (lds)
+        hipLaunchKernelGGL(afex::af_exemplar_lists<true>, dim3(n), dim3(64), (W ? ((size_t)W + 1u) * 8u : 0u) + (size_t)wins * 12u, st, a);
+    else
+        hipLaunchKernelGGL(afex::af_exemplar_lists<false>, dim3(n), dim3(64), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    if (int rc = launch_tiny_tier(cells, afex::kCellWaves, [&](uint32_t blocks, uint64_t c0) {
+            hipLaunchKernelGGL(afex::af_exemplar_cells, dim3(blocks), dim3(64u * afex::kCellWaves), 0, st, a, c0);
+        }))
+        return rc;
+    if (req->state) {
+        const uint64_t words = (uint64_t)cells * K * S;
+        hipLaunchKernelGGL(afex::af_exemplar_state, dim3((uint32_t)std::min<uint64_t>((words + 255u) / 256u, kBlocksPerLaunch)), dim3(256), 0, st, a, words);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // (the host edges and lists are read by the copies until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;

@@ -400,6 +400,36 @@ class Engine:
         _check(self._lib, self._lib.af_engine_summarize_inflight(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_inflight")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_exemplars(self, n: int, n_groups: int, k: int, *, edges: Any = None, window_of: str = "finish", clock_ptr: int,
+                            clock_capacity: int, counts_ptr: int, total_ptr: int, scenario_ptr: int, row_ptr: int, pair_ptr: int,
+                            kept_ptr: int = 0, state_ptr: int = 0, samples_ptr: int = 0, tick_capacity: int = 0,
+                            sample_period: float = 0.0, group_ptr: int = 0) -> tuple[float, int]:
+        """The ``k`` slowest requests per (group, time window) with their identity, on the device
+        (``af_engine_summarize_exemplars``; the host definition is :func:`asyncflow_amd.results.latency_exemplars`): larger
+        latency first, ties by ascending scenario index, then row index.  With W' = len(edges) - 1 windows (``edges=None``: one
+        window over all time) and C = n_groups * W' cells: ``total`` uint64 [C], ``kept`` uint32 [C] (skipped by a pointer of
+        0), ``scenario`` / ``row`` uint32 [C, k], ``pair`` float64 [C, k, 2] (the stored start / finish, 16-byte aligned) and,
+        with ``state_ptr`` (needs ``samples_ptr``, ``tick_capacity`` and ``sample_period``), ``state`` uint32 [C, k,
+        n_series]: the sample row the request met on arrival.  Every byte of the slots at or past ``kept`` is 0xFF.
+        ``window_of``: ``"finish"`` or ``"arrival"`` (needs edges); ``group_ptr`` as in :meth:`summarize_pooled`.  Returns the
+        call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_edges, check_exemplar_k, check_window_of
+
+        by_arrival = check_window_of(window_of) == "arrival"
+        e = None if edges is None else check_edges(edges)
+        if e is None and by_arrival:
+            msg = "window_of='arrival' needs edges: the whole run has no window"
+            raise ValueError(msg)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), int(tick_capacity), C.c_void_p(samples_ptr or None),
+                             C.c_void_p(counts_ptr or None))
+        req = _abi.AfExemplars(int(n), int(n_groups), 0 if e is None else int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
+                               None if e is None else e.ctypes.data_as(C.POINTER(C.c_double)), 1 if by_arrival else 0,
+                               check_exemplar_k(k), float(sample_period), C.c_void_p(total_ptr or None), C.c_void_p(kept_ptr or None),
+                               C.c_void_p(scenario_ptr or None), C.c_void_p(row_ptr or None), C.c_void_p(pair_ptr or None),
+                               C.c_void_p(state_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_exemplars(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_exemplars")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def _state_request(self, column: int, bins: int, lo: float, width: float, sample_period: float, edges: Any) -> tuple[Any, Any]:
         """``af_state_bins_t`` and the checked edges (or None) of the two latency-by-state calls."""
         from .results import _check_series_columns, check_state_bins

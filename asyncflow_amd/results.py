@@ -378,6 +378,92 @@ def in_flight_window_stats(members: Any, tick_edges: Any, threshold: int = 0, bi
     return out
 
 
+MAX_EXEMPLARS = 64   # AF_MAX_EXEMPLARS
+
+
+def check_exemplar_k(k: Any) -> int:
+    """``k`` as a whole number in 1 .. 64 (``AF_MAX_EXEMPLARS``), or ValueError."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= MAX_EXEMPLARS:
+        msg = f"k must be a whole number in [1, {MAX_EXEMPLARS}], not {k!r}"
+        raise ValueError(msg)
+    return int(k)
+
+
+def latency_exemplars(members: Any, k: int, edges: Any = None, window_of: str = "finish", *, scenario_ids: Any = None,
+                      samples: Any = None, sample_period: float | None = None) -> dict[str, np.ndarray]:
+    """The ``k`` SLOWEST requests per time window of one group, WITH THEIR IDENTITY: the definition
+    ``af_engine_summarize_exemplars`` equals word for word.  ``members``: the stored clock rows [m_s, 2] (start, finish) of
+    the group's scenarios in ascending scenario index (one array is one member); ``scenario_ids``: their indices (default
+    0, 1, ...).
+
+    * latency: ``finish - start``, one float64 subtraction; a row whose latency is NaN is in no cell.
+    * window: with ``edges`` the bucket rule of :func:`latency_window_stats` on ``t = finish`` (``window_of="finish"``) or
+      ``t = start`` (``"arrival"``), ``edges[w] < t <= edges[w + 1]``; rows with ``t <= edges[0]``, ``t > edges[W]`` or ``t``
+      NaN are in no cell.  A mask on every row: completion order is neither needed nor checked.  ``edges=None``: one window
+      with no condition on time (``window_of="arrival"`` is then refused).  W' = max(W, 1).
+    * order within a window: larger latency first, compared as float64 values (``-0.0 == +0.0``, ``+inf`` a value like any
+      other); ties by ascending scenario index, then ascending row index.  A total order.
+
+    Returns ``total`` uint64 [W'] (the rows of the window), ``kept`` uint32 [W'] = min(k, total), ``scenario`` and ``row``
+    uint32 [W', k] and ``clock`` float64 [W', k, 2] (the stored pair, bit for bit) of the first ``kept`` places; every byte of
+    the slots at or past ``kept`` is 0xFF.  With ``samples`` (per member the sampled series as uint32 words [n_series,
+    ticks]) and ``sample_period`` also ``state`` uint32 [W', k, n_series]: the raw words of sample row ``q - 1``, ``q =
+    floor(start / sample_period)`` (the tick rule of :func:`latency_state_cells`); no state -- ``q < 1``, ``q - 1 >= ticks``,
+    ``start`` NaN or negative -- is 0xFFFFFFFF in every word."""
+    kk = check_exemplar_k(k)
+    check_window_of(window_of)
+    e = None if edges is None else check_edges(edges)
+    if e is None and window_of == "arrival":
+        msg = "window_of='arrival' needs edges: the whole run has no window"
+        raise ValueError(msg)
+    rows = [np.asarray(members, dtype=np.float64)] if isinstance(members, np.ndarray) and members.ndim == 2 else [np.asarray(m, dtype=np.float64).reshape(-1, 2) for m in members]
+    ids = np.arange(len(rows), dtype=np.int64) if scenario_ids is None else np.asarray(scenario_ids, dtype=np.int64)
+    if ids.shape != (len(rows),) or (np.diff(ids) <= 0).any():
+        msg = "scenario_ids must be one strictly increasing index per member"
+        raise ValueError(msg)
+    n_win = 1 if e is None else int(e.shape[0] - 1)
+    ck = np.concatenate(rows + [np.zeros((0, 2))])
+    scen = np.concatenate([np.full(r.shape[0], i, dtype=np.int64) for r, i in zip(rows, ids)] + [np.zeros(0, np.int64)])
+    member = np.concatenate([np.full(r.shape[0], j, dtype=np.int64) for j, r in enumerate(rows)] + [np.zeros(0, np.int64)])
+    row = np.concatenate([np.arange(r.shape[0], dtype=np.int64) for r in rows] + [np.zeros(0, np.int64)])
+    with np.errstate(invalid="ignore", over="ignore"):
+        lat = ck[:, 1] - ck[:, 0]
+    ok = ~np.isnan(lat)
+    w = np.zeros(lat.shape, dtype=np.int64)
+    if e is not None:
+        eb = np.searchsorted(e, ck[:, 1 if window_of == "finish" else 0], side="left")   # #{edges < t}; a NaN: W + 1
+        ok &= (eb >= 1) & (eb <= n_win)
+        w = eb - 1
+    out = {"total": np.zeros(n_win, dtype=np.uint64), "kept": np.zeros(n_win, dtype=np.uint32),
+           "scenario": np.full((n_win, kk), 0xFFFFFFFF, dtype=np.uint32), "row": np.full((n_win, kk), 0xFFFFFFFF, dtype=np.uint32),
+           "clock": np.full((n_win, kk, 2), 0xFFFFFFFFFFFFFFFF, dtype=np.uint64).view(np.float64)}
+    words = None
+    if samples is not None:
+        words = [np.ascontiguousarray(s).view(np.uint32) for s in samples]
+        period = float(sample_period) if sample_period is not None else float("nan")
+        if len(words) != len(rows) or any(x.ndim != 2 or x.shape[0] != words[0].shape[0] for x in words):
+            msg = "samples must hold one array of words [n_series, ticks] per member"
+            raise ValueError(msg)
+        if not (np.isfinite(period) and period > 0.0):
+            msg = f"sample_period must be a finite number above 0, not {sample_period!r}"
+            raise ValueError(msg)
+        out["state"] = np.full((n_win, kk, words[0].shape[0] if words else 0), 0xFFFFFFFF, dtype=np.uint32)
+    for c in range(n_win):
+        idx = np.flatnonzero(ok & (w == c))
+        order = idx[np.lexsort((row[idx], scen[idx], -lat[idx]))][:kk]
+        n = int(order.shape[0])
+        out["total"][c], out["kept"][c] = idx.shape[0], n
+        out["scenario"][c, :n], out["row"][c, :n], out["clock"][c, :n] = scen[order], row[order], ck[order]
+        if words is not None:
+            for j, i in enumerate(order):
+                x = words[int(member[i])]
+                start = ck[i, 0]
+                q = np.floor(start / period) if start >= 0.0 else 0.0
+                if q >= 1.0 and q - 1.0 < float(x.shape[1]):
+                    out["state"][c, j] = x[:, int(q - 1.0)]
+    return out
+
+
 def check_tick_edges(tick_edges: Any) -> np.ndarray:
     """``tick_edges`` as a uint32 vector, or ValueError: at least two tick indices, whole, in [0, 2^32), strictly increasing."""
     raw = np.asarray(tick_edges)
@@ -1507,6 +1593,24 @@ def series_warmup_cut(summary: dict[str, Any]) -> np.ndarray:
     return np.where(ok, np.where(np.isnan(s), -np.inf, s).max(axis=-1), np.nan)
 
 
+def _exemplar_columns(ex: dict[str, np.ndarray], **extra: Any) -> dict[str, Any]:
+    """The raw outputs of the exemplars call (leading axes any) as what a user reads: int64 indices with -1 in the empty
+    slots, ``start`` / ``finish`` / ``latency`` with NaN there."""
+    with_scenario = extra.pop("with_scenario", True)
+    kept = np.asarray(ex["kept"]).astype(np.int64)
+    k = int(ex["row"].shape[-1])
+    empty = np.arange(k) >= kept[..., None]
+    pair = np.where(empty[..., None], np.nan, np.asarray(ex["clock"], dtype=np.float64))
+    out: dict[str, Any] = {}
+    if with_scenario:
+        out["scenario"] = np.where(empty, -1, np.asarray(ex["scenario"]).astype(np.int64))
+    out["row"] = np.where(empty, -1, np.asarray(ex["row"]).astype(np.int64))
+    with np.errstate(invalid="ignore", over="ignore"):
+        out.update(start=pair[..., 0], finish=pair[..., 1], latency=pair[..., 1] - pair[..., 0])
+    out.update(total=np.asarray(ex["total"]).astype(np.int64), kept=kept, **extra)
+    return out
+
+
 class ScenarioResults:
     """One scenario of a sweep; API of the reference's ``ResultsAnalyzer``."""
 
@@ -1838,6 +1942,15 @@ class ScenarioResults:
         vals = in_flight_series(self.rqs_clock, ticks, self._plan.sample_period)["in_flight"]
         times = (np.arange(len(vals)) * self._plan.sample_period).tolist()
         return times, vals.astype(np.float64).tolist()
+
+    def get_slowest_requests(self, k: int = 16, window_s: float | None = None, edges: Any = None, window_of: str = "finish") -> dict[str, Any]:
+        """The ``k`` slowest requests of the scenario, per time window (``window_s`` seconds or explicit ``edges``, by
+        ``window_of``) or, with neither, of the whole run: :func:`latency_exemplars` on the scenario's clock rows.  ``row``
+        int64 [W', k] indexes ``rqs_clock`` (-1 in an empty slot), ``start`` / ``finish`` / ``latency`` float64 [W', k] (NaN
+        in an empty slot), ``total`` and ``kept`` int64 [W'], ``edges`` (None for the whole run) and ``window_of``."""
+        e = None if window_s is None and edges is None else _resolve_edges(window_s, edges, self._plan.total_time)
+        ex = latency_exemplars([self.rqs_clock], k, e, window_of)
+        return _exemplar_columns(ex, edges=e, window_of=window_of, with_scenario=False)
 
     # ---- bridge to the reference's own analyzer / plots ----------------------------
     def to_reference_analyzer(self) -> Any:
@@ -2618,6 +2731,93 @@ class BatchedResults:
             ratio = np.where(demand > 0.0, inf["mean"][:n_groups] / demand, np.nan)
         return {"L": inf["mean"][:n_groups], "lambda_eff": lam, "W": stats[:, :, 1], "ratio": ratio, "completed": completed,
                 "edges": edges, "tick_edges": b, "replicas": inf["replicas"]}
+
+    # ---- the slowest requests per window and group, with their identity -------------------------------------------
+    def exemplar_summary(self, k: int = 16, window_s: float | None = None, *, edges: Any = None, by: Any = None,
+                         window_of: str = "finish", with_state: bool = False) -> dict[str, Any]:
+        """The ``k`` SLOWEST requests of every (group, time window) WITH THEIR IDENTITY -- a dashboard's "exemplars": from
+        "p99 rose here" to ``batch[s]``, the replica and the time to open; and the top-k latencies an extreme-value fit of
+        the tail starts from.  Computed by ``af_engine_summarize_exemplars``, every word equal to :func:`latency_exemplars`
+        on the group's scenarios: larger latency first, ties by ascending scenario index, then row index.  Windows:
+        ``window_s`` seconds or explicit ``edges`` by ``window_of`` (``"finish"`` or ``"arrival"``, as in
+        :meth:`window_summary`); neither: the whole run as one window (W' = 1, ``edges`` None; ``"arrival"`` is refused).
+        ``by`` as in :meth:`window_summary`.  Returns numpy arrays: ``scenario`` and ``row`` int64 [G, W', k]
+        (``batch[scenario].rqs_clock[row]`` is the request; -1 in an empty slot), ``start`` / ``finish`` / ``latency``
+        float64 [G, W', k] (NaN in an empty slot), ``total`` int64 [G, W'] (the rows of the cell) and ``kept`` = min(k,
+        total); with ``with_state=True`` also ``state`` float64 [G, W', k, series] -- the sample row the request met on
+        arrival, row ``floor(start / sample_period) - 1`` (the rule of :meth:`state_summary`), the ``ram_in_use`` columns
+        decoded from their float32 bits, NaN where there is no state -- and ``series_names``; and ``edges``, ``window_of``,
+        ``replicas`` [G], ``exemplar_ms``, ``scratch_bytes``.  COMPLETED requests only."""
+        import torch
+
+        self._require_clock()
+        kk = check_exemplar_k(k)
+        whole = window_s is None and edges is None
+        if check_window_of(window_of) == "arrival" and whole:
+            msg = "window_of='arrival' needs window_s or edges: the whole run has no window"
+            raise ValueError(msg)
+        if with_state:
+            self._require_samples()
+        e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._window_groups(by)
+        n_win = 1 if e is None else int(e.shape[0] - 1)
+        eng, dev = self._arrival_engine()
+        clock, samples, n_series = self._clock_t, self._samples_t, int(self.plan.n_series)
+        total = torch.empty((n_groups, n_win), dtype=torch.int64, device=dev)
+        kept = torch.empty((n_groups, n_win), dtype=torch.int32, device=dev)
+        scenario, row = (torch.empty((n_groups, n_win, kk), dtype=torch.int32, device=dev) for _ in range(2))
+        pair = torch.empty((n_groups, n_win, kk, 2), dtype=torch.float64, device=dev)
+        state = torch.empty((n_groups, n_win, kk, n_series), dtype=torch.int32, device=dev) if with_state else None
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        ms, scratch = eng.summarize_exemplars(
+            len(self), n_groups, kk, edges=e, window_of=window_of, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), total_ptr=total.data_ptr(), kept_ptr=kept.data_ptr(),
+            scenario_ptr=scenario.data_ptr(), row_ptr=row.data_ptr(), pair_ptr=pair.data_ptr(),
+            state_ptr=state.data_ptr() if state is not None else 0, samples_ptr=samples.data_ptr() if state is not None else 0,
+            tick_capacity=int(samples.shape[1]) if state is not None else 0, sample_period=float(self.plan.sample_period),
+            group_ptr=grp.data_ptr())
+
+        def host(t: Any) -> np.ndarray:
+            return t.cpu().numpy().view(np.uint32)
+
+        raw = {"total": total.cpu().numpy().view(np.uint64), "kept": host(kept), "scenario": host(scenario), "row": host(row),
+               "clock": pair.cpu().numpy()}
+        out = _exemplar_columns(raw, edges=e, window_of=window_of, replicas=np.bincount(ids[ids >= 0], minlength=n_groups),
+                                exemplar_ms=ms, scratch_bytes=scratch)
+        if state is not None:
+            w = host(state)
+            val = w.astype(np.float64)
+            ram = ram_columns(n_series, self.plan.n_edges)
+            val[..., ram] = w[..., ram].view(np.float32).astype(np.float64)
+            out["state"] = np.where(w == 0xFFFFFFFF, np.nan, val)
+            out["series_names"] = self.series_names()
+        return out
+
+    def save_exemplar_summary(self, path: str, by: Any = None, *, k: int = 16, window_s: float | None = None, edges: Any = None,
+                              window_of: str = "finish", with_state: bool = False) -> dict[str, np.ndarray]:
+        """Columnar dump of the slowest requests with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas`` and the [G, W', k] columns ``exemplar_scenario``, ``exemplar_row``, ``exemplar_start``,
+        ``exemplar_finish``, ``exemplar_latency``, the [G, W'] columns ``exemplar_total`` and ``exemplar_kept`` and, with
+        ``with_state``, ``exemplar_state`` [G, W', k, series] with the per-file ``series_names``
+        (:meth:`exemplar_summary`); ``window_edges`` [W + 1] (absent for the whole run) and ``window_of`` are per-file
+        values, as in :meth:`save_window_summary`.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        ex = self.exemplar_summary(k, window_s, edges=edges, by=by, window_of=window_of, with_state=with_state)
+        n_groups = int(ex["replicas"].shape[0])
+        cols: dict[str, np.ndarray] = {}
+        if hasattr(by, "point_columns"):
+            for name, v in by.point_columns().items():
+                cols[f"param:{name}"] = np.asarray(v, dtype=np.float64)
+        cols["replicas"] = np.asarray(ex["replicas"], dtype=np.int64)
+        for name in ("scenario", "row", "start", "finish", "latency", "total", "kept"):
+            cols[f"exemplar_{name}"] = np.ascontiguousarray(ex[name][:n_groups])
+        if with_state:
+            cols["exemplar_state"] = np.ascontiguousarray(ex["state"][:n_groups])
+            cols["series_names"] = np.asarray(ex["series_names"])
+        if ex["edges"] is not None:
+            cols["window_edges"] = np.asarray(ex["edges"], dtype=np.float64)
+        cols["window_of"] = np.asarray(window_of)
+        _write_columns(str(path), cols, n_groups)
+        return cols
 
     def quantile_summary(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
                          by: Any = None, window_of: str = "finish") -> dict[str, Any]:
@@ -4335,6 +4535,14 @@ class ShardedResults:
     def in_flight(self, i: int) -> dict[str, np.ndarray]:
         k, j = self._where[int(i)]
         return self.shards[int(k)].in_flight(int(j))
+
+    def exemplar_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "exemplar_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_exemplar_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_exemplar_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
         msg = "quantile_summary() of a sweep run on several devices: quantiles across devices are not implemented"

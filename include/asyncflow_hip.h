@@ -998,6 +998,58 @@ typedef struct af_inflight {
 } af_inflight_t;
 int af_engine_summarize_inflight(af_engine_t* engine, const af_outputs_t* out, af_inflight_t* inflight);
 
+/* The k SLOWEST REQUESTS per window and group WITH THEIR IDENTITY (asyncflow_amd/csrc/af_exemplars.hpp): the "exemplars" behind a
+ * window's max or p99 -- which scenario, which row of its rqs_clock, when it was sent and what the servers looked like then --
+ * and the input of an extreme-value fit of the tail.  The other analyzers return values only.  Reads outputs.clock and
+ * outputs.counts (with `state` also outputs.samples); no simulation kernel runs.
+ * Per scenario s: m_s = min(counts[s][AF_CNT_COMPLETED], clock_capacity) stored rows (start_i, finish_i).
+ *     latency          lat = finish - start, one f64 subtraction; a row whose latency is NaN is in no cell
+ *     window           with edges: the bucket rule of af_windows_t on t = finish (by_arrival == 0) or t = start (by_arrival != 0):
+ *                      window w where edges[w] < t <= edges[w + 1]; t <= edges[0], t > edges[W] or t NaN: in no cell.  A mask on
+ *                      every row: completion order is neither needed nor checked, in both modes.  Without edges (n_windows == 0,
+ *                      edges NULL) one window with no condition on time; by_arrival is then refused.  W' = max(n_windows, 1)
+ *     order            within cell c = g * W' + w: larger latency first, compared as f64 values (-0.0 and +0.0 are equal, +inf is
+ *                      a value like any other); ties by ascending scenario index, then ascending row index.  A total order: the
+ *                      result does not depend on the algorithm, the launch or the batch a scenario sits in
+ *     total[c]         u64: the rows of the cell;  kept[c] u32 = min(k, total[c])
+ *     scenario, row    [c][j], j < kept[c]: the j-th place of the order;  clock[c][j] = the stored (start, finish) pair bit for bit
+ *     behind kept      every byte of scenario, row, clock (and state) of the slots j >= kept[c] is 0xFF
+ *     state[c][j]      optional: the n_series (af_series_count) raw words of sample row q - 1, q = floor(start / sample_period) --
+ *                      af_state_bins_t's rule: one f64 division, then floor; ram_in_use words stay f32 bits.  No state, every word
+ *                      0xFFFFFFFF: q < 1, q - 1 >= t_s = min(counts[s][AF_CNT_TICKS], tick_capacity), start NaN or negative.  Only
+ *                      the n_series words of a row are read, never the padding of the pitch
+ * An empty or skipped (AF_POOL_SKIP) group's cells: total = kept = 0.
+ * Integer compares only, no atomics: every word is identical from run to run.
+ * Refused, no output touched: n_scenarios or n_groups == 0, k outside 1 .. AF_MAX_EXEMPLARS, edges not finite or not strictly
+ * increasing, edges NULL with n_windows > 0, by_arrival with n_windows == 0, a group id >= n_groups, outputs.clock or
+ * outputs.counts NULL, clock_capacity == 0, total / scenario / row / clock NULL, state without outputs.samples or with a
+ * sample_period that is <= 0, NaN or infinite (AF_ERR_INVALID); n_groups * W' * k or n_scenarios * W' * k >= 2^32
+ * (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).
+ * outputs.clock and exemplars.clock must be 16-byte aligned (any device allocation is): a pair moves as one 16-byte word.
+ * Scratch kept by the engine, shared with the other analyzers: n_scenarios * W' * (12 k + 4) bytes (the per-(scenario, window)
+ * lists and row counts), 8 more per (scenario, window) above 3 276 windows, 8 per edge, 4 per scenario and per group.
+ * Synchronous; the struct is written back. */
+#define AF_MAX_EXEMPLARS 64
+typedef struct af_exemplars {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;          /* 0: one window over all time (edges NULL) */
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const double* edges;         /* HOST [n_windows + 1] strictly increasing, finite; NULL with n_windows == 0 */
+    uint32_t by_arrival;         /* 0: windows by finish time; otherwise by start time (needs n_windows > 0) */
+    uint32_t k;                  /* 1 .. AF_MAX_EXEMPLARS */
+    double sample_period;        /* seconds per tick, > 0 and finite; used with state only */
+    uint64_t* total;             /* DEVICE [C] u64 out, C = n_groups * W' */
+    uint32_t* kept;              /* DEVICE [C] u32 out, optional */
+    uint32_t* scenario;          /* DEVICE [C][k] u32 out */
+    uint32_t* row;               /* DEVICE [C][k] u32 out */
+    double* clock;               /* DEVICE [C][k][2] f64 out, 16-byte aligned */
+    uint32_t* state;             /* DEVICE [C][k][af_series_count] u32 out, optional; needs outputs.samples */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_exemplars_t;
+int af_engine_summarize_exemplars(af_engine_t* engine, const af_outputs_t* out, af_exemplars_t* exemplars);
+
 /* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
  * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
  * use, with the connections on an edge?  A cell is (group g, arrival window w, bin b of ONE sampled series at the row's tick).
