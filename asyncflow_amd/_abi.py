@@ -554,6 +554,30 @@ class AfExemplars(C.Structure):
     ]
 
 
+class AfLatencyHistogram(C.Structure):
+    """``af_latency_histogram_t``: request of ``af_engine_summarize_latency_histogram`` (``elapsed_ms`` and ``scratch_bytes``
+    are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.c_void_p),
+        ("edges", C.POINTER(C.c_double)),
+        ("by_arrival", C.c_uint32),
+        ("sub_bits", C.c_uint32),
+        ("min_exp", C.c_int32),
+        ("octaves", C.c_uint32),
+        ("count", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("under", C.c_void_p),
+        ("over", C.c_void_p),
+        ("nan", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -587,6 +611,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_arrivals",
     "af_engine_summarize_inflight",
     "af_engine_summarize_exemplars",
+    "af_engine_summarize_latency_histogram",
     "af_engine_summarize_state_windows",
     "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
@@ -651,6 +676,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_inflight.restype = C.c_int
     lib.af_engine_summarize_exemplars.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfExemplars)]
     lib.af_engine_summarize_exemplars.restype = C.c_int
+    lib.af_engine_summarize_latency_histogram.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfLatencyHistogram)]
+    lib.af_engine_summarize_latency_histogram.restype = C.c_int
     lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
     lib.af_engine_summarize_state_windows.restype = C.c_int
     lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]

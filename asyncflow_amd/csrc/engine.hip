@@ -70,6 +70,7 @@
 #include "af_arrival_counts.hpp"
 #include "af_inflight.hpp"
 #include "af_exemplars.hpp"
+#include "af_latency_histogram.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -3703,6 +3704,90 @@ int af_engine_summarize_exemplars(af_engine_t* e, const af_outputs_t* out, af_ex
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(st));   // (the host edges and lists are read by the copies until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Log-linear latency histograms per window and group (af_latency_histogram.hpp).  The host checks the request, reads the group
+// ids and the counts back (may a group hold 2^32 rows?), uploads the edges and zeroes the outputs; one launch.
+static_assert(aflh::kSkip == AF_POOL_SKIP && aflh::kMaxBins == AF_MAX_LATENCY_HISTOGRAM_BINS, "the kernel's constants are the header's");
+
+int af_engine_summarize_latency_histogram(af_engine_t* e, const af_outputs_t* out, af_latency_histogram_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0) return fail(AF_ERR_INVALID, "empty latency histogram request (n_scenarios and n_groups must be > 0)");
+    aflh::Binning bin{};
+    if (!aflh::make_binning(req->sub_bits, req->min_exp, req->octaves, bin))
+        return fail(AF_ERR_INVALID, "latency_histogram binning: sub_bits 0 .. 8, min_exp >= -1022, octaves >= 1, min_exp + octaves <= 1023 and octaves << sub_bits <= AF_MAX_LATENCY_HISTOGRAM_BINS (" + std::to_string(AF_MAX_LATENCY_HISTOGRAM_BINS) + ")");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, B = bin.n_bins;
+    if (W > 0 && !req->edges) return fail(AF_ERR_INVALID, "latency_histogram.edges is required with n_windows > 0");
+    if (W == 0 && req->edges) return fail(AF_ERR_INVALID, "latency_histogram.edges must be NULL with n_windows == 0");
+    if (W == 0 && req->by_arrival) return fail(AF_ERR_INVALID, "windows by arrival time need n_windows > 0");
+    if (W > 0)
+        if (int rc = check_window_edges(req->edges, W)) return rc;
+    if (!req->count || !req->hist) return fail(AF_ERR_INVALID, "latency_histogram.count and latency_histogram.hist are required");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "latency histograms need outputs.clock");
+    if (reinterpret_cast<uintptr_t>(out->clock) % 16u) return fail(AF_ERR_INVALID, "outputs.clock must be 16-byte aligned");
+    const uint64_t wins = W ? W : 1u;
+    if ((uint64_t)G * wins >= 0x100000000ull || (uint64_t)G * wins * B >= 0x100000000ull)
+        return fail(AF_ERR_CAPACITY, "n_groups * max(n_windows, 1) * n_bins must be below 2^32");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> grp;
+    if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    {   // may a counter reach 2^32?  Not while no group holds that many stored rows (af_engine_summarize_pooled's rule)
+        std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS);
+        HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+        std::vector<uint64_t> g_rows(G, 0u);
+        for (uint32_t s = 0; s < n; ++s) {
+            const uint32_t g = grp.empty() ? 0u : grp[s];
+            if (g == aflh::kSkip) continue;
+            g_rows[g] += std::min(counts[(size_t)s * AF_CNT_SLOTS + AF_CNT_COMPLETED], out->clock_capacity);
+            if (g_rows[g] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "group " + std::to_string(g) + " holds 2^32 or more latencies");
+        }
+    }
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 8u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    hipStream_t st = e->stream;
+    if (W) HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, req->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+    const size_t cells = (size_t)G * wins;
+    HIP_TRY(hipMemsetAsync(req->count, 0, cells * 8u, st));
+    HIP_TRY(hipMemsetAsync(req->hist, 0, cells * B * 4u, st));
+    if (req->under) HIP_TRY(hipMemsetAsync(req->under, 0, cells * 4u, st));
+    if (req->over) HIP_TRY(hipMemsetAsync(req->over, 0, cells * 4u, st));
+    if (req->nan) HIP_TRY(hipMemsetAsync(req->nan, 0, cells * 4u, st));
+    aflh::LhArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = out->clock_capacity;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.group = req->group;
+    a.n_scen = n;
+    a.n_win = W;
+    a.wins = (uint32_t)wins;
+    a.edges = reinterpret_cast<const double*>(e->d_pool + o_edges);
+    a.by_arrival = req->by_arrival ? 1u : 0u;
+    a.chunks = (uint32_t)(((uint64_t)out->clock_capacity + aflh::kChunkRows - 1u) / aflh::kChunkRows);
+    a.bin = bin;
+    a.count = reinterpret_cast<unsigned long long*>(req->count);
+    a.hist = req->hist;
+    a.under = req->under;
+    a.over = req->over;
+    a.nan = req->nan;
+    const bool in_lds = W <= aflh::kLdsHistogramWindows;
+    const size_t lds = (in_lds && W ? ((size_t)W + 1u) * 8u : 0u) + (size_t)aflh::kWaves * B * 4u;
+    const void* fn = in_lds ? reinterpret_cast<const void*>(aflh::af_latency_histogram_kernel<true>)
+                            : reinterpret_cast<const void*>(aflh::af_latency_histogram_kernel<false>);
+    // (set before every launch: the attribute is per device and engines of several devices run in threads of one process)
+    if (lds > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const uint64_t items = (uint64_t)n * a.chunks;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((items + aflh::kWaves - 1u) / aflh::kWaves, aflh::kMaxBlocks);
+    void* kargs[] = {&a};
+    HIP_TRY(hipLaunchKernel(fn, dim3(blocks), dim3(aflh::kThreads), kargs, lds, st));
+    HIP_TRY(hipStreamSynchronize(st));   // (the host edges are read by the copy until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;

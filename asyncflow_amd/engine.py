@@ -430,6 +430,35 @@ class Engine:
         _check(self._lib, self._lib.af_engine_summarize_exemplars(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_exemplars")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_latency_histogram(self, n: int, n_groups: int, *, edges: Any = None, window_of: str = "finish", sub_bits: int = 5,
+                                    min_exp: int = -20, octaves: int = 32, clock_ptr: int, clock_capacity: int, counts_ptr: int,
+                                    count_ptr: int, hist_ptr: int, under_ptr: int = 0, over_ptr: int = 0, nan_ptr: int = 0,
+                                    group_ptr: int = 0) -> tuple[float, int]:
+        """Log-linear latency histograms per (group, time window) on the device (``af_engine_summarize_latency_histogram``;
+        the host definition is :func:`asyncflow_amd.results.latency_histogram`).  Binning on the bit pattern of the float64
+        latency: ``octaves`` octaves from ``2 ** min_exp`` seconds, ``2 ** sub_bits`` bins each, B = ``octaves << sub_bits``
+        bins (at most 4096).  With W' = len(edges) - 1 windows (``edges=None``: one window over all time) and C = n_groups * W'
+        cells: ``count`` uint64 [C] (the rows of the cell), ``hist`` uint32 [C, B] and, each skipped by a pointer of 0,
+        ``under`` / ``over`` / ``nan`` uint32 [C] (latencies below the first bin, at or above the last bin's end, NaN).
+        ``window_of``: ``"finish"`` or ``"arrival"`` (needs edges); ``group_ptr`` as in :meth:`summarize_pooled`.  Returns the
+        call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_edges, check_latency_bins, check_window_of
+
+        by_arrival = check_window_of(window_of) == "arrival"
+        m, e0, o, _ = check_latency_bins(sub_bits, min_exp, octaves)
+        e = None if edges is None else check_edges(edges)
+        if e is None and by_arrival:
+            msg = "window_of='arrival' needs edges: the whole run has no window"
+            raise ValueError(msg)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), 0, None, C.c_void_p(counts_ptr or None))
+        req = _abi.AfLatencyHistogram(int(n), int(n_groups), 0 if e is None else int(e.shape[0] - 1), C.c_void_p(group_ptr or None),
+                                      None if e is None else e.ctypes.data_as(C.POINTER(C.c_double)), 1 if by_arrival else 0,
+                                      m, e0, o, C.c_void_p(count_ptr or None), C.c_void_p(hist_ptr or None),
+                                      C.c_void_p(under_ptr or None), C.c_void_p(over_ptr or None), C.c_void_p(nan_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_latency_histogram(self._h, C.byref(out), C.byref(req)),
+               "af_engine_summarize_latency_histogram")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def _state_request(self, column: int, bins: int, lo: float, width: float, sample_period: float, edges: Any) -> tuple[Any, Any]:
         """``af_state_bins_t`` and the checked edges (or None) of the two latency-by-state calls."""
         from .results import _check_series_columns, check_state_bins

@@ -464,6 +464,273 @@ def latency_exemplars(members: Any, k: int, edges: Any = None, window_of: str = 
     return out
 
 
+MAX_LATENCY_HISTOGRAM_BINS = 4096   # AF_MAX_LATENCY_HISTOGRAM_BINS
+
+
+def check_latency_bins(sub_bits: Any = 5, min_exp: Any = -20, octaves: Any = 32) -> tuple[int, int, int, int]:
+    """The log-linear binning ``(sub_bits, min_exp, octaves, n_bins)`` as whole numbers, or ValueError: ``sub_bits`` m in
+    0 .. 8 (2^m bins an octave: a bin is 2^-m wide, relatively), ``min_exp`` e >= -1022 (the first bin starts at 2^e seconds),
+    ``octaves`` o >= 1 with e + o <= 1023, and ``n_bins = o << m`` in 1 .. 4096 (``AF_MAX_LATENCY_HISTOGRAM_BINS``)."""
+    vals = []
+    for name, v in (("sub_bits", sub_bits), ("min_exp", min_exp), ("octaves", octaves)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            msg = f"{name} must be a whole number, not {v!r}"
+            raise ValueError(msg)
+        vals.append(int(v))
+    m, e, o = vals
+    if not 0 <= m <= 8:
+        msg = f"sub_bits must lie in [0, 8], not {m}"
+        raise ValueError(msg)
+    if e < -1022 or o < 1 or e + o > 1023:
+        msg = f"min_exp must be >= -1022, octaves >= 1 and min_exp + octaves <= 1023, not min_exp {e}, octaves {o}"
+        raise ValueError(msg)
+    if (o << m) > MAX_LATENCY_HISTOGRAM_BINS:
+        msg = f"octaves << sub_bits must be at most {MAX_LATENCY_HISTOGRAM_BINS} bins, not {o << m}"
+        raise ValueError(msg)
+    return m, e, o, o << m
+
+
+def latency_bin_edges(sub_bits: int = 5, min_exp: int = -20, octaves: int = 32) -> np.ndarray:
+    """The edges E [n_bins + 1] of the log-linear latency bins, float64 seconds, each exact: bin b covers ``[E[b], E[b + 1])``,
+    ``E[b] = ldexp(1 + (b & (2^m - 1)) / 2^m, e + (b >> m))``."""
+    m, e, _, n_bins = check_latency_bins(sub_bits, min_exp, octaves)
+    b = np.arange(n_bins + 1, dtype=np.int64)
+    return np.ldexp(1.0 + (b & ((1 << m) - 1)) / float(1 << m), (e + (b >> m)).astype(np.int32))
+
+
+def latency_bin_index(lat: Any, sub_bits: int = 5, min_exp: int = -20, octaves: int = 32) -> np.ndarray:
+    """The bin of every latency by THE BIT RULE, int64 of ``lat``'s shape: with ``bits`` the 64-bit pattern of the float64
+    value, ``(bits >> (52 - m)) - ((e + 1023) << m)``; -1 below the first bin (``x < 2^e``: zeros, ``-0.0``, negatives,
+    denormals, ``-inf``), -2 at or above the end of the last (``x >= 2^(e + o)``, ``+inf``), -3 for a NaN.  Equal to
+    ``np.searchsorted(latency_bin_edges(...), x, side="right") - 1`` inside the bins."""
+    m, e, o, _ = check_latency_bins(sub_bits, min_exp, octaves)
+    x = np.asarray(lat, dtype=np.float64)
+    bits = np.ascontiguousarray(x).reshape(-1).view(np.uint64)
+    mag = bits & np.uint64(0x7FFFFFFFFFFFFFFF)
+    first, end = np.uint64((e + 1023) << 52), np.uint64((e + o + 1023) << 52)
+    idx = (bits >> np.uint64(52 - m)).astype(np.int64) - ((e + 1023) << m)
+    out = np.where(mag > np.uint64(0x7FF0000000000000), -3,
+                   np.where(((bits >> np.uint64(63)) != 0) | (bits < first), -1, np.where(bits >= end, -2, idx)))
+    return out.astype(np.int64).reshape(x.shape)
+
+
+def latency_histogram(members: Any, edges: Any = None, window_of: str = "finish", *, sub_bits: int = 5, min_exp: int = -20,
+                      octaves: int = 32) -> dict[str, np.ndarray]:
+    """The log-linear latency histogram per time window of ONE group: the definition
+    ``af_engine_summarize_latency_histogram`` equals word for word.  ``members``: the stored clock rows [m_s, 2] (start,
+    finish) of the group's scenarios (one array is one member).
+
+    * latency: ``finish - start``, one float64 subtraction, binned by :func:`latency_bin_index`.
+    * window: with ``edges`` the bucket rule of :func:`latency_exemplars` on ``t = finish`` (``window_of="finish"``) or ``t =
+      start`` (``"arrival"``), ``edges[w] < t <= edges[w + 1]``; rows with ``t <= edges[0]``, ``t > edges[W]`` or ``t`` NaN are
+      in no cell.  A mask on every row: completion order is neither needed nor checked.  ``edges=None``: one window with no
+      condition on time (``window_of="arrival"`` is then refused).  W' = max(W, 1).
+
+    Returns ``count`` uint64 [W'] (the rows of the window), ``hist`` uint32 [W', n_bins] and ``under``, ``over``, ``nan`` uint32
+    [W'] with ``under + over + nan + hist.sum(axis=1) == count``.  Only integer additions: histograms over the same windows
+    and binning add word by word."""
+    m, e0, o, n_bins = check_latency_bins(sub_bits, min_exp, octaves)
+    check_window_of(window_of)
+    e = None if edges is None else check_edges(edges)
+    if e is None and window_of == "arrival":
+        msg = "window_of='arrival' needs edges: the whole run has no window"
+        raise ValueError(msg)
+    rows = [np.asarray(members, dtype=np.float64)] if isinstance(members, np.ndarray) and members.ndim == 2 else [np.asarray(r, dtype=np.float64).reshape(-1, 2) for r in members]
+    ck = np.concatenate(rows + [np.zeros((0, 2))])
+    n_win = 1 if e is None else int(e.shape[0] - 1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        b = latency_bin_index(ck[:, 1] - ck[:, 0], m, e0, o)
+    ok = np.ones(b.shape, dtype=bool)
+    w = np.zeros(b.shape, dtype=np.int64)
+    if e is not None:
+        eb = np.searchsorted(e, ck[:, 1 if window_of == "finish" else 0], side="left")   # #{edges < t}; a NaN: W + 1
+        ok = (eb >= 1) & (eb <= n_win)
+        w = eb - 1
+    out = {"count": np.bincount(w[ok], minlength=n_win).astype(np.uint64)}
+    inside = ok & (b >= 0)
+    out["hist"] = np.bincount(w[inside] * n_bins + b[inside], minlength=n_win * n_bins).reshape(n_win, n_bins).astype(np.uint32)
+    for name, code in (("under", -1), ("over", -2), ("nan", -3)):
+        out[name] = np.bincount(w[ok & (b == code)], minlength=n_win).astype(np.uint32)
+    return out
+
+
+_LHIST_COUNTS = ("hist", "count", "under", "over", "nan")
+
+
+def _latency_histogram_parts(summary: Any) -> dict[str, Any]:
+    """A latency histogram summary -- what ``latency_histogram_summary`` returns, or the columns :func:`load_summary` reads
+    from ``save_latency_histogram_summary``'s file -- with numpy int64 counts: ``hist`` [G, W', B], the others [G, W']."""
+    saved = "lhist_hist" in summary
+    pre = "lhist_" if saved else ""
+    out: dict[str, Any] = {}
+    for k in _LHIST_COUNTS:
+        v = summary[pre + k]
+        out[k] = np.asarray(v.cpu().numpy() if hasattr(v, "cpu") else v).astype(np.int64)
+    for k in ("sub_bits", "min_exp", "octaves"):
+        out[k] = int(np.asarray(summary[pre + k]).reshape(-1)[0])
+    m, e0, o, n_bins = check_latency_bins(out["sub_bits"], out["min_exp"], out["octaves"])
+    edges = summary.get("window_edges") if saved else summary.get("edges")
+    out["edges"] = None if edges is None else np.asarray(edges, dtype=np.float64)
+    out["window_of"] = str(np.asarray(summary["window_of"]).reshape(-1)[0])
+    out["replicas"] = np.asarray(summary["replicas"], dtype=np.int64)
+    out["bin_edges"] = latency_bin_edges(m, e0, o)
+    n_win = 1 if out["edges"] is None else int(out["edges"].shape[0] - 1)
+    if out["hist"].ndim != 3 or out["hist"].shape[1:] != (n_win, n_bins) or any(out[k].shape != out["hist"].shape[:2] for k in _LHIST_COUNTS[1:]):
+        msg = f"not a latency histogram summary: hist of shape {out['hist'].shape} for {n_win} windows and {n_bins} bins"
+        raise ValueError(msg)
+    return out
+
+
+def latency_histogram_quantiles(summary: Any, levels: Any) -> dict[str, np.ndarray]:
+    """BRACKETS of any latency quantiles, read off a latency histogram summary after the fact: numpy float64 ``lo`` and ``hi``
+    [G, W', L] with ``lo <= np.quantile(valid latencies of the cell, q) < hi`` for every level q in [0, 1].  The sample of a
+    cell is its ``N = count - nan`` valid values, ``under`` below bin 0 and ``over`` above the last bin.  ``np.quantile``
+    interpolates between the order statistics ``floor((N - 1) q)`` and ``ceil((N - 1) q)``: ``lo`` is the lower edge of the
+    bin that holds the first, ``hi`` the upper edge of the bin that holds the second -- ``hi / lo <= (1 + 2^-m)^2`` when they
+    lie in the same or in adjacent bins.  In ``under``: ``lo = -inf`` (``hi`` = the first edge); in ``over``: ``hi = +inf``;
+    an empty cell: NaN."""
+    p = _latency_histogram_parts(summary)
+    q = np.array(levels, dtype=np.float64).reshape(-1)
+    if not ((q >= 0.0) & (q <= 1.0)).all():
+        msg = "quantile levels must lie in [0, 1]"
+        raise ValueError(msg)
+    E = p["bin_edges"]
+    lower = np.concatenate([[-np.inf], E])            # entry 0: under, 1 .. B: the bins, B + 1: over
+    upper = np.concatenate([E, [np.inf]])
+    cum = np.cumsum(np.concatenate([p["under"][..., None], p["hist"], p["over"][..., None]], axis=2), axis=2)
+    n = cum[..., -1]
+    shape = n.shape
+    lo = np.full((*shape, q.shape[0]), np.nan)
+    hi = np.full((*shape, q.shape[0]), np.nan)
+    for c in np.ndindex(*shape):
+        if n[c] == 0:
+            continue
+        pos = float(n[c] - 1) * q
+        first = np.searchsorted(cum[c], np.floor(pos).astype(np.int64), side="right")
+        second = np.searchsorted(cum[c], np.ceil(pos).astype(np.int64), side="right")
+        lo[c], hi[c] = lower[first], upper[second]
+    return {"lo": lo, "hi": hi, "levels": q}
+
+
+def _same_latency_histogram_cells(a: dict[str, Any], b: dict[str, Any]) -> None:
+    for k in ("sub_bits", "min_exp", "octaves", "window_of"):
+        if a[k] != b[k]:
+            msg = f"the two latency histograms differ in {k}: {a[k]!r} and {b[k]!r}"
+            raise ValueError(msg)
+    if (a["edges"] is None) != (b["edges"] is None) or (a["edges"] is not None and not np.array_equal(a["edges"], b["edges"])):
+        msg = "the two latency histograms differ in their window edges"
+        raise ValueError(msg)
+    if a["hist"].shape[0] != b["hist"].shape[0]:
+        msg = f"the two latency histograms differ in their number of groups: {a['hist'].shape[0]} and {b['hist'].shape[0]}"
+        raise ValueError(msg)
+
+
+def latency_histogram_merge(a: Any, b: Any, *more: Any) -> dict[str, Any]:
+    """The sum of two (or more) latency histogram summaries over the same cells -- two devices, a member split, yesterday's
+    saved sweep and today's: the counts add word by word, ``replicas`` too.  Each is what ``latency_histogram_summary``
+    returns or what :func:`load_summary` reads from its dump.  Binning, ``edges``, ``window_of`` and the number of groups must
+    be equal, otherwise ValueError.  Returns a summary with numpy int64 counts."""
+    out = _latency_histogram_parts(a)
+    for other in (b, *more):
+        p = _latency_histogram_parts(other)
+        _same_latency_histogram_cells(out, p)
+        for k in _LHIST_COUNTS:
+            out[k] = out[k] + p[k]
+        out["replicas"] = out["replicas"] + p["replicas"]
+    return out
+
+
+def latency_histogram_regroup(summary: Any, groups: Any = None, windows: Any = None) -> dict[str, Any]:
+    """Coarsen a latency histogram summary after the run by summing cells.  ``groups``: for every group its new group, -1 to
+    drop it (marginalise a grid axis: map the points that differ only in it to one id).  ``windows``: ranges ``(w0, w1)`` of
+    consecutive windows ``w0 <= w < w1``, each starting where the one before it ended, so the result has the edges
+    ``edges[w0]`` of every range and ``edges[w1]`` of the last.  Returns a summary (numpy int64 counts): the quantile, merge
+    and distance functions work on it."""
+    p = _latency_histogram_parts(summary)
+    n_groups, n_win = p["hist"].shape[:2]
+    if groups is not None:
+        ids = np.asarray(groups)
+        if ids.shape != (n_groups,) or not np.issubdtype(ids.dtype, np.integer) or ids.max(initial=-1) < 0:
+            msg = f"groups must give one whole new group id per group ({n_groups}), at least one of them kept"
+            raise ValueError(msg)
+        ids = ids.astype(np.int64)
+        kept = ids >= 0
+        new_n = int(ids.max()) + 1
+        for k in _LHIST_COUNTS:
+            acc = np.zeros((new_n, *p[k].shape[1:]), dtype=np.int64)
+            np.add.at(acc, ids[kept], p[k][kept])
+            p[k] = acc
+        p["replicas"] = np.bincount(ids[kept], weights=p["replicas"][kept], minlength=new_n).astype(np.int64)
+    if windows is not None:
+        rng = [(int(a), int(b)) for a, b in windows]
+        if not rng or any(not 0 <= a < b <= n_win for a, b in rng) or any(rng[k][1] != rng[k + 1][0] for k in range(len(rng) - 1)):
+            msg = f"windows must be ranges (w0, w1) with 0 <= w0 < w1 <= {n_win}, each starting where the one before ended"
+            raise ValueError(msg)
+        for k in _LHIST_COUNTS:
+            p[k] = np.stack([p[k][:, a:b].sum(axis=1) for a, b in rng], axis=1)
+        if p["edges"] is not None:
+            p["edges"] = p["edges"][[rng[0][0]] + [b for _, b in rng]]
+    return p
+
+
+def latency_histogram_distance(summary: Any, a: Any, b: Any) -> dict[str, Any]:
+    """The two-sample Kolmogorov-Smirnov distance between cells ``a`` and ``b`` of a latency histogram summary on the bin
+    grid: two grid points, a window before an outage and one after it.  ``a`` and ``b`` are ``(group, window)`` index pairs,
+    or arrays [..., 2] of them.  With the cumulative valid counts ``ca_k``, ``cb_k`` (``under`` first, ``over`` last) and
+    ``Na``, ``Nb`` the valid values of the cells: ``num = max_k |ca_k Nb - cb_k Na|`` and ``den = Na Nb`` as exact Python
+    ints (object arrays for arrays of pairs), ``d = num / den`` float64 -- NaN where either cell is empty."""
+    p = _latency_histogram_parts(summary)
+    pa, pb = np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)
+    if pa.shape != pb.shape or pa.ndim < 1 or pa.shape[-1] != 2:
+        msg = f"a and b must be (group, window) pairs of the same shape, not {pa.shape} and {pb.shape}"
+        raise ValueError(msg)
+    n_groups, n_win = p["hist"].shape[:2]
+    for x in (pa, pb):
+        if ((x < 0) | (x >= np.array([n_groups, n_win]))).any():
+            msg = f"a (group, window) pair lies outside the {n_groups} groups and {n_win} windows"
+            raise ValueError(msg)
+    cum = np.cumsum(np.concatenate([p["under"][..., None], p["hist"], p["over"][..., None]], axis=2), axis=2)
+    shape = pa.shape[:-1]
+    num, den, d = np.empty(shape, dtype=object), np.empty(shape, dtype=object), np.full(shape, np.nan)
+    for c in np.ndindex(*shape):
+        ca, cb = cum[tuple(pa[c])].astype(object), cum[tuple(pb[c])].astype(object)
+        na, nb = int(ca[-1]), int(cb[-1])
+        num[c], den[c] = int(abs(ca * nb - cb * na).max()), na * nb
+        if den[c]:
+            d[c] = num[c] / den[c]
+    if not shape:
+        return {"d": float(d), "num": num[()], "den": den[()]}
+    return {"d": d, "num": num, "den": den}
+
+
+def groups_of_columns(columns: Any) -> tuple[np.ndarray, int]:
+    """Group ids from per-scenario parameter columns (one float vector [n] each): scenarios with equal values in every column
+    form a group, the groups numbered in ascending lexicographic order of their values -- for a grid with ascending axis
+    values the row-major order of its points, so the ids equal ``Sweep.point``.  Returns int64 ids [n] and G."""
+    cols = [np.asarray(c, dtype=np.float64).reshape(-1) for c in columns]
+    if not cols or any(c.shape != cols[0].shape for c in cols) or any(np.isnan(c).any() for c in cols):
+        msg = "parameter columns must be at least one vector per scenario, all of one length, without NaN"
+        raise ValueError(msg)
+    if cols[0].shape[0] == 0:
+        msg = "no scenario is in a group"
+        raise ValueError(msg)
+    uniq, ids = np.unique(np.stack(cols, axis=1), axis=0, return_inverse=True)
+    return np.asarray(ids, dtype=np.int64).reshape(-1), int(uniq.shape[0])
+
+
+def _groups_of_named_columns(by: Any, overrides: dict[str, np.ndarray]) -> tuple[np.ndarray, int] | None:
+    """``by`` given as the name(s) of per-scenario parameter columns (keys of a run's ``overrides``): their groups
+    (:func:`groups_of_columns`); any other ``by``: None."""
+    names = [by] if isinstance(by, str) and by != "scenario" else list(by) if isinstance(by, (list, tuple)) and by and all(isinstance(x, str) for x in by) else None
+    if names is None:
+        return None
+    missing = [k for k in names if k not in overrides]
+    if missing:
+        msg = f"by names parameter columns the run does not have: {missing} (it has {sorted(overrides)})"
+        raise ValueError(msg)
+    return groups_of_columns([overrides[k] for k in names])
+
+
 def check_tick_edges(tick_edges: Any) -> np.ndarray:
     """``tick_edges`` as a uint32 vector, or ValueError: at least two tick indices, whole, in [0, 2^32), strictly increasing."""
     raw = np.asarray(tick_edges)
@@ -1952,6 +2219,18 @@ class ScenarioResults:
         ex = latency_exemplars([self.rqs_clock], k, e, window_of)
         return _exemplar_columns(ex, edges=e, window_of=window_of, with_scenario=False)
 
+    def get_latency_histogram(self, window_s: float | None = None, edges: Any = None, window_of: str = "finish", *, sub_bits: int = 5,
+                              min_exp: int = -20, octaves: int = 32) -> dict[str, Any]:
+        """The log-linear latency histogram of the scenario, per time window (``window_s`` seconds or explicit ``edges``, by
+        ``window_of``) or, with neither, of the whole run: :func:`latency_histogram` on the scenario's clock rows.  ``hist``
+        int64 [W', B], ``count`` / ``under`` / ``over`` / ``nan`` int64 [W'], ``bin_edges`` float64 [B + 1] seconds, ``edges``
+        (None for the whole run), ``window_of`` and the binning."""
+        e = None if window_s is None and edges is None else _resolve_edges(window_s, edges, self._plan.total_time)
+        m, e0, o, _ = check_latency_bins(sub_bits, min_exp, octaves)
+        h = latency_histogram([self.rqs_clock], e, window_of, sub_bits=m, min_exp=e0, octaves=o)
+        return {**{k: v.astype(np.int64) for k, v in h.items()}, "bin_edges": latency_bin_edges(m, e0, o), "edges": e,
+                "window_of": window_of, "sub_bits": m, "min_exp": e0, "octaves": o}
+
     # ---- bridge to the reference's own analyzer / plots ----------------------------
     def to_reference_analyzer(self) -> Any:
         """Hydrate the reference's ``ResultsAnalyzer`` via duck-typed shims (needs `asyncflow`).
@@ -2818,6 +3097,69 @@ class BatchedResults:
         cols["window_of"] = np.asarray(window_of)
         _write_columns(str(path), cols, n_groups)
         return cols
+
+    # ---- mergeable log-linear latency histograms per window and group ----------------------------------------------
+    def _latency_histogram_cells(self, e: np.ndarray | None, ids: np.ndarray, n_groups: int, window_of: str,
+                                 binning: tuple[int, int, int, int]) -> dict[str, Any]:
+        """The device call: the int64 tensors of ``n_groups`` groups for the group ids ``ids`` [n] (negative: left out)."""
+        import torch
+
+        m, e0, o, n_bins = binning
+        n_win = 1 if e is None else int(e.shape[0] - 1)
+        eng, dev = self._arrival_engine()
+        clock = self._clock_t
+        count = torch.empty((n_groups, n_win), dtype=torch.int64, device=dev)
+        hist = torch.empty((n_groups, n_win, n_bins), dtype=torch.int32, device=dev)
+        rest = torch.empty((3, n_groups, n_win), dtype=torch.int32, device=dev)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        ms, scratch = eng.summarize_latency_histogram(
+            len(self), n_groups, edges=e, window_of=window_of, sub_bits=m, min_exp=e0, octaves=o, clock_ptr=clock.data_ptr(),
+            clock_capacity=int(clock.shape[1]), counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(),
+            hist_ptr=hist.data_ptr(), under_ptr=rest[0].data_ptr(), over_ptr=rest[1].data_ptr(), nan_ptr=rest[2].data_ptr(),
+            group_ptr=grp.data_ptr())
+        wide = rest.to(torch.int64) & 0xFFFFFFFF     # (the words are uint32)
+        return {"hist": hist.to(torch.int64) & 0xFFFFFFFF, "count": count, "under": wide[0], "over": wide[1], "nan": wide[2],
+                "latency_histogram_ms": ms, "scratch_bytes": scratch}
+
+    def latency_histogram_summary(self, window_s: float | None = None, *, edges: Any = None, by: Any = None, window_of: str = "finish",
+                                  sub_bits: int = 5, min_exp: int = -20, octaves: int = 32) -> dict[str, Any]:
+        """The DISTRIBUTION of the latencies of every (group, time window) as a mergeable log-linear histogram -- a latency
+        heatmap over time, two cells to compare, quantile brackets at levels chosen afterwards.  Computed by
+        ``af_engine_summarize_latency_histogram`` in one streaming pass over the clock rows, every word equal to
+        :func:`latency_histogram` on the group's scenarios.  Binning on the bit pattern of the float64 latency
+        (:func:`latency_bin_index`): ``octaves`` octaves from ``2 ** min_exp`` seconds with ``2 ** sub_bits`` bins each; the
+        default is 1024 bins from 0.95 us to 4096 s, each 3.1 % wide.  Windows: ``window_s`` seconds or explicit ``edges`` by
+        ``window_of`` (``"finish"`` or ``"arrival"``, as in :meth:`window_summary`); neither: the whole run as one window
+        (W' = 1, ``edges`` None; ``"arrival"`` is refused).  ``by`` as in :meth:`window_summary`, or the name(s) of
+        per-scenario parameter columns (:func:`groups_of_columns`).  Returns int64 tensors on the run's device: ``hist``
+        [G, W', B] and ``count``, ``under``, ``over``, ``nan`` [G, W'] (``under + over + nan + hist.sum(-1) == count``); and
+        numpy ``bin_edges`` [B + 1] (seconds), ``edges``, ``replicas`` [G], ``sub_bits``, ``min_exp``, ``octaves``,
+        ``window_of``, ``latency_histogram_ms`` and ``scratch_bytes``.  Only integer additions: summaries over the same cells
+        add up (:func:`latency_histogram_merge`), coarsen (:func:`latency_histogram_regroup`), give quantile brackets
+        (:func:`latency_histogram_quantiles`) and distances (:func:`latency_histogram_distance`).  COMPLETED requests only."""
+        self._require_clock()
+        binning = check_latency_bins(sub_bits, min_exp, octaves)
+        whole = window_s is None and edges is None
+        if check_window_of(window_of) == "arrival" and whole:
+            msg = "window_of='arrival' needs window_s or edges: the whole run has no window"
+            raise ValueError(msg)
+        e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = _groups_of_named_columns(by, self.overrides) or self._window_groups(by)
+        out = self._latency_histogram_cells(e, ids, n_groups, window_of, binning)
+        out.update(bin_edges=latency_bin_edges(*binning[:3]), edges=e, replicas=np.bincount(ids[ids >= 0], minlength=n_groups),
+                   sub_bits=binning[0], min_exp=binning[1], octaves=binning[2], window_of=window_of)
+        return out
+
+    def save_latency_histogram_summary(self, path: str, by: Any = None, *, window_s: float | None = None, edges: Any = None,
+                                       window_of: str = "finish", sub_bits: int = 5, min_exp: int = -20, octaves: int = 32) -> dict[str, np.ndarray]:
+        """Columnar dump of the latency histograms with one row per group (grid point): ``param:<axis>`` (for a Sweep),
+        ``replicas``, ``lhist_hist`` [G, W', B] and the [G, W'] columns ``lhist_count``, ``lhist_under``, ``lhist_over``,
+        ``lhist_nan`` (:meth:`latency_histogram_summary`); ``lhist_sub_bits``, ``lhist_min_exp``, ``lhist_octaves``,
+        ``window_edges`` [W + 1] (absent for the whole run) and ``window_of`` are per-file values.  ``.npz`` or ``.parquet``;
+        :func:`load_summary` reads it back, and the latency histogram functions (merge, regroup, quantiles, distance) accept
+        what it returns."""
+        return _save_latency_histogram(self.latency_histogram_summary(window_s, edges=edges, by=by, window_of=window_of, sub_bits=sub_bits,
+                                                                      min_exp=min_exp, octaves=octaves), str(path), by)
 
     def quantile_summary(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
                          by: Any = None, window_of: str = "finish") -> dict[str, Any]:
@@ -4260,6 +4602,26 @@ def _write_columns(path: str, cols: dict[str, np.ndarray], n: int) -> None:
         np.savez_compressed(path, **cols)
 
 
+def _save_latency_histogram(summ: dict[str, Any], path: str, by: Any) -> dict[str, np.ndarray]:
+    """The columns of ``save_latency_histogram_summary``, written to ``path``."""
+    p = _latency_histogram_parts(summ)
+    n_groups = int(p["replicas"].shape[0])
+    cols: dict[str, np.ndarray] = {}
+    if hasattr(by, "point_columns"):
+        for name, v in by.point_columns().items():
+            cols[f"param:{name}"] = np.asarray(v, dtype=np.float64)
+    cols["replicas"] = p["replicas"]
+    for k in _LHIST_COUNTS:
+        cols[f"lhist_{k}"] = np.ascontiguousarray(p[k])
+    for k in ("sub_bits", "min_exp", "octaves"):
+        cols[f"lhist_{k}"] = np.asarray(p[k], dtype=np.int64)
+    if p["edges"] is not None:
+        cols["window_edges"] = p["edges"]
+    cols["window_of"] = np.asarray(p["window_of"])
+    _write_columns(path, cols, n_groups)
+    return cols
+
+
 class ShardedResults:
     """A sweep run on several devices by ONE process (``SimulationRunner(devices=[...])``): the shards'
     :class:`BatchedResults` behind the indices of the original sweep."""
@@ -4543,6 +4905,50 @@ class ShardedResults:
     def save_exemplar_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_exemplar_summary() of a sweep run on several devices: windows across devices are not implemented"
         raise NotImplementedError(msg)
+
+    def _histogram_groups(self, by: Any) -> tuple[np.ndarray, int]:
+        """The GLOBAL group ids of ``by``, in the order of the original sweep: None, a Sweep, integer ids [n], ``"scenario"`` or
+        the name(s) of per-scenario parameter columns -- resolved once, as the unsharded run resolves them."""
+        n = len(self)
+        named = _groups_of_named_columns(by, self.overrides)
+        if named is not None:
+            return named
+        if isinstance(by, str):
+            return np.arange(n, dtype=np.int64), n
+        return resolve_groups(by, n)
+
+    def latency_histogram_summary(self, window_s: float | None = None, *, edges: Any = None, by: Any = None, window_of: str = "finish",
+                                  sub_bits: int = 5, min_exp: int = -20, octaves: int = 32) -> dict[str, Any]:
+        """:meth:`BatchedResults.latency_histogram_summary` of a sweep run on several devices -- the grouped latency analyzer
+        that works there, because histograms merge by integer addition.  ``by`` is resolved once over the whole sweep; every
+        shard computes its members' contribution to the GLOBAL groups on its own device (explicit group ids through its
+        ``index``), and the counts are added on the first shard's device.  Same arguments, same result as the unsharded run."""
+        binning = check_latency_bins(sub_bits, min_exp, octaves)
+        whole = window_s is None and edges is None
+        if check_window_of(window_of) == "arrival" and whole:
+            msg = "window_of='arrival' needs window_s or edges: the whole run has no window"
+            raise ValueError(msg)
+        e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._histogram_groups(by)
+        out: dict[str, Any] = {}
+        for shard, ix in zip(self.shards, self.index):
+            shard._require_clock()  # noqa: SLF001
+            part = shard._latency_histogram_cells(e, ids[np.asarray(ix)], n_groups, window_of, binning)  # noqa: SLF001
+            if not out:
+                out = part
+                continue
+            dev = out["hist"].device
+            for k in _LHIST_COUNTS:
+                out[k] = out[k] + part[k].to(dev)
+            out["latency_histogram_ms"] += part["latency_histogram_ms"]
+            out["scratch_bytes"] = max(out["scratch_bytes"], part["scratch_bytes"])
+        out.update(bin_edges=latency_bin_edges(*binning[:3]), edges=e, replicas=np.bincount(ids[ids >= 0], minlength=n_groups),
+                   sub_bits=binning[0], min_exp=binning[1], octaves=binning[2], window_of=window_of)
+        return out
+
+    def save_latency_histogram_summary(self, path: str, by: Any = None, **kw: Any) -> dict[str, np.ndarray]:
+        """:meth:`BatchedResults.save_latency_histogram_summary` over every shard, added up and written once."""
+        return _save_latency_histogram(self.latency_histogram_summary(kw.pop("window_s", None), by=by, **kw), str(path), by)
 
     def quantile_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
         msg = "quantile_summary() of a sweep run on several devices: quantiles across devices are not implemented"

@@ -1050,6 +1050,57 @@ typedef struct af_exemplars {
 } af_exemplars_t;
 int af_engine_summarize_exemplars(af_engine_t* engine, const af_outputs_t* out, af_exemplars_t* exemplars);
 
+/* Mergeable LOG-LINEAR LATENCY HISTOGRAMS per window and group (asyncflow_amd/csrc/af_latency_histogram.hpp): the distribution of
+ * every cell instead of finished numbers about it -- a latency heatmap over time, two cells compared, quantile brackets at levels
+ * chosen afterwards.  An HDR-style sketch whose binning is defined on the bit pattern of the f64 latency, counted with integer +
+ * only: the results of two calls over the same cells add word by word (devices, member splits, saved sweeps), and windows or
+ * groups coarsen by summing cells.  Reads outputs.clock and outputs.counts; no simulation kernel runs.
+ * Per scenario s: m_s = min(counts[s][AF_CNT_COMPLETED], clock_capacity) stored rows (start_i, finish_i).
+ *     binning          sub_bits m in 0 .. 8, min_exp e >= -1022, octaves o >= 1, e + o <= 1023, n_bins = o << m in
+ *                      1 .. AF_MAX_LATENCY_HISTOGRAM_BINS: every octave [2^(e + k), 2^(e + k + 1)) holds 2^m bins of equal width,
+ *                      the relative width of a bin is 2^-m.  m = 5, e = -20, o = 32: 1 024 bins from 2^-20 s to 2^12 s, 3.1 % wide
+ *     latency          x = finish - start, one f64 subtraction; bits = its 64-bit pattern.  x NaN: counted in nan;  x < 2^e
+ *                      (zeros, -0.0, negatives, denormals, -inf): in under;  x >= 2^(e + o) (+inf): in over;  otherwise in bin
+ *                      (bits >> (52 - m)) - ((e + 1023) << m) -- integer arithmetic on the word.  Bin b covers [E[b], E[b + 1]),
+ *                      E[b] = ldexp(1 + (b & (2^m - 1)) / 2^m, e + (b >> m)), exact in f64
+ *     window           af_exemplars_t's rule, a mask on every row: with edges, window w where edges[w] < t <= edges[w + 1], t =
+ *                      finish (by_arrival == 0) or start (by_arrival != 0); t <= edges[0], t > edges[W] or t NaN: in no cell.
+ *                      Completion order is neither needed nor checked.  Without edges (n_windows == 0, edges NULL) one window with
+ *                      no condition on time; by_arrival is then refused.  W' = max(n_windows, 1)
+ *     cell c = g * W' + w   count[c] u64 = the rows of the cell; hist[c][n_bins], under[c], over[c], nan[c] u32;
+ *                      under + over + nan + sum(hist[c]) == count[c]
+ * An empty or skipped (AF_POOL_SKIP) group's cells are all zero.
+ * The outputs are zeroed, then integer add atomics only: every word is identical from run to run and does not depend on the
+ * launch or on the batch a scenario sits in.
+ * Refused, no output touched: n_scenarios or n_groups == 0, a binning outside the ranges above, edges not finite or not strictly
+ * increasing, edges NULL with n_windows > 0 (or given with n_windows == 0), by_arrival with n_windows == 0, a group id >=
+ * n_groups, outputs.clock or outputs.counts NULL, clock_capacity == 0, count or hist NULL (AF_ERR_INVALID); n_groups * W' * n_bins
+ * >= 2^32, a group whose members hold 2^32 or more stored rows together (AF_ERR_CAPACITY); a planning-only engine
+ * (AF_ERR_NO_DEVICE).
+ * outputs.clock must be 16-byte aligned: a row is read as one (start, finish) pair by a 16-byte load (any device allocation is).
+ * Scratch kept by the engine, shared with the other analyzers: 8 B per edge; no per-row and no per-cell records.
+ * Synchronous; the struct is written back. */
+#define AF_MAX_LATENCY_HISTOGRAM_BINS 4096
+typedef struct af_latency_histogram {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;          /* 0: one window over all time (edges NULL) */
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const double* edges;         /* HOST [n_windows + 1] strictly increasing, finite; NULL with n_windows == 0 */
+    uint32_t by_arrival;         /* 0: windows by finish time; otherwise by start time (needs n_windows > 0) */
+    uint32_t sub_bits;           /* m: 0 .. 8 */
+    int32_t min_exp;             /* e: the first bin starts at 2^e seconds */
+    uint32_t octaves;            /* o: n_bins = o << m */
+    uint64_t* count;             /* DEVICE [C] u64 out, C = n_groups * W' */
+    uint32_t* hist;              /* DEVICE [C][n_bins] u32 out */
+    uint32_t* under;             /* DEVICE [C] u32 out, optional */
+    uint32_t* over;              /* DEVICE [C] u32 out, optional */
+    uint32_t* nan;               /* DEVICE [C] u32 out, optional */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_latency_histogram_t;
+int af_engine_summarize_latency_histogram(af_engine_t* engine, const af_outputs_t* out, af_latency_histogram_t* histogram);
+
 /* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
  * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
  * use, with the connections on an edge?  A cell is (group g, arrival window w, bin b of ONE sampled series at the row's tick).
