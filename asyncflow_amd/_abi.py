@@ -578,6 +578,46 @@ class AfLatencyHistogram(C.Structure):
     ]
 
 
+MAX_PAIR_THRESHOLDS = 64   # AF_MAX_PAIR_THRESHOLDS
+PAIR_NONE = 0xFFFFFFFF     # AF_PAIR_NONE: af_pairs_t.row_a / row_b of an arrival without a row
+
+
+class AfPairs(C.Structure):
+    """``af_pairs_t``: request of ``af_engine_summarize_pairs`` (``elapsed_ms`` and ``scratch_bytes`` are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_pairs", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("pair_a", C.c_void_p),
+        ("pair_b", C.c_void_p),
+        ("group", C.c_void_p),
+        ("edges", C.POINTER(C.c_double)),
+        ("times", C.c_void_p),
+        ("time_row", C.c_void_p),
+        ("n_time_rows", C.c_uint32),
+        ("draw_capacity", C.c_uint32),
+        ("thresholds", C.POINTER(C.c_double)),
+        ("n_thresholds", C.c_uint32),
+        ("sub_bits", C.c_uint32),
+        ("min_exp", C.c_int32),
+        ("octaves", C.c_uint32),
+        ("pair_counts", C.c_void_p),
+        ("pair_sums", C.c_void_p),
+        ("unmatched", C.c_void_p),
+        ("cell_counts", C.c_void_p),
+        ("above", C.c_void_p),
+        ("extremes", C.c_void_p),
+        ("hist", C.c_void_p),
+        ("tails", C.c_void_p),
+        ("row_a", C.c_void_p),
+        ("row_b", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -612,6 +652,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_inflight",
     "af_engine_summarize_exemplars",
     "af_engine_summarize_latency_histogram",
+    "af_engine_summarize_pairs",
     "af_engine_summarize_state_windows",
     "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
@@ -678,6 +719,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_exemplars.restype = C.c_int
     lib.af_engine_summarize_latency_histogram.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfLatencyHistogram)]
     lib.af_engine_summarize_latency_histogram.restype = C.c_int
+    lib.af_engine_summarize_pairs.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfPairs)]
+    lib.af_engine_summarize_pairs.restype = C.c_int
     lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
     lib.af_engine_summarize_state_windows.restype = C.c_int
     lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]

@@ -71,6 +71,7 @@
 #include "af_inflight.hpp"
 #include "af_exemplars.hpp"
 #include "af_latency_histogram.hpp"
+#include "af_paired.hpp"
 
 #define LDS_AS __attribute__((address_space(3)))
 
@@ -3788,6 +3789,156 @@ int af_engine_summarize_latency_histogram(af_engine_t* e, const af_outputs_t* ou
     void* kargs[] = {&a};
     HIP_TRY(hipLaunchKernel(fn, dim3(blocks), dim3(aflh::kThreads), kargs, lds, st));
     HIP_TRY(hipStreamSynchronize(st));   // (the host edges are read by the copy until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Paired latency differences under common seeds (af_paired.hpp).  The host checks the request, reads the pair, row and group ids
+// and the counts back (is every id in range?  may a counter reach 2^32?), uploads edges and thresholds and initialises the
+// outputs; then per chunk of pairs the slots are filled with 0xFF, the match pass writes them and the reduce pass reads them.
+static_assert(afpr::kSkip == AF_POOL_SKIP && afpr::kNone == AF_PAIR_NONE && afpr::kMaxThresholds == AF_MAX_PAIR_THRESHOLDS, "the kernel's constants are the header's");
+
+int af_engine_summarize_pairs(af_engine_t* e, const af_outputs_t* out, af_pairs_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_pairs == 0 || req->n_groups == 0 || req->n_scenarios == 0 || req->n_time_rows == 0)
+        return fail(AF_ERR_INVALID, "empty pairs request (n_pairs, n_groups, n_scenarios and n_time_rows must be > 0)");
+    if (req->draw_capacity == 0) return fail(AF_ERR_INVALID, "pairs.draw_capacity must be > 0 (pass the run's value)");
+    aflh::Binning bin{};
+    if (!aflh::make_binning(req->sub_bits, req->min_exp, req->octaves, bin))
+        return fail(AF_ERR_INVALID, "pairs binning: sub_bits 0 .. 8, min_exp >= -1022, octaves >= 1, min_exp + octaves <= 1023 and octaves << sub_bits <= AF_MAX_LATENCY_HISTOGRAM_BINS (" + std::to_string(AF_MAX_LATENCY_HISTOGRAM_BINS) + ")");
+    const uint32_t P = req->n_pairs, G = req->n_groups, W = req->n_windows, B = bin.n_bins, T = req->n_thresholds, n_draw = req->draw_capacity;
+    if (W > 0 && !req->edges) return fail(AF_ERR_INVALID, "pairs.edges is required with n_windows > 0");
+    if (W == 0 && req->edges) return fail(AF_ERR_INVALID, "pairs.edges must be NULL with n_windows == 0");
+    if (W > 0)
+        if (int rc = check_window_edges(req->edges, W)) return rc;
+    if (T > AF_MAX_PAIR_THRESHOLDS) return fail(AF_ERR_INVALID, "pairs.n_thresholds must be at most AF_MAX_PAIR_THRESHOLDS (" + std::to_string(AF_MAX_PAIR_THRESHOLDS) + ")");
+    if (T > 0 && (!req->thresholds || !req->above)) return fail(AF_ERR_INVALID, "pairs.thresholds and pairs.above are required with n_thresholds > 0");
+    for (uint32_t t = 0; t < T; ++t)
+        if (!std::isfinite(req->thresholds[t])) return fail(AF_ERR_INVALID, "pairs threshold " + std::to_string(t) + " is not finite");
+    if (!req->pair_a || !req->pair_b || !req->time_row || !req->times) return fail(AF_ERR_INVALID, "pairs.pair_a, pair_b, time_row and times are required");
+    if (!req->pair_counts || !req->pair_sums || !req->unmatched || !req->cell_counts || !req->extremes || !req->hist || !req->tails)
+        return fail(AF_ERR_INVALID, "pairs.pair_counts, pair_sums, unmatched, cell_counts, extremes, hist and tails are required");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "paired differences need outputs.clock");
+    if (reinterpret_cast<uintptr_t>(out->clock) % 16u) return fail(AF_ERR_INVALID, "outputs.clock must be 16-byte aligned");
+    const uint64_t wins = W ? W : 1u;
+    if ((uint64_t)P * wins >= 0x100000000ull) return fail(AF_ERR_CAPACITY, "n_pairs * max(n_windows, 1) must be below 2^32");
+    if ((uint64_t)G * wins >= 0x100000000ull || (uint64_t)G * wins * B >= 0x100000000ull)
+        return fail(AF_ERR_CAPACITY, "n_groups * max(n_windows, 1) * n_bins must be below 2^32");
+    if (n_draw >= 0x80000000u) return fail(AF_ERR_CAPACITY, "draw_capacity must be below 2^31");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    const uint32_t n = req->n_scenarios;
+    std::vector<uint32_t> ids[3];   // pair_a, pair_b, time_row
+    const uint32_t* src[3] = {req->pair_a, req->pair_b, req->time_row};
+    const char* names[3] = {"pair_a", "pair_b", "time_row"};
+    for (int k = 0; k < 3; ++k) {
+        ids[k].resize(P);
+        HIP_TRY(hipMemcpy(ids[k].data(), src[k], (size_t)P * 4u, hipMemcpyDeviceToHost));
+        const uint32_t limit = k < 2 ? n : req->n_time_rows;
+        for (uint32_t p = 0; p < P; ++p)
+            if (ids[k][p] >= limit)
+                return fail(AF_ERR_INVALID, std::string("pairs.") + names[k] + " out of range (pair " + std::to_string(p) + ": " + std::to_string(ids[k][p]) + ", limit " + std::to_string(limit) + ")");
+    }
+    std::vector<uint32_t> grp;
+    if (int rc = read_groups(req->group, P, G, grp)) return rc;
+    {   // may a u32 counter of a cell reach 2^32?  Not while the pairs of no group can match that many requests
+        std::vector<uint32_t> counts((size_t)n * AF_CNT_SLOTS);
+        HIP_TRY(hipMemcpy(counts.data(), out->counts, counts.size() * 4u, hipMemcpyDeviceToHost));
+        std::vector<uint64_t> g_rows(G, 0u);
+        for (uint32_t p = 0; p < P; ++p) {
+            const uint32_t g = grp.empty() ? 0u : grp[p];
+            if (g == afpr::kSkip) continue;
+            const uint32_t m_a = std::min(counts[(size_t)ids[0][p] * AF_CNT_SLOTS + AF_CNT_COMPLETED], out->clock_capacity);
+            const uint32_t m_b = std::min(counts[(size_t)ids[1][p] * AF_CNT_SLOTS + AF_CNT_COMPLETED], out->clock_capacity);
+            g_rows[g] += std::min(std::min(m_a, m_b), n_draw);
+            if (g_rows[g] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "group " + std::to_string(g) + " could match 2^32 or more requests");
+        }
+    }
+    // the pairs of one chunk: what the slots of the sides without a row_a / row_b output need must fit the memory
+    const size_t slot_sides = (req->row_a ? 0u : 1u) + (req->row_b ? 0u : 1u);
+    const size_t per_pair = slot_sides * (size_t)n_draw * 4u;
+    uint32_t chunk = P;
+    if (per_pair) {
+        size_t mem_free = 0, mem_total = 0;
+        HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
+        size_t budget = e->draw_memory_bytes ? e->draw_memory_bytes : (size_t)160 << 30;
+        const size_t avail = mem_free + e->pool_cap;
+        if (budget > avail / 10u * 6u) budget = avail / 10u * 6u;
+        if (budget / per_pair < chunk) chunk = (uint32_t)(budget / per_pair);
+        if (chunk == 0) return fail(AF_ERR_CAPACITY, "draw_capacity too large for the device memory budget");
+    }
+    if (const char* env = std::getenv("AF_PAIRS_CHUNK")) {   // test hook: small chunks
+        const long k = std::atol(env);
+        if (k > 0 && (uint64_t)k < chunk) chunk = (uint32_t)k;
+    }
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 8u);
+    const size_t o_thr = lay.part(std::max<size_t>(T, 1u) * 8u);
+    const size_t o_slots = lay.part((size_t)chunk * per_pair);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    hipStream_t st = e->stream;
+    if (W) HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, req->edges, ((size_t)W + 1u) * 8u, hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(e->d_pool + o_thr, req->thresholds, (size_t)T * 8u, hipMemcpyHostToDevice, st));
+    const size_t cells = (size_t)G * wins;
+    HIP_TRY(hipMemsetAsync(req->pair_counts, 0, (size_t)P * wins * afpr::kPairCounts * 4u, st));
+    HIP_TRY(hipMemsetAsync(req->pair_sums, 0, (size_t)P * wins * 16u, st));
+    HIP_TRY(hipMemsetAsync(req->cell_counts, 0, cells * afpr::kCellCounts * 8u, st));
+    if (T) HIP_TRY(hipMemsetAsync(req->above, 0, cells * T * 8u, st));
+    HIP_TRY(hipMemsetAsync(req->hist, 0, cells * 2u * B * 4u, st));
+    HIP_TRY(hipMemsetAsync(req->tails, 0, cells * afpr::kTails * 4u, st));
+    hipLaunchKernelGGL(afpr::af_pairs_init_extremes, dim3((uint32_t)((cells + 255u) / 256u)), dim3(256), 0, st, req->extremes, (uint64_t)cells);
+    HIP_TRY(hipGetLastError());
+    afpr::PairArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = out->clock_capacity;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.times = req->times;
+    a.n_draw = n_draw;
+    a.n_win = W;
+    a.wins = (uint32_t)wins;
+    a.edges = reinterpret_cast<const double*>(e->d_pool + o_edges);
+    a.thresholds = reinterpret_cast<const double*>(e->d_pool + o_thr);
+    a.n_thr = T;
+    a.chunks = (uint32_t)(((uint64_t)out->clock_capacity + afpr::kMatchRows - 1u) / afpr::kMatchRows);
+    a.bin = bin;
+    a.cell_counts = reinterpret_cast<unsigned long long*>(req->cell_counts);
+    a.above = reinterpret_cast<unsigned long long*>(req->above);
+    a.extremes = req->extremes;
+    a.hist = req->hist;
+    a.tails = req->tails;
+    const bool in_lds = W <= afpr::kLdsPairWindows;
+    const size_t lds = (in_lds && W ? ((size_t)W + 1u) * 8u : 0u) + (size_t)afpr::kWaves * 2u * B * 4u;
+    const void* fn = in_lds ? reinterpret_cast<const void*>(afpr::af_pairs_reduce<true>) : reinterpret_cast<const void*>(afpr::af_pairs_reduce<false>);
+    // (set before every launch: the attribute is per device and engines of several devices run in threads of one process)
+    if (lds > 48u * 1024u) HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    for (uint32_t lo = 0; lo < P; lo += chunk) {
+        const uint32_t nc = std::min(chunk, P - lo);
+        uint32_t* scratch = reinterpret_cast<uint32_t*>(e->d_pool + o_slots);
+        a.slot_a = req->row_a ? req->row_a + (size_t)lo * n_draw : scratch;
+        a.slot_b = req->row_b ? req->row_b + (size_t)lo * n_draw : scratch + (req->row_a ? 0u : (size_t)nc * n_draw);
+        HIP_TRY(hipMemsetAsync(a.slot_a, 0xFF, (size_t)nc * n_draw * 4u, st));
+        HIP_TRY(hipMemsetAsync(a.slot_b, 0xFF, (size_t)nc * n_draw * 4u, st));
+        a.pair_a = req->pair_a + lo;
+        a.pair_b = req->pair_b + lo;
+        a.group = req->group ? req->group + lo : nullptr;
+        a.time_row = req->time_row + lo;
+        a.n_pairs = nc;
+        a.pair_counts = req->pair_counts + (size_t)lo * wins * afpr::kPairCounts;
+        a.pair_sums = req->pair_sums + (size_t)lo * wins * 2u;
+        a.unmatched = req->unmatched + (size_t)lo * 2u;
+        const uint64_t items = (uint64_t)nc * 2u * a.chunks;
+        const uint32_t match_blocks = (uint32_t)std::min<uint64_t>((items + afpr::kWaves - 1u) / afpr::kWaves, afpr::kMaxBlocks);
+        hipLaunchKernelGGL(afpr::af_pairs_match, dim3(match_blocks), dim3(afpr::kThreads), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        const uint32_t blocks = std::min<uint32_t>((nc + afpr::kWaves - 1u) / afpr::kWaves, afpr::kMaxBlocks);
+        void* kargs[] = {&a};
+        HIP_TRY(hipLaunchKernel(fn, dim3(blocks), dim3(afpr::kThreads), kargs, lds, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));   // (the host edges and thresholds are read by the copies until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;

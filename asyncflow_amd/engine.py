@@ -459,6 +459,40 @@ class Engine:
                "af_engine_summarize_latency_histogram")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_pairs(self, n: int, n_pairs: int, n_groups: int, *, pair_a_ptr: int, pair_b_ptr: int, times_ptr: int, time_row_ptr: int,
+                        n_time_rows: int, draw_capacity: int, clock_ptr: int, clock_capacity: int, counts_ptr: int, pair_counts_ptr: int,
+                        pair_sums_ptr: int, unmatched_ptr: int, cell_counts_ptr: int, extremes_ptr: int, hist_ptr: int, tails_ptr: int,
+                        above_ptr: int = 0, row_a_ptr: int = 0, row_b_ptr: int = 0, group_ptr: int = 0, edges: Any = None,
+                        thresholds: Any = None, sub_bits: int = 5, min_exp: int = -20, octaves: int = 32) -> tuple[float, int]:
+        """Paired latency differences under common seeds on the device (``af_engine_summarize_pairs``; the host definition is
+        :func:`asyncflow_amd.results.latency_pairs` / :func:`~asyncflow_amd.results.latency_pair_cells`).  Pair p compares
+        scenarios ``pair_a[p]`` and ``pair_b[p]`` of the ``n`` scenarios behind ``clock_ptr`` / ``counts_ptr`` through the arrival
+        row ``times[time_row[p]]`` (DEVICE float64 [n_time_rows, draw_capacity], as :meth:`summarize_arrivals` writes them).  All
+        ids are DEVICE uint32 [n_pairs]; ``group_ptr`` as in :meth:`summarize_pooled` (0: all in group 0).  With W' = len(edges) - 1
+        windows by arrival time (``edges=None``: one window), T = len(thresholds), B = ``octaves << sub_bits`` and C = n_groups *
+        W': ``pair_counts`` uint32 [n_pairs, W', 5] (both, only_a, only_b, neither, nan), ``pair_sums`` float64 [n_pairs, W', 2]
+        (sum_d, sum_a), ``unmatched`` uint32 [n_pairs, 2], ``cell_counts`` uint64 [C, 8] (the five counts, slower, faster, equal),
+        ``above`` uint64 [C, T], ``extremes`` float64 [C, 2] (min_d, max_d), ``hist`` uint32 [C, 2, B] (d > 0, d < 0), ``tails``
+        uint32 [C, 4] (under_pos, under_neg, over_pos, over_neg) and, optional, ``row_a`` / ``row_b`` uint32 [n_pairs,
+        draw_capacity].  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_edges, check_latency_bins, check_pair_thresholds
+
+        m, e0, o, _ = check_latency_bins(sub_bits, min_exp, octaves)
+        e = None if edges is None else check_edges(edges)
+        th = check_pair_thresholds(thresholds)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), 0, None, C.c_void_p(counts_ptr or None))
+        req = _abi.AfPairs(int(n), int(n_pairs), int(n_groups), 0 if e is None else int(e.shape[0] - 1), C.c_void_p(pair_a_ptr or None),
+                           C.c_void_p(pair_b_ptr or None), C.c_void_p(group_ptr or None),
+                           None if e is None else e.ctypes.data_as(C.POINTER(C.c_double)), C.c_void_p(times_ptr or None),
+                           C.c_void_p(time_row_ptr or None), int(n_time_rows), int(draw_capacity),
+                           th.ctypes.data_as(C.POINTER(C.c_double)) if th.shape[0] else None, int(th.shape[0]), m, e0, o,
+                           C.c_void_p(pair_counts_ptr or None), C.c_void_p(pair_sums_ptr or None), C.c_void_p(unmatched_ptr or None),
+                           C.c_void_p(cell_counts_ptr or None), C.c_void_p(above_ptr or None), C.c_void_p(extremes_ptr or None),
+                           C.c_void_p(hist_ptr or None), C.c_void_p(tails_ptr or None), C.c_void_p(row_a_ptr or None),
+                           C.c_void_p(row_b_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_pairs(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_pairs")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def _state_request(self, column: int, bins: int, lo: float, width: float, sample_period: float, edges: Any) -> tuple[Any, Any]:
         """``af_state_bins_t`` and the checked edges (or None) of the two latency-by-state calls."""
         from .results import _check_series_columns, check_state_bins

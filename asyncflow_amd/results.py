@@ -703,6 +703,251 @@ def latency_histogram_distance(summary: Any, a: Any, b: Any) -> dict[str, Any]:
     return {"d": d, "num": num, "den": den}
 
 
+PAIR_NONE = 0xFFFFFFFF          # AF_PAIR_NONE: an arrival without a row
+MAX_PAIR_THRESHOLDS = 64        # AF_MAX_PAIR_THRESHOLDS
+_PAIR_COUNTS = ("both", "only_a", "only_b", "neither", "nan")
+_PAIR_CELL_SUMS = (*_PAIR_COUNTS, "slower", "faster", "equal", "above", "hist_pos", "hist_neg", "under_pos", "under_neg", "over_pos", "over_neg")
+
+
+def check_pair_thresholds(thresholds: Any) -> np.ndarray:
+    """The thresholds of the paired differences as float64 [T]: at most 64, finite, of either sign (seconds of ``d``)."""
+    th = np.ascontiguousarray([] if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+    if th.shape[0] > MAX_PAIR_THRESHOLDS or not np.isfinite(th).all():
+        msg = f"at most {MAX_PAIR_THRESHOLDS} finite thresholds, not {th.tolist()}"
+        raise ValueError(msg)
+    return th
+
+
+def _pair_rows(clock: Any, arrivals: np.ndarray) -> tuple[np.ndarray, int, np.ndarray]:
+    """THE MATCH of one side: ``row`` uint32 [m] (``PAIR_NONE``: no row), the unmatched rows and the clock rows [m_x, 2]."""
+    ck = np.ascontiguousarray(clock, dtype=np.float64).reshape(-1, 2)
+    m = int(arrivals.shape[0])
+    start = np.ascontiguousarray(ck[:, 0])
+    j = np.searchsorted(arrivals, start, side="left")                 # a NaN start: m
+    row = np.full(m, PAIR_NONE, dtype=np.uint32)
+    a_bits, s_bits = arrivals.view(np.uint64), start.view(np.uint64)
+    for i in range(ck.shape[0]):                                      # ascending i: the smallest row index keeps the arrival
+        if j[i] < m and a_bits[j[i]] == s_bits[i] and row[j[i]] == PAIR_NONE:
+            row[j[i]] = i
+    return row, int(ck.shape[0] - np.count_nonzero(row != PAIR_NONE)), ck
+
+
+def paired_fixed_sum(values: np.ndarray, mask: np.ndarray, j0: int, j1: int) -> float:
+    """THE FIXED-ORDER SUM of ``values[j]`` over ``j0 <= j < j1`` with ``mask[j]``: whole rows of 64 aligned at j = 0, a masked
+    entry adds nothing (+0.0), the rows added one after the other from +0.0, then the 64 sums halved five times."""
+    if j1 <= j0:
+        return 0.0
+    lo, hi = (j0 // 64) * 64, -(-j1 // 64) * 64
+    v = np.zeros(hi - lo, dtype=np.float64)
+    v[j0 - lo: j1 - lo] = np.where(mask[j0:j1], values[j0:j1], 0.0)
+    part = np.zeros(64, dtype=np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for r in v.reshape(-1, 64):
+            part = part + r
+        h = 32
+        while h:
+            part = part[:h] + part[h: 2 * h]
+            h //= 2
+    return float(part[0])
+
+
+def latency_pairs(clock_a: Any, clock_b: Any, times: Any, edges: Any = None, *, thresholds: Any = None, sub_bits: int = 5,
+                  min_exp: int = -20, octaves: int = 32) -> dict[str, Any]:
+    """The latency differences of ONE pair of scenarios that were sent the same requests: the definition
+    ``af_engine_summarize_pairs`` equals word for word.  ``clock_a`` / ``clock_b``: the stored clock rows [m_x, 2] (start,
+    finish) of side a and b; ``times``: their common arrival row, ascending (``+inf`` entries behind the last arrival are
+    dropped: A = the m finite ones).
+
+    * match: row i of side x maps to ``j = np.searchsorted(A, start_i, "left")`` when ``j < m`` and ``A[j]`` has the bit pattern
+      of ``start_i`` (the uint64 words are compared: a NaN never matches); ``row_x[j]`` is the smallest such i, ``PAIR_NONE``
+      without one; ``unmatched_x`` counts the rows that map nowhere or lose their j to a smaller row index.
+    * arrival j: ``state`` 3 both rows set, 1 only a, 2 only b, 0 neither (dropped, or still in flight at the end of the run,
+      on one or both sides).  For state 3: ``lat_x = finish - start`` and ``d = lat_b - lat_a``; a NaN ``d`` counts in ``nan``
+      and enters nothing else.
+    * window: by ``A[j]``, ``edges[w] < A[j] <= edges[w + 1]``: the ranges of j between ``np.searchsorted(A, edges, "right")``
+      (``bounds``).  ``edges=None``: one window over every arrival.  W' = max(W, 1).
+
+    Returns per arrival ``row_a``, ``row_b`` uint32 [m], ``state`` uint8 [m], ``d``, ``lat_a`` float64 [m] (NaN unless state 3);
+    ``unmatched_a``, ``unmatched_b``; per window uint32 [W'] ``both``, ``only_a``, ``only_b``, ``neither``, ``nan`` and float64
+    ``sum_d``, ``sum_a`` (:func:`paired_fixed_sum` over the state-3 arrivals with ``d`` not NaN); and what the pair brings to
+    its group's cells (:func:`latency_pair_cells`): ``slower`` (d > 0), ``faster`` (d < 0), ``equal`` (d == 0) uint64 [W'],
+    ``above`` uint64 [W', T] (``d > thresholds[t]``), ``min_d`` / ``max_d`` float64 [W'] in float order with -0.0 below +0.0
+    (+inf / -inf without a value), ``hist_pos`` / ``hist_neg`` uint32 [W', n_bins] (:func:`latency_bin_index` of d, of -d),
+    ``under_pos``, ``under_neg``, ``over_pos``, ``over_neg`` uint32 [W']."""
+    sb, e0, o, n_bins = check_latency_bins(sub_bits, min_exp, octaves)
+    th = check_pair_thresholds(thresholds)
+    e = None if edges is None else check_edges(edges)
+    t = np.ascontiguousarray(times, dtype=np.float64).reshape(-1)
+    A = np.ascontiguousarray(t[: int(np.searchsorted(t, np.finfo(np.float64).max, side="right"))])
+    m = int(A.shape[0])
+    row_a, un_a, ca = _pair_rows(clock_a, A)
+    row_b, un_b, cb = _pair_rows(clock_b, A)
+    has_a, has_b = row_a != PAIR_NONE, row_b != PAIR_NONE
+    state = (has_a.astype(np.uint8) | (has_b.astype(np.uint8) << 1)).astype(np.uint8)
+    both = state == 3
+    lat_a, lat_b = np.full(m, np.nan), np.full(m, np.nan)
+    with np.errstate(invalid="ignore", over="ignore"):
+        lat_a[both] = ca[row_a[both], 1] - ca[row_a[both], 0]
+        lat_b[both] = cb[row_b[both], 1] - cb[row_b[both], 0]
+        d = lat_b - lat_a
+    ok = both & ~np.isnan(d)
+    bounds = np.array([0, m], dtype=np.int64) if e is None else np.searchsorted(A, e, side="right").astype(np.int64)
+    n_win = int(bounds.shape[0] - 1)
+    out: dict[str, Any] = {"row_a": row_a, "row_b": row_b, "state": state, "d": d, "lat_a": lat_a, "unmatched_a": un_a, "unmatched_b": un_b,
+                           "bounds": bounds, "arrivals": A, "edges": e, "thresholds": th, "sub_bits": sb, "min_exp": e0, "octaves": o}
+    for k in _PAIR_COUNTS:
+        out[k] = np.zeros(n_win, dtype=np.uint32)
+    for k in ("slower", "faster", "equal"):
+        out[k] = np.zeros(n_win, dtype=np.uint64)
+    for k in ("under_pos", "under_neg", "over_pos", "over_neg"):
+        out[k] = np.zeros(n_win, dtype=np.uint32)
+    out["sum_d"], out["sum_a"] = np.zeros(n_win), np.zeros(n_win)
+    out["above"] = np.zeros((n_win, th.shape[0]), dtype=np.uint64)
+    out["min_d"], out["max_d"] = np.full(n_win, np.inf), np.full(n_win, -np.inf)
+    out["hist_pos"], out["hist_neg"] = np.zeros((n_win, n_bins), dtype=np.uint32), np.zeros((n_win, n_bins), dtype=np.uint32)
+    for w in range(n_win):
+        j0, j1 = int(bounds[w]), int(bounds[w + 1])
+        s = state[j0:j1]
+        out["both"][w], out["only_a"][w], out["only_b"][w], out["neither"][w] = (np.count_nonzero(s == c) for c in (3, 1, 2, 0))
+        out["nan"][w] = np.count_nonzero(both[j0:j1] & ~ok[j0:j1])
+        out["sum_d"][w] = paired_fixed_sum(d, ok, j0, j1)
+        out["sum_a"][w] = paired_fixed_sum(lat_a, ok, j0, j1)
+        x = d[j0:j1][ok[j0:j1]]
+        if x.shape[0] == 0:
+            continue
+        pos, neg = x[x > 0.0], x[x < 0.0]
+        out["slower"][w], out["faster"][w], out["equal"][w] = pos.shape[0], neg.shape[0], np.count_nonzero(x == 0.0)
+        out["above"][w] = [np.count_nonzero(x > v) for v in th]
+        keys = _double_keys(x)
+        out["min_d"][w], out["max_d"][w] = x[np.argmin(keys)], x[np.argmax(keys)]
+        for side, v in (("pos", pos), ("neg", -neg)):
+            b = latency_bin_index(v, sb, e0, o)
+            out[f"hist_{side}"][w] = np.bincount(b[b >= 0], minlength=n_bins)
+            out[f"under_{side}"][w], out[f"over_{side}"][w] = np.count_nonzero(b == -1), np.count_nonzero(b == -2)
+    return out
+
+
+def latency_pair_cells(pairs: Any, groups: Any = None, n_groups: int = 1) -> dict[str, np.ndarray]:
+    """The cells (group g of pairs, window w) of the paired differences: what every pair of ``pairs`` (each a result of
+    :func:`latency_pairs` over the same windows, thresholds and binning) brings, added into the cell of its group
+    (``groups``: one id per pair, negative: in no cell; None: all in group 0).  uint64 sums [G, W'] of ``both``, ``only_a``,
+    ``only_b``, ``neither``, ``nan``, ``slower``, ``faster``, ``equal``, ``above`` [G, W', T]; uint32 sums of ``hist_pos``,
+    ``hist_neg`` [G, W', n_bins], ``under_pos``, ``under_neg``, ``over_pos``, ``over_neg``; ``min_d`` / ``max_d`` float64 in
+    float order with -0.0 below +0.0, +inf / -inf for an empty cell; ``replicas`` [G], the pairs of each group.  Integer
+    sums, min and max only: the order of the pairs does not matter, and ``equal + under_* + over_* + hist_*.sum(-1) + nan ==
+    both``."""
+    pairs = list(pairs)
+    if not pairs:
+        msg = "no pair"
+        raise ValueError(msg)
+    ids = np.zeros(len(pairs), dtype=np.int64) if groups is None else np.asarray(groups, dtype=np.int64).reshape(-1)
+    if ids.shape[0] != len(pairs) or (ids >= n_groups).any():
+        msg = f"groups must give one id below {n_groups} per pair"
+        raise ValueError(msg)
+    first = pairs[0]
+    out: dict[str, np.ndarray] = {}
+    for k in _PAIR_CELL_SUMS:
+        wide = np.uint32 if k.startswith(("hist", "under", "over")) else np.uint64
+        out[k] = np.zeros((n_groups, *first[k].shape), dtype=wide)
+    n_win = int(first["both"].shape[0])
+    out["min_d"], out["max_d"] = np.full((n_groups, n_win), np.inf), np.full((n_groups, n_win), -np.inf)
+    for p, g in zip(pairs, ids):
+        if g < 0:
+            continue
+        for k in _PAIR_CELL_SUMS:
+            out[k][g] += p[k].astype(out[k].dtype)
+        for w in range(n_win):
+            if _double_keys(p["min_d"][w: w + 1])[0] < _double_keys(out["min_d"][g, w: w + 1])[0]:
+                out["min_d"][g, w] = p["min_d"][w]
+            if _double_keys(p["max_d"][w: w + 1])[0] > _double_keys(out["max_d"][g, w: w + 1])[0]:
+                out["max_d"][g, w] = p["max_d"][w]
+    out["replicas"] = np.bincount(ids[ids >= 0], minlength=n_groups)
+    for k in ("edges", "thresholds", "sub_bits", "min_exp", "octaves"):
+        out[k] = first[k]
+    return out
+
+
+def _paired_parts(summary: Any) -> dict[str, Any]:
+    """The cell arrays of a paired summary -- what ``paired_summary`` / :func:`latency_pair_cells` return or what
+    :func:`load_summary` reads from ``save_paired_summary``'s file -- as numpy, the counts int64."""
+    saved = "paired_both" in summary
+    pre = "paired_" if saved else ""
+    out: dict[str, Any] = {}
+    for k in _PAIR_CELL_SUMS:     # (paired_summary names the cells' five counts cell_both ...: both ... are its per-pair ones)
+        out[k] = np.asarray(summary[f"cell_{k}" if f"cell_{k}" in summary else pre + k]).astype(np.int64)
+    for k in ("min_d", "max_d"):
+        out[k] = np.asarray(summary[pre + k], dtype=np.float64)
+    out["replicas"] = np.asarray(summary["replicas"], dtype=np.int64)
+    for k in ("sub_bits", "min_exp", "octaves"):
+        out[k] = int(np.asarray(summary[pre + k]).reshape(-1)[0])
+    edges = summary.get("window_edges") if saved else summary.get("edges")
+    out["edges"] = None if edges is None else np.asarray(edges, dtype=np.float64)
+    th = summary.get("paired_thresholds") if saved else summary.get("thresholds")
+    out["thresholds"] = np.zeros(0) if th is None else np.asarray(th, dtype=np.float64).reshape(-1)
+    _, _, _, n_bins = check_latency_bins(out["sub_bits"], out["min_exp"], out["octaves"])
+    if out["hist_pos"].ndim != 3 or out["hist_pos"].shape[2] != n_bins or out["hist_neg"].shape != out["hist_pos"].shape:
+        msg = f"not a paired summary: hist_pos of shape {out['hist_pos'].shape} for {n_bins} bins"
+        raise ValueError(msg)
+    return out
+
+
+def paired_merge(a: Any, b: Any, *more: Any) -> dict[str, Any]:
+    """The cells of two (or more) paired summaries over the same groups, windows, thresholds and binning as one: the counts
+    and histograms add word by word, ``replicas`` too, ``min_d`` / ``max_d`` take the min / max in float order (-0.0 below
+    +0.0) -- two halves of the pairs, yesterday's saved sweep and today's.  Returns a summary with numpy int64 counts."""
+    out = _paired_parts(a)
+    for other in (b, *more):
+        p = _paired_parts(other)
+        for k in ("sub_bits", "min_exp", "octaves"):
+            if out[k] != p[k]:
+                msg = f"the two paired summaries differ in {k}: {out[k]!r} and {p[k]!r}"
+                raise ValueError(msg)
+        if (out["edges"] is None) != (p["edges"] is None) or (out["edges"] is not None and not np.array_equal(out["edges"], p["edges"])):
+            msg = "the two paired summaries differ in their window edges"
+            raise ValueError(msg)
+        if not np.array_equal(out["thresholds"], p["thresholds"]) or out["both"].shape != p["both"].shape:
+            msg = "the two paired summaries differ in their thresholds or cells"
+            raise ValueError(msg)
+        for k in _PAIR_CELL_SUMS:
+            out[k] = out[k] + p[k]
+        out["replicas"] = out["replicas"] + p["replicas"]
+        out["min_d"] = np.where(_double_keys(p["min_d"]) < _double_keys(out["min_d"]), p["min_d"], out["min_d"])
+        out["max_d"] = np.where(_double_keys(p["max_d"]) > _double_keys(out["max_d"]), p["max_d"], out["max_d"])
+    return out
+
+
+def paired_delta_quantiles(summary: Any, levels: Any) -> dict[str, np.ndarray]:
+    """BRACKETS of the quantiles of ``d`` per cell, read off the two-sided histogram of a paired summary: numpy float64 ``lo``
+    and ``hi`` [G, W', L] with ``lo <= np.quantile(d of the cell, q, method="lower") < hi`` -- the signed counterpart of
+    :func:`latency_histogram_quantiles`.  The sample of a cell is its ``both - nan`` values in the order ``over_neg``, the
+    bins of ``hist_neg`` from the last to the first, ``under_neg``, ``equal``, ``under_pos``, the bins of ``hist_pos``,
+    ``over_pos``; the order statistic ``floor((N - 1) q)`` lies in one of these entries.  A bin b of the positive side covers
+    ``[E[b], E[b + 1])``; on the negative side it covers ``(-E[b + 1], -E[b]]``, so ``hi`` there is the float above ``-E[b]``.
+    ``equal``: ``[-0.0, 5e-324)``.  ``over_neg`` has ``lo = -inf``, ``over_pos`` ``hi = +inf`` (a ``d`` of +inf is not below
+    it).  An empty cell: NaN."""
+    p = _paired_parts(summary)
+    q = np.array(levels, dtype=np.float64).reshape(-1)
+    if not ((q >= 0.0) & (q <= 1.0)).all():
+        msg = "quantile levels must lie in [0, 1]"
+        raise ValueError(msg)
+    E = latency_bin_edges(p["sub_bits"], p["min_exp"], p["octaves"])
+    up = np.nextafter(-E, np.inf)                      # the float above -E[b]
+    lower = np.concatenate([[-np.inf], -E[:0:-1], [-E[0]], [-0.0], [0.0], E[:-1], [E[-1]]])
+    upper = np.concatenate([[up[-1]], up[-2::-1], [0.0], [5e-324], [E[0]], E[1:], [np.inf]])
+    col = lambda k: p[k][..., None]  # noqa: E731
+    cum = np.cumsum(np.concatenate([col("over_neg"), p["hist_neg"][..., ::-1], col("under_neg"), col("equal"), col("under_pos"),
+                                    p["hist_pos"], col("over_pos")], axis=2), axis=2)
+    n = cum[..., -1]
+    lo = np.full((*n.shape, q.shape[0]), np.nan)
+    hi = np.full((*n.shape, q.shape[0]), np.nan)
+    for c in np.ndindex(*n.shape):
+        if n[c] == 0:
+            continue
+        at = np.searchsorted(cum[c], np.floor(float(n[c] - 1) * q).astype(np.int64), side="right")
+        lo[c], hi[c] = lower[at], upper[at]
+    return {"lo": lo, "hi": hi, "levels": q}
+
+
 def groups_of_columns(columns: Any) -> tuple[np.ndarray, int]:
     """Group ids from per-scenario parameter columns (one float vector [n] each): scenarios with equal values in every column
     form a group, the groups numbered in ascending lexicographic order of their values -- for a grid with ascending axis
@@ -3161,6 +3406,171 @@ class BatchedResults:
         return _save_latency_histogram(self.latency_histogram_summary(window_s, edges=edges, by=by, window_of=window_of, sub_bits=sub_bits,
                                                                       min_exp=min_exp, octaves=octaves), str(path), by)
 
+    # ---- paired latency differences between scenarios that share their seeds ---------------------------------------
+    def _check_pairs(self, a: Any, b: Any) -> tuple[np.ndarray, np.ndarray]:
+        """The scenario indices of both sides as int64 [P], or ValueError: out of range, or a pair that was not sent the same
+        requests -- its seeds or a generator column differ."""
+        ia, ib = np.asarray(a, dtype=np.int64).reshape(-1), np.asarray(b, dtype=np.int64).reshape(-1)
+        n = len(self)
+        if ia.shape != ib.shape or ia.shape[0] == 0 or ((ia < 0) | (ia >= n) | (ib < 0) | (ib >= n)).any():
+            msg = f"a and b must be two index vectors of one length > 0 into the {n} scenarios"
+            raise ValueError(msg)
+        seeds = np.asarray(self.seeds, dtype=np.uint64)
+        checks = [("seeds", seeds)] + [(key, np.asarray(self.overrides[key], dtype=np.float64)) for key in self.GENERATOR_COLUMNS if key in self.overrides]
+        for name, col in checks:
+            bad = np.nonzero(col[ia] != col[ib])[0]
+            if bad.shape[0]:
+                p = int(bad[0])
+                msg = (f"pair {p} (scenarios {int(ia[p])} and {int(ib[p])}) was not sent the same requests: {name} differ "
+                       f"({col[ia[p]]!r} and {col[ib[p]]!r}); paired differences need common seeds (expand_grid(common_seeds=True))")
+                raise ValueError(msg)
+        return ia, ib
+
+    def paired_summary(self, a: Any, b: Any, window_s: float | None = None, *, edges: Any = None, by: Any = None, thresholds: Any = None,
+                       sub_bits: int = 5, min_exp: int = -20, octaves: int = 32, with_rows: bool = False) -> dict[str, Any]:
+        """The latency difference of the SAME request under two configurations: pair p compares scenarios ``a[p]`` and ``b[p]``,
+        which must share their seed and every generator column (otherwise ValueError naming the first offender) and so were sent
+        the same requests at the same instants.  The arrival rows of the distinct ``a`` scenarios are regenerated on the device
+        (``af_engine_summarize_arrivals`` with a ``times`` buffer: no simulation), the clock rows of both sides are joined
+        through them and reduced by ``af_engine_summarize_pairs``; every word equals :func:`latency_pairs` /
+        :func:`latency_pair_cells` on ``batch[i].rqs_clock`` and ``batch.arrival_times(i)``.  Windows by ARRIVAL time:
+        ``window_s`` seconds or explicit ``edges``; neither: one window over the run.  ``by``: one group id per pair (negative:
+        in no cell), ``"pair"`` for singletons, None for one group -- ``Sweep.pairs(...)["by"]`` groups by the remaining axes.
+        Returns numpy arrays.  Per (pair, window) [P, W']: ``both``, ``only_a``, ``only_b``, ``neither``, ``nan`` uint32,
+        ``sum_d``, ``sum_a`` float64 and ``mean_d`` = sum_d / (both - nan), ``mean_a``, ``relative`` = mean_d / mean_a; per pair
+        ``unmatched_a``, ``unmatched_b``; per cell [G, W']: the uint64 sums of the five counts, ``slower``, ``faster``, ``equal``,
+        ``above`` [G, W', T], ``min_d``, ``max_d``, ``hist_pos``, ``hist_neg`` uint32 [G, W', B], ``under_pos``, ``under_neg``,
+        ``over_pos``, ``over_neg``, named ``cell_both`` ... for the five counts; with ``with_rows`` the join ``row_a`` /
+        ``row_b`` uint32 [P, draw_capacity].  ``only_a`` / ``only_b`` / ``neither`` cannot tell a dropped request from one still in
+        flight at the end of the run: the last windows always lose requests (the caveat of :meth:`arrival_summary`)."""
+        import torch
+
+        self._require_clock()
+        ia, ib = self._check_pairs(a, b)
+        binning = check_latency_bins(sub_bits, min_exp, octaves)
+        th = check_pair_thresholds(thresholds)
+        e = None if window_s is None and edges is None else _resolve_edges(window_s, edges, self.plan.total_time)
+        n_pairs = int(ia.shape[0])
+        if isinstance(by, str):
+            if by != "pair":
+                msg = f"by must be one group id per pair, 'pair' or None, not {by!r}"
+                raise ValueError(msg)
+            ids, n_groups = np.arange(n_pairs, dtype=np.int64), n_pairs
+        else:
+            ids, n_groups = resolve_groups(by, n_pairs)
+        rows, time_row = np.unique(ia, return_inverse=True)
+        seeds, cols, cap = self._arrival_sweep(rows)
+        eng, dev = self._arrival_engine()
+        n_rows, n_win, n_bins, n_thr = int(rows.shape[0]), 1 if e is None else int(e.shape[0] - 1), binning[3], int(th.shape[0])
+        times = torch.empty((n_rows, cap), dtype=torch.float64, device=dev)
+        arr = torch.empty((n_rows, 1), dtype=torch.int64, device=dev)
+        arrival_ms, _ = eng.summarize_arrivals(seeds, cols, n_rows, np.asarray([0.0, max(float(self.plan.total_time), 1.0)]),
+                                               draw_capacity=cap, arrivals_ptr=arr.data_ptr(), times_ptr=times.data_ptr())
+
+        def u32(v: np.ndarray) -> Any:
+            return torch.from_numpy(np.ascontiguousarray(v).astype(np.uint32).view(np.int32)).to(dev)
+
+        pa, pb, tr, grp = u32(ia), u32(ib), u32(time_row.reshape(-1)), u32(np.where(ids < 0, _abi.POOL_SKIP, ids))
+        cells = n_groups * n_win
+        pair_counts = torch.empty((n_pairs, n_win, 5), dtype=torch.int32, device=dev)
+        pair_sums = torch.empty((n_pairs, n_win, 2), dtype=torch.float64, device=dev)
+        unmatched = torch.empty((n_pairs, 2), dtype=torch.int32, device=dev)
+        cell_counts = torch.empty((cells, 8), dtype=torch.int64, device=dev)
+        above = torch.empty((cells, max(n_thr, 1)), dtype=torch.int64, device=dev)
+        extremes = torch.empty((cells, 2), dtype=torch.float64, device=dev)
+        hist = torch.empty((cells, 2, n_bins), dtype=torch.int32, device=dev)
+        tails = torch.empty((cells, 4), dtype=torch.int32, device=dev)
+        row_a = torch.empty((n_pairs, cap), dtype=torch.int32, device=dev) if with_rows else None
+        row_b = torch.empty((n_pairs, cap), dtype=torch.int32, device=dev) if with_rows else None
+        clock = self._clock_t
+        ms, scratch = eng.summarize_pairs(
+            len(self), n_pairs, n_groups, pair_a_ptr=pa.data_ptr(), pair_b_ptr=pb.data_ptr(), times_ptr=times.data_ptr(),
+            time_row_ptr=tr.data_ptr(), n_time_rows=n_rows, draw_capacity=cap, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
+            counts_ptr=self._counts_t.data_ptr(), pair_counts_ptr=pair_counts.data_ptr(), pair_sums_ptr=pair_sums.data_ptr(),
+            unmatched_ptr=unmatched.data_ptr(), cell_counts_ptr=cell_counts.data_ptr(), extremes_ptr=extremes.data_ptr(),
+            hist_ptr=hist.data_ptr(), tails_ptr=tails.data_ptr(), above_ptr=above.data_ptr() if n_thr else 0,
+            row_a_ptr=row_a.data_ptr() if with_rows else 0, row_b_ptr=row_b.data_ptr() if with_rows else 0, group_ptr=grp.data_ptr(),
+            edges=e, thresholds=th, sub_bits=binning[0], min_exp=binning[1], octaves=binning[2])
+        out: dict[str, Any] = {"edges": e, "thresholds": th, "sub_bits": binning[0], "min_exp": binning[1], "octaves": binning[2],
+                               "bin_edges": latency_bin_edges(*binning[:3]), "a": ia, "b": ib, "groups": ids,
+                               "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "pairs_ms": ms, "arrival_ms": arrival_ms,
+                               "scratch_bytes": scratch}
+        pc = pair_counts.cpu().numpy().view(np.uint32)
+        for k, name in enumerate(_PAIR_COUNTS):
+            out[name] = np.ascontiguousarray(pc[:, :, k])
+        ps = pair_sums.cpu().numpy()
+        out["sum_d"], out["sum_a"] = np.ascontiguousarray(ps[:, :, 0]), np.ascontiguousarray(ps[:, :, 1])
+        un = unmatched.cpu().numpy().view(np.uint32)
+        out["unmatched_a"], out["unmatched_b"] = un[:, 0].copy(), un[:, 1].copy()
+        valid = out["both"].astype(np.float64) - out["nan"]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out["mean_d"] = np.where(valid > 0, out["sum_d"] / valid, np.nan)
+            out["mean_a"] = np.where(valid > 0, out["sum_a"] / valid, np.nan)
+            out["relative"] = out["mean_d"] / out["mean_a"]
+        cc = cell_counts.cpu().numpy().view(np.uint64).reshape(n_groups, n_win, 8)
+        for k, name in enumerate((*(f"cell_{c}" for c in _PAIR_COUNTS), "slower", "faster", "equal")):
+            out[name] = np.ascontiguousarray(cc[:, :, k])
+        out["above"] = above.cpu().numpy().view(np.uint64).reshape(n_groups, n_win, -1)[:, :, :n_thr].copy()
+        ex = extremes.cpu().numpy().reshape(n_groups, n_win, 2)
+        out["min_d"], out["max_d"] = np.ascontiguousarray(ex[:, :, 0]), np.ascontiguousarray(ex[:, :, 1])
+        hh = hist.cpu().numpy().view(np.uint32).reshape(n_groups, n_win, 2, n_bins)
+        out["hist_pos"], out["hist_neg"] = np.ascontiguousarray(hh[:, :, 0]), np.ascontiguousarray(hh[:, :, 1])
+        tt = tails.cpu().numpy().view(np.uint32).reshape(n_groups, n_win, 4)
+        for k, name in enumerate(("under_pos", "under_neg", "over_pos", "over_neg")):
+            out[name] = np.ascontiguousarray(tt[:, :, k])
+        if with_rows:
+            out["row_a"], out["row_b"] = row_a.cpu().numpy().view(np.uint32), row_b.cpu().numpy().view(np.uint32)
+        return out
+
+    def paired_bands(self, a: Any, b: Any, window_s: float | None = None, *, edges: Any = None, by: Any = None, level: float = 0.95,
+                     q: tuple[float, float] = (0.05, 0.95)) -> dict[str, Any]:
+        """The paired-t comparison: per (group, window), over the group's pairs with a matched request in the window (``n``
+        [G, W'] of them), the ``mean`` of the per-pair ``mean_d`` with ``std``, ``ci_halfwidth`` (at ``level``) and the linear
+        quantiles ``q_lo`` / ``q_hi`` as :func:`window_bands_by_group` gives them: numpy float64 [G, W', 3], the columns
+        ``mean_d``, ``mean_a`` and ``relative`` (``keys``).  The variance is that of the DIFFERENCES: what common seeds buy.
+        ``pooled`` is ``paired_summary(a, b, ..., by=by)``."""
+        return self._paired_bands_of(self.paired_summary(a, b, window_s, edges=edges, by=by), level, q)
+
+    def _paired_bands_of(self, per: dict[str, Any], level: float, q: tuple[float, float]) -> dict[str, Any]:
+        """:meth:`paired_bands` of a paired summary."""
+        import torch
+
+        ids, n_groups = per["groups"], int(per["replicas"].shape[0])
+        dev = self._counts_t.device
+        body = torch.from_numpy(np.nan_to_num(np.stack([per["mean_d"], per["mean_a"], per["relative"]], axis=2))).to(dev)
+        valid = torch.from_numpy(per["both"].astype(np.int64) - per["nan"] > 0).to(dev)
+        out = window_bands_by_group(body, ids, n_groups, level, q, valid=valid)
+        out["keys"] = ("mean_d", "mean_a", "relative")
+        out["pooled"] = per
+        out["edges"] = per["edges"]
+        return out
+
+    def save_paired_summary(self, path: str, a: Any, b: Any, by: Any = None, *, window_s: float | None = None, edges: Any = None,
+                            thresholds: Any = None, sub_bits: int = 5, min_exp: int = -20, octaves: int = 32,
+                            level: float = 0.95) -> dict[str, np.ndarray]:
+        """Columnar dump of the paired differences with one row per group of pairs: ``replicas`` and, prefixed ``paired_``, the
+        cell arrays of :meth:`paired_summary` (``both`` ... ``nan``, ``slower``, ``faster``, ``equal``, ``above``, ``min_d``,
+        ``max_d``, ``hist_pos``, ``hist_neg``, ``under_*``, ``over_*``) and ``mean_d_mean`` / ``mean_d_ci`` [G, W'] over the pairs
+        (:meth:`paired_bands`); ``paired_sub_bits``, ``paired_min_exp``, ``paired_octaves``, ``paired_thresholds`` and
+        ``window_edges`` (absent for one window) are per-file values.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it
+        back, and :func:`paired_merge` / :func:`paired_delta_quantiles` accept what it returns."""
+        summ = self.paired_summary(a, b, window_s, edges=edges, by=by, thresholds=thresholds, sub_bits=sub_bits, min_exp=min_exp, octaves=octaves)
+        bands = self._paired_bands_of(summ, level, (0.05, 0.95))
+        cols: dict[str, np.ndarray] = {"replicas": np.asarray(summ["replicas"], dtype=np.int64)}
+        for k in _PAIR_CELL_SUMS:
+            cols[f"paired_{k}"] = np.ascontiguousarray(summ[f"cell_{k}" if k in _PAIR_COUNTS else k]).astype(np.int64)
+        for k in ("min_d", "max_d"):
+            cols[f"paired_{k}"] = summ[k]
+        cols["paired_mean_d_mean"] = np.ascontiguousarray(bands["mean"][:, :, 0])
+        cols["paired_mean_d_ci"] = np.ascontiguousarray(bands["ci_halfwidth"][:, :, 0])
+        for k in ("sub_bits", "min_exp", "octaves"):
+            cols[f"paired_{k}"] = np.asarray(summ[k], dtype=np.int64)
+        cols["paired_thresholds"] = summ["thresholds"]
+        if summ["edges"] is not None:
+            cols["window_edges"] = summ["edges"]
+        _write_columns(str(path), cols, int(cols["replicas"].shape[0]))
+        return cols
+
     def quantile_summary(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
                          by: Any = None, window_of: str = "finish") -> dict[str, Any]:
         """Any latency quantiles and SLO shares of every (group, time window): p99.9 at a grid point, p90 during an
@@ -4904,6 +5314,19 @@ class ShardedResults:
 
     def save_exemplar_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_exemplar_summary() of a sweep run on several devices: windows across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def paired_summary(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = ("paired_summary() of a sweep run on several devices: the two sides of a pair may sit on different devices, and sharing "
+               "arrival rows across devices is not implemented")
+        raise NotImplementedError(msg)
+
+    def paired_bands(self, *a: Any, **kw: Any) -> dict[str, Any]:
+        msg = "paired_bands() of a sweep run on several devices: pairs across devices are not implemented"
+        raise NotImplementedError(msg)
+
+    def save_paired_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
+        msg = "save_paired_summary() of a sweep run on several devices: pairs across devices are not implemented"
         raise NotImplementedError(msg)
 
     def _histogram_groups(self, by: Any) -> tuple[np.ndarray, int]:

@@ -1101,6 +1101,78 @@ typedef struct af_latency_histogram {
 } af_latency_histogram_t;
 int af_engine_summarize_latency_histogram(af_engine_t* engine, const af_outputs_t* out, af_latency_histogram_t* histogram);
 
+/* PAIRED LATENCY DIFFERENCES between scenarios that share their seeds (asyncflow_amd/csrc/af_paired.hpp): two scenarios of one batch
+ * with the same seed and the same generator columns were sent the same requests at the same instants, and every stored `start` is,
+ * bit for bit, one of the arrival times af_arrivals_t.times hands out.  The call joins the clock rows of both sides through that
+ * arrival row and reports the latency difference of the SAME request under A and under B -- the paired estimator common random
+ * numbers are shared for.  Reads outputs.clock and outputs.counts; no simulation kernel runs.
+ * Pair p: a = pair_a[p], b = pair_b[p]; A = times[time_row[p]], ascending, +inf behind the last arrival, m = its finite entries;
+ * side x has m_x = min(counts[x][AF_CNT_COMPLETED], clock_capacity) stored rows (start_i, finish_i).
+ *     match            row i of side x maps to j = #{ k < m : A[k] < start_i } (np.searchsorted "left") when j < m and the u64 word
+ *                      of A[j] is the word of start_i (a NaN never matches).  row_x[j] = the smallest i that maps to j, AF_PAIR_NONE
+ *                      without one.  unmatched_x = m_x - #{ j : row_x[j] set }: the rows that map nowhere or lose their j to a
+ *                      smaller row index (two arrivals of one bit pattern: the result stays a function of the data alone)
+ *     arrival j        both (row_a[j] and row_b[j] set), only_a, only_b, neither -- the latter three were dropped or still in flight
+ *                      at the end of the run on one or both sides; the two are not told apart.  Of a `both` arrival lat_x = finish -
+ *                      start of row row_x[j] and d = lat_b - lat_a, three f64 subtractions; d NaN: counted in nan, nothing else
+ *     window           by the arrival time, the same on both sides: edges[w] < A[j] <= edges[w + 1] (af_windows_t's rule), a
+ *                      contiguous range of j; A[j] <= edges[0] or > edges[W]: in no window.  Without edges (n_windows == 0, edges
+ *                      NULL) one window over every arrival.  W' = max(n_windows, 1)
+ *     per (pair, window)   pair_counts[5] u32 = both, only_a, only_b, neither, nan (nan is part of both);  pair_sums[2] f64 = sum_d,
+ *                      sum_a over the `both` arrivals with d not NaN in a FIXED order: lane l = j mod 64 adds its values in
+ *                      ascending j from +0.0, then part[l] += part[l + h] for l < h, h = 32, 16, 8, 4, 2, 1; sum = part[0]
+ *     per cell c = g * W' + w, over the pairs of group g   cell_counts[8] u64 = the five counts, slower (d > 0), faster (d < 0),
+ *                      equal (d == 0);  above[n_thresholds] u64 = #{ d > thresholds[t] };  extremes[2] f64 = min_d, max_d in float
+ *                      order (-0.0 below +0.0), +inf / -inf for a cell without a value;  hist[2][n_bins] u32 on af_latency_histogram_t's
+ *                      bit rule: [0] bins d > 0 on d, [1] bins d < 0 on -d;  tails[4] u32 = under_pos, under_neg (0 < |d| < 2^min_exp),
+ *                      over_pos, over_neg (at or above the last bin's end, the infinities).  equal + sum(tails) + sum(hist) + nan == both
+ * Cells take integer + and min / max only: no word depends on the launch, on the chunks or on the order of the pairs.
+ * A skipped pair (AF_POOL_SKIP) is in no cell; its per-pair outputs are written like any other's.
+ * Refused, no output touched: n_pairs, n_groups, n_scenarios or draw_capacity == 0, a NULL pair_a / pair_b / time_row / times /
+ * outputs.clock / outputs.counts or output other than row_a / row_b (above may be NULL with n_thresholds == 0), a binning outside
+ * af_latency_histogram_t's ranges, edges not finite or not strictly increasing, edges NULL with n_windows > 0 (or given with 0), more
+ * than AF_MAX_PAIR_THRESHOLDS thresholds or one that is not finite, a pair_a / pair_b >= n_scenarios, a time_row >= n_time_rows, a
+ * group id >= n_groups -- the ids are read back and checked on the host -- (AF_ERR_INVALID); n_pairs * W' >= 2^32, n_groups * W' *
+ * n_bins >= 2^32, draw_capacity >= 2^31, a group whose pairs could match 2^32 or more requests, no room for one pair's slots
+ * (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).
+ * outputs.clock must be 16-byte aligned.  Scratch kept by the engine: 8 B per edge and threshold and 2 * 4 B per (pair, draw) for
+ * the pairs of one chunk (a side whose row_a / row_b is given needs none); the pairs are taken in chunks that fit the memory.
+ * Synchronous; the struct is written back. */
+#define AF_MAX_PAIR_THRESHOLDS 64
+#define AF_PAIR_NONE 0xFFFFFFFFu
+typedef struct af_pairs {
+    uint32_t n_scenarios;        /* the scenarios of `out`: pair_a / pair_b index them */
+    uint32_t n_pairs;
+    uint32_t n_groups;
+    uint32_t n_windows;          /* 0: one window over every arrival (edges NULL) */
+    const uint32_t* pair_a;      /* DEVICE [n_pairs] */
+    const uint32_t* pair_b;      /* DEVICE [n_pairs] */
+    const uint32_t* group;       /* DEVICE [n_pairs] group id per pair (AF_POOL_SKIP: in no cell); NULL: all in group 0 */
+    const double* edges;         /* HOST [n_windows + 1] strictly increasing, finite; NULL with n_windows == 0 */
+    const double* times;         /* DEVICE [n_time_rows][draw_capacity]: arrival rows as af_arrivals_t.times hands them out */
+    const uint32_t* time_row;    /* DEVICE [n_pairs]: the row of `times` that holds the pair's arrivals */
+    uint32_t n_time_rows;
+    uint32_t draw_capacity;
+    const double* thresholds;    /* HOST [n_thresholds] finite, signed; NULL with n_thresholds == 0 */
+    uint32_t n_thresholds;       /* 0 .. AF_MAX_PAIR_THRESHOLDS */
+    uint32_t sub_bits;           /* the binning of |d|: af_latency_histogram_t's m, e, o */
+    int32_t min_exp;
+    uint32_t octaves;
+    uint32_t* pair_counts;       /* DEVICE [n_pairs][W'][5] u32 out */
+    double* pair_sums;           /* DEVICE [n_pairs][W'][2] f64 out */
+    uint32_t* unmatched;         /* DEVICE [n_pairs][2] u32 out: unmatched_a, unmatched_b */
+    uint64_t* cell_counts;       /* DEVICE [C][8] u64 out, C = n_groups * W' */
+    uint64_t* above;             /* DEVICE [C][n_thresholds] u64 out */
+    double* extremes;            /* DEVICE [C][2] f64 out */
+    uint32_t* hist;              /* DEVICE [C][2][n_bins] u32 out */
+    uint32_t* tails;             /* DEVICE [C][4] u32 out */
+    uint32_t* row_a;             /* DEVICE [n_pairs][draw_capacity] u32 out, optional: the join itself (AF_PAIR_NONE: no row) */
+    uint32_t* row_b;             /* DEVICE [n_pairs][draw_capacity] u32 out, optional */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_pairs_t;
+int af_engine_summarize_pairs(af_engine_t* engine, const af_outputs_t* out, af_pairs_t* pairs);
+
 /* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
  * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
  * use, with the connections on an edge?  A cell is (group g, arrival window w, bin b of ONE sampled series at the row's tick).
