@@ -618,6 +618,58 @@ class AfPairs(C.Structure):
     ]
 
 
+MAX_ALERT_RULES = 32   # AF_MAX_ALERT_RULES
+
+
+class AfAlertRule(C.Structure):
+    """``af_alert_rule_t``: one burn-rate rule of ``af_engine_summarize_alerts``, in ticks and as the fraction ``num / den``."""
+
+    _fields_ = [
+        ("long_ticks", C.c_uint32),
+        ("short_ticks", C.c_uint32),
+        ("num", C.c_uint32),
+        ("den", C.c_uint32),
+        ("min_total", C.c_uint32),
+        ("hold_ticks", C.c_uint32),
+    ]
+
+
+class AfAlerts(C.Structure):
+    """``af_alerts_t``: request of ``af_engine_summarize_alerts`` (``elapsed_ms`` and ``scratch_bytes`` are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("n_rules", C.c_uint32),
+        ("group", C.c_void_p),
+        ("tick_edges", C.POINTER(C.c_uint32)),
+        ("rules", C.POINTER(AfAlertRule)),
+        ("sample_period", C.c_double),
+        ("slo", C.c_double),
+        ("n_bins", C.c_uint32),
+        ("delay_width", C.c_uint32),
+        ("count", C.c_void_p),
+        ("fired", C.c_void_p),
+        ("episodes", C.c_void_p),
+        ("longest", C.c_void_p),
+        ("longest_start", C.c_void_p),
+        ("first", C.c_void_p),
+        ("last", C.c_void_p),
+        ("members", C.c_void_p),
+        ("fired_members", C.c_void_p),
+        ("open_members", C.c_void_p),
+        ("fire_ticks", C.c_void_p),
+        ("fire_episodes", C.c_void_p),
+        ("delay_hist", C.c_void_p),
+        ("total", C.c_void_p),
+        ("bad", C.c_void_p),
+        ("firing", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -653,6 +705,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_exemplars",
     "af_engine_summarize_latency_histogram",
     "af_engine_summarize_pairs",
+    "af_engine_summarize_alerts",
     "af_engine_summarize_state_windows",
     "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
@@ -721,6 +774,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_latency_histogram.restype = C.c_int
     lib.af_engine_summarize_pairs.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfPairs)]
     lib.af_engine_summarize_pairs.restype = C.c_int
+    lib.af_engine_summarize_alerts.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfAlerts)]
+    lib.af_engine_summarize_alerts.restype = C.c_int
     lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
     lib.af_engine_summarize_state_windows.restype = C.c_int
     lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]

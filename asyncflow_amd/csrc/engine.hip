@@ -69,6 +69,7 @@
 #include "af_quantiles.hpp"
 #include "af_arrival_counts.hpp"
 #include "af_inflight.hpp"
+#include "af_alerts.hpp"
 #include "af_exemplars.hpp"
 #include "af_latency_histogram.hpp"
 #include "af_paired.hpp"
@@ -3590,6 +3591,109 @@ int af_engine_summarize_inflight(af_engine_t* e, const af_outputs_t* out, af_inf
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(st));   // (the host edges are read by the copy until here)
+    req->scratch_bytes = e->pool_cap;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Burn-rate alert rules per tick over rolling look-backs of the completions (af_alerts.hpp).  The host checks the request, reads
+// the group ids back, uploads the edges and the rules and initialises the group cells; two launches: the prefix arrays by a
+// workgroup per scenario, the evaluation by a wave per scenario.
+static_assert(afal::kSkip == AF_POOL_SKIP && afal::kNone == AF_TICK_NONE && afal::kMaxRules == AF_MAX_ALERT_RULES &&
+                  afal::kMaxBins == AF_MAX_SERIES_HISTOGRAM_BINS && sizeof(afal::Rule) == sizeof(af_alert_rule_t),
+              "the kernel's constants are the header's");
+
+int af_engine_summarize_alerts(af_engine_t* e, const af_outputs_t* out, af_alerts_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0 || req->n_rules == 0)
+        return fail(AF_ERR_INVALID, "empty alerts request (n_scenarios, n_groups, n_windows and n_rules must be > 0)");
+    if (req->n_rules > AF_MAX_ALERT_RULES) return fail(AF_ERR_INVALID, "alerts.n_rules must be 1 .. AF_MAX_ALERT_RULES (" + std::to_string(AF_MAX_ALERT_RULES) + ")");
+    if (!req->tick_edges) return fail(AF_ERR_INVALID, "alerts.tick_edges is required");
+    if (!req->rules) return fail(AF_ERR_INVALID, "alerts.rules is required");
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, R = req->n_rules, cap = out->tick_capacity;
+    const uint32_t B = req->delay_hist ? req->n_bins : 0u;
+    if (req->delay_hist && (B == 0 || B > AF_MAX_SERIES_HISTOGRAM_BINS))
+        return fail(AF_ERR_INVALID, "alerts.n_bins must be 1 .. AF_MAX_SERIES_HISTOGRAM_BINS (" + std::to_string(AF_MAX_SERIES_HISTOGRAM_BINS) + ")");
+    if (req->delay_hist && req->delay_width == 0) return fail(AF_ERR_INVALID, "alerts.delay_width must be above 0");
+    for (uint32_t k = 1; k <= W; ++k)
+        if (!(req->tick_edges[k - 1] < req->tick_edges[k]))
+            return fail(AF_ERR_INVALID, "tick_edges must be strictly increasing (edge " + std::to_string(k) + ")");
+    if (!(std::isfinite(req->sample_period) && req->sample_period > 0.0)) return fail(AF_ERR_INVALID, "alerts.sample_period must be a finite number above 0");
+    if (std::isnan(req->slo)) return fail(AF_ERR_INVALID, "alerts.slo must not be NaN");
+    for (uint32_t r = 0; r < R; ++r) {
+        const af_alert_rule_t& ru = req->rules[r];
+        if (ru.short_ticks == 0 || ru.long_ticks < ru.short_ticks || ru.den == 0 || ru.num > ru.den || ru.hold_ticks == 0)
+            return fail(AF_ERR_INVALID, "alerts.rules[" + std::to_string(r) + "]: long_ticks >= short_ticks >= 1, den >= 1, num <= den and hold_ticks >= 1 must hold");
+    }
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "alerts need outputs.clock");
+    if (cap == 0) return fail(AF_ERR_INVALID, "alerts need outputs.tick_capacity > 0");
+    if ((uint64_t)G * W >= 0xFFFFFFFFull || (uint64_t)G * W * R >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows * n_rules must be below 2^32 - 1");
+    if ((uint64_t)n * W >= 0xFFFFFFFFull || (uint64_t)n * W * R >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * n_windows * n_rules must be below 2^32 - 1");
+    if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> grp;
+    if (int rc = read_groups(req->group, n, G, grp)) return rc;
+    ScratchLayout lay;
+    const size_t o_edges = lay.part(((size_t)W + 1u) * 4u);
+    const size_t o_rules = lay.part((size_t)R * sizeof(afal::Rule));
+    const size_t o_prefix = lay.part((size_t)n * cap * 8u);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    hipStream_t st = e->stream;
+    HIP_TRY(hipMemcpyAsync(e->d_pool + o_edges, req->tick_edges, ((size_t)W + 1u) * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(e->d_pool + o_rules, req->rules, (size_t)R * sizeof(afal::Rule), hipMemcpyHostToDevice, st));
+    const size_t cells = (size_t)G * W * R;
+    if (req->members) HIP_TRY(hipMemsetAsync(req->members, 0, cells * 4u, st));
+    if (req->fired_members) HIP_TRY(hipMemsetAsync(req->fired_members, 0, cells * 4u, st));
+    if (req->open_members) HIP_TRY(hipMemsetAsync(req->open_members, 0, cells * 4u, st));
+    if (req->fire_ticks) HIP_TRY(hipMemsetAsync(req->fire_ticks, 0, cells * 8u, st));
+    if (req->fire_episodes) HIP_TRY(hipMemsetAsync(req->fire_episodes, 0, cells * 8u, st));
+    if (req->delay_hist) HIP_TRY(hipMemsetAsync(req->delay_hist, 0, cells * B * 4u, st));
+    afal::AlArgs a{};
+    a.clock = out->clock;
+    a.counts = out->counts;
+    a.clock_cap = out->clock_capacity;
+    a.tick_cap = cap;
+    a.cnt_completed_slot = AF_CNT_COMPLETED;
+    a.cnt_ticks_slot = AF_CNT_TICKS;
+    a.period = req->sample_period;
+    a.slo = req->slo;
+    a.n_scen = n;
+    a.n_win = W;
+    a.n_rules = R;
+    a.n_bins = B;
+    a.delay_width = req->delay_width;
+    a.group = req->group;
+    a.edges = reinterpret_cast<const uint32_t*>(e->d_pool + o_edges);
+    a.rules = reinterpret_cast<const afal::Rule*>(e->d_pool + o_rules);
+    a.prefix = reinterpret_cast<uint2*>(e->d_pool + o_prefix);
+    a.total = req->total;
+    a.bad = req->bad;
+    a.firing = req->firing;
+    a.count = req->count;
+    a.fired = req->fired;
+    a.episodes = req->episodes;
+    a.longest = req->longest;
+    a.longest_start = req->longest_start;
+    a.first = req->first;
+    a.last = req->last;
+    a.members = req->members;
+    a.fired_members = req->fired_members;
+    a.open_members = req->open_members;
+    a.fire_ticks = reinterpret_cast<unsigned long long*>(req->fire_ticks);
+    a.fire_episodes = reinterpret_cast<unsigned long long*>(req->fire_episodes);
+    a.delay_hist = req->delay_hist;
+    const size_t lds = (size_t)afal::kChunkTicks * 8u;
+    const void* fn = reinterpret_cast<const void*>(afal::af_alerts_prefix_kernel<WaveHip>);
+    // (set before every launch: the attribute is per device and engines of several devices run in threads of one process)
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    void* kargs[] = {&a};
+    HIP_TRY(hipLaunchKernel(fn, dim3(n), dim3(afal::kThreads), kargs, lds, st));
+    hipLaunchKernelGGL(afal::af_alerts_eval_kernel, dim3((n + afal::kEvalWaves - 1u) / afal::kEvalWaves), dim3(afal::kEvalThreads), 0, st, a);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));   // (the host edges and rules are read by the copies until here)
     req->scratch_bytes = e->pool_cap;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;

@@ -400,6 +400,39 @@ class Engine:
         _check(self._lib, self._lib.af_engine_summarize_inflight(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_inflight")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def summarize_alerts(self, n: int, n_groups: int, tick_edges: Any, sample_period: float, slo: float, rules: Any, *,
+                         clock_ptr: int, clock_capacity: int, tick_capacity: int, counts_ptr: int, group_ptr: int = 0,
+                         delay_bins: int = 0, delay_width: int = 1, ptrs: dict[str, int] | None = None) -> tuple[float, int]:
+        """Burn-rate alert rules per tick on the device (``af_engine_summarize_alerts``; the host definitions are
+        :func:`asyncflow_amd.results.completion_ticks`, :func:`~asyncflow_amd.results.alert_firing`,
+        :func:`~asyncflow_amd.results.alert_window_stats` and :func:`~asyncflow_amd.results.alert_cells`).  ``rules``: rows of
+        ``(long_ticks, short_ticks, num, den, min_total, hold_ticks)``; ``slo``: a request is bad when its latency is above it.
+        ``ptrs`` maps output names of ``af_alerts_t`` to device pointers; an output without a pointer is skipped: ``count``
+        uint32 [n, W]; ``fired``, ``episodes``, ``longest``, ``longest_start``, ``first``, ``last`` uint32 [n, W, R];
+        ``members``, ``fired_members``, ``open_members`` uint32 and ``fire_ticks``, ``fire_episodes`` uint64 [n_groups, W, R];
+        ``delay_hist`` uint32 [n_groups, W, R, delay_bins]; ``total``, ``bad``, ``firing`` uint32 [n, tick_capacity] (rows at or
+        past a scenario's ticks are left untouched).  ``tick_edges``: HOST uint32 tick indices, strictly increasing;
+        ``group_ptr`` as in :meth:`summarize_pooled`.  COMPLETED requests only: dropped requests and requests still in flight
+        at the end of the run are in no clock row.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_tick_edges
+
+        b = check_tick_edges(tick_edges)
+        rows = np.ascontiguousarray(rules, dtype=np.uint32).reshape(-1, 6)
+        p = dict(ptrs or {})
+        names = ("count", "fired", "episodes", "longest", "longest_start", "first", "last", "members", "fired_members",
+                 "open_members", "fire_ticks", "fire_episodes", "delay_hist", "total", "bad", "firing")
+        unknown = set(p) - set(names)
+        if unknown:
+            msg = f"unknown alert outputs {sorted(unknown)}"
+            raise ValueError(msg)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), int(tick_capacity), None, C.c_void_p(counts_ptr or None))
+        req = _abi.AfAlerts(int(n), int(n_groups), int(b.shape[0] - 1), int(rows.shape[0]), C.c_void_p(group_ptr or None),
+                            b.ctypes.data_as(C.POINTER(C.c_uint32)), rows.ctypes.data_as(C.POINTER(_abi.AfAlertRule)),
+                            float(sample_period), float(slo), int(delay_bins), int(delay_width),
+                            *(C.c_void_p(p.get(k) or None) for k in names), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_summarize_alerts(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_alerts")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def summarize_exemplars(self, n: int, n_groups: int, k: int, *, edges: Any = None, window_of: str = "finish", clock_ptr: int,
                             clock_capacity: int, counts_ptr: int, total_ptr: int, scenario_ptr: int, row_ptr: int, pair_ptr: int,
                             kept_ptr: int = 0, state_ptr: int = 0, samples_ptr: int = 0, tick_capacity: int = 0,

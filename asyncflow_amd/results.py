@@ -378,6 +378,338 @@ def in_flight_window_stats(members: Any, tick_edges: Any, threshold: int = 0, bi
     return out
 
 
+MAX_ALERT_RULES = 32   # AF_MAX_ALERT_RULES
+ALERT_CELL_KEYS = ("fired", "episodes", "longest", "longest_start", "first", "last")
+ALERT_GROUP_KEYS = ("members", "fired_members", "open_members", "fire_ticks", "fire_episodes")
+
+
+def _exact_fraction(x: Any, name: str) -> Any:
+    """``x`` as an exact ``Fraction``: ints and Fractions as they are, a float by its ``repr`` (0.999 is 999/1000)."""
+    from fractions import Fraction
+
+    if isinstance(x, bool):
+        msg = f"{name} must be a number, not {x!r}"
+        raise ValueError(msg)
+    if isinstance(x, (int, np.integer)):
+        return Fraction(int(x))
+    if isinstance(x, Fraction):
+        return x
+    v = float(x)
+    if not math.isfinite(v):
+        msg = f"{name} must be finite, not {x!r}"
+        raise ValueError(msg)
+    return Fraction(repr(v))
+
+
+def alert_rule(long_s: float, short_s: float | None = None, *, bad_share: Any = None, objective: Any = None, burn_rate: Any = None,
+               hold_s: float = 0.0, min_total: int = 1) -> dict[str, Any]:
+    """One burn-rate alert rule in SECONDS, as an SLO is written: the alert burns where the share of bad requests (latency
+    above the call's ``slo_s``) over the last ``long_s`` seconds AND over the last ``short_s`` seconds (default: ``long_s``, a
+    single-window rule) is ABOVE the share, with at least ``min_total`` completions in the long look-back, and fires once that
+    has held for ``hold_s`` seconds of consecutive evaluations (the ``for:`` clause; 0: at once).  The share is either
+    ``bad_share`` or ``burn_rate * (1 - objective)`` -- exactly one of the two ways --, kept as an exact ``Fraction``: ints
+    and Fractions as they are, a float by its ``repr`` (``objective=0.999, burn_rate=14.4`` is 9/625).  ValueError if the share
+    is below 0, above 1 or has a denominator above 2^32 - 1.  The seconds become ticks where the plan's sample period is
+    known (:func:`alert_rule_ticks`).  Returns a dict: ``long_s``, ``short_s``, ``share``, ``hold_s``, ``min_total``."""
+    if (bad_share is None) == (objective is None and burn_rate is None) or (objective is None) != (burn_rate is None):
+        msg = "pass exactly one of bad_share, or objective together with burn_rate"
+        raise ValueError(msg)
+    if bad_share is not None:
+        share = _exact_fraction(bad_share, "bad_share")
+    else:
+        share = _exact_fraction(burn_rate, "burn_rate") * (1 - _exact_fraction(objective, "objective"))
+    if share < 0 or share > 1 or share.denominator > 0xFFFFFFFF:
+        msg = f"the bad share must lie in [0, 1] with a denominator of at most 2^32 - 1, not {share}"
+        raise ValueError(msg)
+    if isinstance(min_total, bool) or int(min_total) != min_total or not 0 <= int(min_total) <= 0xFFFFFFFF:
+        msg = f"min_total must be a whole number in [0, 2^32), not {min_total!r}"
+        raise ValueError(msg)
+    long_v, short_v, hold_v = float(long_s), float(long_s if short_s is None else short_s), float(hold_s)
+    if not (math.isfinite(long_v) and math.isfinite(short_v) and 0.0 < short_v <= long_v):
+        msg = f"0 < short_s <= long_s must hold, not short_s = {short_v!r}, long_s = {long_v!r}"
+        raise ValueError(msg)
+    if not (math.isfinite(hold_v) and hold_v >= 0.0):
+        msg = f"hold_s must be a number of seconds >= 0, not {hold_s!r}"
+        raise ValueError(msg)
+    return {"long_s": long_v, "short_s": short_v, "share": share, "hold_s": hold_v, "min_total": int(min_total)}
+
+
+def seconds_to_ticks(x: float, sample_period: float) -> int:
+    """``x`` seconds as ``round(x / p)`` ticks; ValueError unless ``|ticks * p - x| <= 1e-9 * max(1, x)``."""
+    v, p = float(x), float(sample_period)
+    if not (math.isfinite(v) and v >= 0.0):
+        msg = f"a number of seconds >= 0 is needed, not {x!r}"
+        raise ValueError(msg)
+    t = int(round(v / p))
+    if abs(t * p - v) > 1e-9 * max(1.0, v):
+        msg = f"{x!r} s is not a multiple of the sample period ({sample_period!r} s)"
+        raise ValueError(msg)
+    return t
+
+
+def alert_rule_ticks(rule: Any, sample_period: float) -> tuple[int, int, int, int, int, int]:
+    """A rule as the device takes it, ``(long_ticks, short_ticks, num, den, min_total, hold_ticks)``: a dict of
+    :func:`alert_rule` converted with :func:`seconds_to_ticks` (``hold_s = 0`` is ``hold_ticks = 1``), or six whole numbers
+    that are ticks already."""
+    if isinstance(rule, dict):
+        share = rule["share"]
+        hold = seconds_to_ticks(rule["hold_s"], sample_period)
+        return (seconds_to_ticks(rule["long_s"], sample_period), seconds_to_ticks(rule["short_s"], sample_period),
+                int(share.numerator), int(share.denominator), int(rule["min_total"]), max(hold, 1))
+    r = tuple(int(v) for v in rule)
+    if len(r) != 6 or any(int(v) != v for v in rule):
+        msg = f"a rule is alert_rule(...) or six whole numbers (long_ticks, short_ticks, num, den, min_total, hold_ticks), not {rule!r}"
+        raise ValueError(msg)
+    return r   # type: ignore[return-value]
+
+
+def check_alert_rules(rules: Any, sample_period: float | None = None) -> np.ndarray:
+    """The rules as uint32 [R, 6] (:func:`alert_rule_ticks`), or ValueError: 1 .. 32 rules, ``long_ticks >= short_ticks >= 1``,
+    ``den >= 1``, ``num <= den``, ``hold_ticks >= 1``, every field in [0, 2^32)."""
+    items = [rules] if isinstance(rules, dict) else list(rules)
+    if len(items) == 6 and all(isinstance(v, (int, np.integer)) for v in items):
+        items = [tuple(items)]
+    if not 1 <= len(items) <= MAX_ALERT_RULES:
+        msg = f"1 .. {MAX_ALERT_RULES} rules are needed, not {len(items)}"
+        raise ValueError(msg)
+    rows = []
+    for j, it in enumerate(items):
+        if isinstance(it, dict) and sample_period is None:
+            msg = "a rule in seconds needs the sample period"
+            raise ValueError(msg)
+        r = alert_rule_ticks(it, sample_period if sample_period is not None else 1.0)
+        long_t, short_t, num, den, min_total, hold = r
+        if any(not 0 <= v <= 0xFFFFFFFF for v in r) or short_t < 1 or long_t < short_t or den < 1 or num > den or hold < 1:
+            msg = f"rule {j}: long_ticks >= short_ticks >= 1, den >= 1, num <= den and hold_ticks >= 1 must hold, not {r}"
+            raise ValueError(msg)
+        rows.append(r)
+    return np.asarray(rows, dtype=np.uint32).reshape(-1, 6)
+
+
+def completion_ticks(rows: Any, ticks: int, period: float, slo: float) -> dict[str, np.ndarray]:
+    """Completions and bad completions per tick of one scenario: the first half of the host definition
+    ``af_engine_summarize_alerts`` is held to, word for word.  ``rows``: float64 [m, 2], the stored ``(start, finish)`` rows;
+    ``ticks``: the scenario's sample rows ``t_s``.  The tick of a completion is ``f_i = floor(finish_i / period)``, one float64
+    division and then floor (the rule of :func:`in_flight_series`); row i is COUNTED iff ``start_i`` and ``finish_i`` are not NaN
+    and ``0 <= f_i < t_s``, compared on the float64 quotient (a huge or infinite quotient clips).  Nothing else is rejected:
+    ``start < 0``, ``finish < start`` and a latency below a tick are counted -- a monitor sees every completion.  Row i is BAD
+    iff ``finish_i - start_i > slo`` as float64 (``slo = +inf``: nothing is bad; NaN is refused).  Returns uint32 [t_s] each:
+    ``total[k] = #{counted i : f_i == k}`` and ``bad[k]``, whatever the order of the rows.  COMPLETED requests only: a
+    dropped request and one still in flight when the run ended are in no clock row."""
+    p, t_s, s = float(period), int(ticks), float(slo)
+    if not (np.isfinite(p) and p > 0.0):
+        msg = f"period must be a finite number above 0, not {period!r}"
+        raise ValueError(msg)
+    if t_s != ticks or not 0 <= t_s < 2 ** 31:
+        msg = f"ticks must be a whole number in [0, 2^31), not {ticks!r}"
+        raise ValueError(msg)
+    if math.isnan(s):
+        msg = "slo must not be NaN"
+        raise ValueError(msg)
+    ck = np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+    start, finish = ck[:, 0], ck[:, 1]
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        qf = np.floor(finish / p)
+        ok = ~np.isnan(start) & ~np.isnan(finish) & (qf >= 0.0) & (qf < float(t_s))
+        is_bad = ok & ((finish - start) > s)
+    total = np.bincount(qf[ok].astype(np.int64), minlength=t_s)[:t_s]
+    bad = np.bincount(qf[is_bad].astype(np.int64), minlength=t_s)[:t_s]
+    return {"total": total.astype(np.uint32), "bad": bad.astype(np.uint32)}
+
+
+def alert_firing(total: Any, bad: Any, rules: Any) -> dict[str, np.ndarray]:
+    """The rules of ``af_engine_summarize_alerts`` at every tick of one scenario, on the host.  ``total`` / ``bad``:
+    :func:`completion_ticks`; ``rules``: ticks (:func:`check_alert_rules`).  With the prefix sums ``PT[k] = sum(total[:k + 1])``
+    and ``PB`` the ROLLING sums of a look-back of L ticks are ``T_L[k] = PT[k] - (PT[k - L] if k >= L else 0)`` and ``B_L``
+    likewise -- the first L - 1 ticks see the rows that exist.  ``cond[r, k] = B_long * den > num * T_long and B_short * den
+    > num * T_short and T_long >= min_total`` (exact integers) and ``firing[r, k]`` iff ``k + 1 >= hold_ticks`` and ``cond[r,
+    j]`` for every ``j`` in ``(k - hold_ticks, k]``: no hysteresis.  Returns ``cond`` and ``firing``, bool [R, ticks]."""
+    r6 = check_alert_rules(rules)
+    tot, bd = np.asarray(total, dtype=np.uint64).reshape(-1), np.asarray(bad, dtype=np.uint64).reshape(-1)
+    if tot.shape != bd.shape:
+        msg = "total and bad must have one length"
+        raise ValueError(msg)
+    t_s = int(tot.shape[0])
+    pt, pb = np.cumsum(tot, dtype=np.uint64), np.cumsum(bd, dtype=np.uint64)
+    k = np.arange(t_s, dtype=np.int64)
+
+    def roll(p: np.ndarray, look: int) -> np.ndarray:
+        back = np.zeros(t_s, dtype=np.uint64)
+        if look < t_s:
+            back[look:] = p[: t_s - look]
+        return p - back
+
+    cond, firing = np.zeros((r6.shape[0], t_s), dtype=bool), np.zeros((r6.shape[0], t_s), dtype=bool)
+    for j, (long_t, short_t, num, den, min_total, hold) in enumerate(r6.tolist()):
+        tl, bl, ts, bs = roll(pt, long_t), roll(pb, long_t), roll(pt, short_t), roll(pb, short_t)
+        n64, d64 = np.uint64(num), np.uint64(den)                        # (each factor is below 2^32: no product wraps)
+        c = (bl * d64 > n64 * tl) & (bs * d64 > n64 * ts) & (tl >= np.uint64(min_total))
+        last_off = np.maximum.accumulate(np.where(c, -1, k)) if t_s else k
+        cond[j], firing[j] = c, c & (k - last_off >= hold)
+    return {"cond": cond, "firing": firing}
+
+
+def alert_window_stats(firing: Any, tick_edges: Any) -> dict[str, np.ndarray]:
+    """The cells of one scenario of ``af_engine_summarize_alerts`` on the host.  ``firing``: bool [R, t_s]
+    (:func:`alert_firing`); window w is the ticks ``lo = min(b[w], t_s) <= k < hi = min(b[w + 1], t_s)``.  Windows choose where
+    firing is reported, never what a rule sees.  Returns int64: ``count``, ``lo``, ``hi`` [W] and, [W, R] each, ``fired`` (the
+    firing ticks), ``episodes`` (the maximal runs of firing ticks, clipped at the window's edges: a run across an edge counts in
+    both windows), ``longest`` (the longest run), ``longest_start`` (the start of the earliest run of that length), ``first``
+    and ``last`` (-1: no such tick; ``last == hi - 1``: still firing at the window's end)."""
+    b = check_tick_edges(tick_edges).astype(np.int64)
+    f = np.atleast_2d(np.asarray(firing, dtype=bool))
+    n_rules, t_s = f.shape
+    n_win = int(b.shape[0] - 1)
+    lo, hi = np.minimum(b[:-1], t_s), np.minimum(b[1:], t_s)
+    out = {k: np.zeros((n_win, n_rules), dtype=np.int64) for k in ("fired", "episodes", "longest")}
+    out.update({k: np.full((n_win, n_rules), -1, dtype=np.int64) for k in ("longest_start", "first", "last")})
+    out.update(count=hi - lo, lo=lo, hi=hi)
+    for w in range(n_win):
+        for r in range(n_rules):
+            v = f[r, lo[w]: hi[w]]
+            at = np.flatnonzero(v)
+            if at.size == 0:
+                continue
+            d = np.diff(np.concatenate([[0], v.astype(np.int8), [0]]))
+            starts, ends = np.flatnonzero(d == 1), np.flatnonzero(d == -1)
+            lengths = ends - starts
+            best = int(np.argmax(lengths))                                # (the first of the longest)
+            out["fired"][w, r], out["episodes"][w, r] = at.size, starts.size
+            out["longest"][w, r], out["longest_start"][w, r] = int(lengths[best]), int(lo[w] + starts[best])
+            out["first"][w, r], out["last"][w, r] = int(lo[w] + at[0]), int(lo[w] + at[-1])
+    return out
+
+
+def alert_cells(members: Any, group_ids: Any, n_groups: int, delay_bins: int = 0, delay_width: int = 1) -> dict[str, np.ndarray]:
+    """The group cells of ``af_engine_summarize_alerts`` on the host.  ``members``: :func:`alert_window_stats` of every
+    scenario; ``group_ids``: its group (negative: in none).  Returns int64 [G, W, R]: ``members`` (those with ``hi > lo``),
+    ``fired_members`` (``first`` is a tick), ``open_members`` (``last == hi - 1``), ``fire_ticks`` (the sum of ``fired``),
+    ``fire_episodes`` (the sum of ``episodes``); and with ``delay_bins`` > 0 ``delay_hist`` [G, W, R, delay_bins]: a member that
+    fired adds 1 to bin ``min((first - lo) // delay_width, delay_bins - 1)``."""
+    stats = list(members)
+    ids = np.asarray(group_ids, dtype=np.int64).reshape(-1)
+    n_bins, width = int(delay_bins), int(delay_width)
+    if len(stats) != ids.shape[0] or (ids >= int(n_groups)).any():
+        msg = "one group id below n_groups per member is needed"
+        raise ValueError(msg)
+    if not 0 <= n_bins <= 1024 or width < 1:
+        msg = f"delay_bins must lie in [0, 1024] and delay_width must be >= 1, not {delay_bins!r} and {delay_width!r}"
+        raise ValueError(msg)
+    n_win, n_rules = stats[0]["fired"].shape if stats else (0, 0)
+    out = {k: np.zeros((int(n_groups), n_win, n_rules), dtype=np.int64) for k in ALERT_GROUP_KEYS}
+    if n_bins:
+        out["delay_hist"] = np.zeros((int(n_groups), n_win, n_rules, n_bins), dtype=np.int64)
+    for st, g in zip(stats, ids.tolist()):
+        if g < 0:
+            continue
+        some = (st["hi"] > st["lo"])[:, None]
+        did = some & (st["first"] >= 0)
+        out["members"][g] += some & np.ones_like(did)
+        out["fired_members"][g] += did
+        out["open_members"][g] += did & (st["last"] == (st["hi"] - 1)[:, None])
+        out["fire_ticks"][g] += st["fired"]
+        out["fire_episodes"][g] += st["episodes"]
+        if n_bins:
+            w_at, r_at = np.nonzero(did)
+            bins = np.minimum((st["first"][w_at, r_at] - st["lo"][w_at]) // width, n_bins - 1)
+            np.add.at(out["delay_hist"][g], (w_at, r_at, bins), 1)
+    return out
+
+
+def alert_delay_quantiles(summary: dict[str, Any], levels: Any) -> dict[str, np.ndarray]:
+    """Brackets of the detection delay read off ``delay_hist`` of :meth:`BatchedResults.alert_summary`: per (group, window,
+    rule) and level q the bin that holds the member of rank ``max(ceil(q N), 1)`` among the N members that fired, delays
+    ascending -- exact integer ranks, q taken by its ``repr``.  Returns float64 [G, W, R, Q]: ``lo_s <= delay < hi_s`` from
+    ``delay_edges_s``; NaN where no member fired; ``hi_s`` is +inf in the last bin, which takes every longer delay."""
+    if "delay_hist" not in summary:
+        msg = "the summary has no delay_hist: pass delay_bins to alert_summary"
+        raise ValueError(msg)
+    hist = np.asarray(summary["delay_hist"], dtype=np.int64)
+    edges = np.asarray(summary["delay_edges_s"], dtype=np.float64)
+    qs = [_exact_fraction(q, "level") for q in np.atleast_1d(np.asarray(levels, dtype=object)).tolist()]
+    if any(q < 0 or q > 1 for q in qs):
+        msg = "levels must lie in [0, 1]"
+        raise ValueError(msg)
+    cum = np.cumsum(hist, axis=-1)
+    n_fired = cum[..., -1]
+    lo_s = np.full(hist.shape[:-1] + (len(qs),), np.nan)
+    hi_s = lo_s.copy()
+    for cell in np.ndindex(*hist.shape[:-1]):
+        n_cell = int(n_fired[cell])
+        if n_cell == 0:
+            continue
+        for j, q in enumerate(qs):
+            rank = max(-((-q.numerator * n_cell) // q.denominator), 1)
+            b = int(np.searchsorted(cum[cell], rank, side="left"))
+            lo_s[cell + (j,)], hi_s[cell + (j,)] = edges[b], edges[b + 1]
+    return {"lo_s": lo_s, "hi_s": hi_s, "fired": n_fired}
+
+
+def scenario_alerts(rows: Any, ticks: int, period: float, slo: float, rules: Any, tick_edges: Any) -> dict[str, np.ndarray]:
+    """One scenario through the whole host definition: :func:`completion_ticks`, :func:`alert_firing` and
+    :func:`alert_window_stats`, in one dict (``rules`` in ticks, or in seconds against ``period``)."""
+    r6 = check_alert_rules(rules, period)
+    out = completion_ticks(rows, ticks, period, slo)
+    out.update(alert_firing(out["total"], out["bad"], r6))
+    out.update(alert_window_stats(out["firing"], tick_edges))
+    out["rules"] = r6
+    return out
+
+
+def _finish_alert_summary(out: dict[str, Any], r6: np.ndarray, b: np.ndarray, ids: np.ndarray, n_groups: int, period: float,
+                          slo: float, delay_bins: int, delay_width: int) -> dict[str, Any]:
+    """The derived columns of ``alert_summary`` from the raw device words (int64; a tick that does not exist is -1)."""
+    from fractions import Fraction
+
+    out["first_s"] = np.where(out["first"] >= 0, out["first"].astype(np.float64) * period, np.nan)
+    out["longest_s"] = out["longest"].astype(np.float64) * period
+    out["fired_s"] = out["fired"].astype(np.float64) * period
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out["fired_share"] = np.where(out["members"] > 0, out["fired_members"] / np.maximum(out["members"], 1).astype(np.float64), np.nan)
+    if delay_bins:
+        edges = np.arange(delay_bins + 1, dtype=np.float64) * (delay_width * period)
+        edges[-1] = np.inf                                               # (the last bin takes every longer delay)
+        out["delay_edges_s"], out["delay_width"] = edges, int(delay_width)
+    out["rules"] = [{"long_ticks": r[0], "short_ticks": r[1], "share": Fraction(r[2], r[3]), "min_total": r[4], "hold_ticks": r[5]}
+                    for r in r6.tolist()]
+    out.update(rule_ticks=r6, slo_s=float(slo), tick_edges=b, times=b[:-1].astype(np.float64) * period,
+               replicas=np.bincount(ids[ids >= 0], minlength=n_groups))
+    return out
+
+
+def _alert_delay_bins(delay_bins: Any, delay_width_s: Any, period: float) -> tuple[int, int]:
+    if isinstance(delay_bins, bool) or int(delay_bins) != delay_bins or not 0 <= int(delay_bins) <= 1024:
+        msg = f"delay_bins must be a whole number in [0, 1024], not {delay_bins!r}"
+        raise ValueError(msg)
+    width = 1 if delay_width_s is None else seconds_to_ticks(delay_width_s, period)
+    if width < 1 or width > 0xFFFFFFFF:
+        msg = f"delay_width_s must be at least one sample period, not {delay_width_s!r}"
+        raise ValueError(msg)
+    return int(delay_bins), width
+
+
+def _save_alert_summary(summ: dict[str, Any], path: str, by: Any) -> dict[str, np.ndarray]:
+    """The columns of ``save_alert_summary``, written to ``path``."""
+    n_groups = int(summ["replicas"].shape[0])
+    cols: dict[str, np.ndarray] = {}
+    if hasattr(by, "point_columns"):
+        for name, v in by.point_columns().items():
+            cols[f"param:{name}"] = np.asarray(v, dtype=np.float64)
+    cols["replicas"] = np.asarray(summ["replicas"], dtype=np.int64)
+    for k in ALERT_GROUP_KEYS:
+        cols[f"alert_{k}"] = np.ascontiguousarray(summ[k][:n_groups]).astype(np.int64)
+    cols["alert_fired_share"] = np.ascontiguousarray(summ["fired_share"][:n_groups])
+    if "delay_hist" in summ:
+        cols["alert_delay_hist"] = np.ascontiguousarray(summ["delay_hist"][:n_groups]).astype(np.int64)
+        cols["alert_delay_edges_s"] = np.asarray(summ["delay_edges_s"], dtype=np.float64)
+    cols["alert_rule_ticks"] = np.asarray(summ["rule_ticks"], dtype=np.float64).reshape(-1)
+    cols["alert_slo_s"] = np.asarray([summ["slo_s"]], dtype=np.float64)
+    cols["alert_tick_edges"] = np.asarray(summ["tick_edges"], dtype=np.float64)
+    cols["alert_times"] = np.asarray(summ["times"], dtype=np.float64)
+    _write_columns(path, cols, n_groups)
+    return cols
+
+
 MAX_EXEMPLARS = 64   # AF_MAX_EXEMPLARS
 
 
@@ -2455,6 +2787,18 @@ class ScenarioResults:
         times = (np.arange(len(vals)) * self._plan.sample_period).tolist()
         return times, vals.astype(np.float64).tolist()
 
+    def get_alerts(self, slo_s: float, rules: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                   tick_edges: Any = None) -> dict[str, np.ndarray]:
+        """Burn-rate alert rules on this scenario's clock rows, through the host definition (:func:`scenario_alerts`):
+        ``total`` / ``bad`` uint32 [ticks], ``cond`` / ``firing`` bool [R, ticks] and the window cells of
+        :func:`alert_window_stats` (``fired``, ``episodes``, ``longest``, ``longest_start``, ``first``, ``last`` int64 [W, R], -1:
+        no such tick).  ``rules`` and the windows as in :meth:`BatchedResults.alert_summary`.  COMPLETED requests only."""
+        ticks = min(int(self.counts[_abi.CNT_TICKS]), max(int(self._plan.tick_count), 0))
+        if self._samples is not None:
+            ticks = min(ticks, int(self._samples.shape[1]))
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
+        return scenario_alerts(self.rqs_clock, ticks, self._plan.sample_period, slo_s, rules, b)
+
     def get_slowest_requests(self, k: int = 16, window_s: float | None = None, edges: Any = None, window_of: str = "finish") -> dict[str, Any]:
         """The ``k`` slowest requests of the scenario, per time window (``window_s`` seconds or explicit ``edges``, by
         ``window_of``) or, with neither, of the whole run: :func:`latency_exemplars` on the scenario's clock rows.  ``row``
@@ -3255,6 +3599,90 @@ class BatchedResults:
             ratio = np.where(demand > 0.0, inf["mean"][:n_groups] / demand, np.nan)
         return {"L": inf["mean"][:n_groups], "lambda_eff": lam, "W": stats[:, :, 1], "ratio": ratio, "completed": completed,
                 "edges": edges, "tick_edges": b, "replicas": inf["replicas"]}
+
+    # ---- burn-rate alert rules per tick over rolling look-backs ---------------------------------------------------
+    def _alert_call(self, b: np.ndarray, ids: np.ndarray, n_groups: int, slo: float, r6: np.ndarray, delay_bins: int,
+                    delay_width: int, per_tick: bool) -> dict[str, Any]:
+        """One ``af_engine_summarize_alerts`` over resolved tick edges, group ids and rules in ticks: the raw outputs on the
+        host, int64 (a tick that does not exist: -1)."""
+        import torch
+
+        self._require_clock()
+        eng, dev = self._arrival_engine()
+        n, n_win, n_rules, clock, cap = len(self), int(b.shape[0] - 1), int(r6.shape[0]), self._clock_t, self._in_flight_ticks()
+        t: dict[str, Any] = {"count": torch.empty((n, n_win), dtype=torch.int32, device=dev)}
+        for k in ALERT_CELL_KEYS:
+            t[k] = torch.empty((n, n_win, n_rules), dtype=torch.int32, device=dev)
+        for k in ALERT_GROUP_KEYS:
+            t[k] = torch.empty((n_groups, n_win, n_rules), dtype=torch.int64 if k.startswith("fire_") else torch.int32, device=dev)
+        if delay_bins:
+            t["delay_hist"] = torch.empty((n_groups, n_win, n_rules, delay_bins), dtype=torch.int32, device=dev)
+        if per_tick:
+            for k in ("total", "bad", "firing"):
+                t[k] = torch.zeros((n, cap), dtype=torch.int32, device=dev)   # (rows at or past t_s are not written)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        ms, scratch = eng.summarize_alerts(
+            n, n_groups, b, self.plan.sample_period, slo, r6, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
+            tick_capacity=cap, counts_ptr=self._counts_t.data_ptr(), group_ptr=grp.data_ptr(), delay_bins=delay_bins,
+            delay_width=delay_width, ptrs={k: v.data_ptr() for k, v in t.items()})
+        out: dict[str, Any] = {}
+        for k, v in t.items():
+            a = v.cpu().numpy()
+            if a.dtype == np.int32 and k not in ("longest_start", "first", "last"):
+                a = a.view(np.uint32)
+            out[k] = a.astype(np.int64) if k != "firing" else a                # (0xFFFFFFFF is -1; a tick is below 2^31)
+        out.update(alerts_ms=ms, scratch_bytes=scratch)
+        return out
+
+    def alert_summary(self, slo_s: float, rules: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                      tick_edges: Any = None, by: Any = None, delay_bins: int = 0, delay_width_s: float | None = None,
+                      per_tick: bool = False) -> dict[str, Any]:
+        """WOULD MY ALERT HAVE FIRED: burn-rate alert rules evaluated at every tick over ROLLING look-backs of the completions,
+        as a monitoring system evaluates them at every scrape -- during an injected outage, how many seconds after it began
+        (the detection delay, as a distribution over the replicas of a grid point), under plain load (a false alarm), for how
+        long and how often (flapping).  The tumbling windows of the other analyzers cannot say.  Computed from the clock rows
+        by ``af_engine_summarize_alerts``, every word equal to :func:`completion_ticks`, :func:`alert_firing`,
+        :func:`alert_window_stats` and :func:`alert_cells`.
+
+        ``slo_s``: a request is bad when its latency is above it (``inf``: none is).  ``rules``: up to 32 of
+        :func:`alert_rule` (seconds, converted against the plan's sample period; ValueError where a duration is no multiple
+        of it) or of six whole numbers in ticks.  Windows and ``by`` as in :meth:`in_flight_summary`; they choose where firing is
+        REPORTED, never what a rule sees -- a look-back reaches across window edges.  Put a window edge at an event's tick and
+        ``delay_hist`` of that window is the detection-delay distribution of each grid point's replicas (``delay_bins`` bins
+        of ``delay_width_s`` seconds, default one tick; the last bin takes every longer delay).
+
+        Returns numpy arrays.  Per replica, int64: ``count`` [n, W]; ``fired`` (firing ticks), ``episodes`` (maximal runs of
+        firing ticks, clipped at the window's edges), ``longest``, ``longest_start``, ``first``, ``last`` (tick indices, -1:
+        none; ``last == hi - 1``: still firing at the window's end) [n, W, R]; float64 ``first_s`` (tick k at ``k *
+        sample_period``, NaN: none), ``longest_s``, ``fired_s``.  Per group, int64 [G, W, R]: ``members``, ``fired_members``,
+        ``open_members``, ``fire_ticks``, ``fire_episodes``; ``fired_share`` = ``fired_members / members`` (NaN where empty);
+        with ``delay_bins`` ``delay_hist`` [G, W, R, delay_bins] and ``delay_edges_s`` (:func:`alert_delay_quantiles` reads
+        brackets off them).  ``per_tick=True`` adds ``total``, ``bad`` int64 and ``firing`` uint32 (bit r: rule r fires) [n,
+        tick capacity], 0 at and past a scenario's ticks.  And ``rules`` (echoed as ticks and fractions), ``rule_ticks`` [R, 6],
+        ``slo_s``, ``tick_edges``, ``times``, ``replicas`` [G], ``alerts_ms``, ``scratch_bytes``.
+        COMPLETED requests only: a dropped request and one still in flight when the run ended are in no clock row, so an alert
+        on availability cannot be expressed, and the last ticks of a run see fewer completions."""
+        period = float(self.plan.sample_period)
+        slo = float(slo_s)
+        if math.isnan(slo):
+            msg = "slo_s must not be NaN"
+            raise ValueError(msg)
+        r6 = check_alert_rules(rules, period)
+        n_bins, width = _alert_delay_bins(delay_bins, delay_width_s, period)
+        b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
+        ids, n_groups = self._window_groups(by)
+        out = self._alert_call(b, ids, n_groups, slo, r6, n_bins, width, bool(per_tick))
+        return _finish_alert_summary(out, r6, b, ids, n_groups, period, slo, n_bins, width)
+
+    def save_alert_summary(self, path: str, slo_s: float, rules: Any, by: Any = None, **kw: Any) -> dict[str, np.ndarray]:
+        """Columnar dump of :meth:`alert_summary` (same keywords) with one row per group (grid point): ``param:<axis>`` (for a
+        Sweep), ``replicas`` and the [G, W, R] columns ``alert_members``, ``alert_fired_members``, ``alert_open_members``,
+        ``alert_fire_ticks``, ``alert_fire_episodes``, ``alert_fired_share`` and, with ``delay_bins``, ``alert_delay_hist`` [G,
+        W, R, bins] with ``alert_delay_edges_s``; ``alert_rule_ticks`` (R x 6, flat), ``alert_slo_s``, ``alert_tick_edges`` and
+        ``alert_times`` are per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        kw.pop("per_tick", None)
+        return _save_alert_summary(self.alert_summary(slo_s, rules, by=by, **kw), str(path), by)
 
     # ---- the slowest requests per window and group, with their identity -------------------------------------------
     def exemplar_summary(self, k: int = 16, window_s: float | None = None, *, edges: Any = None, by: Any = None,
@@ -5368,6 +5796,43 @@ class ShardedResults:
         out.update(bin_edges=latency_bin_edges(*binning[:3]), edges=e, replicas=np.bincount(ids[ids >= 0], minlength=n_groups),
                    sub_bits=binning[0], min_exp=binning[1], octaves=binning[2], window_of=window_of)
         return out
+
+    def alert_summary(self, slo_s: float, rules: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
+                      tick_edges: Any = None, by: Any = None, delay_bins: int = 0, delay_width_s: float | None = None,
+                      per_tick: bool = False) -> dict[str, Any]:
+        """:meth:`BatchedResults.alert_summary` of a sweep run on several devices: the group cells are integer sums, so every
+        shard adds its members' part of the GLOBAL groups on its own device (``by`` is resolved once over the whole sweep, as
+        in :meth:`latency_histogram_summary`) and the parts are added; the per-replica arrays go behind the indices of the
+        original sweep.  Same arguments, same result as the unsharded run."""
+        period = float(self.plan.sample_period)
+        slo = float(slo_s)
+        if math.isnan(slo):
+            msg = "slo_s must not be NaN"
+            raise ValueError(msg)
+        r6 = check_alert_rules(rules, period)
+        n_bins, width = _alert_delay_bins(delay_bins, delay_width_s, period)
+        b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, period, self.plan.tick_count)
+        ids, n_groups = self._histogram_groups(by)
+        n = len(self)
+        out: dict[str, Any] = {"alerts_ms": 0.0, "scratch_bytes": 0}
+        for shard, ix in zip(self.shards, self.index):
+            ix = np.asarray(ix)
+            part = shard._alert_call(b, ids[ix], n_groups, slo, r6, n_bins, width, bool(per_tick))  # noqa: SLF001
+            out["alerts_ms"] += part.pop("alerts_ms")
+            out["scratch_bytes"] = max(out["scratch_bytes"], part.pop("scratch_bytes"))
+            for k, v in part.items():
+                if k in ALERT_GROUP_KEYS or k == "delay_hist":
+                    out[k] = out[k] + v if k in out else v
+                else:
+                    if k not in out:
+                        out[k] = np.zeros((n, *v.shape[1:]), dtype=v.dtype)
+                    out[k][ix] = v
+        return _finish_alert_summary(out, r6, b, ids, n_groups, period, slo, n_bins, width)
+
+    def save_alert_summary(self, path: str, slo_s: float, rules: Any, by: Any = None, **kw: Any) -> dict[str, np.ndarray]:
+        """:meth:`BatchedResults.save_alert_summary` over every shard, added up and written once."""
+        kw.pop("per_tick", None)
+        return _save_alert_summary(self.alert_summary(slo_s, rules, by=by, **kw), str(path), by)
 
     def save_latency_histogram_summary(self, path: str, by: Any = None, **kw: Any) -> dict[str, np.ndarray]:
         """:meth:`BatchedResults.save_latency_histogram_summary` over every shard, added up and written once."""

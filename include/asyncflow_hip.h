@@ -1173,6 +1173,98 @@ typedef struct af_pairs {
 } af_pairs_t;
 int af_engine_summarize_pairs(af_engine_t* engine, const af_outputs_t* out, af_pairs_t* pairs);
 
+/* BURN-RATE ALERT RULES evaluated at every tick over ROLLING look-backs of the completions (asyncflow_amd/csrc/af_alerts.hpp):
+ * would my alert have fired during this outage, how many ticks after it began (the detection delay, as a distribution over the
+ * replicas of a grid point), does it fire under plain load, how long does it stay on and how often does it flap.  Every other
+ * analyzer puts requests into TUMBLING windows; a monitor evaluates a rule at every scrape over the last L ticks.  Reads
+ * outputs.clock and outputs.counts only; no simulation kernel runs.
+ * Per scenario s: m_s = min(counts[s][AF_CNT_COMPLETED], clock_capacity) stored rows (start_i, finish_i), t_s =
+ * min(counts[s][AF_CNT_TICKS], tick_capacity) sample rows, p = sample_period; sample row k is taken at (k + 1) p.
+ *     tick of a row    f_i = floor(finish_i / p): one f64 division rounded to nearest, then floor -- the rule of af_inflight_t.
+ *                      Row i is COUNTED iff start_i and finish_i are not NaN and 0 <= f_i < t_s; the comparison is made on the
+ *                      f64 quotient before any conversion to an integer: a huge or infinite quotient clips, it does not wrap.
+ *                      Nothing else is rejected: start < 0, finish < start and a latency below a tick are counted, because a
+ *                      monitor sees every completion
+ *     bad              lat_i = finish_i - start_i, one f64 subtraction;  bad_i iff lat_i > slo as f64 (slo = +inf: nothing is bad)
+ *     total[s][k]      = #{ counted i : f_i == k },  bad[s][k] = #{ counted bad i : f_i == k };  u32, whatever the order of the rows
+ *     prefix           PT[k] = sum over j <= k of total[j], PB likewise; u32 (at most m_s)
+ *     rolling          for a look-back of L >= 1 ticks  T_L[k] = PT[k] - (k >= L ? PT[k - L] : 0), B_L likewise: the first L - 1
+ *                      ticks are evaluated on the rows that exist.  A look-back reaches across window edges: it is a property of
+ *                      the tick
+ *     rule r           cond_r[k] = B_long[k] den > num T_long[k]  &&  B_short[k] den > num T_short[k]  &&  T_long[k] >= min_total,
+ *                      every product in u64;  firing_r[k] iff k + 1 >= hold_ticks and cond_r[j] for every j in (k - hold_ticks, k].
+ *                      No hysteresis: the alert resolves at the first tick whose condition fails
+ * Windows: tick_edges b[0] < ... < b[W] as in af_series_excursions_t, lo = min(b[w], t_s), hi = min(b[w + 1], t_s).  They choose
+ * where firing is REPORTED, never what a rule sees.  Cell (s, w) / (s, w, r), u32, AF_TICK_NONE for "no such tick", written for
+ * every scenario (a skipped one too):
+ *     count            hi - lo                                     fired          the firing ticks of [lo, hi)
+ *     episodes         the maximal runs of firing ticks, clipped at the window's edges: a run across an edge counts in both
+ *     longest          the length of the longest run               longest_start  the start of the earliest run of that length
+ *     first / last     the first / last firing tick;  last == hi - 1: still firing at the window's end
+ * An empty cell: count 0, the counts 0 and the ticks AF_TICK_NONE.
+ * Groups: group / AF_POOL_SKIP as in af_inflight_t.  Cell (g, w, r), integer atomics on arrays the call initialises itself:
+ *     members u32 = the members with hi > lo;  fired_members u32 = those with first != AF_TICK_NONE;  open_members u32 = those
+ *     with last == hi - 1;  fire_ticks u64 = the sum of fired;  fire_episodes u64 = the sum of episodes;  delay_hist u32
+ *     [n_bins]: a member with first != AF_TICK_NONE adds 1 to bin min((first - lo) / delay_width, n_bins - 1) -- integer
+ *     division, the last bin takes the rest.  With a window edge at an event's tick delay_hist is the detection-delay distribution
+ *     of the grid point's replicas.
+ * total / bad / firing: optional DEVICE [n_scenarios][tick_capacity]; firing has bit r set where rule r fires; rows k < t_s are
+ * written, rows at or past t_s are left untouched; written for skipped scenarios too.  Every output pointer may be NULL: that
+ * output is skipped.
+ * COMPLETED REQUESTS ONLY: a dropped request, and a request still in flight when the run ended, is in no row -- an alert on
+ * availability cannot be expressed, and the last ticks of a run see fewer completions.
+ * Every word is identical from run to run and does not depend on the batch a scenario sits in.
+ * Refused, no output touched: n_scenarios, n_groups, n_windows or n_rules == 0, n_rules > AF_MAX_ALERT_RULES, rules NULL,
+ * tick_edges NULL or not strictly increasing, a sample_period that is <= 0, NaN or infinite, slo NaN, a rule with short_ticks
+ * == 0, long_ticks < short_ticks, den == 0, num > den or hold_ticks == 0, a group id >= n_groups, outputs.clock or outputs.counts
+ * NULL, clock_capacity or tick_capacity == 0, with delay_hist n_bins == 0 or above AF_MAX_SERIES_HISTOGRAM_BINS or delay_width
+ * == 0 (AF_ERR_INVALID); n_groups * n_windows * n_rules >= 2^32 - 1, n_scenarios * n_windows * n_rules >= 2^32 - 1,
+ * tick_capacity >= 2^31 (AF_ERR_CAPACITY); a planning-only engine (AF_ERR_NO_DEVICE).
+ * outputs.clock must be 16-byte aligned: a row is read as one (start, finish) pair by a 16-byte load (any device allocation is).
+ * Scratch kept by the engine, shared with the other analyzers: 8 B per scenario and tick of tick_capacity for the prefix arrays,
+ * 4 B per edge, 24 B per rule.  Synchronous; the struct is written back. */
+#define AF_MAX_ALERT_RULES 32
+typedef struct af_alert_rule {
+    uint32_t long_ticks;         /* the long look-back, >= short_ticks */
+    uint32_t short_ticks;        /* the short look-back, >= 1; == long_ticks: a single-window rule */
+    uint32_t num;                /* the rule burns where the bad share is above num / den; num <= den */
+    uint32_t den;                /* >= 1 */
+    uint32_t min_total;          /* the fewest completions in the long look-back */
+    uint32_t hold_ticks;         /* the `for:` clause: consecutive evaluations, >= 1 */
+} af_alert_rule_t;
+typedef struct af_alerts {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;
+    uint32_t n_rules;            /* 1 .. AF_MAX_ALERT_RULES */
+    const uint32_t* group;       /* DEVICE [n_scenarios] group id per scenario (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* tick_edges;  /* HOST [n_windows + 1] strictly increasing tick indices */
+    const af_alert_rule_t* rules; /* HOST [n_rules] */
+    double sample_period;        /* p: seconds per tick, > 0 and finite */
+    double slo;                  /* a request is bad when its latency is above slo; not NaN */
+    uint32_t n_bins;             /* with delay_hist: 1 .. AF_MAX_SERIES_HISTOGRAM_BINS; ignored without */
+    uint32_t delay_width;        /* with delay_hist: ticks per bin, >= 1; ignored without */
+    uint32_t* count;             /* DEVICE [n_scenarios][n_windows] u32 out, optional */
+    uint32_t* fired;             /* DEVICE [n_scenarios][n_windows][n_rules] u32 out, optional */
+    uint32_t* episodes;          /* DEVICE [n_scenarios][n_windows][n_rules] u32 out, optional */
+    uint32_t* longest;           /* DEVICE [n_scenarios][n_windows][n_rules] u32 out, optional */
+    uint32_t* longest_start;     /* DEVICE [n_scenarios][n_windows][n_rules] u32 out, optional */
+    uint32_t* first;             /* DEVICE [n_scenarios][n_windows][n_rules] u32 out, optional */
+    uint32_t* last;              /* DEVICE [n_scenarios][n_windows][n_rules] u32 out, optional */
+    uint32_t* members;           /* DEVICE [n_groups][n_windows][n_rules] u32 out, optional */
+    uint32_t* fired_members;     /* DEVICE [n_groups][n_windows][n_rules] u32 out, optional */
+    uint32_t* open_members;      /* DEVICE [n_groups][n_windows][n_rules] u32 out, optional */
+    uint64_t* fire_ticks;        /* DEVICE [n_groups][n_windows][n_rules] u64 out, optional */
+    uint64_t* fire_episodes;     /* DEVICE [n_groups][n_windows][n_rules] u64 out, optional */
+    uint32_t* delay_hist;        /* DEVICE [n_groups][n_windows][n_rules][n_bins] u32 out, optional */
+    uint32_t* total;             /* DEVICE [n_scenarios][tick_capacity] u32 out, optional */
+    uint32_t* bad;               /* DEVICE [n_scenarios][tick_capacity] u32 out, optional */
+    uint32_t* firing;            /* DEVICE [n_scenarios][tick_capacity] u32 out, optional: bit r = rule r fires */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_alerts_t;
+int af_engine_summarize_alerts(af_engine_t* engine, const af_outputs_t* out, af_alerts_t* alerts);
+
 /* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
  * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
  * use, with the connections on an edge?  A cell is (group g, arrival window w, bin b of ONE sampled series at the row's tick).
