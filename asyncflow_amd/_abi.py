@@ -727,6 +727,7 @@ EXPORTED_SYMBOLS = (
     "af_abi_version",
     "af_probe_math",
     "af_probe_store",
+    "af_probe_scratch",
 )
 
 
@@ -818,4 +819,6 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_probe_math.restype = C.c_int
     lib.af_probe_store.argtypes = [C.c_int, C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(C.c_double)]
     lib.af_probe_store.restype = C.c_int
+    lib.af_probe_scratch.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32]
+    lib.af_probe_scratch.restype = C.c_int
     return lib

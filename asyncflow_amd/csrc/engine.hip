@@ -981,6 +981,8 @@ struct af_engine {
     size_t retry_cap = 0;
     unsigned char* d_pool = nullptr;           // af_engine_summarize_pooled's scratch (af_pooled.hpp: compacted latencies, histograms, ...)
     size_t pool_cap = 0;
+    bool pool_poisoned = false;                // af_probe_scratch was called: every later growth of the pool is filled with pool_word
+    uint32_t pool_word = 0;
     int wait_value_ok = -1;                    // hipDeviceAttributeCanUseStreamWaitValue (-1: not asked yet)
     uint64_t done_ptrs[2] = {0, 0};            // host copy of d_fb[kDoneWords ..] (a member: an asynchronous copy reads it)
     bool shared_instants_likely = false;
@@ -2750,7 +2752,20 @@ int af_engine_summarize(af_engine_t* e, const af_outputs_t* out, const af_summar
 }
 
 // The pooled analyzer's engine-owned scratch: grown on demand (the contents are lost then), kept until the engine is destroyed.
-static int pool_reserve(af_engine_t* e, size_t bytes) { return reserve_device((void**)&e->d_pool, e->pool_cap, bytes); }
+// (After af_probe_scratch a grown pool starts as that call's word instead of as whatever hipMalloc returns.)
+static int pool_fill(af_engine_t* e) {
+    const size_t words = e->pool_cap / 4u, tail = e->pool_cap % 4u;
+    if (words) HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)e->d_pool, (int)e->pool_word, words, e->stream));
+    if (tail) HIP_TRY(hipMemsetAsync(e->d_pool + words * 4u, (int)(e->pool_word & 0xFFu), tail, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return AF_OK;
+}
+static int pool_reserve(af_engine_t* e, size_t bytes) {
+    const size_t had = e->pool_cap;
+    if (int rc = reserve_device((void**)&e->d_pool, e->pool_cap, bytes)) return rc;
+    if (e->pool_poisoned && e->pool_cap != had) return pool_fill(e);
+    return AF_OK;
+}
 
 // the layout of a request's scratch: 256-byte aligned parts, one after the other
 struct ScratchLayout {
@@ -5287,6 +5302,27 @@ int af_probe_store(int device, int pattern, uint32_t n_waves, uint64_t bytes_per
     (void)hipEventDestroy(e1);
     (void)hipFree(buf);
     return AF_OK;
+}
+
+// Test hook: the scratch pool of `engine` becomes exactly `bytes` of `word` (0 bytes: no pool), and from now on every growth of
+// the pool starts as `word` too, so that an analyzer which relies on what its scratch held before gives itself away.
+int af_probe_scratch(af_engine_t* e, uint64_t bytes, uint32_t word) {
+    if (!e) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "a plan-only engine has no scratch");
+    HIP_TRY(hipSetDevice(e->device));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->pool_poisoned = true;
+    e->pool_word = word;
+    if ((size_t)bytes != e->pool_cap) {
+        if (e->d_pool) HIP_TRY(hipFree(e->d_pool));
+        e->d_pool = nullptr;
+        e->pool_cap = 0;
+        if (bytes) {
+            HIP_TRY(hipMalloc((void**)&e->d_pool, (size_t)bytes));
+            e->pool_cap = (size_t)bytes;
+        }
+    }
+    return pool_fill(e);
 }
 
 int af_probe_math(int device, int kind, uint64_t seed, const double* in, const double* in2, double* out, size_t n) {

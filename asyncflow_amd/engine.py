@@ -824,6 +824,12 @@ class Engine:
         _check(self._lib, self._lib.af_engine_gather(self._h, comm, int(world_size), C.byref(a), C.byref(b)), "af_engine_gather")
         return self.stats()
 
+    def probe_scratch(self, bytes: int, word: int) -> None:  # noqa: A002
+        """Test probe (``af_probe_scratch``): the engine's scratch pool becomes exactly ``bytes`` large and every 32-bit word
+        of it ``word``; every later growth of the pool starts as ``word`` too."""
+        _check(self._lib, self._lib.af_probe_scratch(self._h, C.c_uint64(int(bytes)), C.c_uint32(int(word) & 0xFFFFFFFF)),
+               "af_probe_scratch")
+
     def flow_reason(self) -> str:
         """'' when the stage-parallel kernel can run this plan, else why it always runs on the next-event kernels."""
         return (self._lib.af_engine_flow_reason(self._h) or b"").decode()

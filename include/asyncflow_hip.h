@@ -1391,6 +1391,14 @@ int af_probe_math(int device, int kind, uint64_t seed, const double* in, const d
  * ms_out (may be NULL): HIP-event time of the launch. */
 int af_probe_store(int device, int pattern, uint32_t n_waves, uint64_t bytes_per_wave, uint32_t lanes, double* ms_out);
 
+/* Test probe (device): the scratch pool of `engine`, from which every analyzer call takes its device scratch, becomes
+ * exactly `bytes` large (freed and allocated anew when its size differs, so it can shrink; 0 frees it) and every 32-bit
+ * word of it `word`.  From then on every growth of that engine's pool is filled with `word` before anything else uses it.
+ * No analyzer may rely on what its scratch held before the call: with this probe a test chooses what it held
+ * (tests/test_gpu_scratch_history.py).  An engine that never received the call works exactly as without the probe.
+ * AF_ERR_NO_DEVICE on a planning-only engine. */
+int af_probe_scratch(af_engine_t* engine, uint64_t bytes, uint32_t word);
+
 #ifdef __cplusplus
 }
 #endif
