@@ -670,6 +670,27 @@ class AfAlerts(C.Structure):
     ]
 
 
+OUTCOME_ROWS_TRUNCATED = 1   # AF_OUTCOME_ROWS_TRUNCATED
+OUTCOME_DEFICIT = 2          # AF_OUTCOME_DEFICIT
+
+
+class AfAlertOutcomes(C.Structure):
+    """``af_alert_outcomes_t``: the arrival rows, the client timeout and the outcome outputs of
+    ``af_engine_outcome_alerts``."""
+
+    _fields_ = [
+        ("times", C.c_void_p),
+        ("time_row", C.c_void_p),
+        ("n_time_rows", C.c_uint32),
+        ("draw_capacity", C.c_uint32),
+        ("timeout", C.c_double),
+        ("timeouts", C.c_void_p),
+        ("timed_out", C.c_void_p),
+        ("deficit", C.c_void_p),
+        ("flags", C.c_void_p),
+    ]
+
+
 class AfStateBins(C.Structure):
     """``af_state_bins_t``: the series, its binning and the sample period of ``af_engine_summarize_state_windows`` /
     ``af_engine_summarize_state_quantiles``."""
@@ -706,6 +727,7 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_latency_histogram",
     "af_engine_summarize_pairs",
     "af_engine_summarize_alerts",
+    "af_engine_outcome_alerts",
     "af_engine_summarize_state_windows",
     "af_engine_summarize_state_quantiles",
     "af_engine_run_summarized",
@@ -777,6 +799,8 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_pairs.restype = C.c_int
     lib.af_engine_summarize_alerts.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfAlerts)]
     lib.af_engine_summarize_alerts.restype = C.c_int
+    lib.af_engine_outcome_alerts.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfAlertOutcomes), C.POINTER(AfAlerts)]
+    lib.af_engine_outcome_alerts.restype = C.c_int
     lib.af_engine_summarize_state_windows.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfWindows)]
     lib.af_engine_summarize_state_windows.restype = C.c_int
     lib.af_engine_summarize_state_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfStateBins), C.POINTER(AfQuantiles)]

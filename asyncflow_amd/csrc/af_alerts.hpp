@@ -25,7 +25,7 @@
 //                    open_members (last == hi - 1), fire_ticks and fire_episodes (u64 sums), delay_hist: a member that fired
 //                    adds 1 to bin min((first - lo) / delay_width, n_bins - 1).
 // COMPLETED REQUESTS ONLY: a dropped request, and one still in flight when the run ended, is in no clock row -- an alert on
-// availability cannot be expressed, and the last ticks of a run see fewer completions.
+// availability needs af_alert_outcomes.hpp, and the last ticks of a run see fewer completions.
 //
 // KERNELS.
 //   af_alerts_prefix_kernel   a workgroup owns a scenario and walks its ticks in CHUNKS of kChunkTicks.  Per chunk every stored

@@ -70,6 +70,7 @@
 #include "af_arrival_counts.hpp"
 #include "af_inflight.hpp"
 #include "af_alerts.hpp"
+#include "af_alert_outcomes.hpp"
 #include "af_exemplars.hpp"
 #include "af_latency_histogram.hpp"
 #include "af_paired.hpp"
@@ -3618,9 +3619,8 @@ static_assert(afal::kSkip == AF_POOL_SKIP && afal::kNone == AF_TICK_NONE && afal
                   afal::kMaxBins == AF_MAX_SERIES_HISTOGRAM_BINS && sizeof(afal::Rule) == sizeof(af_alert_rule_t),
               "the kernel's constants are the header's");
 
-int af_engine_summarize_alerts(af_engine_t* e, const af_outputs_t* out, af_alerts_t* req) {
-    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
-    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+// What both alert calls refuse before anything is touched.
+static int alerts_check(const af_outputs_t* out, const af_alerts_t* req) {
     if (req->n_scenarios == 0 || req->n_groups == 0 || req->n_windows == 0 || req->n_rules == 0)
         return fail(AF_ERR_INVALID, "empty alerts request (n_scenarios, n_groups, n_windows and n_rules must be > 0)");
     if (req->n_rules > AF_MAX_ALERT_RULES) return fail(AF_ERR_INVALID, "alerts.n_rules must be 1 .. AF_MAX_ALERT_RULES (" + std::to_string(AF_MAX_ALERT_RULES) + ")");
@@ -3647,8 +3647,14 @@ int af_engine_summarize_alerts(af_engine_t* e, const af_outputs_t* out, af_alert
     if ((uint64_t)G * W >= 0xFFFFFFFFull || (uint64_t)G * W * R >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * n_windows * n_rules must be below 2^32 - 1");
     if ((uint64_t)n * W >= 0xFFFFFFFFull || (uint64_t)n * W * R >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * n_windows * n_rules must be below 2^32 - 1");
     if (cap >= 0x80000000u) return fail(AF_ERR_CAPACITY, "tick_capacity must be below 2^31");
-    const auto t0 = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(e->device));
+    return AF_OK;
+}
+
+// The checked request on the device: the group ids read back, the edges and the rules uploaded, the group cells initialised, the
+// prefix arrays by a workgroup per scenario -- from the completions (oc NULL) or from the outcomes --, then the evaluation.
+static int alerts_run(af_engine_t* e, const af_outputs_t* out, af_alerts_t* req, const af_alert_outcomes_t* oc) {
+    const uint32_t n = req->n_scenarios, G = req->n_groups, W = req->n_windows, R = req->n_rules, cap = out->tick_capacity;
+    const uint32_t B = req->delay_hist ? req->n_bins : 0u;
     std::vector<uint32_t> grp;
     if (int rc = read_groups(req->group, n, G, grp)) return rc;
     ScratchLayout lay;
@@ -3700,16 +3706,74 @@ int af_engine_summarize_alerts(af_engine_t* e, const af_outputs_t* out, af_alert
     a.fire_ticks = reinterpret_cast<unsigned long long*>(req->fire_ticks);
     a.fire_episodes = reinterpret_cast<unsigned long long*>(req->fire_episodes);
     a.delay_hist = req->delay_hist;
-    const size_t lds = (size_t)afal::kChunkTicks * 8u;
-    const void* fn = reinterpret_cast<const void*>(afal::af_alerts_prefix_kernel<WaveHip>);
-    // (set before every launch: the attribute is per device and engines of several devices run in threads of one process)
-    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    void* kargs[] = {&a};
-    HIP_TRY(hipLaunchKernel(fn, dim3(n), dim3(afal::kThreads), kargs, lds, st));
+    // (the attribute is set before every launch: it is per device and engines of several devices run in threads of one process)
+    if (oc) {
+        afao::OcArgs o{};
+        o.al = a;
+        o.times = oc->times;
+        o.time_row = oc->time_row;
+        o.draw_cap = oc->draw_capacity;
+        o.tau = oc->timeout;
+        o.timeouts = oc->timeouts;
+        o.timed_out = oc->timed_out;
+        o.deficit = oc->deficit;
+        o.flags = oc->flags;
+        const size_t lds = (size_t)afao::kChunkTicks * 12u;
+        const void* fn = reinterpret_cast<const void*>(afao::af_alert_outcomes_prefix_kernel<WaveHip>);
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        void* kargs[] = {&o};
+        HIP_TRY(hipLaunchKernel(fn, dim3(n), dim3(afao::kThreads), kargs, lds, st));
+    } else {
+        const size_t lds = (size_t)afal::kChunkTicks * 8u;
+        const void* fn = reinterpret_cast<const void*>(afal::af_alerts_prefix_kernel<WaveHip>);
+        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        void* kargs[] = {&a};
+        HIP_TRY(hipLaunchKernel(fn, dim3(n), dim3(afal::kThreads), kargs, lds, st));
+    }
     hipLaunchKernelGGL(afal::af_alerts_eval_kernel, dim3((n + afal::kEvalWaves - 1u) / afal::kEvalWaves), dim3(afal::kEvalThreads), 0, st, a);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(st));   // (the host edges and rules are read by the copies until here)
     req->scratch_bytes = e->pool_cap;
+    return AF_OK;
+}
+
+int af_engine_summarize_alerts(af_engine_t* e, const af_outputs_t* out, af_alerts_t* req) {
+    if (!e || !out || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (int rc = alerts_check(out, req)) return rc;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    if (int rc = alerts_run(e, out, req, nullptr)) return rc;
+    req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// Alert rules on request outcomes (af_alert_outcomes.hpp): af_engine_summarize_alerts's request and evaluation; the prefix arrays
+// come from the completions in time and the timeouts of the arrival rows.  The row ids are read back and checked on the host.
+static_assert(afao::kRowsTruncated == AF_OUTCOME_ROWS_TRUNCATED && afao::kDeficit == AF_OUTCOME_DEFICIT, "the kernel's flags are the header's");
+
+int af_engine_outcome_alerts(af_engine_t* e, const af_outputs_t* out, af_alert_outcomes_t* oc, af_alerts_t* req) {
+    if (!e || !out || !oc || !req) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (int rc = alerts_check(out, req)) return rc;
+    if (!oc->times) return fail(AF_ERR_INVALID, "alert_outcomes.times is required");
+    if (oc->draw_capacity == 0) return fail(AF_ERR_INVALID, "alert_outcomes.draw_capacity must be > 0 (pass the run's value)");
+    if (oc->n_time_rows == 0) return fail(AF_ERR_INVALID, "alert_outcomes.n_time_rows must be > 0");
+    if (!oc->time_row && oc->n_time_rows != req->n_scenarios)
+        return fail(AF_ERR_INVALID, "time_row NULL means scenario s reads row s: n_time_rows must be n_scenarios");
+    if (!(std::isfinite(oc->timeout) && oc->timeout > 0.0)) return fail(AF_ERR_INVALID, "alert_outcomes.timeout must be a finite number above 0");
+    if (oc->draw_capacity >= 0x80000000u) return fail(AF_ERR_CAPACITY, "draw_capacity must be below 2^31");
+    if (out->clock_capacity >= 0x80000000u) return fail(AF_ERR_CAPACITY, "clock_capacity must be below 2^31 (a tick's arrivals minus its rows is an i32)");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    if (oc->time_row) {
+        std::vector<uint32_t> ids(req->n_scenarios);
+        HIP_TRY(hipMemcpy(ids.data(), oc->time_row, ids.size() * 4u, hipMemcpyDeviceToHost));
+        for (uint32_t s = 0; s < req->n_scenarios; ++s)
+            if (ids[s] >= oc->n_time_rows)
+                return fail(AF_ERR_INVALID, "alert_outcomes.time_row out of range (scenario " + std::to_string(s) + ": " + std::to_string(ids[s]) + ", limit " + std::to_string(oc->n_time_rows) + ")");
+    }
+    if (int rc = alerts_run(e, out, req, oc)) return rc;
     req->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }

@@ -7,6 +7,7 @@ visible, :class:`EngineUnavailableError` is raised.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from pathlib import Path
 from typing import Any, Sequence
@@ -402,7 +403,8 @@ class Engine:
 
     def summarize_alerts(self, n: int, n_groups: int, tick_edges: Any, sample_period: float, slo: float, rules: Any, *,
                          clock_ptr: int, clock_capacity: int, tick_capacity: int, counts_ptr: int, group_ptr: int = 0,
-                         delay_bins: int = 0, delay_width: int = 1, ptrs: dict[str, int] | None = None) -> tuple[float, int]:
+                         delay_bins: int = 0, delay_width: int = 1, ptrs: dict[str, int] | None = None,
+                         outcomes: dict[str, Any] | None = None) -> tuple[float, int]:
         """Burn-rate alert rules per tick on the device (``af_engine_summarize_alerts``; the host definitions are
         :func:`asyncflow_amd.results.completion_ticks`, :func:`~asyncflow_amd.results.alert_firing`,
         :func:`~asyncflow_amd.results.alert_window_stats` and :func:`~asyncflow_amd.results.alert_cells`).  ``rules``: rows of
@@ -413,7 +415,14 @@ class Engine:
         ``delay_hist`` uint32 [n_groups, W, R, delay_bins]; ``total``, ``bad``, ``firing`` uint32 [n, tick_capacity] (rows at or
         past a scenario's ticks are left untouched).  ``tick_edges``: HOST uint32 tick indices, strictly increasing;
         ``group_ptr`` as in :meth:`summarize_pooled`.  COMPLETED requests only: dropped requests and requests still in flight
-        at the end of the run are in no clock row.  Returns the call's wall time in ms and the engine's scratch size in bytes."""
+        at the end of the run are in no clock row -- unless ``outcomes`` is given: then the call is
+        ``af_engine_outcome_alerts`` (host definition: :func:`asyncflow_amd.results.outcome_ticks`), a request without an
+        answer within ``timeout`` seconds is an error at ``arrival + timeout``, and ``total`` / ``bad`` hold completions in time
+        plus timeouts.  ``outcomes`` maps the fields of ``af_alert_outcomes_t``: ``times_ptr`` DEVICE float64 [n_time_rows,
+        draw_capacity] (as :meth:`summarize_arrivals` hands them out), ``time_row_ptr`` DEVICE uint32 [n] (0: scenario s reads
+        row s), ``n_time_rows``, ``draw_capacity``, ``timeout``, and the optional DEVICE outputs ``timeouts`` uint32 [n,
+        tick_capacity], ``timed_out``, ``deficit``, ``flags`` uint32 [n] (``_abi.OUTCOME_ROWS_TRUNCATED``,
+        ``_abi.OUTCOME_DEFICIT``).  Returns the call's wall time in ms and the engine's scratch size in bytes."""
         from .results import check_tick_edges
 
         b = check_tick_edges(tick_edges)
@@ -430,7 +439,20 @@ class Engine:
                             b.ctypes.data_as(C.POINTER(C.c_uint32)), rows.ctypes.data_as(C.POINTER(_abi.AfAlertRule)),
                             float(sample_period), float(slo), int(delay_bins), int(delay_width),
                             *(C.c_void_p(p.get(k) or None) for k in names), 0.0, 0)
-        _check(self._lib, self._lib.af_engine_summarize_alerts(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_alerts")
+        if outcomes is None:
+            _check(self._lib, self._lib.af_engine_summarize_alerts(self._h, C.byref(out), C.byref(req)), "af_engine_summarize_alerts")
+            return float(req.elapsed_ms), int(req.scratch_bytes)
+        oc = dict(outcomes)
+        keys = ("times_ptr", "time_row_ptr", "n_time_rows", "draw_capacity", "timeout", "timeouts", "timed_out", "deficit", "flags")
+        unknown = set(oc) - set(keys)
+        if unknown:
+            msg = f"unknown alert outcome fields {sorted(unknown)}"
+            raise ValueError(msg)
+        ocs = _abi.AfAlertOutcomes(C.c_void_p(oc.get("times_ptr") or None), C.c_void_p(oc.get("time_row_ptr") or None),
+                                   int(oc.get("n_time_rows", 0)), int(oc.get("draw_capacity", 0)), float(oc.get("timeout", math.nan)),
+                                   *(C.c_void_p(oc.get(k) or None) for k in ("timeouts", "timed_out", "deficit", "flags")))
+        _check(self._lib, self._lib.af_engine_outcome_alerts(self._h, C.byref(out), C.byref(ocs), C.byref(req)),
+               "af_engine_outcome_alerts")
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
     def summarize_exemplars(self, n: int, n_groups: int, k: int, *, edges: Any = None, window_of: str = "finish", clock_ptr: int,

@@ -656,6 +656,87 @@ def scenario_alerts(rows: Any, ticks: int, period: float, slo: float, rules: Any
     return out
 
 
+def check_timeout(timeout: Any) -> float:
+    """The client timeout in seconds as a float, or ValueError: it must be a finite number above 0."""
+    try:
+        tau = float(timeout)
+    except (TypeError, ValueError):
+        tau = math.nan
+    if isinstance(timeout, bool) or not (math.isfinite(tau) and tau > 0.0):
+        msg = f"timeout must be a finite number of seconds above 0, not {timeout!r}"
+        raise ValueError(msg)
+    return tau
+
+
+def outcome_ticks(rows: Any, arrivals: Any, ticks: int, period: float, slo: float, timeout: float) -> dict[str, Any]:
+    """Request OUTCOMES per tick of one scenario under a client timeout: the first half of the host definition
+    ``af_engine_outcome_alerts`` is held to, word for word.  ``rows``: float64 [m, 2], the stored ``(start, finish)``
+    rows; ``arrivals``: the scenario's arrival row, ascending (ValueError otherwise, as :func:`arrival_window_counts`), entries
+    that are not finite (the ``+inf`` behind the last arrival) are no arrivals; ``ticks``: the sample rows ``t_s``; ``p =
+    period``; ``tau = timeout``, finite and > 0; ``slo`` as in :func:`completion_ticks` (not NaN; ``+inf`` allowed).
+
+    The tick of a time ``x`` is ``q(x) = floor(x / p)``: one float64 division, then floor.  It is in range iff ``0 <= q < t_s``,
+    compared on the float64 quotient (the rule of :func:`completion_ticks`).
+
+    - IN-TIME row: ``start_i`` and ``finish_i`` are not NaN and ``lat_i = finish_i - start_i <= tau``: one float64 subtraction,
+      a NaN latency is not in time.  A row that is not in time is never seen as a completion: the client gave up at ``start + tau``.
+    - ``C[k]`` = the number of in-time rows with ``q(finish_i) == k``;  ``Cbad[k]`` = those of ``C[k]`` with ``lat_i > slo``.
+    - ``G[k]`` = the number of in-time rows with ``q(start_i + tau) == k``: one float64 addition, then the tick rule.
+    - ``A[k]`` = the number of arrivals ``a`` (finite) with ``q(a + tau) == k``: the same operations.
+    - ``timeouts[k] = max(A[k] - G[k], 0)``;  ``deficit = sum_k max(G[k] - A[k], 0)``;  ``timed_out = sum_k timeouts[k]``.
+    - ``total[k] = C[k] + timeouts[k]``;  ``bad[k] = Cbad[k] + timeouts[k]``.
+
+    ``deficit`` is 0 whenever the arrival row is the run's own (every stored ``start`` is, bit for bit, one of its arrivals, so a
+    row and its arrival land on the same timeout tick); a deficit above 0 says the arrivals do not belong to these rows; the
+    result is still defined.  Returns ``total``, ``bad``, ``timeouts``, ``completions`` (= C) uint32 [t_s] and the ints
+    ``deficit`` and ``timed_out``."""
+    p, t_s, s, tau = float(period), int(ticks), float(slo), check_timeout(timeout)
+    if not (np.isfinite(p) and p > 0.0):
+        msg = f"period must be a finite number above 0, not {period!r}"
+        raise ValueError(msg)
+    if t_s != ticks or not 0 <= t_s < 2 ** 31:
+        msg = f"ticks must be a whole number in [0, 2^31), not {ticks!r}"
+        raise ValueError(msg)
+    if math.isnan(s):
+        msg = "slo must not be NaN"
+        raise ValueError(msg)
+    a = np.asarray(arrivals, dtype=np.float64).reshape(-1)
+    if a.shape[0] > 1 and not (a[1:] >= a[:-1]).all():
+        msg = "arrival times must be ascending"
+        raise ValueError(msg)
+    ck = np.asarray(rows, dtype=np.float64).reshape(-1, 2)
+    start, finish = ck[:, 0], ck[:, 1]
+
+    def per_tick(x: np.ndarray, keep: np.ndarray) -> np.ndarray:
+        q = np.floor(x / p)
+        ok = keep & (q >= 0.0) & (q < float(t_s))
+        return np.bincount(q[ok].astype(np.int64), minlength=t_s)[:t_s].astype(np.int64)
+
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        lat = finish - start
+        in_time = ~np.isnan(start) & ~np.isnan(finish) & (lat <= tau)
+        c = per_tick(finish, in_time)
+        c_bad = per_tick(finish, in_time & (lat > s))
+        g = per_tick(start + tau, in_time)
+        arr = per_tick(a + tau, np.isfinite(a))
+    timeouts = np.maximum(arr - g, 0)
+    return {"total": (c + timeouts).astype(np.uint32), "bad": (c_bad + timeouts).astype(np.uint32), "timeouts": timeouts.astype(np.uint32),
+            "completions": c.astype(np.uint32), "deficit": int(np.maximum(g - arr, 0).sum()), "timed_out": int(timeouts.sum())}
+
+
+def scenario_outcome_alerts(rows: Any, arrivals: Any, ticks: int, period: float, slo: float, timeout: float, rules: Any,
+                            tick_edges: Any) -> dict[str, Any]:
+    """One scenario through the whole host definition of ``af_engine_outcome_alerts``: :func:`outcome_ticks`, then
+    :func:`alert_firing` and :func:`alert_window_stats` on its ``total`` / ``bad``, in one dict (``rules`` in ticks, or in
+    seconds against ``period``)."""
+    r6 = check_alert_rules(rules, period)
+    out = outcome_ticks(rows, arrivals, ticks, period, slo, timeout)
+    out.update(alert_firing(out["total"], out["bad"], r6))
+    out.update(alert_window_stats(out["firing"], tick_edges))
+    out["rules"] = r6
+    return out
+
+
 def _finish_alert_summary(out: dict[str, Any], r6: np.ndarray, b: np.ndarray, ids: np.ndarray, n_groups: int, period: float,
                           slo: float, delay_bins: int, delay_width: int) -> dict[str, Any]:
     """The derived columns of ``alert_summary`` from the raw device words (int64; a tick that does not exist is -1)."""
@@ -704,6 +785,8 @@ def _save_alert_summary(summ: dict[str, Any], path: str, by: Any) -> dict[str, n
         cols["alert_delay_edges_s"] = np.asarray(summ["delay_edges_s"], dtype=np.float64)
     cols["alert_rule_ticks"] = np.asarray(summ["rule_ticks"], dtype=np.float64).reshape(-1)
     cols["alert_slo_s"] = np.asarray([summ["slo_s"]], dtype=np.float64)
+    if "timeout_s" in summ:
+        cols["alert_timeout_s"] = np.asarray([summ["timeout_s"]], dtype=np.float64)
     cols["alert_tick_edges"] = np.asarray(summ["tick_edges"], dtype=np.float64)
     cols["alert_times"] = np.asarray(summ["times"], dtype=np.float64)
     _write_columns(path, cols, n_groups)
@@ -2788,16 +2871,24 @@ class ScenarioResults:
         return times, vals.astype(np.float64).tolist()
 
     def get_alerts(self, slo_s: float, rules: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
-                   tick_edges: Any = None) -> dict[str, np.ndarray]:
+                   tick_edges: Any = None, timeout_s: float | None = None) -> dict[str, np.ndarray]:
         """Burn-rate alert rules on this scenario's clock rows, through the host definition (:func:`scenario_alerts`):
         ``total`` / ``bad`` uint32 [ticks], ``cond`` / ``firing`` bool [R, ticks] and the window cells of
         :func:`alert_window_stats` (``fired``, ``episodes``, ``longest``, ``longest_start``, ``first``, ``last`` int64 [W, R], -1:
-        no such tick).  ``rules`` and the windows as in :meth:`BatchedResults.alert_summary`.  COMPLETED requests only."""
+        no such tick).  ``rules`` and the windows as in :meth:`BatchedResults.alert_summary`.  COMPLETED requests only -- unless
+        ``timeout_s`` is given: then a request without an answer within ``timeout_s`` is an error at ``arrival + timeout_s``
+        (:func:`scenario_outcome_alerts` on the scenario's arrival times, with ``timeouts``, ``completions``, ``deficit`` and
+        ``timed_out`` in the result; only for a scenario taken from a run's results)."""
         ticks = min(int(self.counts[_abi.CNT_TICKS]), max(int(self._plan.tick_count), 0))
         if self._samples is not None:
             ticks = min(ticks, int(self._samples.shape[1]))
         b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, self._plan.sample_period, self._plan.tick_count)
-        return scenario_alerts(self.rqs_clock, ticks, self._plan.sample_period, slo_s, rules, b)
+        if timeout_s is None:
+            return scenario_alerts(self.rqs_clock, ticks, self._plan.sample_period, slo_s, rules, b)
+        if self._arrival_times is None:
+            msg = "this ScenarioResults does not come from a run: it has no arrival times"
+            raise ValueError(msg)
+        return scenario_outcome_alerts(self.rqs_clock, self._arrival_times(), ticks, self._plan.sample_period, slo_s, timeout_s, rules, b)
 
     def get_slowest_requests(self, k: int = 16, window_s: float | None = None, edges: Any = None, window_of: str = "finish") -> dict[str, Any]:
         """The ``k`` slowest requests of the scenario, per time window (``window_s`` seconds or explicit ``edges``, by
@@ -3601,10 +3692,28 @@ class BatchedResults:
                 "edges": edges, "tick_edges": b, "replicas": inf["replicas"]}
 
     # ---- burn-rate alert rules per tick over rolling look-backs ---------------------------------------------------
+    def _outcome_rows(self, eng: Any, dev: Any) -> tuple[Any, Any, int, int]:
+        """The arrival rows of the run on the device, regenerated once per distinct (seed, generator columns) with
+        ``af_engine_summarize_arrivals``: ``times`` float64 [rows, draw_capacity], ``time_row`` uint32 [n] (scenarios that were sent
+        the same requests share a row), the number of rows and the draw capacity."""
+        import torch
+
+        seeds, cols, cap = self._arrival_sweep(None)
+        key = np.stack([seeds.view(np.uint64)] + [np.ascontiguousarray(c[2], dtype=np.float64).view(np.uint64) for c in cols], axis=1)
+        _, first, time_row = np.unique(key, axis=0, return_index=True, return_inverse=True)
+        seeds, cols, cap = self._arrival_sweep(first)
+        n_rows = int(first.shape[0])
+        times = torch.empty((n_rows, cap), dtype=torch.float64, device=dev)
+        arr = torch.empty((n_rows, 1), dtype=torch.int64, device=dev)
+        eng.summarize_arrivals(seeds, cols, n_rows, np.asarray([0.0, max(float(self.plan.total_time), 1.0)]),
+                               draw_capacity=cap, arrivals_ptr=arr.data_ptr(), times_ptr=times.data_ptr())
+        tr = torch.from_numpy(np.ascontiguousarray(time_row.reshape(-1)).astype(np.uint32).view(np.int32)).to(dev)
+        return times, tr, n_rows, cap
+
     def _alert_call(self, b: np.ndarray, ids: np.ndarray, n_groups: int, slo: float, r6: np.ndarray, delay_bins: int,
-                    delay_width: int, per_tick: bool) -> dict[str, Any]:
-        """One ``af_engine_summarize_alerts`` over resolved tick edges, group ids and rules in ticks: the raw outputs on the
-        host, int64 (a tick that does not exist: -1)."""
+                    delay_width: int, per_tick: bool, timeout: float | None = None) -> dict[str, Any]:
+        """One ``af_engine_summarize_alerts`` -- with ``timeout`` one ``af_engine_outcome_alerts`` -- over resolved tick
+        edges, group ids and rules in ticks: the raw outputs on the host, int64 (a tick that does not exist: -1)."""
         import torch
 
         self._require_clock()
@@ -3621,23 +3730,38 @@ class BatchedResults:
             for k in ("total", "bad", "firing"):
                 t[k] = torch.zeros((n, cap), dtype=torch.int32, device=dev)   # (rows at or past t_s are not written)
         grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32).view(np.int32)).to(dev)
+        oc: dict[str, Any] | None = None
+        extra: dict[str, Any] = {}
+        if timeout is not None:
+            times, tr, n_rows, draw_cap = self._outcome_rows(eng, dev)
+            extra = {k: torch.empty((n,), dtype=torch.int32, device=dev) for k in ("timed_out", "deficit", "flags")}
+            if per_tick:
+                extra["timeouts"] = torch.zeros((n, cap), dtype=torch.int32, device=dev)
+            oc = {"times_ptr": times.data_ptr(), "time_row_ptr": tr.data_ptr(), "n_time_rows": n_rows, "draw_capacity": draw_cap,
+                  "timeout": float(timeout), **{k: v.data_ptr() for k, v in extra.items()}}
         torch.cuda.synchronize(dev)
         ms, scratch = eng.summarize_alerts(
             n, n_groups, b, self.plan.sample_period, slo, r6, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
             tick_capacity=cap, counts_ptr=self._counts_t.data_ptr(), group_ptr=grp.data_ptr(), delay_bins=delay_bins,
-            delay_width=delay_width, ptrs={k: v.data_ptr() for k, v in t.items()})
+            delay_width=delay_width, ptrs={k: v.data_ptr() for k, v in t.items()}, outcomes=oc)
         out: dict[str, Any] = {}
-        for k, v in t.items():
+        for k, v in {**t, **extra}.items():
             a = v.cpu().numpy()
             if a.dtype == np.int32 and k not in ("longest_start", "first", "last"):
                 a = a.view(np.uint32)
             out[k] = a.astype(np.int64) if k != "firing" else a                # (0xFFFFFFFF is -1; a tick is below 2^31)
+        if timeout is not None:
+            cut = np.flatnonzero(out["flags"] & _abi.OUTCOME_ROWS_TRUNCATED)
+            if cut.shape[0]:
+                msg = (f"scenario {int(cut[0])} completed more requests than the clock rows hold: the missing rows would be counted as "
+                       "timeouts (run with a larger clock capacity)")
+                raise ValueError(msg)
         out.update(alerts_ms=ms, scratch_bytes=scratch)
         return out
 
     def alert_summary(self, slo_s: float, rules: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
                       tick_edges: Any = None, by: Any = None, delay_bins: int = 0, delay_width_s: float | None = None,
-                      per_tick: bool = False) -> dict[str, Any]:
+                      per_tick: bool = False, timeout_s: float | None = None) -> dict[str, Any]:
         """WOULD MY ALERT HAVE FIRED: burn-rate alert rules evaluated at every tick over ROLLING look-backs of the completions,
         as a monitoring system evaluates them at every scrape -- during an injected outage, how many seconds after it began
         (the detection delay, as a distribution over the replicas of a grid point), under plain load (a false alarm), for how
@@ -3661,18 +3785,30 @@ class BatchedResults:
         brackets off them).  ``per_tick=True`` adds ``total``, ``bad`` int64 and ``firing`` uint32 (bit r: rule r fires) [n,
         tick capacity], 0 at and past a scenario's ticks.  And ``rules`` (echoed as ticks and fractions), ``rule_ticks`` [R, 6],
         ``slo_s``, ``tick_edges``, ``times``, ``replicas`` [G], ``alerts_ms``, ``scratch_bytes``.
-        COMPLETED requests only: a dropped request and one still in flight when the run ended are in no clock row, so an alert
-        on availability cannot be expressed, and the last ticks of a run see fewer completions."""
+        Without ``timeout_s`` COMPLETED requests only: a dropped request and one still in flight when the run ended are in no
+        clock row, and the last ticks of a run see fewer completions.
+
+        ``timeout_s`` (seconds, finite and > 0) is the CLIENT TIMEOUT that makes drops alertable: a request sent at ``a`` without
+        an answer by ``a + timeout_s`` is an error at ``a + timeout_s``, so every arrival produces exactly one event, the bad
+        share has the arrivals as its denominator, and ``slo_s=inf`` is a pure availability alert
+        (``af_engine_outcome_alerts``; every word equal to :func:`outcome_ticks` and the functions above).  The arrival
+        rows are regenerated on the device once per distinct (seed, generator columns); nothing is simulated.  The summary gains
+        ``timed_out`` and ``deficit`` int64 [n] (``deficit`` is 0 for a run's own rows), ``flags`` [n], ``timeout_s`` and, with
+        ``per_tick``, ``timeouts`` [n, tick capacity]; ``total`` / ``bad`` are then completions in time plus timeouts.
+        ValueError names the first scenario whose clock rows were cut: its missing rows would count as timeouts."""
         period = float(self.plan.sample_period)
         slo = float(slo_s)
         if math.isnan(slo):
             msg = "slo_s must not be NaN"
             raise ValueError(msg)
+        tau = None if timeout_s is None else check_timeout(timeout_s)
         r6 = check_alert_rules(rules, period)
         n_bins, width = _alert_delay_bins(delay_bins, delay_width_s, period)
         b = self._series_tick_edges(window_s, ticks_per_window, tick_edges)
         ids, n_groups = self._window_groups(by)
-        out = self._alert_call(b, ids, n_groups, slo, r6, n_bins, width, bool(per_tick))
+        out = self._alert_call(b, ids, n_groups, slo, r6, n_bins, width, bool(per_tick), tau)
+        if tau is not None:
+            out["timeout_s"] = tau
         return _finish_alert_summary(out, r6, b, ids, n_groups, period, slo, n_bins, width)
 
     def save_alert_summary(self, path: str, slo_s: float, rules: Any, by: Any = None, **kw: Any) -> dict[str, np.ndarray]:
@@ -3680,7 +3816,7 @@ class BatchedResults:
         Sweep), ``replicas`` and the [G, W, R] columns ``alert_members``, ``alert_fired_members``, ``alert_open_members``,
         ``alert_fire_ticks``, ``alert_fire_episodes``, ``alert_fired_share`` and, with ``delay_bins``, ``alert_delay_hist`` [G,
         W, R, bins] with ``alert_delay_edges_s``; ``alert_rule_ticks`` (R x 6, flat), ``alert_slo_s``, ``alert_tick_edges`` and
-        ``alert_times`` are per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
+        ``alert_times`` (with ``timeout_s`` also ``alert_timeout_s``) are per-file vectors.  ``.npz`` or ``.parquet``; :func:`load_summary` reads it back."""
         kw.pop("per_tick", None)
         return _save_alert_summary(self.alert_summary(slo_s, rules, by=by, **kw), str(path), by)
 
@@ -5799,16 +5935,18 @@ class ShardedResults:
 
     def alert_summary(self, slo_s: float, rules: Any, window_s: float | None = None, *, ticks_per_window: int | None = None,
                       tick_edges: Any = None, by: Any = None, delay_bins: int = 0, delay_width_s: float | None = None,
-                      per_tick: bool = False) -> dict[str, Any]:
+                      per_tick: bool = False, timeout_s: float | None = None) -> dict[str, Any]:
         """:meth:`BatchedResults.alert_summary` of a sweep run on several devices: the group cells are integer sums, so every
         shard adds its members' part of the GLOBAL groups on its own device (``by`` is resolved once over the whole sweep, as
         in :meth:`latency_histogram_summary`) and the parts are added; the per-replica arrays go behind the indices of the
-        original sweep.  Same arguments, same result as the unsharded run."""
+        original sweep.  With ``timeout_s`` every shard regenerates its own arrival rows.  Same arguments, same result as the
+        unsharded run."""
         period = float(self.plan.sample_period)
         slo = float(slo_s)
         if math.isnan(slo):
             msg = "slo_s must not be NaN"
             raise ValueError(msg)
+        tau = None if timeout_s is None else check_timeout(timeout_s)
         r6 = check_alert_rules(rules, period)
         n_bins, width = _alert_delay_bins(delay_bins, delay_width_s, period)
         b = _resolve_tick_edges(window_s, ticks_per_window, tick_edges, period, self.plan.tick_count)
@@ -5817,7 +5955,7 @@ class ShardedResults:
         out: dict[str, Any] = {"alerts_ms": 0.0, "scratch_bytes": 0}
         for shard, ix in zip(self.shards, self.index):
             ix = np.asarray(ix)
-            part = shard._alert_call(b, ids[ix], n_groups, slo, r6, n_bins, width, bool(per_tick))  # noqa: SLF001
+            part = shard._alert_call(b, ids[ix], n_groups, slo, r6, n_bins, width, bool(per_tick), tau)  # noqa: SLF001
             out["alerts_ms"] += part.pop("alerts_ms")
             out["scratch_bytes"] = max(out["scratch_bytes"], part.pop("scratch_bytes"))
             for k, v in part.items():
@@ -5827,6 +5965,8 @@ class ShardedResults:
                     if k not in out:
                         out[k] = np.zeros((n, *v.shape[1:]), dtype=v.dtype)
                     out[k][ix] = v
+        if tau is not None:
+            out["timeout_s"] = tau
         return _finish_alert_summary(out, r6, b, ids, n_groups, period, slo, n_bins, width)
 
     def save_alert_summary(self, path: str, slo_s: float, rules: Any, by: Any = None, **kw: Any) -> dict[str, np.ndarray]:

@@ -1212,7 +1212,7 @@ int af_engine_summarize_pairs(af_engine_t* engine, const af_outputs_t* out, af_p
  * written, rows at or past t_s are left untouched; written for skipped scenarios too.  Every output pointer may be NULL: that
  * output is skipped.
  * COMPLETED REQUESTS ONLY: a dropped request, and a request still in flight when the run ended, is in no row -- an alert on
- * availability cannot be expressed, and the last ticks of a run see fewer completions.
+ * availability needs af_engine_outcome_alerts (below), and the last ticks of a run see fewer completions.
  * Every word is identical from run to run and does not depend on the batch a scenario sits in.
  * Refused, no output touched: n_scenarios, n_groups, n_windows or n_rules == 0, n_rules > AF_MAX_ALERT_RULES, rules NULL,
  * tick_edges NULL or not strictly increasing, a sample_period that is <= 0, NaN or infinite, slo NaN, a rule with short_ticks
@@ -1264,6 +1264,55 @@ typedef struct af_alerts {
     uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
 } af_alerts_t;
 int af_engine_summarize_alerts(af_engine_t* engine, const af_outputs_t* out, af_alerts_t* alerts);
+
+/* ALERT RULES ON REQUEST OUTCOMES (asyncflow_amd/csrc/af_alert_outcomes.hpp): a CLIENT TIMEOUT makes a request that never came back
+ * visible to the monitor.  A request sent at a that has no answer by a + timeout is an error at a + timeout, so every arrival
+ * produces exactly one event, a completion or a timeout: the bad share has the arrivals as its denominator, and slo = +inf is a
+ * pure availability alert.  At tick k a live monitor also knows only the completions so far and the timeouts of the requests sent
+ * before k p - timeout.  Reads outputs.clock, outputs.counts and the arrival rows; no simulation kernel runs.
+ * Scenario s has m_s stored rows (start_i, finish_i), t_s sample rows and p = sample_period, all as in af_alerts_t; an arrival row
+ * a[0 .. draw_capacity), row time_row[s] of `times`, ascending with +inf behind the last arrival; tau = timeout, finite and > 0;
+ * slo as in af_alerts_t: not NaN, +inf allowed.
+ *     tick of a time   q(x) = floor(x / p): one f64 division, then floor.  It is in range iff 0 <= q < t_s, compared on the f64
+ *                      quotient (af_alerts_t's rule)
+ *     in-time row      start_i and finish_i are not NaN and lat_i = finish_i - start_i <= tau: one f64 subtraction, a NaN latency
+ *                      is not in time.  A row that is not in time is never seen as a completion: the client gave up at start + tau
+ *     C[k]             = #{ in-time rows with q(finish_i) == k }
+ *     Cbad[k]          = those of C[k] with lat_i > slo
+ *     G[k]             = #{ in-time rows with q(start_i + tau) == k }: one f64 addition, then the tick rule
+ *     A[k]             = #{ j < draw_capacity : a[j] finite and q(a[j] + tau) == k }: the same operations
+ *     timeouts[k]      = max(A[k] - G[k], 0)
+ *     deficit[s]       = sum over k of max(G[k] - A[k], 0)
+ *     timed_out[s]     = sum over k of timeouts[k]
+ *     total[k]         = C[k] + timeouts[k]
+ *     bad[k]           = Cbad[k] + timeouts[k]
+ * deficit is 0 whenever the arrival row is the run's own (every stored start is, bit for bit, one of its arrivals, so a row and its
+ * arrival land on the same timeout tick); a deficit above 0 says the arrival rows do not belong to these clock rows.  The result
+ * is still defined.  Prefix sums, rolling look-backs, rules, windows, cells, group cells and delay_hist are exactly
+ * af_engine_summarize_alerts's on these total / bad (alerts->total / bad receive them).  All per-tick values are u32.
+ * The arrival rows are not checked for order on the device: a row that is not ascending gives meaningless counts and nothing worse.
+ * flags[s]: AF_OUTCOME_ROWS_TRUNCATED when counts[s][AF_CNT_COMPLETED] > clock_capacity (rows are missing and would be miscounted
+ * as timeouts), AF_OUTCOME_DEFICIT when deficit[s] > 0.  timeouts: rows k < t_s are written.
+ * Refused, no output touched: everything af_engine_summarize_alerts refuses, and times NULL, draw_capacity or n_time_rows == 0,
+ * time_row NULL with n_time_rows != n_scenarios, a time_row >= n_time_rows -- the ids are read back and checked on the host --, a
+ * timeout that is NaN, infinite or <= 0 (AF_ERR_INVALID); draw_capacity or clock_capacity >= 2^31 (AF_ERR_CAPACITY).
+ * Scratch as af_engine_summarize_alerts.  Synchronous; elapsed_ms and scratch_bytes of `alerts` are written back. */
+#define AF_OUTCOME_ROWS_TRUNCATED 1u
+#define AF_OUTCOME_DEFICIT 2u
+typedef struct af_alert_outcomes {
+    const double* times;         /* DEVICE [n_time_rows][draw_capacity], as af_arrivals_t.times hands them out */
+    const uint32_t* time_row;    /* DEVICE [n_scenarios]; NULL: scenario s reads row s (n_time_rows == n_scenarios) */
+    uint32_t n_time_rows;
+    uint32_t draw_capacity;
+    double timeout;              /* finite, > 0 */
+    uint32_t* timeouts;          /* DEVICE [n_scenarios][tick_capacity] u32 out, optional */
+    uint32_t* timed_out;         /* DEVICE [n_scenarios] u32 out, optional */
+    uint32_t* deficit;           /* DEVICE [n_scenarios] u32 out, optional */
+    uint32_t* flags;             /* DEVICE [n_scenarios] u32 out, optional */
+} af_alert_outcomes_t;
+/* (Not an af_engine_summarize_* name on purpose: the rules, cells and scratch are af_engine_summarize_alerts's; what is new is
+ * where total / bad come from.) */
+int af_engine_outcome_alerts(af_engine_t* engine, const af_outputs_t* out, af_alert_outcomes_t* outcomes, af_alerts_t* alerts);
 
 /* Latency by the STATE A REQUEST MET ON ARRIVAL (asyncflow_amd/csrc/af_state.hpp): how slow were the requests that arrived while
  * the ready queue, the IO sleep set, the RAM or an edge was at level b -- does p95 rise with the queue at a server, with RAM in
