@@ -197,7 +197,22 @@ struct FlowArgs {
 // FEAT_PROF: where a wave's time goes (measurement builds only: AF_FLOW_PROF)
 enum : uint32_t { PROF_SETUP, PROF_GEN, PROF_SELECT, PROF_SERIES_RECV, PROF_STATION, PROF_SERVERS, PROF_SERVER_SERIES, PROF_DRAW, PROF_SEND_SERIES,
                   PROF_APPEND, PROF_COMPLETE, PROF_FLUSH, PROF_PAR_SETUP, PROF_PAR_WALK, PROF_PAR_RANK, PROF_PAR_FINAL,
-                  PROF_N_PAR_ROUNDS /* counts, not cycles */, PROF_N_PAR_ITERS, PROF_N_PAR_LANES, PROF_N_WALKED_ROUNDS, PROF_PAR_STANDING, PROF_PAR_COMMIT_WALK, kProfSections = 22u };
+                  PROF_N_PAR_ROUNDS /* counts, not cycles */, PROF_N_PAR_ITERS, PROF_N_PAR_LANES, PROF_N_WALKED_ROUNDS, PROF_PAR_STANDING, PROF_PAR_COMMIT_WALK,
+                  PROF_N_SELECT_WINDOW /* counts: select() calls ranked by the lane window / that fell back to the bucket rank */, PROF_N_SELECT_BUCKET, kProfSections = 24u };
+
+// select()'s lane window (Flow::select_regs): an entry is compared with the AF_SELECT_WINDOW entries in front of it in list order
+// where a prefix maximum proves that nothing further away is out of order.  0: always the bucket rank.
+// (The width is measured, not reasoned -- host emulator, LB-2 at its own parameters: the proof holds in 96.4 / 99.7 / 100 / 100 %
+// of calls at 4 / 6 / 8 / 12 lanes; on the device, config 2: 41.80 ms per step at 6, 42.75 at 8, 43.12 without the window --
+// profiles/r08/ab_select_window.txt.  The plan-specialised builds switch it off per spec: engine.hip, flow_jit_spec_string.)
+#ifndef AF_SELECT_WINDOW
+#define AF_SELECT_WINDOW 6
+#endif
+#if !defined(__HIPCC__)
+// host builds only: select_regs calls ranked by the window / handed on to the bucket rank (of the instantiations that have the
+// window at all), for the stand-alone programs that drive the selection on crafted lists
+inline unsigned long long g_select_window_calls[2] = {0ull, 0ull};
+#endif
 
 // ---- the algorithm, written against a wave backend W ---------------------------------------------
 //   W::lane()                       0..63
@@ -211,6 +226,8 @@ enum : uint32_t { PROF_SETUP, PROF_GEN, PROF_SELECT, PROF_SERIES_RECV, PROF_STAT
 //   W::rcp(x)                       ~1/x (only ever used where the exact value does not matter)
 //   W::scan_incl_u32(v)             inclusive prefix sum over the lanes (DPP row shifts / broadcasts on the device)
 //   W::bcast32 / bcast64(v, lane)   value of a WAVE-UNIFORM lane (v_readlane on the device)
+//   device only (select()'s lane window; host builds make them from shfl32): W::scan_incl_max_u32(v) inclusive prefix maximum,
+//                                   W::lane_below_u32(v) value of lane - 1 (0 in lane 0), W::my_bit(mask) bit `lane` of a wave-uniform mask
 // Every W:: call is made by all 64 lanes from wave-uniform control flow.
 // IPL = list entries per lane (list capacity = 64 * IPL).
 // FEAT = features compiled in (the host picks the leanest instantiation that covers the launch: every
@@ -728,6 +745,34 @@ struct Flow {
         n_list_set(s, n + popc64(m));
     }
 
+    // select()'s lane window: DPP on the device (engine.hip: WaveHip), the same values from W::shfl32 in host builds
+    AF_CORE uint32_t win_lane_below(uint32_t v) const {   // v of lane - 1; 0 in lane 0
+#if defined(__HIP_DEVICE_COMPILE__)
+        return W::lane_below_u32(v);
+#else
+        const uint32_t x = W::shfl32(v, (lane + 63u) & 63u);
+        return lane != 0u ? x : 0u;
+#endif
+    }
+    AF_CORE uint32_t win_prefix_max(uint32_t v) const {   // max of v over lanes 0 .. mine
+#if defined(__HIP_DEVICE_COMPILE__)
+        return W::scan_incl_max_u32(v);
+#else
+        for (uint32_t step = 1u; step < 64u; step <<= 1) {
+            const uint32_t x = W::shfl32(v, (lane + 64u - step) & 63u);
+            if (lane >= step && x > v) v = x;
+        }
+        return v;
+#endif
+    }
+    AF_CORE bool win_my_bit(uint64_t m) const {   // bit `lane` of a wave-uniform mask
+#if defined(__HIP_DEVICE_COMPILE__)
+        return W::my_bit(m);
+#else
+        return ((m >> lane) & 1ull) != 0ull;
+#endif
+    }
+
     // Rank the messages of list s with time < min(H_in, T); hand the `n_sel` earliest (<= room, <= 64) to
     // lanes 0..n_sel-1 in time order; keep the rest.  Returns n_sel.
     // `hs`: the horizon slot of the station that selects (= s, except for the server levels of FEAT_CHAIN: level_slot());
@@ -760,8 +805,16 @@ struct Flow {
         // approximate reciprocal is as good as a division here)
         double sc = 64.0 * W::rcp(hi - lo);
         if (!(sc < 1e300)) sc = 1e300;
-        hist()[lane] = 0u;   // (zeroing them in front of the entry sync instead -- one sync less -- measured: no gain)
-        W::sync();
+        // Round 8: the lane window.  A list is the previous station's batch in time order plus a jitter far below the batch's span,
+        // so it arrives almost sorted: the form with one entry per lane first tries to rank an entry against the kWindow lanes in
+        // front of it alone (below), and zeroes and fills the bucket counts only where that is not proved exact.
+        constexpr uint32_t kWindow = (IPLx == 1u && !kTieBreak && !kChain) ? (uint32_t)(AF_SELECT_WINDOW) : 0u;
+        static_assert(kWindow < 32u, "AF_SELECT_WINDOW: lanes an entry looks back");
+        if (kWindow == 0u) {
+            hist()[lane] = 0u;   // (zeroing them in front of the entry sync instead -- one sync less -- measured: no gain)
+            W::sync();
+        }
+        uint32_t code = 0u;   // kWindow: the bucket map at 2^26 times the scale -- the bucket is its top six bits
         // my (up to 4) entries; bucket counts
         double k[IPLx], t[IPLx], sent[IPLx];
         uint32_t a[IPLx], b[IPLx], slot[IPLx];
@@ -781,84 +834,143 @@ struct Flow {
                 if (kTieBreak) sent[q] = TS[i];
                 a[q] = (s == 2u || (kFar && s == 3u)) ? AX[i] : 0u;
                 elig[q] = valid[q] && k[q] < hi && (!kChain || level == kAnyLevel || level_of(a[q] & (kSrvSlots - 1u)) == level);
-                double x = (k[q] - lo) * sc;
-                x = x < 63.0 ? x : 63.0;        // (also what a NaN from a stale entry becomes)
-                b[q] = x > 0.0 ? (uint32_t)x : 0u;
-                if (elig[q]) slot[q] = W::lds_add(hist() + b[q], 1u);
+                if (kWindow == 0u) {
+                    double x = (k[q] - lo) * sc;
+                    x = x < 63.0 ? x : 63.0;        // (also what a NaN from a stale entry becomes)
+                    b[q] = x > 0.0 ? (uint32_t)x : 0u;
+                    if (elig[q]) slot[q] = W::lds_add(hist() + b[q], 1u);
+                } else {
+                    // (a power of two more in the scale commutes with the rounding; an eligible entry's code is in 1 .. 0xFFFFFF00:
+                    // 0 and ~0 stand for "no entry" below.  Non-decreasing in the key, so a smaller code IS an earlier key.)
+                    double y = (k[q] - lo) * (sc * 67108864.0);
+                    y = y < 4294967040.0 ? y : 4294967040.0;
+                    code = y > 1.0 ? (uint32_t)y : 1u;
+                    b[q] = code >> 26;
+                }
             }
         }
-        W::sync();
-        uint32_t E;
-        const uint32_t cnt = hist()[lane];
-        const uint32_t base = excl_scan(cnt, E);
-        // a lane's bucket start and count straight from the bucket's lane (two ds_bpermute) instead of an LDS array written,
-        // synchronised and read back (round 4: -0.4 %)
-        uint32_t bb[IPLx], bc[IPLx];
-#pragma unroll
-        for (uint32_t q = 0u; q < IPLx; ++q) {
-            bb[q] = W::shfl32(base, b[q]);
-            bc[q] = W::shfl32(cnt, b[q]);
-        }
-#pragma unroll
-        for (uint32_t q = 0u; q < IPLx; ++q)
-            if (elig[q]) {
-                sorted()[bb[q] + slot[q]] = k[q];
-                if (kTieBreak) sorted_ts()[bb[q] + slot[q]] = sent[q];
-            }
-        W::sync();
+        uint32_t E = 0u;
         uint32_t rank[IPLx];
+        bool ranked = false;   // wave-uniform
+        if constexpr (kWindow != 0u) {
+            // c[d - 1]: the code of the entry d lanes in front of me, 0 where that is no eligible entry; `own`: mine, ~0 if I am not
+            // eligible -- so neither "in front > own" nor "in front == own" ever holds for a pair with a non-eligible half
+            const uint32_t own = elig[0] ? code : 0xFFFFFFFFu;
+            uint32_t c[kWindow + 1u];
+            c[0] = win_lane_below(elig[0] ? code : 0u);
 #pragma unroll
-        for (uint32_t q = 0u; q < IPLx; ++q) {
-            rank[q] = 0u;
-            if (elig[q]) {
-                const uint32_t p0 = bb[q], p1 = p0 + bc[q], me = p0 + slot[q];
-                uint32_t r = p0;
-                // no region inside the loop (round 4): count the bucket's keys below mine and the ones not above it; they differ
-                // by exactly one (me) unless another message of the station shares my instant
-                if (!kTieBreak) {
-                    uint32_t c = p0;
-                    // (round 6: the first kAhead keys of my bucket fetched at once -- 64 buckets for ~60 messages: the fullest holds
-                    // three or four, and the wave walked it one LDS round trip per key; what lies behind the bucket is masked.
-                    // Interleaved A/B, 0 / 2 / 4 ahead: config 2 37.75 / 37.50 / 37.06 ms, config 3 55.3 / 55.0 / 54.25, config 5
-                    // 189.2 / 187.7 / 187.5: profiles/r06/ab_select_bucket_ahead.txt)
-#if defined(AF_SELECT_BUCKET_AHEAD)
-                    constexpr uint32_t kAhead = AF_SELECT_BUCKET_AHEAD;
-#else
-                    constexpr uint32_t kAhead = 4u;
+            for (uint32_t d = 1u; d <= kWindow; ++d) c[d] = win_lane_below(c[d - 1u]);
+            // An entry's rank is its place among the eligible ones in list order, less the entries of its window in front of it that
+            // are later, plus the ones behind it that are earlier: each comparison is made once, by the lane behind, and its wave
+            // mask shifted down by d (a scalar shift) tells the lane in front.
+            const uint64_t em = W::ballot(elig[0]);
+            uint32_t r = W::mbcnt(em);
+            uint64_t same = 0ull;
+#pragma unroll
+            for (uint32_t d = 1u; d <= kWindow; ++d) {
+                const bool later_in_front = c[d - 1u] > own;
+                const uint64_t m = W::ballot(later_in_front);
+                same |= W::ballot(c[d - 1u] == own);
+                r -= later_in_front ? 1u : 0u;
+                r += win_my_bit(m >> d) ? 1u : 0u;   // the lane d behind me found me later than itself
+            }
+            // The proof that this is exact: every eligible entry's code is strictly above every eligible code more than kWindow
+            // lanes in front of it (their maximum: the prefix maximum of the codes shifted by kWindow + 1 lanes) -- two entries
+            // further apart than the window are then in order and differ -- and no two codes inside a window are equal (equal
+            // codes say nothing about their keys -- equal, or closer than the code resolves: the bucket rank compares the keys
+            // themselves and raises FLOW_WHY_TIE where they are equal).
+            // (Measured, config 2, profiles/r08/ab_select_window.txt: with the proof in FRONT of the comparisons -- a branch
+            // between the shifts and their use -- the window was 0.4 ms SLOWER than the bucket rank, behind them 1.3 ms faster:
+            // the comparisons fill the wait states of the shift chain, and on the benched lists the proof holds in 99.7 % of calls.)
+            const uint32_t far_max = win_prefix_max(c[kWindow]);
+            ranked = W::ballot(!(own > far_max)) == 0ull && same == 0ull;
+            rank[0] = r;
+            E = popc64(em);
+            if (kProf) {   // (constant indices: the accumulators stay in scalar registers)
+                if (ranked) prof_acc[PROF_N_SELECT_WINDOW] += 1ull;
+                else prof_acc[PROF_N_SELECT_BUCKET] += 1ull;
+            }
+#if !defined(__HIPCC__)
+            if (lane == 0u) g_select_window_calls[ranked ? 0 : 1] += 1ull;
 #endif
-                    double kq[kAhead > 0u ? kAhead : 1u];
+            if (!ranked) {
+                hist()[lane] = 0u;
+                W::sync();
+                if (elig[0]) slot[0] = W::lds_add(hist() + b[0], 1u);
+            }
+        }
+        if (!ranked) {
+            W::sync();
+            const uint32_t cnt = hist()[lane];
+            const uint32_t base = excl_scan(cnt, E);
+            // a lane's bucket start and count straight from the bucket's lane (two ds_bpermute) instead of an LDS array written,
+            // synchronised and read back (round 4: -0.4 %)
+            uint32_t bb[IPLx], bc[IPLx];
 #pragma unroll
-                    for (uint32_t u = 0u; u < kAhead; ++u) kq[u] = sorted()[p0 + u];
+            for (uint32_t q = 0u; q < IPLx; ++q) {
+                bb[q] = W::shfl32(base, b[q]);
+                bc[q] = W::shfl32(cnt, b[q]);
+            }
 #pragma unroll
-                    for (uint32_t u = 0u; u < kAhead; ++u) {
-                        const bool in = u < bc[q];
-                        r += in && kq[u] < k[q] ? 1u : 0u;
-                        c += in && kq[u] <= k[q] ? 1u : 0u;
-                    }
+            for (uint32_t q = 0u; q < IPLx; ++q)
+                if (elig[q]) {
+                    sorted()[bb[q] + slot[q]] = k[q];
+                    if (kTieBreak) sorted_ts()[bb[q] + slot[q]] = sent[q];
+                }
+            W::sync();
+#pragma unroll
+            for (uint32_t q = 0u; q < IPLx; ++q) {
+                rank[q] = 0u;
+                if (elig[q]) {
+                    const uint32_t p0 = bb[q], p1 = p0 + bc[q], me = p0 + slot[q];
+                    uint32_t r = p0;
+                    // no region inside the loop (round 4): count the bucket's keys below mine and the ones not above it; they differ
+                    // by exactly one (me) unless another message of the station shares my instant
+                    if (!kTieBreak) {
+                        uint32_t c = p0;
+                        // (round 6: the first kAhead keys of my bucket fetched at once -- 64 buckets for ~60 messages: the fullest holds
+                        // three or four, and the wave walked it one LDS round trip per key; what lies behind the bucket is masked.
+                        // Interleaved A/B, 0 / 2 / 4 ahead: config 2 37.75 / 37.50 / 37.06 ms, config 3 55.3 / 55.0 / 54.25, config 5
+                        // 189.2 / 187.7 / 187.5: profiles/r06/ab_select_bucket_ahead.txt)
+#if defined(AF_SELECT_BUCKET_AHEAD)
+                        constexpr uint32_t kAhead = AF_SELECT_BUCKET_AHEAD;
+#else
+                        constexpr uint32_t kAhead = 4u;
+#endif
+                        double kq[kAhead > 0u ? kAhead : 1u];
+#pragma unroll
+                        for (uint32_t u = 0u; u < kAhead; ++u) kq[u] = sorted()[p0 + u];
+#pragma unroll
+                        for (uint32_t u = 0u; u < kAhead; ++u) {
+                            const bool in = u < bc[q];
+                            r += in && kq[u] < k[q] ? 1u : 0u;
+                            c += in && kq[u] <= k[q] ? 1u : 0u;
+                        }
 #pragma nounroll
-                    for (uint32_t p = p0 + kAhead; p < p1; ++p) {
+                        for (uint32_t p = p0 + kAhead; p < p1; ++p) {
+                            const double kk = sorted()[p];
+                            r += kk < k[q] ? 1u : 0u;
+                            c += kk <= k[q] ? 1u : 0u;
+                        }
+                        why |= c != r + 1u ? FLOW_WHY_TIE : 0u;
+                        (void)me;
+                    } else
+#pragma nounroll   // (a bucket holds one or two messages: the unrolled-by-eight form was 115 instructions per site for ~1.5 trips)
+                    for (uint32_t p = p0; p < p1; ++p) {
                         const double kk = sorted()[p];
                         r += kk < k[q] ? 1u : 0u;
-                        c += kk <= k[q] ? 1u : 0u;
-                    }
-                    why |= c != r + 1u ? FLOW_WHY_TIE : 0u;
-                    (void)me;
-                } else
-#pragma nounroll   // (a bucket holds one or two messages: the unrolled-by-eight form was 115 instructions per site for ~1.5 trips)
-                for (uint32_t p = p0; p < p1; ++p) {
-                    const double kk = sorted()[p];
-                    r += kk < k[q] ? 1u : 0u;
-                    if (kk == k[q] && p != me) {   // two deliveries of this station at one instant
-                        if (kTieBreak) {           // SimPy pops the one whose Timeout was created -- that was sent -- first
-                            const double other = sorted_ts()[p];
-                            r += other < sent[q] ? 1u : 0u;
-                            if (other == sent[q]) why |= FLOW_WHY_TIE;
-                        } else {
-                            why |= FLOW_WHY_TIE;
+                        if (kk == k[q] && p != me) {   // two deliveries of this station at one instant
+                            if (kTieBreak) {           // SimPy pops the one whose Timeout was created -- that was sent -- first
+                                const double other = sorted_ts()[p];
+                                r += other < sent[q] ? 1u : 0u;
+                                if (other == sent[q]) why |= FLOW_WHY_TIE;
+                            } else {
+                                why |= FLOW_WHY_TIE;
+                            }
                         }
                     }
+                    rank[q] = r;
                 }
-                rank[q] = r;
             }
         }
         uint32_t n_sel = E < room ? E : room;

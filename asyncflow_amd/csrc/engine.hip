@@ -373,6 +373,22 @@ struct WaveHip {
         v += dpp<0x143, 0xC>(v);   // row_bcast:31 -> rows 2 and 3
         return v;
     }
+    // select()'s lane window (af_flow.hpp, AF_SELECT_WINDOW): the inclusive prefix MAXIMUM by the same six DPP steps (the lanes a
+    // row shift leaves without a source read 0, the identity of an unsigned maximum, and so does a lane whose row is masked off),
+    // the value of the lane below mine by one DPP wave shift (lane 0 reads 0), and my own bit of a wave-uniform mask as a lane
+    // condition (an SGPR pair used as a carry-in or a select mask: no 64-bit vector shift)
+    static __device__ __forceinline__ uint32_t umax(uint32_t a, uint32_t b) { return a > b ? a : b; }
+    static __device__ __forceinline__ uint32_t scan_incl_max_u32(uint32_t v) {
+        v = umax(v, dpp<0x111, 0xF>(v));   // row_shr:1
+        v = umax(v, dpp<0x112, 0xF>(v));   // row_shr:2
+        v = umax(v, dpp<0x114, 0xF>(v));   // row_shr:4
+        v = umax(v, dpp<0x118, 0xF>(v));   // row_shr:8
+        v = umax(v, dpp<0x142, 0xA>(v));   // row_bcast:15 -> rows 1 and 3
+        v = umax(v, dpp<0x143, 0xC>(v));   // row_bcast:31 -> rows 2 and 3
+        return v;
+    }
+    static __device__ __forceinline__ uint32_t lane_below_u32(uint32_t v) { return dpp<0x138, 0xF>(v); }   // wave_shr:1
+    static __device__ __forceinline__ bool my_bit(uint64_t m) { return __builtin_amdgcn_inverse_ballot_w64(m); }
     static __device__ __forceinline__ uint32_t mbcnt(uint64_t m) {
         return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
     }
@@ -985,6 +1001,11 @@ struct af_engine {
     bool pool_poisoned = false;                // af_probe_scratch was called: every later growth of the pool is filled with pool_word
     uint32_t pool_word = 0;
     int wait_value_ok = -1;                    // hipDeviceAttributeCanUseStreamWaitValue (-1: not asked yet)
+    struct ResidentWaves {                     // gate_for_launch: waves of a flow kernel the device holds at once, per function and LDS size
+        const void* fn;
+        uint32_t lds, waves;
+    };
+    std::vector<ResidentWaves> resident_waves;
     uint64_t done_ptrs[2] = {0, 0};            // host copy of d_fb[kDoneWords ..] (a member: an asynchronous copy reads it)
     bool shared_instants_likely = false;
     hipModule_t jit_module = nullptr;  // plan-specialised kernels (af_engine_set_kernels), valid for jit_spec only
@@ -1597,6 +1618,11 @@ std::string flow_jit_spec_string(const af_engine* e, const FlowPlan& P, const af
     // config 3: 55.7 -> 56.4; general servers, config 6: 281 -> 293; config 5: nothing): profiles/r05/philox_keys_ab.txt
     const bool keys = (P.feat == 0u || (P.feat & aff::FEAT_MARKS) != 0u) && (P.feat & aff::FEAT_GENSRV) == 0u;
     if (keys && !std::getenv("AF_FLOW_KEYS_HOISTED")) spec += " -DAF_FJ_KEYS_PER_CALL=1";
+    // select()'s lane window (af_flow.hpp: AF_SELECT_WINDOW) where it was measured to pay: the lean form (config 2: 43.1 -> 41.8 ms).
+    // The forms with FEAT_FAR / timeline marks run plans whose lists are far from sorted (config 3's grid reaches 50 ms edges:
+    // the proof fails in most calls) and were slower with it in its first form (config 3 67.1 -> 69.3, config 4 747 -> 772 ms):
+    // they keep the bucket rank alone (profiles/r08/ab_select_window.txt)
+    if (P.feat != 0u && !std::getenv("AF_FLOW_SELECT_WINDOW_ALL")) spec += " -DAF_SELECT_WINDOW=0";
     return spec;
 }
 }  // namespace
@@ -2360,12 +2386,24 @@ static int gate_for_launch(const Run& r, uint32_t nc, const FlowLaunch& fl, uint
         if (hipDeviceGetAttribute(&v, hipDeviceAttributeCanUseStreamWaitValue, e->device) != hipSuccess) { (void)hipGetLastError(); v = 0; }
         e->wait_value_ok = v;
     }
-    int per_cu = 0;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, e->device));
-    if (fl.jit) HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, e->flow_jit_fn, (int)kWave, fl.lds));
-    else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fl.fn, (int)kWave, fl.lds));
-    const uint32_t resident = (uint32_t)(per_cu > 0 ? per_cu : 0) * (uint32_t)prop.multiProcessorCount;
+    // the resident waves of (function, LDS size) are asked once per engine: the device properties and the occupancy query cost
+    // host time inside every af_engine_run_summarized otherwise; a newly loaded specialised kernel clears the list
+    const void* fn = fl.jit ? (const void*)e->flow_jit_fn : fl.fn;
+    uint32_t resident = 0u;
+    bool known = false;
+    for (const af_engine_t::ResidentWaves& rw : e->resident_waves)
+        if (rw.fn == fn && rw.lds == fl.lds) {
+            resident = rw.waves;
+            known = true;
+        }
+    if (!known) {
+        int per_cu = 0, n_cu = 0;
+        HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, e->device));
+        if (fl.jit) HIP_TRY(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, e->flow_jit_fn, (int)kWave, fl.lds));
+        else HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fl.fn, (int)kWave, fl.lds));
+        resident = (uint32_t)(per_cu > 0 ? per_cu : 0) * (uint32_t)(n_cu > 0 ? n_cu : 0);
+        e->resident_waves.push_back({fn, fl.lds, resident});
+    }
     if (e->wait_value_ok > 0) gate = analyzer_gate(nc, resident);
     if (std::getenv("AF_DEBUG")) std::fprintf(stderr, "[af] analyzer beside the last round: %u resident waves, gate at %u of %u scenarios\n", resident, gate, nc);
     return AF_OK;
@@ -2434,7 +2472,8 @@ static int dump_flow_profile(const FlowPlan& FP, uint32_t nc, const FlowLaunch& 
                                                     "append + send_floor", "complete", "flush_ticks + round end",
                                                     "general servers: lanes", "general servers: walk", "general servers: rank + relax", "general servers: state at the horizon",
                                                     "COUNT rounds solved at once", "COUNT relaxation sweeps", "COUNT lanes in solved rounds", "COUNT rounds walked by event",
-                                                    "general servers: standing (ranks, RAM)", "general servers: commit walk (series)"};
+                                                    "general servers: standing (ranks, RAM)", "general servers: commit walk (series)",
+                                                    "COUNT selects ranked by the lane window", "COUNT selects that fell back to the bucket rank"};
     double acc[aff::kProfSections] = {}, total = 0.0;
     for (uint32_t i = 0; i < nc; ++i)
         for (uint32_t k = 0; k < aff::kProfSections; ++k) acc[k] += (double)hp[(size_t)i * aff::kProfSections + k];
@@ -2695,6 +2734,7 @@ int af_engine_set_kernels(af_engine_t* e, const char* spec, const void* image, s
         e->flow_jit_module = nullptr;
         e->flow_jit_fn = nullptr;
         e->flow_jit_spec.clear();
+        e->resident_waves.clear();   // (the next module's function may get the handle this one had)
     }
     if (is_flow && !unload_all) {   // a plan-specialised stage-parallel kernel (one entry point)
         hipModule_t mod = nullptr;
