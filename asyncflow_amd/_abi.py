@@ -313,6 +313,50 @@ class AfQuantiles(C.Structure):
     ]
 
 
+class AfCellsExport(C.Structure):
+    """``af_cells_export_t``: request of ``af_engine_export_cells`` (``lat_count``, ``elapsed_ms`` and ``scratch_bytes`` are
+    written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("by_arrival", C.c_uint32),
+        ("group", C.c_void_p),
+        ("edges", C.POINTER(C.c_double)),
+        ("lat", C.c_void_p),
+        ("lat_capacity", C.c_uint64),
+        ("seg_bounds", C.c_void_p),
+        ("lat_count", C.c_uint64),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
+class AfCells(C.Structure):
+    """``af_cells_t``: request of ``af_engine_import_cells`` (``elapsed_ms`` and ``scratch_bytes`` are written back)."""
+
+    _fields_ = [
+        ("n_scenarios", C.c_uint32),
+        ("n_groups", C.c_uint32),
+        ("n_windows", C.c_uint32),
+        ("group", C.POINTER(C.c_uint32)),
+        ("seg_bounds", C.POINTER(C.c_uint32)),
+        ("seg_begin", C.POINTER(C.c_uint64)),
+        ("lat", C.c_void_p),
+        ("n_lat", C.c_uint64),
+        ("stats", C.c_void_p),
+        ("n_levels", C.c_uint32),
+        ("levels", C.POINTER(C.c_double)),
+        ("n_thresholds", C.c_uint32),
+        ("thresholds", C.POINTER(C.c_double)),
+        ("count", C.c_void_p),
+        ("quantiles", C.c_void_p),
+        ("within", C.c_void_p),
+        ("elapsed_ms", C.c_double),
+        ("scratch_bytes", C.c_uint64),
+    ]
+
+
 MAX_SERIES_QUANTILE_LEVELS = 16   # AF_MAX_SERIES_QUANTILE_LEVELS
 
 
@@ -721,6 +765,8 @@ EXPORTED_SYMBOLS = (
     "af_engine_summarize_series_warmup",
     "af_engine_summarize_quantiles",
     "af_engine_summarize_arrival_quantiles",
+    "af_engine_export_cells",
+    "af_engine_import_cells",
     "af_engine_summarize_arrivals",
     "af_engine_summarize_inflight",
     "af_engine_summarize_exemplars",
@@ -787,6 +833,10 @@ def declare(lib: C.CDLL) -> C.CDLL:
     lib.af_engine_summarize_quantiles.restype = C.c_int
     lib.af_engine_summarize_arrival_quantiles.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfQuantiles)]
     lib.af_engine_summarize_arrival_quantiles.restype = C.c_int
+    lib.af_engine_export_cells.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfCellsExport)]
+    lib.af_engine_export_cells.restype = C.c_int
+    lib.af_engine_import_cells.argtypes = [C.c_void_p, C.POINTER(AfCells)]
+    lib.af_engine_import_cells.restype = C.c_int
     lib.af_engine_summarize_arrivals.argtypes = [C.c_void_p, C.POINTER(AfSweep), C.POINTER(AfArrivals)]
     lib.af_engine_summarize_arrivals.restype = C.c_int
     lib.af_engine_summarize_inflight.argtypes = [C.c_void_p, C.POINTER(AfOutputs), C.POINTER(AfInflight)]

@@ -16,7 +16,7 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent / "csrc"
 LIB_PATH = CSRC / "libasyncflow_hip.so"
-SOURCES = ("engine.hip", "af_flow.hpp", "af_flow_host.hpp", "af_core.hpp", "af_math.hpp", "af_plan_pack.hpp", "af_summary.hpp", "af_select.hpp", "af_pooled.hpp", "af_windowed.hpp", "af_arrival.hpp", "af_state.hpp", "af_series_windows.hpp", "af_series_quantiles.hpp", "af_series_excursions.hpp", "af_series_histogram.hpp", "af_series_combined.hpp", "af_series_joint.hpp", "af_series_warmup.hpp", "af_wide.hpp", "af_quantiles.hpp", "af_pregen.hpp", "af_arrival_counts.hpp", "af_inflight.hpp", "af_exemplars.hpp", "af_latency_histogram.hpp", "af_paired.hpp", "af_alerts.hpp", "af_alert_outcomes.hpp")
+SOURCES = ("engine.hip", "af_flow.hpp", "af_flow_host.hpp", "af_core.hpp", "af_math.hpp", "af_plan_pack.hpp", "af_summary.hpp", "af_select.hpp", "af_pooled.hpp", "af_windowed.hpp", "af_arrival.hpp", "af_state.hpp", "af_series_windows.hpp", "af_series_quantiles.hpp", "af_series_excursions.hpp", "af_series_histogram.hpp", "af_series_combined.hpp", "af_series_joint.hpp", "af_series_warmup.hpp", "af_wide.hpp", "af_quantiles.hpp", "af_cells.hpp", "af_pregen.hpp", "af_arrival_counts.hpp", "af_inflight.hpp", "af_exemplars.hpp", "af_latency_histogram.hpp", "af_paired.hpp", "af_alerts.hpp", "af_alert_outcomes.hpp")
 ARCH = "gfx950"
 
 # -ffp-contract=off / -fno-fast-math: every f64 expression is evaluated exactly as

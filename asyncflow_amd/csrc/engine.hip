@@ -67,6 +67,7 @@
 #include "af_arrival.hpp"
 #include "af_state.hpp"
 #include "af_quantiles.hpp"
+#include "af_cells.hpp"
 #include "af_arrival_counts.hpp"
 #include "af_inflight.hpp"
 #include "af_alerts.hpp"
@@ -2915,13 +2916,16 @@ static int check_window_edges(const double* edges, uint32_t W) {
 }
 
 // the group ids of n scenarios to the host (none: all in group 0, grp stays empty), every one below G or AF_POOL_SKIP
-static int read_groups(const uint32_t* group, uint32_t n, uint32_t G, std::vector<uint32_t>& grp) {
-    grp.resize(group ? n : 0u);
-    if (group) HIP_TRY(hipMemcpy(grp.data(), group, grp.size() * 4u, hipMemcpyDeviceToHost));
+static int check_group_ids(const std::vector<uint32_t>& grp, uint32_t G) {
     for (uint32_t s = 0; s < grp.size(); ++s)
         if (grp[s] != afp::kSkip && grp[s] >= G)
             return fail(AF_ERR_INVALID, "group id out of range (scenario " + std::to_string(s) + ": " + std::to_string(grp[s]) + ", n_groups " + std::to_string(G) + ")");
     return AF_OK;
+}
+static int read_groups(const uint32_t* group, uint32_t n, uint32_t G, std::vector<uint32_t>& grp) {
+    grp.resize(group ? n : 0u);
+    if (group) HIP_TRY(hipMemcpy(grp.data(), group, grp.size() * 4u, hipMemcpyDeviceToHost));
+    return check_group_ids(grp, G);
 }
 
 // The cells of a request over whole runs: one per group, its sample the latencies of the group's members in ascending scenario
@@ -2950,8 +2954,8 @@ static int layout_pooled_cells(const af_outputs_t* out, const std::vector<uint32
     }
     return AF_OK;
 }
-// ... and their latencies to lat (o_dst, o_lat: parts of the scratch of n * 8 and cell_off[G] * 8 bytes)
-static int compact_pooled_cells(af_engine_t* e, const af_outputs_t* out, const uint32_t* group, uint32_t n, const PooledCells& pc, size_t o_dst, size_t o_lat) {
+// ... and their latencies to lat (o_dst: a part of the scratch of n * 8 bytes; lat: cell_off[G] * 8 bytes, in the scratch or the caller's)
+static int compact_pooled_cells(af_engine_t* e, const af_outputs_t* out, const uint32_t* group, uint32_t n, const PooledCells& pc, size_t o_dst, double* lat) {
     afp::PoolArgs a{};
     a.clock = out->clock;
     a.counts = out->counts;
@@ -2959,7 +2963,7 @@ static int compact_pooled_cells(af_engine_t* e, const af_outputs_t* out, const u
     a.cnt_completed_slot = AF_CNT_COMPLETED;
     a.group = group;
     a.dst = reinterpret_cast<const uint64_t*>(e->d_pool + o_dst);
-    a.lat = reinterpret_cast<double*>(e->d_pool + o_lat);
+    a.lat = lat;
     HIP_TRY(hipMemcpyAsync(e->d_pool + o_dst, pc.dst.data(), (size_t)n * 8u, hipMemcpyHostToDevice, e->stream));
     hipLaunchKernelGGL(afp::af_pool_compact, dim3(n), dim3(afp::kThreads), 0, e->stream, a);
     HIP_TRY(hipGetLastError());
@@ -2991,7 +2995,7 @@ int af_engine_summarize_pooled(af_engine_t* e, const af_outputs_t* out, af_poole
     const size_t o_lat = lay.part(pc.cell_off[G] * 8u), o_dst = lay.part((size_t)n * 8u);
     const PoolParts pp = pool_parts(lay, G, tiles.size(), pieces);
     if (int rc = pool_reserve(e, lay.at)) return rc;
-    if (int rc = compact_pooled_cells(e, out, pl->group, n, pc, o_dst, o_lat)) return rc;
+    if (int rc = compact_pooled_cells(e, out, pl->group, n, pc, o_dst, reinterpret_cast<double*>(e->d_pool + o_lat))) return rc;
     afp::PoolArgs a{};
     a.lat = reinterpret_cast<double*>(e->d_pool + o_lat);
     pool_bind(a, e->d_pool, pp);
@@ -3019,6 +3023,10 @@ struct WindowCells {
     size_t o_edges, o_err, o_bounds, o_lat, o_pre, o_off;
     std::vector<uint32_t> hb, pre;    // the bounds [n][W + 1]; per (scenario, window) the latencies of its cell that earlier members bring
     std::vector<uint64_t> cell_off;   // [G * W + 1]
+    // the export (af_engine_export_cells): the latencies go to the caller's buffer, and every scenario is its own group
+    double* lat_dst = nullptr;                           // the caller's, or null: the compacted array lies in the scratch (o_lat)
+    const std::vector<uint32_t>* own_group = nullptr;    // [n] group ids for the compaction, kept in the scratch at o_group
+    size_t o_group = 0;
 };
 static void bind_window_bounds(const af_engine_t* e, WindowCells& wc) {
     wc.a.edges = reinterpret_cast<const double*>(e->d_pool + wc.o_edges);
@@ -3068,28 +3076,14 @@ static int layout_window_cells(af_engine_t* e, const af_outputs_t* out, const ui
     HIP_TRY(hipMemcpyAsync(wc.hb.data(), wc.a.bounds, NE * 4u, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     // the cells: sizes, and per (scenario, window) the latencies of its cell that earlier members bring
-    wc.cell_off.assign(C + 1u, 0u);   // (first the sizes, at [c + 1])
-    wc.pre.resize((size_t)n * W);
-    for (uint32_t s = 0; s < n; ++s) {
-        const uint32_t g = grp.empty() ? 0u : grp[s];
-        if (g == afw::kSkip) continue;
-        const uint32_t* r = wc.hb.data() + (size_t)s * (W + 1u);
-        uint64_t* sz = wc.cell_off.data() + 1u + (size_t)g * W;
-        uint32_t* ps = wc.pre.data() + (size_t)s * W;
-        for (uint32_t w = 0; w < W; ++w) {
-            if (by == CellsBy::kFinish && r[w + 1u] < r[w])   // (a binary search on a sorted column cannot: the compaction would find the inversion too)
-                return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(s) + " is not in completion order (finish decreases): windows by finish time need it");
-            if (sz[w] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, std::string(by_state ? "cell " : "window ") + std::to_string(w) + " of group " + std::to_string(g) + " holds 2^32 or more latencies");
-            ps[w] = (uint32_t)sz[w];
-            sz[w] += r[w + 1u] - r[w];
-        }
-    }
-    for (size_t c = 0; c < C; ++c) {
-        if (wc.cell_off[c + 1u] > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, std::string(by_state ? "cell " : "window ") + std::to_string(c % W) + " of group " + std::to_string(c / W) + " holds 2^32 or more latencies");
-        wc.cell_off[c + 1u] += wc.cell_off[c];
-    }
-    // scratch, second part: the compacted latencies, pre, the cells' offsets; the caller's parts follow
-    wc.o_lat = lay.part(wc.cell_off[C] * 8u);
+    // (by finish: decreasing bounds -- a binary search on a sorted column cannot give them: the compaction would find the inversion too)
+    const afc::LayoutResult lr = afc::layout_cells(wc.hb.data(), grp, n, G, W, by == CellsBy::kFinish, wc.cell_off, wc.pre);
+    if (lr.error == afc::LayoutError::kOrder)
+        return fail(AF_ERR_INVALID, "rqs_clock of scenario " + std::to_string(lr.scenario) + " is not in completion order (finish decreases): windows by finish time need it");
+    if (lr.error == afc::LayoutError::kCellTooLarge)
+        return fail(AF_ERR_CAPACITY, std::string(by_state ? "cell " : "window ") + std::to_string(lr.window) + " of group " + std::to_string(lr.group) + " holds 2^32 or more latencies");
+    // scratch, second part: the compacted latencies (unless they go to the caller), pre, the cells' offsets; the caller's parts follow
+    wc.o_lat = wc.lat_dst ? 0u : lay.part(wc.cell_off[C] * 8u);
     wc.o_pre = lay.part((size_t)n * W * 4u);
     wc.o_off = lay.part((C + 1u) * 8u);
     return AF_OK;
@@ -3105,7 +3099,11 @@ static int compact_window_cells(af_engine_t* e, const ScratchLayout& lay, Window
         if (!wc.row_bounds) HIP_TRY(hipMemcpyAsync(wc.a.bounds, wc.hb.data(), NE * 4u, hipMemcpyHostToDevice, st));
     }
     unsigned char* b = e->d_pool;
-    wc.a.lat = reinterpret_cast<double*>(b + wc.o_lat);
+    wc.a.lat = wc.lat_dst ? wc.lat_dst : reinterpret_cast<double*>(b + wc.o_lat);
+    if (wc.own_group) {
+        HIP_TRY(hipMemcpyAsync(b + wc.o_group, wc.own_group->data(), (size_t)n * 4u, hipMemcpyHostToDevice, st));
+        wc.a.group = reinterpret_cast<const uint32_t*>(b + wc.o_group);
+    }
     wc.a.pre = reinterpret_cast<uint32_t*>(b + wc.o_pre);
     wc.a.cell_off = reinterpret_cast<const uint64_t*>(b + wc.o_off);
     const uint32_t no_error = afw::kNoError;
@@ -3175,6 +3173,59 @@ static int launch_tiny_tier(uint64_t C, uint32_t tiny_waves, const std::function
     return AF_OK;
 }
 
+// The windowed analyzer behind the compacted array: what it needs are the cells' offsets alone.  plan_window_tiers sorts the C
+// cells into the tiers of their sizes and adds the tiers' parts to the scratch layout (before the scratch is reserved);
+// reduce_window_cells runs the tiers on lat / d_cell_off (DEVICE, the offsets [C + 1]) into stats; the last kernel is launched,
+// not waited for.
+struct WindowTiers {
+    std::vector<afp::PoolGroup> groups;   // the large cells
+    std::vector<afp::PoolTile> tiles;
+    std::vector<uint32_t> stat_row, small;
+    size_t o_row = 0, o_small = 0;
+    PoolParts pp{};
+};
+static void plan_window_tiers(const std::vector<uint64_t>& cell_off, size_t C, ScratchLayout& lay, WindowTiers& t) {
+    uint64_t pieces = 0;
+    for (size_t c = 0; c < C; ++c) {
+        const uint64_t len = cell_off[c + 1u] - cell_off[c];
+        if (len > afw::kSmallMax) {
+            pool_add_group(t.groups, t.tiles, pieces, cell_off[c], (uint32_t)len);
+            t.stat_row.push_back((uint32_t)c);
+        } else if (len > afw::kTinyMax) {
+            t.small.push_back((uint32_t)c);
+        }
+    }
+    t.o_row = lay.part(t.groups.size() * 4u);
+    t.o_small = lay.part(t.small.size() * 4u);
+    t.pp = !t.groups.empty() ? pool_parts(lay, t.groups.size(), t.tiles.size(), pieces) : PoolParts{};
+}
+static int reduce_window_cells(af_engine_t* e, const WindowTiers& t, afw::WinArgs a, size_t C, double* stats) {
+    hipStream_t st = e->stream;
+    unsigned char* b = e->d_pool;
+    const uint32_t n_large = (uint32_t)t.groups.size(), n_small = (uint32_t)t.small.size();
+    a.small = reinterpret_cast<const uint32_t*>(b + t.o_small);
+    a.stats = stats;
+    if (n_small) HIP_TRY(hipMemcpyAsync(b + t.o_small, t.small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
+    if (int rc = launch_tiny_tier(C, afw::kTinyWaves, [&](uint32_t blocks, uint64_t c0) {
+            hipLaunchKernelGGL(afw::af_win_tiny, dim3(blocks), dim3(afw::kTinyWaves * 64), 0, st, a, c0, (uint64_t)C);
+        }))
+        return rc;
+    for (uint64_t c0 = 0; c0 < n_small; c0 += kBlocksPerLaunch) {
+        hipLaunchKernelGGL(afw::af_win_small, dim3((uint32_t)std::min<uint64_t>(kBlocksPerLaunch, n_small - c0)), dim3(afw::kThreads), 0, st, a, (uint32_t)c0);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n_large) {
+        afp::PoolArgs pa{};
+        pa.lat = a.lat;
+        pool_bind(pa, b, t.pp);
+        pa.stats = stats;
+        pa.stat_row = reinterpret_cast<const uint32_t*>(b + t.o_row);
+        HIP_TRY(hipMemcpyAsync(b + t.o_row, t.stat_row.data(), (size_t)n_large * 4u, hipMemcpyHostToDevice, st));
+        if (int rc = pool_run(e, pa, t.groups, t.tiles)) return rc;
+    }
+    return AF_OK;
+}
+
 // Windowed analyzer (af_windowed.hpp; windows by arrival: af_arrival.hpp; by the state met on arrival, `sb`: af_state.hpp, the
 // "windows" W of everything below are then the keys of a group and n_windows == 0 is one window over all time).  The host reads
 // the row bounds back and lays out the cells (group g, window w) of the compacted array; cells of at most one numpy piece are
@@ -3207,49 +3258,13 @@ static int summarize_windows(af_engine_t* e, const af_outputs_t* out, af_windows
     ScratchLayout lay;
     WindowCells wc;
     if (int rc = layout_window_cells(e, out, win->group, grp, n, G, W, win->edges, win->row_bounds, by, sb ? &sa : nullptr, lay, wc)) return rc;
-    std::vector<afp::PoolGroup> groups;
-    std::vector<afp::PoolTile> tiles;
-    std::vector<uint32_t> stat_row, small;
-    uint64_t pieces = 0;
-    for (size_t c = 0; c < C; ++c) {
-        const uint64_t len = wc.cell_off[c + 1u] - wc.cell_off[c];
-        if (len > afw::kSmallMax) {
-            pool_add_group(groups, tiles, pieces, wc.cell_off[c], (uint32_t)len);
-            stat_row.push_back((uint32_t)c);
-        } else if (len > afw::kTinyMax) {
-            small.push_back((uint32_t)c);
-        }
-    }
-    const uint32_t n_large = (uint32_t)groups.size(), n_small = (uint32_t)small.size();
-    const size_t o_row = lay.part((size_t)n_large * 4u), o_small = lay.part((size_t)n_small * 4u);
-    const PoolParts pp = n_large ? pool_parts(lay, n_large, tiles.size(), pieces) : PoolParts{};
+    WindowTiers tiers;
+    plan_window_tiers(wc.cell_off, C, lay, tiers);
     const int rc_compact = compact_window_cells(e, lay, wc);
     win->scratch_bytes = e->pool_cap;
     if (rc_compact) return rc_compact;
-    hipStream_t st = e->stream;
-    unsigned char* b = e->d_pool;
-    afw::WinArgs& a = wc.a;
-    a.small = reinterpret_cast<const uint32_t*>(b + o_small);
-    a.stats = win->stats;
-    if (n_small) HIP_TRY(hipMemcpyAsync(b + o_small, small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
-    if (int rc = launch_tiny_tier(C, afw::kTinyWaves, [&](uint32_t blocks, uint64_t c0) {
-            hipLaunchKernelGGL(afw::af_win_tiny, dim3(blocks), dim3(afw::kTinyWaves * 64), 0, st, a, c0, (uint64_t)C);
-        }))
-        return rc;
-    for (uint64_t c0 = 0; c0 < n_small; c0 += kBlocksPerLaunch) {
-        hipLaunchKernelGGL(afw::af_win_small, dim3((uint32_t)std::min<uint64_t>(kBlocksPerLaunch, n_small - c0)), dim3(afw::kThreads), 0, st, a, (uint32_t)c0);
-        HIP_TRY(hipGetLastError());
-    }
-    if (n_large) {
-        afp::PoolArgs pa{};
-        pa.lat = a.lat;
-        pool_bind(pa, b, pp);
-        pa.stats = win->stats;
-        pa.stat_row = reinterpret_cast<const uint32_t*>(b + o_row);
-        HIP_TRY(hipMemcpyAsync(b + o_row, stat_row.data(), (size_t)n_large * 4u, hipMemcpyHostToDevice, st));
-        if (int rc = pool_run(e, pa, groups, tiles)) return rc;
-    }
-    HIP_TRY(hipStreamSynchronize(st));
+    if (int rc = reduce_window_cells(e, tiers, wc.a, C, win->stats)) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
     win->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
 }
@@ -3257,6 +3272,150 @@ int af_engine_summarize_windows(af_engine_t* e, const af_outputs_t* out, af_wind
 int af_engine_summarize_arrival_windows(af_engine_t* e, const af_outputs_t* out, af_windows_t* win) { return summarize_windows(e, out, win, CellsBy::kArrival); }
 int af_engine_summarize_state_windows(af_engine_t* e, const af_outputs_t* out, const af_state_bins_t* sb, af_windows_t* win) {
     return summarize_windows(e, out, win, CellsBy::kState, sb);
+}
+
+// the levels and thresholds of a quantile request (af_quantiles_t's rules)
+static int check_quantile_levels(uint32_t Q, const double* levels, uint32_t T, const double* thresholds) {
+    if (Q > AF_MAX_QUANTILE_LEVELS) return fail(AF_ERR_INVALID, "more than AF_MAX_QUANTILE_LEVELS (" + std::to_string(AF_MAX_QUANTILE_LEVELS) + ") levels");
+    if (T > AF_MAX_SLO_THRESHOLDS) return fail(AF_ERR_INVALID, "more than AF_MAX_SLO_THRESHOLDS (" + std::to_string(AF_MAX_SLO_THRESHOLDS) + ") thresholds");
+    if (Q == 0 && T == 0) return fail(AF_ERR_INVALID, "quantiles request without levels and without thresholds");
+    if (Q && !levels) return fail(AF_ERR_INVALID, "quantiles.levels is required with n_levels > 0");
+    if (T && !thresholds) return fail(AF_ERR_INVALID, "quantiles.thresholds is required with n_thresholds > 0");
+    for (uint32_t i = 0; i < Q; ++i)
+        if (!(levels[i] >= 0.0 && levels[i] <= 1.0)) return fail(AF_ERR_INVALID, "quantile level " + std::to_string(i) + " is not in [0, 1]");
+    for (uint32_t i = 0; i < T; ++i)
+        if (std::isnan(thresholds[i])) return fail(AF_ERR_INVALID, "threshold " + std::to_string(i) + " is NaN");
+    return AF_OK;
+}
+
+// The quantile analyzer behind the compacted array, as the windowed analyzer's pair above: plan_quantile_tiers sorts the C cells
+// into their tiers and adds the tiers' parts to the scratch layout; reduce_quantile_cells runs them on lat / d_cell_off (DEVICE).
+struct QuantileOutputs {
+    uint32_t Q, T;
+    const double *levels, *thresholds;   // HOST
+    uint32_t* count;                     // DEVICE, each may be null
+    double* quantiles;
+    uint32_t* within;
+};
+struct QuantileTiers {
+    struct SmallCell { uint32_t pad, cell; };
+    std::vector<SmallCell> small_by;
+    std::vector<uint32_t> small;
+    std::vector<afq::QCell> lcells;
+    std::vector<afp::PoolTile> ctiles, jtiles;
+    std::vector<afp::PoolGroup> jgroups;
+    std::vector<afq::QJob> jobs;
+    size_t o_small = 0, o_lev = 0, o_thr = 0, o_lcell = 0, o_ctile = 0, o_job = 0, o_thist = 0;
+    PoolParts pp{};
+};
+static void plan_quantile_tiers(const std::vector<uint64_t>& cell_off, size_t C, const QuantileOutputs& qo, ScratchLayout& lay, QuantileTiers& t) {
+    const uint32_t Q = qo.Q, T = qo.T;
+    for (size_t c = 0; c < C; ++c) {
+        const uint64_t len = cell_off[c + 1u] - cell_off[c];
+        if (len > afq::kSmallMax) {
+            t.lcells.push_back(afq::QCell{cell_off[c], (uint32_t)len, (uint32_t)c});
+        } else if (len > afq::kTinyMax) {
+            uint32_t pad = afq::kSmallMinPad;
+            while (pad < len) pad <<= 1;
+            t.small_by.push_back(QuantileTiers::SmallCell{pad, (uint32_t)c});
+        }
+    }
+    std::stable_sort(t.small_by.begin(), t.small_by.end(), [](const QuantileTiers::SmallCell& x, const QuantileTiers::SmallCell& y) { return x.pad < y.pad; });
+    t.small.resize(t.small_by.size());
+    for (size_t i = 0; i < t.small_by.size(); ++i) t.small[i] = t.small_by[i].cell;
+    const uint32_t n_small = (uint32_t)t.small.size(), n_large = (uint32_t)t.lcells.size();
+    const bool want_q = Q > 0 && qo.quantiles;
+    // large cells: their tiles, and a job per cell and kLv levels
+    uint64_t pieces_unused = 0;
+    for (uint32_t lc = 0; lc < n_large; ++lc) {
+        const uint32_t np = (uint32_t)(((uint64_t)t.lcells[lc].n + afp::kPiece - 1u) / afp::kPiece);
+        for (uint32_t p = 0; p < np; p += afp::kTilePieces) t.ctiles.push_back(afp::PoolTile{lc, p, std::min(afp::kTilePieces, np - p), 0u});
+        for (uint32_t l0 = 0; want_q && l0 < Q; l0 += afq::kLv) {
+            pool_add_group(t.jgroups, t.jtiles, pieces_unused, t.lcells[lc].off, t.lcells[lc].n);
+            t.jobs.push_back(afq::QJob{lc, l0, std::min<uint32_t>(afq::kLv, Q - l0), 0u});
+        }
+    }
+    const uint32_t n_jobs = (uint32_t)t.jobs.size(), n_ctiles = (uint32_t)t.ctiles.size();
+    t.o_small = lay.part((size_t)n_small * 4u);
+    t.o_lev = lay.part((size_t)Q * 8u);
+    t.o_thr = lay.part((size_t)T * 8u);
+    t.o_lcell = lay.part((size_t)n_large * sizeof(afq::QCell));
+    t.o_ctile = lay.part((size_t)n_ctiles * sizeof(afp::PoolTile));
+    t.o_job = lay.part((size_t)n_jobs * sizeof(afq::QJob));
+    t.o_thist = lay.part((size_t)n_large * T * 4u);
+    t.pp = n_jobs ? pool_parts(lay, n_jobs, t.jtiles.size(), 1u) : PoolParts{};
+}
+static int reduce_quantile_cells(af_engine_t* e, const QuantileTiers& t, const QuantileOutputs& qo, const double* lat, const uint64_t* d_cell_off, size_t C) {
+    hipStream_t st = e->stream;
+    unsigned char* b = e->d_pool;
+    const uint32_t Q = qo.Q, T = qo.T;
+    const uint32_t n_small = (uint32_t)t.small.size(), n_large = (uint32_t)t.lcells.size();
+    const uint32_t n_jobs = (uint32_t)t.jobs.size(), n_ctiles = (uint32_t)t.ctiles.size();
+    const bool want_q = Q > 0 && qo.quantiles, want_w = T > 0 && qo.within;
+    afq::QArgs qa{};
+    qa.lat = lat;
+    qa.cell_off = d_cell_off;
+    qa.n_lev = Q;
+    qa.n_thr = T;
+    qa.levels = reinterpret_cast<const double*>(b + t.o_lev);
+    qa.thr = reinterpret_cast<const double*>(b + t.o_thr);
+    qa.count = qo.count;
+    qa.quant = qo.quantiles;
+    qa.within = qo.within;
+    qa.small = reinterpret_cast<const uint32_t*>(b + t.o_small);
+    qa.lcells = reinterpret_cast<const afq::QCell*>(b + t.o_lcell);
+    qa.ctiles = reinterpret_cast<const afp::PoolTile*>(b + t.o_ctile);
+    qa.jobs = reinterpret_cast<const afq::QJob*>(b + t.o_job);
+    qa.thist = reinterpret_cast<uint32_t*>(b + t.o_thist);
+    if (Q) HIP_TRY(hipMemcpyAsync(b + t.o_lev, qo.levels, (size_t)Q * 8u, hipMemcpyHostToDevice, st));
+    if (T) HIP_TRY(hipMemcpyAsync(b + t.o_thr, qo.thresholds, (size_t)T * 8u, hipMemcpyHostToDevice, st));
+    if (n_small) HIP_TRY(hipMemcpyAsync(b + t.o_small, t.small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
+    if (qo.count || want_q || want_w) {
+        if (int rc = launch_tiny_tier(C, afq::kTinyWaves, [&](uint32_t blocks, uint64_t c0) {
+                hipLaunchKernelGGL(afq::af_q_tiny, dim3(blocks), dim3(afq::kTinyWaves * 64), 0, st, qa, c0, (uint64_t)C);
+            }))
+            return rc;
+        for (size_t i0 = 0; i0 < t.small_by.size();) {   // the small cells, one padded size after the other
+            size_t i1 = i0;
+            while (i1 < t.small_by.size() && t.small_by[i1].pad == t.small_by[i0].pad && i1 - i0 < kBlocksPerLaunch) ++i1;
+            hipLaunchKernelGGL(afq::af_q_small, dim3((uint32_t)(i1 - i0)), dim3(afq::kThreads), (size_t)t.small_by[i0].pad * 8u, st, qa, (uint32_t)i0, t.small_by[i0].pad);
+            HIP_TRY(hipGetLastError());
+            i0 = i1;
+        }
+    }
+    if (n_large) {
+        HIP_TRY(hipMemcpyAsync(b + t.o_lcell, t.lcells.data(), (size_t)n_large * sizeof(afq::QCell), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(b + t.o_ctile, t.ctiles.data(), (size_t)n_ctiles * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
+        afp::PoolArgs pa{};
+        pa.lat = const_cast<double*>(qa.lat);
+        if (n_jobs) {
+            pool_bind(pa, b, t.pp);
+            HIP_TRY(hipMemcpyAsync(b + t.o_job, t.jobs.data(), (size_t)n_jobs * sizeof(afq::QJob), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(pa.groups, t.jgroups.data(), (size_t)n_jobs * sizeof(afp::PoolGroup), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemcpyAsync(const_cast<afp::PoolTile*>(pa.tiles), t.jtiles.data(), t.jtiles.size() * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
+            HIP_TRY(hipMemsetAsync(pa.hist0, 0, (size_t)n_large * afp::kExpBins * 4u, st));   // (one per cell: the first n_large of the jobs')
+        }
+        if (want_w) HIP_TRY(hipMemsetAsync(qa.thist, 0, (size_t)n_large * T * 4u, st));
+        if (n_jobs || want_w) {
+            hipLaunchKernelGGL(afq::af_q_pass0, dim3(n_ctiles), dim3(afq::kThreads), 0, st, qa, pa.hist0);
+            HIP_TRY(hipGetLastError());
+        }
+        if (n_jobs) {
+            const uint32_t n_jtiles = (uint32_t)t.jtiles.size();
+            if (int rc = radix_levels(st, pa, n_jobs, n_jtiles, "quantile", [&](int level) { hipLaunchKernelGGL(afq::af_q_select, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa, level); }))
+                return rc;
+            HIP_TRY(hipMemsetAsync(pa.cand_n, 0, (size_t)n_jobs * afp::kRanks * 4u, st));
+            hipLaunchKernelGGL(afq::af_q_cand, dim3(n_jtiles), dim3(afq::kThreads), 0, st, pa);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(afq::af_q_final, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa);
+            HIP_TRY(hipGetLastError());
+        }
+        if (qo.count || want_w) {
+            hipLaunchKernelGGL(afq::af_q_large_rows, dim3(n_large), dim3(64), 0, st, qa);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    return AF_OK;
 }
 
 // Quantile analyzer (af_quantiles.hpp).  The cells are laid out and compacted as the windowed analyzer's (n_windows > 0; by the
@@ -3269,15 +3428,7 @@ static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quant
     if (qr->n_scenarios == 0 || qr->n_groups == 0) return fail(AF_ERR_INVALID, "empty quantiles request (n_scenarios and n_groups must be > 0)");
     const uint32_t n = qr->n_scenarios, G = qr->n_groups, cap = out->clock_capacity, Q = qr->n_levels, T = qr->n_thresholds;
     uint32_t W = qr->n_windows;   // the cells of a group laid out as windows (0: a cell per group over the whole run); by state: the keys
-    if (Q > AF_MAX_QUANTILE_LEVELS) return fail(AF_ERR_INVALID, "more than AF_MAX_QUANTILE_LEVELS (" + std::to_string(AF_MAX_QUANTILE_LEVELS) + ") levels");
-    if (T > AF_MAX_SLO_THRESHOLDS) return fail(AF_ERR_INVALID, "more than AF_MAX_SLO_THRESHOLDS (" + std::to_string(AF_MAX_SLO_THRESHOLDS) + ") thresholds");
-    if (Q == 0 && T == 0) return fail(AF_ERR_INVALID, "quantiles request without levels and without thresholds");
-    if (Q && !qr->levels) return fail(AF_ERR_INVALID, "quantiles.levels is required with n_levels > 0");
-    if (T && !qr->thresholds) return fail(AF_ERR_INVALID, "quantiles.thresholds is required with n_thresholds > 0");
-    for (uint32_t i = 0; i < Q; ++i)
-        if (!(qr->levels[i] >= 0.0 && qr->levels[i] <= 1.0)) return fail(AF_ERR_INVALID, "quantile level " + std::to_string(i) + " is not in [0, 1]");
-    for (uint32_t i = 0; i < T; ++i)
-        if (std::isnan(qr->thresholds[i])) return fail(AF_ERR_INVALID, "threshold " + std::to_string(i) + " is NaN");
+    if (int rc = check_quantile_levels(Q, qr->levels, T, qr->thresholds)) return rc;
     if (W > 0 && !qr->edges) return fail(AF_ERR_INVALID, "quantiles.edges is required with n_windows > 0");
     if (W == 0 && qr->edges) return fail(AF_ERR_INVALID, "quantiles.edges given with n_windows == 0 (whole-run mode takes none)");
     if (W > 0)
@@ -3308,43 +3459,9 @@ static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quant
     }
     const std::vector<uint64_t>& cell_off = W ? wc.cell_off : pc.cell_off;
     const size_t o_lat = W ? wc.o_lat : lay.part(cell_off[C] * 8u), o_dst = W ? 0u : lay.part((size_t)n * 8u), o_off = W ? wc.o_off : lay.part((C + 1u) * 8u);
-    // the tiers
-    struct SmallCell { uint32_t pad, cell; };
-    std::vector<SmallCell> small_by;
-    std::vector<afq::QCell> lcells;
-    for (size_t c = 0; c < C; ++c) {
-        const uint64_t len = cell_off[c + 1u] - cell_off[c];
-        if (len > afq::kSmallMax) {
-            lcells.push_back(afq::QCell{cell_off[c], (uint32_t)len, (uint32_t)c});
-        } else if (len > afq::kTinyMax) {
-            uint32_t pad = afq::kSmallMinPad;
-            while (pad < len) pad <<= 1;
-            small_by.push_back(SmallCell{pad, (uint32_t)c});
-        }
-    }
-    std::stable_sort(small_by.begin(), small_by.end(), [](const SmallCell& x, const SmallCell& y) { return x.pad < y.pad; });
-    std::vector<uint32_t> small(small_by.size());
-    for (size_t i = 0; i < small_by.size(); ++i) small[i] = small_by[i].cell;
-    const uint32_t n_small = (uint32_t)small.size(), n_large = (uint32_t)lcells.size();
-    const bool want_q = Q > 0 && qr->quantiles, want_w = T > 0 && qr->within;
-    // large cells: their tiles, and a job per cell and kLv levels
-    std::vector<afp::PoolTile> ctiles, jtiles;
-    std::vector<afp::PoolGroup> jgroups;
-    std::vector<afq::QJob> jobs;
-    uint64_t pieces_unused = 0;
-    for (uint32_t lc = 0; lc < n_large; ++lc) {
-        const uint32_t np = (uint32_t)(((uint64_t)lcells[lc].n + afp::kPiece - 1u) / afp::kPiece);
-        for (uint32_t p = 0; p < np; p += afp::kTilePieces) ctiles.push_back(afp::PoolTile{lc, p, std::min(afp::kTilePieces, np - p), 0u});
-        for (uint32_t l0 = 0; want_q && l0 < Q; l0 += afq::kLv) {
-            pool_add_group(jgroups, jtiles, pieces_unused, lcells[lc].off, lcells[lc].n);
-            jobs.push_back(afq::QJob{lc, l0, std::min<uint32_t>(afq::kLv, Q - l0), 0u});
-        }
-    }
-    const uint32_t n_jobs = (uint32_t)jobs.size(), n_ctiles = (uint32_t)ctiles.size();
-    const size_t o_small = lay.part((size_t)n_small * 4u), o_lev = lay.part((size_t)Q * 8u), o_thr = lay.part((size_t)T * 8u),
-                 o_lcell = lay.part((size_t)n_large * sizeof(afq::QCell)), o_ctile = lay.part((size_t)n_ctiles * sizeof(afp::PoolTile)),
-                 o_job = lay.part((size_t)n_jobs * sizeof(afq::QJob)), o_thist = lay.part((size_t)n_large * T * 4u);
-    const PoolParts pp = n_jobs ? pool_parts(lay, n_jobs, jtiles.size(), 1u) : PoolParts{};
+    const QuantileOutputs qo{Q, T, qr->levels, qr->thresholds, qr->count, qr->quantiles, qr->within};
+    QuantileTiers tiers;
+    plan_quantile_tiers(cell_off, C, qo, lay, tiers);
     if (W) {
         const int rc = compact_window_cells(e, lay, wc);
         qr->scratch_bytes = e->pool_cap;
@@ -3353,72 +3470,9 @@ static int summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_quant
         if (int rc = pool_reserve(e, lay.at)) return rc;
         qr->scratch_bytes = e->pool_cap;
         HIP_TRY(hipMemcpyAsync(e->d_pool + o_off, cell_off.data(), (C + 1u) * 8u, hipMemcpyHostToDevice, st));
-        if (int rc = compact_pooled_cells(e, out, qr->group, n, pc, o_dst, o_lat)) return rc;
+        if (int rc = compact_pooled_cells(e, out, qr->group, n, pc, o_dst, reinterpret_cast<double*>(e->d_pool + o_lat))) return rc;
     }
-    unsigned char* b = e->d_pool;
-    afq::QArgs qa{};
-    qa.lat = reinterpret_cast<double*>(b + o_lat);
-    qa.cell_off = reinterpret_cast<const uint64_t*>(b + o_off);
-    qa.n_lev = Q;
-    qa.n_thr = T;
-    qa.levels = reinterpret_cast<const double*>(b + o_lev);
-    qa.thr = reinterpret_cast<const double*>(b + o_thr);
-    qa.count = qr->count;
-    qa.quant = qr->quantiles;
-    qa.within = qr->within;
-    qa.small = reinterpret_cast<const uint32_t*>(b + o_small);
-    qa.lcells = reinterpret_cast<const afq::QCell*>(b + o_lcell);
-    qa.ctiles = reinterpret_cast<const afp::PoolTile*>(b + o_ctile);
-    qa.jobs = reinterpret_cast<const afq::QJob*>(b + o_job);
-    qa.thist = reinterpret_cast<uint32_t*>(b + o_thist);
-    if (Q) HIP_TRY(hipMemcpyAsync(b + o_lev, qr->levels, (size_t)Q * 8u, hipMemcpyHostToDevice, st));
-    if (T) HIP_TRY(hipMemcpyAsync(b + o_thr, qr->thresholds, (size_t)T * 8u, hipMemcpyHostToDevice, st));
-    if (n_small) HIP_TRY(hipMemcpyAsync(b + o_small, small.data(), (size_t)n_small * 4u, hipMemcpyHostToDevice, st));
-    if (qr->count || want_q || want_w) {
-        if (int rc = launch_tiny_tier(C, afq::kTinyWaves, [&](uint32_t blocks, uint64_t c0) {
-                hipLaunchKernelGGL(afq::af_q_tiny, dim3(blocks), dim3(afq::kTinyWaves * 64), 0, st, qa, c0, (uint64_t)C);
-            }))
-            return rc;
-        for (size_t i0 = 0; i0 < small_by.size();) {   // the small cells, one padded size after the other
-            size_t i1 = i0;
-            while (i1 < small_by.size() && small_by[i1].pad == small_by[i0].pad && i1 - i0 < kBlocksPerLaunch) ++i1;
-            hipLaunchKernelGGL(afq::af_q_small, dim3((uint32_t)(i1 - i0)), dim3(afq::kThreads), (size_t)small_by[i0].pad * 8u, st, qa, (uint32_t)i0, small_by[i0].pad);
-            HIP_TRY(hipGetLastError());
-            i0 = i1;
-        }
-    }
-    if (n_large) {
-        HIP_TRY(hipMemcpyAsync(b + o_lcell, lcells.data(), (size_t)n_large * sizeof(afq::QCell), hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(b + o_ctile, ctiles.data(), (size_t)n_ctiles * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
-        afp::PoolArgs pa{};
-        pa.lat = const_cast<double*>(qa.lat);
-        if (n_jobs) {
-            pool_bind(pa, b, pp);
-            HIP_TRY(hipMemcpyAsync(b + o_job, jobs.data(), (size_t)n_jobs * sizeof(afq::QJob), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(pa.groups, jgroups.data(), (size_t)n_jobs * sizeof(afp::PoolGroup), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemcpyAsync(const_cast<afp::PoolTile*>(pa.tiles), jtiles.data(), jtiles.size() * sizeof(afp::PoolTile), hipMemcpyHostToDevice, st));
-            HIP_TRY(hipMemsetAsync(pa.hist0, 0, (size_t)n_large * afp::kExpBins * 4u, st));   // (one per cell: the first n_large of the jobs')
-        }
-        if (want_w) HIP_TRY(hipMemsetAsync(qa.thist, 0, (size_t)n_large * T * 4u, st));
-        if (n_jobs || want_w) {
-            hipLaunchKernelGGL(afq::af_q_pass0, dim3(n_ctiles), dim3(afq::kThreads), 0, st, qa, pa.hist0);
-            HIP_TRY(hipGetLastError());
-        }
-        if (n_jobs) {
-            const uint32_t n_jtiles = (uint32_t)jtiles.size();
-            if (int rc = radix_levels(st, pa, n_jobs, n_jtiles, "quantile", [&](int level) { hipLaunchKernelGGL(afq::af_q_select, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa, level); }))
-                return rc;
-            HIP_TRY(hipMemsetAsync(pa.cand_n, 0, (size_t)n_jobs * afp::kRanks * 4u, st));
-            hipLaunchKernelGGL(afq::af_q_cand, dim3(n_jtiles), dim3(afq::kThreads), 0, st, pa);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(afq::af_q_final, dim3(n_jobs), dim3(afq::kThreads), 0, st, qa, pa);
-            HIP_TRY(hipGetLastError());
-        }
-        if (qr->count || want_w) {
-            hipLaunchKernelGGL(afq::af_q_large_rows, dim3(n_large), dim3(64), 0, st, qa);
-            HIP_TRY(hipGetLastError());
-        }
-    }
+    if (int rc = reduce_quantile_cells(e, tiers, qo, reinterpret_cast<const double*>(e->d_pool + o_lat), reinterpret_cast<const uint64_t*>(e->d_pool + o_off), C)) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     qr->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return AF_OK;
@@ -3427,6 +3481,163 @@ int af_engine_summarize_quantiles(af_engine_t* e, const af_outputs_t* out, af_qu
 int af_engine_summarize_arrival_quantiles(af_engine_t* e, const af_outputs_t* out, af_quantiles_t* qr) { return summarize_quantiles(e, out, qr, CellsBy::kArrival); }
 int af_engine_summarize_state_quantiles(af_engine_t* e, const af_outputs_t* out, const af_state_bins_t* sb, af_quantiles_t* qr) {
     return summarize_quantiles(e, out, qr, CellsBy::kState, sb);
+}
+
+// Cells across devices (af_cells.hpp), the exporting side: the windowed layout and compaction above with every scenario as its own
+// group -- so pre == 0 and a scenario's windows follow one another -- into the caller's buffer.  The bounds stay in the scratch
+// until the call cannot fail any more: a refused call writes nothing.
+int af_engine_export_cells(af_engine_t* e, const af_outputs_t* out, af_cells_export_t* ex) {
+    if (!e || !out || !ex) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (ex->n_scenarios == 0) return fail(AF_ERR_INVALID, "empty export request (n_scenarios must be > 0)");
+    if (!ex->seg_bounds) return fail(AF_ERR_INVALID, "cells_export.seg_bounds is required");
+    if (ex->lat_capacity > 0 && !ex->lat) return fail(AF_ERR_INVALID, "cells_export.lat is required with lat_capacity > 0");
+    if (ex->n_windows > 0 && !ex->edges) return fail(AF_ERR_INVALID, "cells_export.edges is required with n_windows > 0");
+    if (ex->n_windows == 0 && ex->edges) return fail(AF_ERR_INVALID, "cells_export.edges given with n_windows == 0 (the whole run takes none)");
+    if (ex->n_windows == 0 && ex->by_arrival) return fail(AF_ERR_INVALID, "an export by arrival time needs windows (n_windows must be > 0)");
+    if (!out->counts) return fail(AF_ERR_INVALID, "outputs.counts is required");
+    if (!out->clock || out->clock_capacity == 0) return fail(AF_ERR_INVALID, "the export of cells needs outputs.clock");
+    const uint32_t n = ex->n_scenarios, W = ex->n_windows;
+    if (W > 0)
+        if (int rc = check_window_edges(ex->edges, W)) return rc;
+    if ((uint64_t)n * std::max(W, 1u) >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * max(n_windows, 1) must be below 2^32 - 1");
+    if ((uint64_t)n * ((uint64_t)W + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (n_windows + 1) must be below 2^32");
+    const auto t0 = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(e->device));
+    std::vector<uint32_t> grp;   // (only AF_POOL_SKIP matters here: the ids are the importing call's to check)
+    if (int rc = read_groups(ex->group, n, 0xFFFFFFFFu, grp)) return rc;
+    hipStream_t st = e->stream;
+    ScratchLayout lay;
+    std::vector<uint32_t> own(n);   // every scenario its own group
+    for (uint32_t s = 0; s < n; ++s) own[s] = s;
+    if (W == 0) {   // the whole run: the pooled compaction, a scenario's rows behind those of the scenarios before it
+        PooledCells pc;   // (laid out for every scenario, the skipped ones too: cell_off[s + 1] - cell_off[s] is m_s)
+        if (int rc = layout_pooled_cells(out, own, n, n, "holds", pc)) return rc;
+        std::vector<uint32_t> hb((size_t)n * 2u);
+        uint64_t total = 0;
+        for (uint32_t s = 0; s < n; ++s) {
+            hb[2u * s] = 0u;
+            hb[2u * s + 1u] = (uint32_t)(pc.cell_off[s + 1u] - pc.cell_off[s]);
+            pc.dst[s] = total;
+            if (grp.empty() || grp[s] != afp::kSkip) total += hb[2u * s + 1u];
+        }
+        if (total > ex->lat_capacity)
+            return fail(AF_ERR_CAPACITY, "cells_export.lat_capacity " + std::to_string(ex->lat_capacity) + " is below the " + std::to_string(total) + " latencies to export");
+        const size_t o_dst = lay.part((size_t)n * 8u);
+        if (int rc = pool_reserve(e, lay.at)) return rc;
+        ex->scratch_bytes = e->pool_cap;
+        if (int rc = compact_pooled_cells(e, out, ex->group, n, pc, o_dst, ex->lat)) return rc;
+        HIP_TRY(hipMemcpyAsync(ex->seg_bounds, hb.data(), hb.size() * 4u, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ex->lat_count = total;
+    } else {
+        for (uint32_t s = 0; s < n; ++s)
+            if (!grp.empty() && grp[s] == afp::kSkip) own[s] = afp::kSkip;
+        WindowCells wc;
+        wc.lat_dst = ex->lat;
+        wc.own_group = &own;
+        wc.o_group = lay.part((size_t)n * 4u);
+        if (int rc = layout_window_cells(e, out, nullptr, own, n, n, W, ex->edges, nullptr, ex->by_arrival ? CellsBy::kArrival : CellsBy::kFinish, nullptr, lay, wc))
+            return rc;
+        const uint64_t total = wc.cell_off[(size_t)n * W];
+        if (total > ex->lat_capacity)
+            return fail(AF_ERR_CAPACITY, "cells_export.lat_capacity " + std::to_string(ex->lat_capacity) + " is below the " + std::to_string(total) + " latencies to export");
+        const int rc = compact_window_cells(e, lay, wc);
+        ex->scratch_bytes = e->pool_cap;
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(ex->seg_bounds, wc.hb.data(), wc.hb.size() * 4u, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        ex->lat_count = total;
+    }
+    ex->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
+}
+
+// ... and the importing side: the segments are checked and the cells laid out on the host from the bounds alone, af_cells_merge
+// brings every member's segment to its cells, and the windowed / quantile tiers above reduce the merged array.
+int af_engine_import_cells(af_engine_t* e, af_cells_t* cr) {
+    if (!e || !cr) return fail(AF_ERR_INVALID, "NULL argument");
+    if (e->plan_only) return fail(AF_ERR_NO_DEVICE, "planning-only engine (AF_DEVICE_PLAN_ONLY)");
+    if (cr->n_scenarios == 0 || cr->n_groups == 0) return fail(AF_ERR_INVALID, "empty cells request (n_scenarios and n_groups must be > 0)");
+    if (!cr->seg_bounds || !cr->seg_begin) return fail(AF_ERR_INVALID, "cells.seg_bounds and cells.seg_begin are required");
+    if (cr->n_lat > 0 && !cr->lat) return fail(AF_ERR_INVALID, "cells.lat is required with n_lat > 0");
+    const uint32_t n = cr->n_scenarios, G = cr->n_groups, Wc = std::max(cr->n_windows, 1u), Q = cr->n_levels, T = cr->n_thresholds;
+    const bool want_quantiles = cr->count || cr->quantiles || cr->within;
+    if (!cr->stats && !want_quantiles) return fail(AF_ERR_INVALID, "cells request without an output (stats, count, quantiles or within)");
+    if (want_quantiles)
+        if (int rc = check_quantile_levels(Q, cr->levels, T, cr->thresholds)) return rc;
+    if ((uint64_t)G * Wc >= 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_groups * max(n_windows, 1) must be below 2^32 - 1");
+    if ((uint64_t)n * ((uint64_t)Wc + 1u) > 0xFFFFFFFFull) return fail(AF_ERR_CAPACITY, "n_scenarios * (max(n_windows, 1) + 1) must be below 2^32");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<uint32_t> grp;
+    if (cr->group) grp.assign(cr->group, cr->group + n);
+    if (int rc = check_group_ids(grp, G)) return rc;
+    // the segments: inside the imported array, no two of them overlapping
+    const size_t C = (size_t)G * Wc;
+    std::vector<std::pair<uint64_t, uint64_t>> segs;   // (begin, length) of the members that bring something
+    for (uint32_t s = 0; s < n; ++s) {
+        if (!grp.empty() && grp[s] == afc::kSkip) continue;
+        const uint32_t* r = cr->seg_bounds + (size_t)s * (Wc + 1u);
+        if (r[Wc] < r[0]) return fail(AF_ERR_INVALID, "cells.seg_bounds of scenario " + std::to_string(s) + " decrease");
+        const uint64_t len = r[Wc] - r[0], begin = cr->seg_begin[s];
+        if (begin > cr->n_lat || len > cr->n_lat - begin)
+            return fail(AF_ERR_INVALID, "the segment of scenario " + std::to_string(s) + " (" + std::to_string(begin) + " + " + std::to_string(len) + ") ends past n_lat " + std::to_string(cr->n_lat));
+        if (len) segs.emplace_back(begin, len);
+    }
+    std::sort(segs.begin(), segs.end());
+    for (size_t i = 1; i < segs.size(); ++i)
+        if (segs[i].first < segs[i - 1u].first + segs[i - 1u].second)
+            return fail(AF_ERR_INVALID, "two segments overlap (at element " + std::to_string(segs[i].first) + " of cells.lat)");
+    std::vector<uint64_t> cell_off;
+    std::vector<uint32_t> pre;
+    const afc::LayoutResult lr = afc::layout_cells(cr->seg_bounds, grp, n, G, Wc, true, cell_off, pre);
+    if (lr.error == afc::LayoutError::kOrder) return fail(AF_ERR_INVALID, "cells.seg_bounds of scenario " + std::to_string(lr.scenario) + " decrease");
+    if (lr.error == afc::LayoutError::kCellTooLarge)
+        return fail(AF_ERR_CAPACITY, "window " + std::to_string(lr.window) + " of group " + std::to_string(lr.group) + " holds 2^32 or more latencies");
+    HIP_TRY(hipSetDevice(e->device));
+    hipStream_t st = e->stream;
+    ScratchLayout lay;
+    const size_t NE = (size_t)n * (Wc + 1u);
+    const size_t o_lat = lay.part(cell_off[C] * 8u), o_bounds = lay.part(NE * 4u), o_pre = lay.part((size_t)n * Wc * 4u), o_off = lay.part((C + 1u) * 8u),
+                 o_begin = lay.part((size_t)n * 8u), o_group = lay.part((size_t)n * 4u);
+    WindowTiers wt;
+    QuantileTiers qt;
+    const QuantileOutputs qo{Q, T, cr->levels, cr->thresholds, cr->count, cr->quantiles, cr->within};
+    if (cr->stats) plan_window_tiers(cell_off, C, lay, wt);
+    if (want_quantiles) plan_quantile_tiers(cell_off, C, qo, lay, qt);
+    if (int rc = pool_reserve(e, lay.at)) return rc;
+    cr->scratch_bytes = e->pool_cap;
+    unsigned char* b = e->d_pool;
+    HIP_TRY(hipMemcpyAsync(b + o_bounds, cr->seg_bounds, NE * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_pre, pre.data(), pre.size() * 4u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_off, cell_off.data(), cell_off.size() * 8u, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(b + o_begin, cr->seg_begin, (size_t)n * 8u, hipMemcpyHostToDevice, st));
+    if (!grp.empty()) HIP_TRY(hipMemcpyAsync(b + o_group, grp.data(), (size_t)n * 4u, hipMemcpyHostToDevice, st));
+    afc::MergeArgs m{};
+    m.src = cr->lat;
+    m.begin = reinterpret_cast<const uint64_t*>(b + o_begin);
+    m.bounds = reinterpret_cast<const uint32_t*>(b + o_bounds);
+    m.pre = reinterpret_cast<const uint32_t*>(b + o_pre);
+    m.cell_off = reinterpret_cast<const uint64_t*>(b + o_off);
+    m.group = grp.empty() ? nullptr : reinterpret_cast<const uint32_t*>(b + o_group);
+    m.n_win = Wc;
+    m.lat = reinterpret_cast<double*>(b + o_lat);
+    if (Wc <= afc::kLdsWindows)
+        hipLaunchKernelGGL(afc::af_cells_merge<true>, dim3(n), dim3(afc::kThreads), (size_t)Wc * 8u + ((size_t)Wc + 1u) * 4u, st, m);
+    else
+        hipLaunchKernelGGL(afc::af_cells_merge<false>, dim3(n), dim3(afc::kThreads), 0, st, m);
+    HIP_TRY(hipGetLastError());
+    if (cr->stats) {
+        afw::WinArgs a{};
+        a.lat = m.lat;
+        a.cell_off = m.cell_off;
+        if (int rc = reduce_window_cells(e, wt, a, C, cr->stats)) return rc;
+    }
+    if (want_quantiles)
+        if (int rc = reduce_quantile_cells(e, qt, qo, m.lat, m.cell_off, C)) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    cr->elapsed_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return AF_OK;
 }
 
 // Sampled-series analyzer per (group, window of ticks) (af_series_windows.hpp).  The host reads the group ids and the counts

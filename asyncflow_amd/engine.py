@@ -340,6 +340,64 @@ class Engine:
         _check(self._lib, getattr(self._lib, name)(self._h, C.byref(out), C.byref(req)), name)
         return float(req.elapsed_ms), int(req.scratch_bytes)
 
+    def export_cells(self, n: int, *, edges: Any = None, clock_ptr: int, clock_capacity: int, counts_ptr: int, lat_ptr: int,
+                     lat_capacity: int, seg_bounds_ptr: int, group_ptr: int = 0, window_of: str = "finish") -> tuple[int, float, int]:
+        """The exporting side of the cells across devices (``af_engine_export_cells``): the latencies of the ``n`` scenarios
+        that fall into the windows, scenario after scenario and window after window, into ``lat`` (DEVICE float64
+        [lat_capacity], the caller's), and the windows' bounds into ``seg_bounds`` (DEVICE uint32 [n, W + 1]; ``edges``
+        None: the whole run, W = 1 and the bounds (0, stored rows)).  ``group_ptr``: DEVICE uint32 [n], only
+        ``_abi.POOL_SKIP`` matters (nothing is exported for the scenario).  ``window_of`` as in :meth:`summarize_windows`.
+        Returns the elements written, the call's wall time in ms and the engine's scratch size in bytes."""
+        from .results import check_window_of
+
+        by_arrival = check_window_of(window_of) == "arrival"
+        e = None
+        if edges is not None:
+            e = np.ascontiguousarray(edges, dtype=np.float64)
+            if e.ndim != 1 or e.shape[0] < 2:
+                msg = f"window edges must be a vector of at least two values, not of shape {e.shape}"
+                raise ValueError(msg)
+        out = _abi.AfOutputs(int(clock_capacity), C.c_void_p(clock_ptr or None), 0, None, C.c_void_p(counts_ptr))
+        req = _abi.AfCellsExport(int(n), 0 if e is None else int(e.shape[0] - 1), int(by_arrival), C.c_void_p(group_ptr or None),
+                                 e.ctypes.data_as(C.POINTER(C.c_double)) if e is not None else None, C.c_void_p(lat_ptr or None),
+                                 int(lat_capacity), C.c_void_p(seg_bounds_ptr or None), 0, 0.0, 0)
+        _check(self._lib, self._lib.af_engine_export_cells(self._h, C.byref(out), C.byref(req)), "af_engine_export_cells")
+        return int(req.lat_count), float(req.elapsed_ms), int(req.scratch_bytes)
+
+    def import_cells(self, n_groups: int, n_windows: int, seg_bounds: Any, seg_begin: Any, *, lat_ptr: int, n_lat: int,
+                        group: Any = None, stats_ptr: int = 0, levels: Any = None, thresholds: Any = None, count_ptr: int = 0,
+                        quantiles_ptr: int = 0, within_ptr: int = 0) -> tuple[float, int]:
+        """The importing side (``af_engine_import_cells``): the exported segments in ``lat`` (DEVICE float64 [n_lat], on
+        this engine's device) are merged into the cells of the members' groups and reduced.  ``seg_bounds``: HOST uint32
+        [n, Wc + 1] and ``seg_begin``: HOST uint64 [n], the members in the order the cells concatenate them (Wc =
+        max(n_windows, 1)); ``group``: HOST uint32 [n] (``_abi.POOL_SKIP`` leaves a member out) or None.  Outputs, each
+        optional: ``stats_ptr`` f64 [n_groups, Wc, 8] as :meth:`summarize_windows`; ``count_ptr`` / ``quantiles_ptr`` /
+        ``within_ptr`` with ``levels`` / ``thresholds`` as :meth:`summarize_quantiles`.  Returns the call's wall time in ms
+        and the engine's scratch size in bytes."""
+        from .results import check_levels, check_slo_thresholds
+
+        wc = max(int(n_windows), 1)
+        b = np.ascontiguousarray(seg_bounds, dtype=np.uint32)
+        if b.ndim != 2 or b.shape[1] != wc + 1:
+            msg = f"seg_bounds must be [n, {wc + 1}], not of shape {b.shape}"
+            raise ValueError(msg)
+        n = int(b.shape[0])
+        begin = np.ascontiguousarray(seg_begin, dtype=np.uint64)
+        g = None if group is None else np.ascontiguousarray(group, dtype=np.uint32)
+        if begin.shape != (n,) or (g is not None and g.shape != (n,)):
+            msg = f"seg_begin and group must be vectors of {n} members"
+            raise ValueError(msg)
+        q = np.ascontiguousarray(check_levels([] if levels is None else levels))
+        th = np.ascontiguousarray(check_slo_thresholds(thresholds))
+        pd, pu32 = C.POINTER(C.c_double), C.POINTER(C.c_uint32)
+        req = _abi.AfCells(n, int(n_groups), int(n_windows), g.ctypes.data_as(pu32) if g is not None else None, b.ctypes.data_as(pu32),
+                           begin.ctypes.data_as(C.POINTER(C.c_uint64)), C.c_void_p(lat_ptr or None), int(n_lat), C.c_void_p(stats_ptr or None),
+                           int(q.shape[0]), q.ctypes.data_as(pd) if q.shape[0] else None,
+                           int(th.shape[0]), th.ctypes.data_as(pd) if th.shape[0] else None,
+                           C.c_void_p(count_ptr or None), C.c_void_p(quantiles_ptr or None), C.c_void_p(within_ptr or None), 0.0, 0)
+        _check(self._lib, self._lib.af_engine_import_cells(self._h, C.byref(req)), "af_engine_import_cells")
+        return float(req.elapsed_ms), int(req.scratch_bytes)
+
     def summarize_arrivals(self, seeds: Any, overrides: Sequence[tuple[int, int, np.ndarray]], n_groups: int, edges: Any, *,
                            draw_capacity: int, arrivals_ptr: int, group_ptr: int = 0, row_bounds_ptr: int = 0,
                            generated_ptr: int = 0, flags_ptr: int = 0, times_ptr: int = 0, times_given: bool = False,

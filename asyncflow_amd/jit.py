@@ -29,7 +29,7 @@ from .build import ARCH, CSRC, hipcc_path
 
 CACHE_DIR = Path(os.environ["ASYNCFLOW_JIT_CACHE"]) if os.environ.get("ASYNCFLOW_JIT_CACHE") else CSRC / "_jit"
 _FALLBACK_CACHE_DIR = Path.home() / ".cache" / "asyncflow_amd" / "jit"
-_SOURCES = ("engine.hip", "af_flow.hpp", "af_flow_host.hpp", "af_core.hpp", "af_math.hpp", "af_plan_pack.hpp", "af_summary.hpp", "af_select.hpp", "af_pooled.hpp", "af_windowed.hpp", "af_arrival.hpp", "af_state.hpp", "af_series_windows.hpp", "af_series_quantiles.hpp", "af_series_excursions.hpp", "af_series_histogram.hpp", "af_series_combined.hpp", "af_series_joint.hpp", "af_series_warmup.hpp", "af_wide.hpp", "af_quantiles.hpp", "af_pregen.hpp", "af_arrival_counts.hpp", "af_inflight.hpp", "af_exemplars.hpp", "af_latency_histogram.hpp", "af_paired.hpp", "af_alerts.hpp", "af_alert_outcomes.hpp")
+_SOURCES = ("engine.hip", "af_flow.hpp", "af_flow_host.hpp", "af_core.hpp", "af_math.hpp", "af_plan_pack.hpp", "af_summary.hpp", "af_select.hpp", "af_pooled.hpp", "af_windowed.hpp", "af_arrival.hpp", "af_state.hpp", "af_series_windows.hpp", "af_series_quantiles.hpp", "af_series_excursions.hpp", "af_series_histogram.hpp", "af_series_combined.hpp", "af_series_joint.hpp", "af_series_warmup.hpp", "af_wide.hpp", "af_quantiles.hpp", "af_cells.hpp", "af_pregen.hpp", "af_arrival_counts.hpp", "af_inflight.hpp", "af_exemplars.hpp", "af_latency_histogram.hpp", "af_paired.hpp", "af_alerts.hpp", "af_alert_outcomes.hpp")
 _FLAGS = (f"--offload-arch={ARCH}", "--genco", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
           "-Wno-unused-function",
           # the five stations of af_flow_jit are unrolled by pragma (af_flow.hpp, Flow::run): no size limit on that

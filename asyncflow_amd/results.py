@@ -3315,7 +3315,7 @@ class BatchedResults:
         group (``by``) and window, over the group's replicas whose window is not empty (``n`` [G, W] of them): ``mean``,
         unbiased ``std``, normal confidence half-width ``ci_halfwidth`` at ``level`` and the linear quantiles ``q_lo`` /
         ``q_hi`` (``q``) of each of the eight statistics, numpy float64 [G, W, 8] each (NaN where no replica has a
-        completion in the window; ``std`` NaN below two).  Reduced on the device; ``pooled`` is
+        completion in the window; ``std`` NaN below two).  The same bits in every run (:func:`window_bands_by_group`); ``pooled`` is
         ``window_summary(by=by)["stats"]`` as numpy.  ``window_of`` as in :meth:`window_summary`, for both."""
         e = _resolve_edges(window_s, edges, self.plan.total_time)
         ids, n_groups = self._window_groups(by)
@@ -4178,13 +4178,33 @@ class BatchedResults:
             len(self), n_groups, q, edges=e, thresholds=th, clock_ptr=clock.data_ptr(), clock_capacity=int(clock.shape[1]),
             counts_ptr=self._counts_t.data_ptr(), count_ptr=count.data_ptr(), quantiles_ptr=quant.data_ptr() if q.shape[0] else 0,
             within_ptr=within.data_ptr() if th.shape[0] else 0, group_ptr=grp.data_ptr(), window_of=window_of)
-        cnt = count.to(torch.int64) & 0xFFFFFFFF   # (the device's words are uint32)
-        wth = within.to(torch.int64) & 0xFFFFFFFF
-        nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
-        share = torch.where((cnt > 0)[:, :, None], wth.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)[:, :, None], nan)
-        return {"quantiles": quant, "count": cnt, "within": wth, "share": share, "levels": q, "thresholds": th, "edges": e,
-                "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "quantile_ms": ms, "scratch_bytes": scratch,
-                "window_of": window_of}
+        return _finish_quantile_summary(quant, count, within, q, th, e, ids, n_groups, ms, scratch, window_of)
+
+    def _export_cells(self, e: np.ndarray | None, ids: np.ndarray, window_of: str) -> tuple[Any, Any, float, int]:
+        """This run's part of cells that span several runs (``af_engine_export_cells``): the latencies of its scenarios that
+        fall into the windows ``e`` (None: the whole run), scenario-major, as a float64 tensor on the run's device, and the
+        windows' bounds as an int32 tensor [n, W + 1] (uint32 words).  ``ids`` [n]: a negative id exports nothing for the
+        scenario.  Also the call's wall time in ms and the engine's scratch size."""
+        import torch
+
+        from .engine import Engine
+
+        self._require_clock()
+        clock = self._clock_t
+        dev = clock.device
+        n, cap = len(self), int(clock.shape[1])
+        n_win = 1 if e is None else int(e.shape[0] - 1)
+        capacity = int(np.minimum(self.counts[:, _abi.CNT_COMPLETED].astype(np.int64), cap).sum())   # always suffices
+        lat = torch.empty(capacity, dtype=torch.float64, device=dev)
+        bounds = torch.empty((n, n_win + 1), dtype=torch.int32, device=dev)
+        grp = torch.from_numpy(np.where(ids < 0, _abi.POOL_SKIP, 0).astype(np.uint32).view(np.int32)).to(dev)
+        torch.cuda.synchronize(dev)
+        if self._summ_engine is None:
+            self._summ_engine = Engine(self.plan, dev.index if dev.index is not None else torch.cuda.current_device())
+        count, ms, scratch = self._summ_engine.export_cells(
+            n, edges=e, clock_ptr=clock.data_ptr(), clock_capacity=cap, counts_ptr=self._counts_t.data_ptr(), lat_ptr=lat.data_ptr(),
+            lat_capacity=capacity, seg_bounds_ptr=bounds.data_ptr(), group_ptr=grp.data_ptr(), window_of=window_of)
+        return lat[:count], bounds, ms, scratch
 
     def quantile_bands(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
                        by: Any = None, level: float = 0.95, q: tuple[float, float] = (0.05, 0.95),
@@ -5441,11 +5461,40 @@ def resolve_groups(by: Any, n: int) -> tuple[np.ndarray, int]:
     return ids, n_groups
 
 
+def _sum_rows_by_cell(index: Any, body: Any, cells: int) -> Any:
+    """Per cell the float64 sum of its rows of ``body`` [N, K] (``index`` [N]: the row's cell), on ``body``'s device and the same
+    bits in every run: the rows are sorted by cell (stably: a cell's rows stay in row order) and every cell is added up as a
+    fixed binary tree -- row 0 + row 1, row 2 + row 3, ... level after level, ceil(log2(largest cell)) elementwise steps, no
+    atomics.  The tree depends on the cells' sizes alone, so a sweep on one device and on several give the same words.  (A device
+    ``index_add_`` adds floats atomically, in no fixed order: an ulp of difference from run to run.)  An empty cell: 0."""
+    import torch
+
+    dev = body.device
+    cells = int(cells)
+    idx, order = torch.sort(index.to(torch.int64), stable=True)
+    v = body.to(torch.float64)[order]
+    c = torch.bincount(idx, minlength=cells)                     # rows per cell, at this level of the tree
+    out = torch.zeros((cells, int(body.shape[1])), dtype=torch.float64, device=dev)
+    if v.shape[0] == 0:
+        return out
+    cell_ids = torch.arange(cells, device=dev)
+    for _ in range((int(c.max()) - 1).bit_length()):
+        cell = torch.repeat_interleave(cell_ids, c)
+        rank = torch.arange(v.shape[0], device=dev) - (torch.cumsum(c, 0) - c)[cell]
+        first = rank % 2 == 0
+        paired = first & (rank + 1 < c[cell])                    # the row has a right neighbour in its cell
+        v = torch.where(paired[:, None], v + torch.roll(v, -1, 0), v)[first]
+        c = (c + 1) // 2
+    out[c > 0] = v + 0.0                                         # (one row per non-empty cell, in cell order; -0.0 + 0.0 = 0.0 as a sum from 0 gives)
+    return out
+
+
 def aggregate_by_group(summ: dict[str, Any], ids: np.ndarray, n_groups: int, level: float = 0.95) -> dict[str, Any]:
     """:func:`aggregate_summary` per group (``ids`` from :func:`resolve_groups`): for every group the mean, unbiased
     standard deviation and normal confidence half-width of each per-replica statistic over its scenarios with >= 1
     completion (``n`` [G] of them), and per 1-s window the mean and the 5th / 95th linear quantiles of the RPS over
-    the group's scenarios.  Reduced on the device (no loop over groups); returned as numpy arrays [G, 8] / [G, T]."""
+    the group's scenarios.  Reduced on the device, no loop over groups; the float sums as fixed trees (:func:`_sum_rows_by_cell`): the
+    same bits in every run.  Returned as numpy arrays [G, 8] / [G, T]."""
     from statistics import NormalDist
 
     import torch
@@ -5458,9 +5507,9 @@ def aggregate_by_group(summ: dict[str, Any], ids: np.ndarray, n_groups: int, lev
     z = NormalDist().inv_cdf(0.5 + level / 2.0)
     g_ok, body = gid[ok], st[ok]
     k = torch.bincount(g_ok, minlength=n_groups).to(torch.float64)
-    total = torch.zeros((n_groups, 8), dtype=torch.float64, device=dev).index_add_(0, g_ok, body)
+    total = _sum_rows_by_cell(g_ok, body, n_groups)
     mean = total / k[:, None]
-    dev2 = torch.zeros((n_groups, 8), dtype=torch.float64, device=dev).index_add_(0, g_ok, (body - mean[g_ok]) ** 2)
+    dev2 = _sum_rows_by_cell(g_ok, (body - mean[g_ok]) ** 2, n_groups)
     sd = torch.where((k > 1)[:, None], (dev2 / (k - 1.0).clamp(min=1.0)[:, None]).sqrt(), torch.full_like(dev2, float("nan")))
     mean = torch.where((k > 0)[:, None], mean, torch.full_like(mean, float("nan")))
     out: dict[str, Any] = {
@@ -5477,8 +5526,7 @@ def aggregate_by_group(summ: dict[str, Any], ids: np.ndarray, n_groups: int, lev
         g = gid[member]
         T = int(r.shape[1])
         c = torch.bincount(g, minlength=n_groups)
-        out["rps_mean"] = (torch.zeros((n_groups, T), dtype=torch.float64, device=dev).index_add_(0, g, r)
-                           / c.to(torch.float64)[:, None]).cpu().numpy()
+        out["rps_mean"] = (_sum_rows_by_cell(g, r, n_groups) / c.to(torch.float64)[:, None]).cpu().numpy()
         # every window sorted by value, then (stably) by group: each group's values ascending in one segment
         v, order = torch.sort(r, dim=0, stable=True)
         gs = g[order]
@@ -5508,7 +5556,8 @@ def window_bands_by_group(per: Any, ids: np.ndarray, n_groups: int, level: float
     (``ids`` from :func:`resolve_groups`), per window, over the scenarios whose window is ``valid`` (torch bool [n, W];
     None: the latency statistics' rule, ``per[:, :, 0] > 0``, the windows that hold a completion): see
     :meth:`BatchedResults.window_bands` (K = 8) and :meth:`BatchedResults.series_window_bands` (K = the sampled series).
-    Reduced on ``per``'s device without a loop over groups or windows."""
+    Reduced on ``per``'s device without a loop over groups or windows, the float sums as fixed trees (:func:`_sum_rows_by_cell`):
+    the same bits in every run."""
     from statistics import NormalDist
 
     import torch
@@ -5524,9 +5573,9 @@ def window_bands_by_group(per: Any, ids: np.ndarray, n_groups: int, level: float
     c = torch.bincount(k_ok, minlength=cells)
     k = c.to(torch.float64)
     nan = torch.full((cells, n_col), float("nan"), dtype=torch.float64, device=dev)
-    total = torch.zeros((cells, n_col), dtype=torch.float64, device=dev).index_add_(0, k_ok, body)
+    total = _sum_rows_by_cell(k_ok, body, cells)
     mean = total / k[:, None]
-    dev2 = torch.zeros((cells, n_col), dtype=torch.float64, device=dev).index_add_(0, k_ok, (body - mean[k_ok]) ** 2)
+    dev2 = _sum_rows_by_cell(k_ok, (body - mean[k_ok]) ** 2, cells)
     sd = torch.where((k > 1)[:, None], (dev2 / (k - 1.0).clamp(min=1.0)[:, None]).sqrt(), nan)
     mean = torch.where((k > 0)[:, None], mean, nan)
     shape = (n_groups, n_win, n_col)
@@ -5594,6 +5643,64 @@ def _save_latency_histogram(summ: dict[str, Any], path: str, by: Any) -> dict[st
     cols["window_of"] = np.asarray(p["window_of"])
     _write_columns(path, cols, n_groups)
     return cols
+
+
+def _finish_quantile_summary(quant: Any, count: Any, within: Any, q: np.ndarray, th: np.ndarray, e: np.ndarray | None, ids: np.ndarray,
+                             n_groups: int, ms: float, scratch: int, window_of: str) -> dict[str, Any]:
+    """What ``quantile_summary`` returns, from the device's words: the counts as int64 and the shares."""
+    import torch
+
+    cnt = count.to(torch.int64) & 0xFFFFFFFF   # (the device's words are uint32)
+    wth = within.to(torch.int64) & 0xFFFFFFFF
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=quant.device)
+    share = torch.where((cnt > 0)[:, :, None], wth.to(torch.float64) / cnt.clamp(min=1).to(torch.float64)[:, :, None], nan)
+    return {"quantiles": quant, "count": cnt, "within": wth, "share": share, "levels": q, "thresholds": th, "edges": e,
+            "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "quantile_ms": ms, "scratch_bytes": scratch,
+            "window_of": window_of}
+
+
+def sweep_order_segments(bounds: Any, index: Any, ids: Any) -> tuple[np.ndarray, np.ndarray, int]:
+    """The exports of several runs (:meth:`BatchedResults._export_cells`) as ONE list of segments in the order of the whole
+    sweep.  ``bounds[k]``: run k's window bounds, uint32 [n_k, W + 1]; ``index[k]`` [n_k]: its scenarios' places in the
+    sweep; ``ids`` [n]: the sweep's group ids (negative: nothing was exported for the scenario).  A run's export holds its
+    scenarios' segments one after the other, ``bounds[s][W] - bounds[s][0]`` latencies each, and the exports are
+    concatenated in run order.  Returns the bounds [n, W + 1] and the segments' first elements uint64 [n] in sweep order,
+    and the length of the concatenation."""
+    ids = np.asarray(ids)
+    n = int(sum(len(ix) for ix in index))
+    width = int(np.asarray(bounds[0]).shape[1])
+    out_b = np.zeros((n, width), dtype=np.uint32)
+    begin = np.zeros(n, dtype=np.uint64)
+    base = 0
+    for b, ix in zip(bounds, index):
+        b, ix = np.asarray(b, dtype=np.uint32), np.asarray(ix, dtype=np.int64)
+        length = np.where(ids[ix] < 0, 0, b[:, -1].astype(np.int64) - b[:, 0].astype(np.int64))
+        out_b[ix] = b
+        begin[ix] = (base + np.cumsum(length) - length).astype(np.uint64)
+        base += int(length.sum())
+    return out_b, begin, base
+
+
+def merge_cell_segments(parts: Any, index: Any, ids: Any, n_groups: int, W: int) -> list[np.ndarray]:
+    """Host definition of the cells across devices (``af_engine_import_cells``): ``parts[k] = (lat, bounds)`` is run k's
+    export, ``index`` / ``ids`` as in :func:`sweep_order_segments`, ``W`` the number of windows (0: the whole run, one cell
+    per group).  Returns the ``n_groups * max(W, 1)`` cells, cell ``g * max(W, 1) + w`` the concatenation, in ascending
+    sweep index over the members of group g, of the members' window w: the arrays the statistics are numpy's on."""
+    ids = np.asarray(ids)
+    wc = max(int(W), 1)
+    bounds, begin, total = sweep_order_segments([p[1] for p in parts], index, ids)
+    lat = np.concatenate([np.asarray(p[0], dtype=np.float64).reshape(-1) for p in parts]) if parts else np.zeros(0)
+    if lat.shape[0] != total or bounds.shape[1] != wc + 1:
+        msg = f"the exports hold {lat.shape[0]} latencies and {bounds.shape[1] - 1} windows, their bounds say {total} and the request {wc}"
+        raise ValueError(msg)
+    cells: list[list[np.ndarray]] = [[] for _ in range(int(n_groups) * wc)]
+    for s in range(ids.shape[0]):
+        if ids[s] < 0:
+            continue
+        at = int(begin[s]) - int(bounds[s, 0])
+        for w in range(wc):
+            cells[int(ids[s]) * wc + w].append(lat[at + int(bounds[s, w]): at + int(bounds[s, w + 1])])
+    return [np.concatenate(c) if c else np.zeros(0, dtype=np.float64) for c in cells]
 
 
 class ShardedResults:
@@ -5989,6 +6096,143 @@ class ShardedResults:
     def save_quantile_summary(self, *a: Any, **kw: Any) -> dict[str, np.ndarray]:
         msg = "save_quantile_summary() of a sweep run on several devices: quantiles across devices are not implemented"
         raise NotImplementedError(msg)
+
+
+class ShardedCellResults(ShardedResults):
+    """What ``SimulationRunner(devices=[...])`` returns: a :class:`ShardedResults` whose shards are live runs of ONE process, so
+    that the cells of the exact grouped latency analyzers can cross the devices (csrc/af_cells.hpp).  A plain
+    :class:`ShardedResults` -- shards put behind an index by hand -- keeps refusing them."""
+
+    # ---- the exact grouped latency analyzers: cells across devices (csrc/af_cells.hpp) ------------------------------------------
+    # A cell's sample is ONE array in a fixed order (ascending scenario index, then row order), and the members of a group sit on
+    # several devices.  Every shard exports, on its own device, only the latencies that fall into the windows (8 B each); the
+    # exports are concatenated on the first shard's device, their bounds and places reordered into sweep order on the host
+    # (metadata only), and the first shard's analyzer engine merges them into the very array the unsharded call compacts and
+    # reduces it with the same kernels: every word equals the unsharded run's.  The bands and the dumps compose from these
+    # exactly as BatchedResults' do: they ARE its methods.
+
+    def _require_clock(self) -> None:
+        for s in self.shards:
+            s._require_clock()  # noqa: SLF001
+
+    def _window_groups(self, by: Any) -> tuple[np.ndarray, int]:
+        return self._histogram_groups(by)
+
+    def _behind_index(self, parts: list[Any]) -> Any:
+        """Per-scenario tensors of the shards, concatenated on the first shard's device in the order of the original sweep."""
+        import torch
+
+        dev = parts[0].device
+        order = torch.as_tensor(np.argsort(np.concatenate(self.index), kind="stable"), device=dev)
+        return torch.cat([p.to(dev) for p in parts], dim=0).index_select(0, order)
+
+    def _summarize_cells(self, e: np.ndarray | None, ids: np.ndarray, n_groups: int, window_of: str, *, stats: bool = False,
+                         levels: np.ndarray | None = None, thresholds: np.ndarray | None = None) -> dict[str, Any]:
+        """Export on every shard's device, concatenate on the first's, merge and reduce there (``af_engine_import_cells``).
+        Returns the outputs asked for (``stats`` [G, W, 8]; ``count`` [G, W], ``quantiles`` [G, W, Q], ``within`` [G, W, T]
+        with ``levels``), the bounds in sweep order (``row_bounds`` uint32 [n, W + 1]), ``ms`` (exports + reduction) and
+        ``scratch_bytes`` (the largest of the engines')."""
+        import torch
+
+        from .engine import Engine
+
+        parts = [shard._export_cells(e, ids[np.asarray(ix)], window_of) for shard, ix in zip(self.shards, self.index)]  # noqa: SLF001
+        first = self.shards[0]
+        dev = first._clock_t.device  # noqa: SLF001
+        lat = torch.cat([p[0].to(dev) for p in parts])
+        bounds, begin, n_lat = sweep_order_segments([p[1].cpu().numpy().view(np.uint32) for p in parts], self.index, ids)
+        parts = [(None, None, p[2], p[3]) for p in parts]      # the exports are not needed any more: their devices get the memory back
+        n_win = 0 if e is None else int(e.shape[0] - 1)
+        wc = max(n_win, 1)
+        out: dict[str, Any] = {"row_bounds": bounds}
+        kw: dict[str, Any] = {}
+        if stats:
+            out["stats"] = torch.empty((n_groups, wc, 8), dtype=torch.float64, device=dev)
+            kw["stats_ptr"] = out["stats"].data_ptr()
+        if levels is not None:
+            q, th = levels, thresholds if thresholds is not None else np.zeros(0)
+            out["quantiles"] = torch.empty((n_groups, wc, q.shape[0]), dtype=torch.float64, device=dev)
+            out["count"] = torch.empty((n_groups, wc), dtype=torch.int32, device=dev)
+            out["within"] = torch.empty((n_groups, wc, th.shape[0]), dtype=torch.int32, device=dev)
+            kw.update(levels=q, thresholds=th, count_ptr=out["count"].data_ptr(), quantiles_ptr=out["quantiles"].data_ptr() if q.shape[0] else 0,
+                      within_ptr=out["within"].data_ptr() if th.shape[0] else 0)
+        torch.cuda.synchronize(dev)
+        if first._summ_engine is None:  # noqa: SLF001
+            first._summ_engine = Engine(first.plan, dev.index if dev.index is not None else torch.cuda.current_device())  # noqa: SLF001
+        group = np.where(ids < 0, _abi.POOL_SKIP, ids).astype(np.uint32)
+        ms, scratch = first._summ_engine.import_cells(n_groups, n_win, bounds, begin, lat_ptr=lat.data_ptr(), n_lat=n_lat,  # noqa: SLF001
+                                                         group=group, **kw)
+        out["ms"] = ms + sum(p[2] for p in parts)
+        out["scratch_bytes"] = max([scratch] + [p[3] for p in parts])
+        return out
+
+    def pooled_summary(self, by: Any = None) -> dict[str, Any]:
+        """:meth:`BatchedResults.pooled_summary` of a sweep run on several devices: ``by`` is resolved once over the whole sweep,
+        every shard exports its members' latencies on its own device, and the first shard's device merges and reduces them
+        (one cell per group).  Same arguments, same keys, every word equal to the unsharded run's."""
+        self._require_clock()
+        ids, n_groups = self._histogram_groups(by)
+        got = self._summarize_cells(None, ids, n_groups, "finish", stats=True)
+        return {"stats": got["stats"][:, 0, :], "keys": LATENCY_KEYS, "replicas": np.bincount(ids[ids >= 0], minlength=n_groups), "pooled_ms": got["ms"]}
+
+    def window_summary(self, window_s: float | None = None, *, edges: Any = None, by: Any = None,
+                       row_bounds: bool = False, window_of: str = "finish") -> dict[str, Any]:
+        """:meth:`BatchedResults.window_summary` of a sweep run on several devices, with its arguments and keys; every word
+        equals the unsharded run's.  ``by="scenario"``: every shard runs its own call and the rows go behind the indices of
+        the original sweep.  Otherwise the cells cross the shards: each exports the windowed latencies of its members on its
+        own device, the first shard's device holds the import and the merged cells (16 B per windowed latency) and reduces
+        them.  The returned tensors lie on the first shard's device."""
+        import torch
+
+        self._require_clock()
+        check_window_of(window_of)
+        e = _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._histogram_groups(by)
+        out: dict[str, Any] = {"edges": e, "keys": LATENCY_KEYS, "window_of": window_of, "replicas": np.bincount(ids[ids >= 0], minlength=n_groups)}
+        if isinstance(by, str) and by == "scenario":
+            parts = [s.window_summary(edges=e, by="scenario", row_bounds=row_bounds, window_of=window_of) for s in self.shards]
+            out.update(stats=self._behind_index([p["stats"] for p in parts]), window_ms=sum(p["window_ms"] for p in parts),
+                       scratch_bytes=max(p["scratch_bytes"] for p in parts))
+            if row_bounds:
+                out["row_bounds"] = self._behind_index([p["row_bounds"] for p in parts])
+            return out
+        got = self._summarize_cells(e, ids, n_groups, window_of, stats=True)
+        out.update(stats=got["stats"], window_ms=got["ms"], scratch_bytes=got["scratch_bytes"])
+        if row_bounds:
+            out["row_bounds"] = torch.from_numpy(got["row_bounds"].view(np.int32)).to(got["stats"].device)
+        return out
+
+    def quantile_summary(self, levels: Any, *, thresholds: Any = None, window_s: float | None = None, edges: Any = None,
+                         by: Any = None, window_of: str = "finish") -> dict[str, Any]:
+        """:meth:`BatchedResults.quantile_summary` of a sweep run on several devices, with its arguments and keys; every word
+        equals the unsharded run's.  The cells cross the shards as in :meth:`window_summary` (``by="scenario"``: per shard)."""
+        self._require_clock()
+        q, th = check_levels(levels), check_slo_thresholds(thresholds)
+        if q.shape[0] == 0 and th.shape[0] == 0:
+            msg = "quantile_summary needs at least one level or one threshold"
+            raise ValueError(msg)
+        whole = window_s is None and edges is None
+        if check_window_of(window_of) == "arrival" and whole:
+            msg = "window_of='arrival' needs window_s or edges: the whole run has no window"
+            raise ValueError(msg)
+        e = None if whole else _resolve_edges(window_s, edges, self.plan.total_time)
+        ids, n_groups = self._histogram_groups(by)
+        if isinstance(by, str) and by == "scenario":
+            parts = [s.quantile_summary(q, thresholds=th, edges=e, by="scenario", window_of=window_of) for s in self.shards]
+            out = {k: self._behind_index([p[k] for p in parts]) for k in ("quantiles", "count", "within", "share")}
+            out.update(levels=q, thresholds=th, edges=e, replicas=np.bincount(ids[ids >= 0], minlength=n_groups),
+                       quantile_ms=sum(p["quantile_ms"] for p in parts), scratch_bytes=max(p["scratch_bytes"] for p in parts), window_of=window_of)
+            return out
+        got = self._summarize_cells(e, ids, n_groups, window_of, levels=q, thresholds=th)
+        return _finish_quantile_summary(got["quantiles"], got["count"], got["within"], q, th, e, ids, n_groups, got["ms"], got["scratch_bytes"],
+                                        window_of)
+
+    aggregate = BatchedResults.aggregate
+    save_point_summary = BatchedResults.save_point_summary
+    window_bands = BatchedResults.window_bands
+    save_window_summary = BatchedResults.save_window_summary
+    quantile_bands = BatchedResults.quantile_bands
+    save_quantile_summary = BatchedResults.save_quantile_summary
 
 
 def load_summary(path: str) -> dict[str, np.ndarray]:

@@ -455,7 +455,7 @@ class SimulationRunner:
         import threading
 
         from .distributed import interleave_by_load, shard_bounds
-        from .results import ShardedResults
+        from .results import ShardedCellResults
 
         n, k = int(self.seeds.size), len(self.devices)
         users = self.sweep.get("rqs_input.avg_active_users.mean")
@@ -486,7 +486,7 @@ class SimulationRunner:
         if errors:
             raise errors[0]
         keep = [r for r in range(k) if shards[r] is not None]
-        return ShardedResults([shards[r] for r in keep], [index[r] for r in keep], time.perf_counter() - t0)
+        return ShardedCellResults([shards[r] for r in keep], [index[r] for r in keep], time.perf_counter() - t0)
 
     def _engine_kw(self, cap: int, fifo: int) -> dict[str, Any]:
         return dict(request_capacity=cap, fifo_capacity=fifo, force_global_state=self.force_global_state,

@@ -885,6 +885,68 @@ int af_engine_summarize_quantiles(af_engine_t* engine, const af_outputs_t* out, 
  * neither needed nor checked.  Everything else as af_engine_summarize_quantiles. */
 int af_engine_summarize_arrival_quantiles(af_engine_t* engine, const af_outputs_t* out, af_quantiles_t* quantiles);
 
+/* CELLS ACROSS DEVICES (asyncflow_amd/csrc/af_cells.hpp): the cells of af_windows_t / af_quantiles_t when the members of a
+ * group ran on several devices.  Every device EXPORTS the latencies of its scenarios that fall into the windows -- 8 B each,
+ * instead of its [n][clock_capacity][2] clock buffer -- and the reducing device merges the exports into the very array the
+ * one-device call compacts, element for element, and runs the same reduction on it: every output word equals that call's.
+ *
+ * af_engine_export_cells: scenario s is one SEGMENT of lat.  With n_windows > 0 and edges as in af_windows_t, seg_bounds[s][k]
+ * is r_s[k] (by_arrival == 0; the same completion-order check and AF_ERR_INVALID) or c_s[k] (by_arrival != 0), also for a
+ * skipped scenario; with n_windows == 0 (edges NULL, by_arrival 0) there is one window over every stored row:
+ * seg_bounds[s] = {0, m_s}.  Wc = max(n_windows, 1).  The segments follow one another in scenario order: segment s begins at
+ * seg_begin[s] = the sum of seg_bounds[t][Wc] - seg_bounds[t][0] over the scenarios t < s that are not skipped
+ * (group[t] != AF_POOL_SKIP; the other ids are not looked at), and holds finish - start of window 0's rows in row order, then
+ * window 1's, ...: (s, w) starts at seg_begin[s] + seg_bounds[s][w] - seg_bounds[s][0].  lat_count = the elements written.
+ * lat_capacity below that: AF_ERR_CAPACITY, nothing written (the sum of min(counts[AF_CNT_COMPLETED], clock_capacity) always
+ * suffices).  seg_bounds is written only by a call that succeeds.  Scratch: 4 B per scenario + af_windows_t's without the
+ * latencies, with a cell per (scenario, window). */
+typedef struct af_cells_export {
+    uint32_t n_scenarios;
+    uint32_t n_windows;      /* 0 (with edges NULL): the whole run */
+    uint32_t by_arrival;     /* 0: windows by finish time; otherwise by arrival time (needs n_windows > 0) */
+    const uint32_t* group;   /* DEVICE [n_scenarios] or NULL: AF_POOL_SKIP exports nothing for the scenario */
+    const double* edges;     /* HOST [n_windows + 1] strictly increasing, finite; NULL with n_windows == 0 */
+    double* lat;             /* DEVICE [lat_capacity] f64 out, the caller's */
+    uint64_t lat_capacity;   /* elements */
+    uint32_t* seg_bounds;    /* DEVICE [n_scenarios][Wc + 1] u32 out */
+    uint64_t lat_count;      /* out: elements of lat written */
+    double elapsed_ms;       /* out: wall time of the call */
+    uint64_t scratch_bytes;  /* out: size of the engine's scratch after the call */
+} af_cells_export_t;
+int af_engine_export_cells(af_engine_t* engine, const af_outputs_t* out, af_cells_export_t* cells_export);
+
+/* af_engine_import_cells: n_scenarios members in the order the cells concatenate them (the order of the whole sweep), each
+ * with its group id, its bounds (as exported) and the place seg_begin[s] of its segment in lat -- the exports of several
+ * devices simply one after the other, in any order.  Cell c = g * Wc + w is the concatenation over the members of g, in
+ * member order, of the members' window w.  stats is af_windows_t's ([n_groups][Wc][8]); count / quantiles / within with levels
+ * and thresholds are af_quantiles_t's; every output is optional, at least one is needed, one merge serves all.
+ * Refused with no output word written: a group id >= n_groups, bounds that decrease, a segment that ends past n_lat, two
+ * segments (of members that are not skipped) that overlap, af_quantiles_t's rules for levels and thresholds (AF_ERR_INVALID);
+ * a cell of 2^32 or more latencies, n_groups * Wc >= 2^32 - 1, n_scenarios * (Wc + 1) > 2^32 (AF_ERR_CAPACITY).
+ * Scratch kept by the engine: 8 B per latency in a cell (the merged cells, beside the caller's 8 B per imported latency) +
+ * 8 B per (scenario, edge) + 12 B per scenario + the per-cell parts of af_windows_t and af_quantiles_t.  Synchronous. */
+typedef struct af_cells {
+    uint32_t n_scenarios;
+    uint32_t n_groups;
+    uint32_t n_windows;          /* 0: one cell per group (Wc = 1) */
+    const uint32_t* group;       /* HOST [n_scenarios] group id per member (AF_POOL_SKIP: left out); NULL: all in group 0 */
+    const uint32_t* seg_bounds;  /* HOST [n_scenarios][Wc + 1] */
+    const uint64_t* seg_begin;   /* HOST [n_scenarios] first element of the member's segment in lat */
+    const double* lat;           /* DEVICE [n_lat] f64, on the engine's device */
+    uint64_t n_lat;
+    double* stats;               /* DEVICE [n_groups][Wc][8] f64; NULL skips */
+    uint32_t n_levels;
+    const double* levels;        /* HOST [n_levels] in [0, 1] */
+    uint32_t n_thresholds;
+    const double* thresholds;    /* HOST [n_thresholds] seconds, not NaN */
+    uint32_t* count;             /* DEVICE [C] u32; NULL skips */
+    double* quantiles;           /* DEVICE [C][n_levels] f64; NULL skips */
+    uint32_t* within;            /* DEVICE [C][n_thresholds] u32; NULL skips */
+    double elapsed_ms;           /* out: wall time of the call */
+    uint64_t scratch_bytes;      /* out: size of the engine's scratch after the call */
+} af_cells_t;
+int af_engine_import_cells(af_engine_t* engine, af_cells_t* cells);
+
 /* ARRIVALS per window and group (asyncflow_amd/csrc/af_arrival_counts.hpp): the offered load, and the denominator the
  * by-arrival cohorts above lack -- their count is the cohort's completions; a request that was dropped or was still in flight
  * when the run ended is in no rqs_clock row.  Arrival times are a pure function of the seed and the generator's parameters;
