@@ -153,6 +153,30 @@ class Batch:
     def members(self, ids: np.ndarray, g: int) -> np.ndarray:
         return np.nonzero(np.asarray(ids) == g)[0]
 
+    # ---- what a batch of other strides answers differently (tests/test_gpu_wide_strides.py)
+    def draw_capacity(self, gen_cap: int) -> int:
+        """The stride of the arrival rows on the device; the host definitions keep the run's own `gen_cap`."""
+        return gen_cap
+
+    @property
+    def run_draw_capacity(self) -> int:
+        """The draw capacity of the run of the run_summarized probe."""
+        return self.cap
+
+    def time_rows(self, ia: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """The scenario whose arrival times row r of the pairs' time rows holds, and the row that every pair reads."""
+        return np.unique(ia, return_inverse=True)
+
+    def arrival_rows(self, host: np.ndarray) -> Any:
+        """The pairs' time rows [rows, draw_capacity] on the device."""
+        return self.torch.as_tensor(host, device=self.dev)
+
+    def run_buffers(self) -> tuple[Any, Any]:
+        """The clock and sample rows that the run of the run_summarized probe writes, of this batch's capacities."""
+        if "run_out" not in self.__dict__:
+            self.run_out = (self.torch.empty_like(self.clock_t), self.torch.zeros_like(self.samples_t))
+        return self.run_out
+
 
 # ---- host definitions over the groups ------------------------------------------------------------------------------------------
 def latency_cells(b: Batch, kind: str, ids: np.ndarray, n_groups: int, edges: Any) -> list[np.ndarray]:
@@ -462,6 +486,7 @@ def build_probes(b: Batch) -> list[Probe]:
 
     # ---- arrivals, and pairs through them
     gen_seeds, gen_cols, gen_cap = b.res._arrival_sweep()  # noqa: SLF001
+    draw_cap = b.draw_capacity(gen_cap)
     arrivals = cached(lambda: _host_arrivals(b, gen_cap))
 
     def arrivals_want():
@@ -470,16 +495,16 @@ def build_probes(b: Batch) -> list[Probe]:
         return {"arrivals": np.stack([per[b.members(b.three, g)].sum(axis=0) for g in range(3)]).astype(np.uint64), "row_bounds": rb.astype(np.uint32),
                 "generated": np.array([np.isfinite(t).sum() for t, _ in arrivals()], dtype=np.uint32), "flags": np.array([f for _, f in arrivals()], dtype=np.uint32)}
     probes.append(Probe("arrivals", [("arrivals", u64, (3, N_WIN)), ("row_bounds", u32, (n, N_WIN + 1)), ("generated", u32, (n,)), ("flags", u32, (n,))],
-                        lambda e, p: e.summarize_arrivals(gen_seeds, gen_cols, 3, b.edges, draw_capacity=gen_cap, arrivals_ptr=p["arrivals"], group_ptr=gp3,
+                        lambda e, p: e.summarize_arrivals(gen_seeds, gen_cols, 3, b.edges, draw_capacity=draw_cap, arrivals_ptr=p["arrivals"], group_ptr=gp3,
                                                           row_bounds_ptr=p["row_bounds"], generated_ptr=p["generated"], flags_ptr=p["flags"])[1],
                         arrivals_want,
                         refused=lambda e, p: _raises_invalid(lambda: e.summarize_arrivals(
-                            gen_seeds, gen_cols, 3, [0.0, 7.0, 7.0], draw_capacity=gen_cap, arrivals_ptr=p["arrivals"], group_ptr=gp3,
+                            gen_seeds, gen_cols, 3, [0.0, 7.0, 7.0], draw_capacity=draw_cap, arrivals_ptr=p["arrivals"], group_ptr=gp3,
                             row_bounds_ptr=p["row_bounds"], generated_ptr=p["generated"], flags_ptr=p["flags"]))))
     # as arrival_summary calls it: the bounds that the group sums read lie in the pool, the flags in the engine's own buffer
     own_part = _r256((N_WIN + 1) * 8) + _r256(n * (N_WIN + 1) * 4)
     probes.append(Probe("arrivals-own_scratch", [("arrivals", u64, (3, N_WIN)), ("generated", u32, (n,))],
-                        lambda e, p: e.summarize_arrivals(gen_seeds, gen_cols, 3, b.edges, draw_capacity=gen_cap, arrivals_ptr=p["arrivals"], group_ptr=gp3,
+                        lambda e, p: e.summarize_arrivals(gen_seeds, gen_cols, 3, b.edges, draw_capacity=draw_cap, arrivals_ptr=p["arrivals"], group_ptr=gp3,
                                                           generated_ptr=p["generated"])[1],
                         lambda: {k: arrivals_want()[k] for k in ("arrivals", "generated")},
                         lambda: _assert(fresh("arrivals-own_scratch")[1] == own_part, "the bounds [n, W + 1] do not lie in the pool")))
@@ -488,8 +513,8 @@ def build_probes(b: Batch) -> list[Probe]:
     NPR = int(ia.shape[0])
     p_ids = np.where(pr["by"] == 0, 0, 2).astype(np.int64)
     p_ids[[1, 8]] = -1
-    t_rows, time_row = np.unique(ia, return_inverse=True)
-    times_t = b.torch.as_tensor(np.stack([arrivals()[s][0] for s in t_rows]), device=b.dev)
+    t_rows, time_row = b.time_rows(ia)
+    times_t = b.arrival_rows(np.stack([arrivals()[s][0] for s in t_rows]))
     pa_t, pb_t, tr_t, pg_t = b.u32(ia), b.u32(ib), b.u32(time_row.reshape(-1)), b.u32(np.where(p_ids < 0, _abi.POOL_SKIP, p_ids))
     p_thr = (0.0, 0.004)
     PB = PAIR_BINNING[2] << PAIR_BINNING[0]
@@ -510,7 +535,7 @@ def build_probes(b: Batch) -> list[Probe]:
 
     def pairs_call(e, p, thresholds=p_thr):
         return e.summarize_pairs(n, NPR, 3, pair_a_ptr=pa_t.data_ptr(), pair_b_ptr=pb_t.data_ptr(), times_ptr=times_t.data_ptr(), time_row_ptr=tr_t.data_ptr(),
-                                 n_time_rows=int(t_rows.shape[0]), draw_capacity=gen_cap, **{f"{k}_ptr": p[k] for k in pr_keys}, group_ptr=pg_t.data_ptr(),
+                                 n_time_rows=int(t_rows.shape[0]), draw_capacity=draw_cap, **{f"{k}_ptr": p[k] for k in pr_keys}, group_ptr=pg_t.data_ptr(),
                                  edges=b.edges, thresholds=thresholds, **dict(zip(("sub_bits", "min_exp", "octaves"), PAIR_BINNING)), **b.clock_kw)[1]
     probes.append(Probe("pairs", [("pair_counts", u32, (NPR, N_WIN, 5)), ("pair_sums", f64, (NPR, N_WIN, 2)), ("unmatched", u32, (NPR, 2)),
                                   ("cell_counts", u64, (C_EX, 8)), ("above", u64, (C_EX, len(p_thr))), ("extremes", f64, (C_EX, 2)), ("hist", u32, (C_EX, 2, PB)),
@@ -518,7 +543,7 @@ def build_probes(b: Batch) -> list[Probe]:
                         pairs_call, pairs_want,
                         refused=lambda e, p: _raises_invalid(lambda: e.summarize_pairs(
                             n, NPR, 3, pair_a_ptr=pa_t.data_ptr(), pair_b_ptr=pb_t.data_ptr(), times_ptr=times_t.data_ptr(), time_row_ptr=tr_t.data_ptr(),
-                            n_time_rows=0, draw_capacity=gen_cap, **{f"{k}_ptr": p[k] for k in pr_keys}, group_ptr=pg_t.data_ptr(), edges=b.edges,
+                            n_time_rows=0, draw_capacity=draw_cap, **{f"{k}_ptr": p[k] for k in pr_keys}, group_ptr=pg_t.data_ptr(), edges=b.edges,
                             thresholds=p_thr, **dict(zip(("sub_bits", "min_exp", "octaves"), PAIR_BINNING)), **b.clock_kw))))
 
     # ---- the per-scenario summary, of a finished run and in one call with the run
@@ -539,13 +564,13 @@ def build_probes(b: Batch) -> list[Probe]:
                         lambda e, p: _unreported(e.summarize(n, samples_ptr=b.samples_t.data_ptr(), tick_capacity=b.tick_cap, **summ_kw(p), **b.clock_kw)),
                         summary_want, uses_pool=False,
                         refused=lambda e, p: _raises_invalid(lambda: e.summarize(0, samples_ptr=b.samples_t.data_ptr(), tick_capacity=b.tick_cap, **summ_kw(p), **b.clock_kw))))
-    run_out = {"clock": b.torch.empty_like(b.clock_t), "samples": b.torch.zeros_like(b.samples_t)}
 
     def run_summarized(e, p):
         counts = b.torch.zeros_like(b.counts_t)                   # (a run adds to its counts)
+        run_clock, run_samples = b.run_buffers()
         b.torch.cuda.synchronize(b.dev)
-        e.run(b.res.seeds, b.run_cols, clock_ptr=run_out["clock"].data_ptr(), clock_capacity=b.cap, samples_ptr=run_out["samples"].data_ptr(),
-              tick_capacity=b.tick_cap, counts_ptr=counts.data_ptr(), draw_capacity=b.cap, summary=summ_kw(p))
+        e.run(b.res.seeds, b.run_cols, clock_ptr=run_clock.data_ptr(), clock_capacity=b.cap, samples_ptr=run_samples.data_ptr(),
+              tick_capacity=b.tick_cap, counts_ptr=counts.data_ptr(), draw_capacity=b.run_draw_capacity, summary=summ_kw(p))
         b.torch.cuda.synchronize(b.dev)
         assert b.torch.equal(counts, b.counts_t), "the run of af_engine_run_summarized counted something else than the batch's run"
         return None
@@ -686,12 +711,8 @@ def scratch_after(eng: Any, p: Probe, scratch: int | None) -> int | None:
     return pool_size(eng) if scratch is None else scratch
 
 
-# ---- (a) ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", NAMES)
-def test_fresh_engine_equals_the_host_definition(name):
-    p = probes()[name]
-    p.path()                                                      # the scratch-heavy path, from the cell sizes of the batch
-    got, scratch = fresh(name)
+def equals_host(name: str, p: Probe, got: dict[str, np.ndarray]) -> None:
+    """Every output word of a call against the probe's host definition: floats by bit pattern, NaN in the same places."""
     want = p.host()
     assert set(want) == {k for k, _, _ in p.outs}
     for k, dt, shape in p.outs:
@@ -709,6 +730,15 @@ def test_fresh_engine_equals_the_host_definition(name):
             assert (w <= np.iinfo(dt).max).all()
             bad = np.argwhere(g.astype(np.uint64) != w)
             assert bad.shape[0] == 0, (name, k, bad[:5].tolist(), [int(g[tuple(t)]) for t in bad[:5]], [int(w[tuple(t)]) for t in bad[:5]])
+
+
+# ---- (a) ---------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", NAMES)
+def test_fresh_engine_equals_the_host_definition(name):
+    p = probes()[name]
+    p.path()                                                      # the scratch-heavy path, from the cell sizes of the batch
+    got, scratch = fresh(name)
+    equals_host(name, p, got)
     if p.uses_pool:
         assert scratch > 0
     if p.first_part:
