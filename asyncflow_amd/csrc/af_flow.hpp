@@ -208,10 +208,51 @@ enum : uint32_t { PROF_SETUP, PROF_GEN, PROF_SELECT, PROF_SERIES_RECV, PROF_STAT
 #ifndef AF_SELECT_WINDOW
 #define AF_SELECT_WINDOW 6
 #endif
+// Round 9: the width per station list (list 0: what the generator sent, one edge's jitter on a sorted batch; lists 1 .. 3: the
+// jitter of later edges on an order already disturbed).  -DAF_SELECT_WINDOW_S<list>=w on the command line comes first, then what
+// the plan-specialised build was given for its plan (AF_FJ_SELECT_WINDOW_S<list>: engine.hip, flow_jit_spec_string), then
+// AF_SELECT_WINDOW; AF_SELECT_WINDOW=0 switches the window off in every list whatever the others say (select_window_of).
+#ifndef AF_SELECT_WINDOW_S0
+#ifdef AF_FJ_SELECT_WINDOW_S0
+#define AF_SELECT_WINDOW_S0 AF_FJ_SELECT_WINDOW_S0
+#else
+#define AF_SELECT_WINDOW_S0 AF_SELECT_WINDOW
+#endif
+#endif
+#ifndef AF_SELECT_WINDOW_S1
+#ifdef AF_FJ_SELECT_WINDOW_S1
+#define AF_SELECT_WINDOW_S1 AF_FJ_SELECT_WINDOW_S1
+#else
+#define AF_SELECT_WINDOW_S1 AF_SELECT_WINDOW
+#endif
+#endif
+#ifndef AF_SELECT_WINDOW_S2
+#ifdef AF_FJ_SELECT_WINDOW_S2
+#define AF_SELECT_WINDOW_S2 AF_FJ_SELECT_WINDOW_S2
+#else
+#define AF_SELECT_WINDOW_S2 AF_SELECT_WINDOW
+#endif
+#endif
+#ifndef AF_SELECT_WINDOW_S3
+#ifdef AF_FJ_SELECT_WINDOW_S3
+#define AF_SELECT_WINDOW_S3 AF_FJ_SELECT_WINDOW_S3
+#else
+#define AF_SELECT_WINDOW_S3 AF_SELECT_WINDOW
+#endif
+#endif
+constexpr uint32_t select_window_of(uint32_t s) {
+    return (uint32_t)(AF_SELECT_WINDOW) == 0u ? 0u
+           : s == 0u ? (uint32_t)(AF_SELECT_WINDOW_S0) : s == 1u ? (uint32_t)(AF_SELECT_WINDOW_S1) : s == 2u ? (uint32_t)(AF_SELECT_WINDOW_S2) : (uint32_t)(AF_SELECT_WINDOW_S3);
+}
+// (one width for all four: select() stays ONE copy of select_regs, as the library's loop over the stations needs it)
+constexpr bool kSelectWindowUniform = select_window_of(0u) == select_window_of(1u) && select_window_of(1u) == select_window_of(2u) && select_window_of(2u) == select_window_of(3u);
 #if !defined(__HIPCC__)
 // host builds only: select_regs calls ranked by the window / handed on to the bucket rank (of the instantiations that have the
-// window at all), for the stand-alone programs that drive the selection on crafted lists
-inline unsigned long long g_select_window_calls[2] = {0ull, 0ull};
+// window at all), for the stand-alone programs that drive the selection on crafted lists; [2], [3]: of the ranked ones, those that
+// kept entries in the list / selected fewer than were eligible; and the first two per station list (how a width suits a list:
+// profiles/r09/emulator_widths_per_list.txt)
+inline unsigned long long g_select_window_calls[4] = {0ull, 0ull, 0ull, 0ull};
+inline unsigned long long g_select_window_by_list[4][2] = {};
 #endif
 
 // ---- the algorithm, written against a wave backend W ---------------------------------------------
@@ -779,11 +820,23 @@ struct Flow {
     // `level` != kAnyLevel: only the entries of the server list whose target server is of that level.
     AF_CORE uint32_t select(uint32_t s, double H_in, uint32_t room, double& okey, double& ot0, uint32_t& oaux, uint32_t hs, uint32_t level = kAnyLevel) {
         if (kBig) return select_big(s, H_in, room, okey, ot0, oaux, hs, level);
-        return select_regs<IPL>(s, H_in, room, okey, ot0, oaux, hs, level);
+        // (round 9: a window width per list.  Where they differ, each list has its own copy of select_regs: the plan-specialised
+        // builds, whose unrolled stations call with a constant `s`, keep exactly one of the four at each call site.)
+        if constexpr (kSelectWindowUniform) {
+            return select_regs<IPL, select_window_of(0u)>(s, H_in, room, okey, ot0, oaux, hs, level);
+        } else {
+            switch (s) {
+                case 0u: return select_regs<IPL, select_window_of(0u)>(s, H_in, room, okey, ot0, oaux, hs, level);
+                case 1u: return select_regs<IPL, select_window_of(1u)>(s, H_in, room, okey, ot0, oaux, hs, level);
+                case 2u: return select_regs<IPL, select_window_of(2u)>(s, H_in, room, okey, ot0, oaux, hs, level);
+                default: return select_regs<IPL, select_window_of(3u)>(s, H_in, room, okey, ot0, oaux, hs, level);
+            }
+        }
     }
     // (IPLx entries per lane in registers: the class's own IPL for the register-resident lists; round 6: also what select_big()
     // hands a list of at most 64 x kBigRegIpl entries to)
-    template <uint32_t IPLx>
+    // (WIN: the lane window's width for this list, select_window_of(); 0 = the bucket rank alone)
+    template <uint32_t IPLx, uint32_t WIN = 0u>
     AF_CORE uint32_t select_regs(uint32_t s, double H_in, uint32_t room, double& okey, double& ot0, uint32_t& oaux, uint32_t hs, uint32_t level) {
         W::sync();   // appends of the previous station are visible
         const double lo = H_get(hs);
@@ -808,7 +861,7 @@ struct Flow {
         // Round 8: the lane window.  A list is the previous station's batch in time order plus a jitter far below the batch's span,
         // so it arrives almost sorted: the form with one entry per lane first tries to rank an entry against the kWindow lanes in
         // front of it alone (below), and zeroes and fills the bucket counts only where that is not proved exact.
-        constexpr uint32_t kWindow = (IPLx == 1u && !kTieBreak && !kChain) ? (uint32_t)(AF_SELECT_WINDOW) : 0u;
+        constexpr uint32_t kWindow = (IPLx == 1u && !kTieBreak && !kChain) ? WIN : 0u;
         static_assert(kWindow < 32u, "AF_SELECT_WINDOW: lanes an entry looks back");
         if (kWindow == 0u) {
             hist()[lane] = 0u;   // (zeroing them in front of the entry sync instead -- one sync less -- measured: no gain)
@@ -891,7 +944,10 @@ struct Flow {
                 else prof_acc[PROF_N_SELECT_BUCKET] += 1ull;
             }
 #if !defined(__HIPCC__)
-            if (lane == 0u) g_select_window_calls[ranked ? 0 : 1] += 1ull;
+            if (lane == 0u) {
+                g_select_window_calls[ranked ? 0 : 1] += 1ull;
+                g_select_window_by_list[s & 3u][ranked ? 0 : 1] += 1ull;
+            }
 #endif
             if (!ranked) {
                 hist()[lane] = 0u;
@@ -983,6 +1039,8 @@ struct Flow {
                 if (mb != 0ull) h_left = bcast_f64(k[q], (uint32_t)__builtin_ctzll(mb));
             }
         }
+        // (round 9: handing the window's batch over by a forward lane permute instead of the buffer below was measured and was
+        // 1.4 ms per step slower -- DESIGN.md section 5, profiles/r09/ab_select_widths.txt)
         uint32_t kept = 0u;
 #pragma unroll
         for (uint32_t q = 0u; q < IPLx; ++q) {
@@ -1009,6 +1067,12 @@ struct Flow {
             }
         }
         n_list_set(s, kept);
+#if !defined(__HIPCC__)
+        if (lane == 0u && ranked) {
+            g_select_window_calls[2] += kept != 0u ? 1ull : 0ull;
+            g_select_window_calls[3] += n_sel < E ? 1ull : 0ull;
+        }
+#endif
         W::sync();
         H_set(hs, n_sel < E ? h_left : hi);
         if (lane < n_sel) {

@@ -1624,6 +1624,18 @@ std::string flow_jit_spec_string(const af_engine* e, const FlowPlan& P, const af
     // the proof fails in most calls) and were slower with it in its first form (config 3 67.1 -> 69.3, config 4 747 -> 772 ms):
     // they keep the bucket rank alone (profiles/r08/ab_select_window.txt)
     if (P.feat != 0u && !std::getenv("AF_FLOW_SELECT_WINDOW_ALL")) spec += " -DAF_SELECT_WINDOW=0";
+    // Round 9: the lean form's width per station list (af_flow.hpp: AF_FJ_SELECT_WINDOW_S<list>; a -DAF_SELECT_WINDOW_S<list> on the
+    // compiler's command line still comes first).  CONSTANTS, measured on config 2 and not worked out from the plan: four lanes for
+    // what the generator and the servers sent, three for what the client and the load balancer sent.  On the host emulator the
+    // proof then holds in 92 / 96 / 94 / 95 % of the four lists' calls (99.2 / 100 / 100 / 99.7 % at six lanes), and each lane of
+    // width costs every call more than the rare bucket rank costs the few: 42.27 ms per step at 6-6-6-6, 41.70 at 4-4-4-4, 41.57 at
+    // 4-3-3-4, 41.61 at 3-3-3-3 (the two are within run-to-run noise of each other), 41.75 at 3-2-2-3, 42.18 at 2-2-2-2
+    // (profiles/r09/ab_select_widths.txt).  No rule from the plan's numbers (in-edge latency x offered rate) was tested against
+    // other plans, so none is claimed: EVERY plan of the lean form (single server, other topologies) gets these widths, measured
+    // on LB-2 alone -- results are the same at any width, only the share of calls that fall back to the bucket rank differs.
+    // The library's generic kernels were not measured at other widths and keep AF_SELECT_WINDOW in every list.
+    else if (P.feat == 0u)
+        spec += " -DAF_FJ_SELECT_WINDOW_S0=4 -DAF_FJ_SELECT_WINDOW_S1=3 -DAF_FJ_SELECT_WINDOW_S2=3 -DAF_FJ_SELECT_WINDOW_S3=4";
     return spec;
 }
 }  // namespace
